@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py - frames/s of the extraction + matching hot path on MI355X (contract: see the task statement / DESIGN.md).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, the stage times and the
+roofline of the timed steps).  --full adds everything else after the timed region: the parity gate against the CPU oracle (no
+value when it fails), the sustained rate, the ViT-inside / bf16 / host-upload / directory legs, single-frame latency, the
+measured matrix-pipe peak, the CPU baseline and, for N > 1, the per-rank upload and ViT legs.  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB in all: see dump_outputs).
 
 One "step" = one pass of the hot path over one frame sequence per GPU: A0 (Pillow-exact preprocessing), A2 (token
 BatchNorm), A3 (saliency CNN), A4/A5 (NMS + top-k), A6+A7 (gather + descriptor MLP), A9 (intensity), M1 for every
@@ -171,6 +177,49 @@ def index_parity_vs_torch(grid):
             "note": "bit_exact is against the CPU oracle; against torch itself see index_parity_vs_torch (set-level at G >= 40)"}
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20        # under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out: dict, path: str, budget: int = DUMP_BUDGET_BYTES, seed: int = 0) -> dict:
+    """Write every tensor of one step's result as path/<name>.npy: float32 stays float32, every other dtype becomes float64
+    (exact for the int32 / int64 indices and counts).  At most `budget` bytes in all: when the arrays do not fit, the largest
+    ones share what the others leave, each cut to a fixed sample of its leading-axis rows (sorted, drawn from a generator seeded
+    by `seed` and the array's name), and the row numbers kept go to path/<name>_rows.npy.  Same shapes -> same sample, so two
+    runs compare file for file."""
+    import zlib
+    ts = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+    item = {k: 4 if v.dtype in (torch.float32, torch.float16, torch.bfloat16) else 8 for k, v in ts.items()}
+    size = {k: v.numel() * item[k] for k, v in ts.items()}
+    # water-filling: arrays below the cap are written whole, the ones above share the rest equally (row-index files included)
+    left, todo = budget - 256 * 2 * len(ts), sorted(ts, key=lambda k: size[k])      # 2 x 128-byte headers per array
+    cap = None
+    for i, k in enumerate(todo):
+        share = left // (len(todo) - i)
+        if size[k] > share:
+            cap = share
+            break
+        left -= size[k]
+    os.makedirs(path, exist_ok=True)
+    sampled, total = {}, 0
+    for k, v in ts.items():
+        rows = None
+        if cap is not None and size[k] > cap and v.dim() >= 1:
+            n0 = v.shape[0]
+            row_bytes = size[k] // max(n0, 1)
+            keep = max(1, min(n0, (cap - 8 * n0) // max(row_bytes, 1)))
+            rng = np.random.default_rng([seed, zlib.crc32(k.encode())])
+            rows = np.sort(rng.choice(n0, size=keep, replace=False))
+            v = v.index_select(0, torch.from_numpy(rows).to(v.device))
+        a = v.detach().cpu().numpy().astype(np.float32 if item[k] == 4 else np.float64)
+        np.save(os.path.join(path, f"{k}.npy"), a)
+        total += a.nbytes
+        if rows is not None:
+            np.save(os.path.join(path, f"{k}_rows.npy"), rows.astype(np.float64))
+            total += rows.size * 8
+            sampled[k] = [int(rows.size), int(ts[k].shape[0])]
+    return {"dir": path, "arrays": len(ts), "bytes": total, "sampled_rows": sampled}
+
+
 def launch_plan(gpus: int, env: dict, device_count: int, shared_gpu: bool = False):
     """What `bench.py --gpus N` does, decided BEFORE anything touches a GPU.  Returns (action, message):
       "run"   - this process is one rank (WORLD_SIZE == N, the torch.distributed.run contract), or N == 1;
@@ -211,6 +260,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the parity gate and every additional leg (the --no-* options below pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / float64, under 64 MB in all)")
     ap.add_argument("--workload", default="fr1_desk_613", choices=list(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sustain", type=float, default=10.0, help="N = 1: seconds of back-to-back steps for the `sustained` rate (0: skip)")
@@ -240,6 +293,8 @@ def main():
                     help="TEST ONLY (N > 1): flip one match index of the first cross-rank pair in the gathered result before the parity "
                          "gate - the run must then report no value and exit 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # nothing above this line and nothing in launch_plan touches a GPU (torch.cuda.device_count() only counts devices)
     action, msg = launch_plan(args.gpus, os.environ, torch.cuda.device_count(), args.rehearse_shared_gpu)
@@ -362,12 +417,15 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(out, args.dump_outputs)
+        print(f"bench.py: last timed step -> {dumped}", file=sys.stderr)
 
     # additional leg (N = 1): the SUSTAINED rate.  `value` is `steps` passes of ~11 ms, i.e. a burst on a chip whose clock is
     # power-managed; here the same step loops for `--sustain` seconds (default 10) and the rate - and the dominant kernel's
     # TFLOP/s from its HIP events - is taken over the LAST half of that time, when clocks and temperature have settled.
     sustained = None
-    if world == 1 and args.sustain > 0:
+    if args.full and world == 1 and args.sustain > 0:
         keep = dict(ev)                  # the timed region's stage events
         ev.clear()
         marks, a3_seen = [], []           # event at the end of each step; A3 launches recorded up to it (launch groups per step)
@@ -407,7 +465,7 @@ def main():
     # additional leg (N = 1): the same pass with the tokens computed on the GPU by the HIP ViT-S/16 (A1, random weights
     # of the DINOv3 architecture - pretrained weights are a remote fetch): images -> A0 -> A1 -> A2 .. M1
     vit_leg = None
-    if world == 1 and not args.no_vit:
+    if args.full and world == 1 and not args.no_vit:
         from sslam_amd.vit import DinoV3ViT
         torch.manual_seed(0)
         pipe_v = SequencePipeline(cfg, ssd, rsd, device=dev, vit=DinoV3ViT().to(dev).eval())
@@ -563,7 +621,7 @@ def main():
 
     # additional block (N = 1): single-frame latency, the shape every reference caller has (tools/bench_latency.py)
     latency = None
-    if world == 1 and not args.no_vit:
+    if args.full and world == 1 and not args.no_vit:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_latency
         latency = bench_latency.measure(pipe_v, toks[:8], imgs[:8], vit_pipe=pipe_v, reps=50)
@@ -573,7 +631,7 @@ def main():
     # chunks on a side stream while the previous chunk is extracted and matched (sslam_amd.harness.run_frames); tokens-in
     # mode like `value`.  Beside it: the raw H2D rate of the same bytes, i.e. the PCIe bound on frames/s.
     upload_leg = None
-    if world == 1 and not args.no_upload:
+    if args.full and world == 1 and not args.no_upload:
         from sslam_amd.harness import run_frames
         imgs_pin = imgs.cpu().pin_memory()
         probe = torch.empty_like(imgs)
@@ -609,7 +667,7 @@ def main():
     # extract(path) -> match, visualize_matches_sequence.py:272-357): sorted rgb/*.png -> PIL decode on a host thread pool ->
     # pinned double buffer -> H2D on a side stream -> extract once -> all spacings.  Decode-inclusive, so host-bound.
     dir_leg = None
-    if world == 1 and not args.no_directory:
+    if args.full and world == 1 and not args.no_directory:
         import shutil
         import tempfile
 
@@ -652,7 +710,7 @@ def main():
     # the descriptor MLP on bf16 MFMA.  Not index-exact, so it is never `value`: reported with its agreement rates against
     # the exact pass above on the same frames.
     bf16_leg = None
-    if world == 1 and not args.no_bf16:
+    if args.full and world == 1 and not args.no_bf16:
         import dataclasses
         pipe_b = SequencePipeline(dataclasses.replace(cfg, precision="bf16"), ssd, rsd, device=dev)
         for _ in range(max(1, args.warmup)):
@@ -686,7 +744,7 @@ def main():
     # be; a per-rank local pass (no halo, no gather); (b) the sharded step with the HIP ViT inside (images -> A0 -> A1 -> ... -> M1,
     # halo + gather included).  Same bracket as `value`: barrier + synchronize on both sides, MAX over ranks.
     multi_legs = None
-    if world > 1 and not (args.no_upload and args.no_vit):
+    if args.full and world > 1 and not (args.no_upload and args.no_vit):
         multi_legs = {}
 
         def rank_max(x):
@@ -752,47 +810,49 @@ def main():
     # the oracle on them and compares the boundary pairs' rows of the GATHERED result (the only pairs that exercise the halo),
     # and compares a digest of every rank's local match arrays with the digest of that rank's rows in the gathered arrays
     # (what arrived is what was computed).  Any mismatch on any rank: no value.
-    from oracle import ora
-    from oracle_check import blocks_for, check_pass, compare_block
-    if rank == 0:
-        ora.lib()                 # (re)builds oracle/_build/liboracle.so if its sources are newer: one rank only, the others load it after
-    if world > 1:
-        dist.barrier()
-    ora.set_num_threads(max(1, ora.host_threads() // world))
-    # default: the whole block (the oracle covers the largest workload, 2 965 frames at G = 40, in 28 s on 16 host threads)
-    want = args.parity_frames if args.parity_frames >= 0 else n
-    tpar = time.perf_counter()
-    parity = check_pass(out, imgs, toks, ssd, rsd, size, K, cfg, blocks_for(n, want, cfg.spacing), frame0=lo)
-    parity["checked"] = "keypoint indices, scores, descriptors, intensities, match counts, match pairs, match quality"
-    parity["frames_total"], parity["pairs_total"] = n * world, n * world - cfg.spacing
-    if world > 1:
-        from oracle_check import check_boundaries, check_gathered_rows, digest_matches, merge_rank_reports
-        mine = dict(parity, rank=rank, digest=digest_matches(out["matches"], out["quality"], out["match_count"]))
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
+    parity = None                 # a plain run reports the timed steps only
+    if args.full:
+        from oracle import ora
+        from oracle_check import blocks_for, check_pass, compare_block
         if rank == 0:
-            merged = merge_rank_reports(per_rank)
-            gm = {"matches": out["all_matches"], "quality": out["all_quality"], "match_count": out["all_match_count"]}
-            if args.test_corrupt_gathered:
-                row_ = ranges[1][0] - cfg.spacing
-                gm["matches"][row_, 0, 1] = (gm["matches"][row_, 0, 1] + 1) % K
+            ora.lib()                 # (re)builds oracle/_build/liboracle.so if its sources are newer: one rank only, the others load it after
+        if world > 1:
+            dist.barrier()
+        ora.set_num_threads(max(1, ora.host_threads() // world))
+        # default: the whole block (the oracle covers the largest workload, 2 965 frames at G = 40, in 28 s on 16 host threads)
+        want = args.parity_frames if args.parity_frames >= 0 else n
+        tpar = time.perf_counter()
+        parity = check_pass(out, imgs, toks, ssd, rsd, size, K, cfg, blocks_for(n, want, cfg.spacing), frame0=lo)
+        parity["checked"] = "keypoint indices, scores, descriptors, intensities, match counts, match pairs, match quality"
+        parity["frames_total"], parity["pairs_total"] = n * world, n * world - cfg.spacing
+        if world > 1:
+            from oracle_check import check_boundaries, check_gathered_rows, digest_matches, merge_rank_reports
+            mine = dict(parity, rank=rank, digest=digest_matches(out["matches"], out["quality"], out["match_count"]))
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+            if rank == 0:
+                merged = merge_rank_reports(per_rank)
+                gm = {"matches": out["all_matches"], "quality": out["all_quality"], "match_count": out["all_match_count"]}
+                if args.test_corrupt_gathered:
+                    row_ = ranges[1][0] - cfg.spacing
+                    gm["matches"][row_, 0, 1] = (gm["matches"][row_, 0, 1] + 1) % K
 
-            def regen(a_, b_):          # frames [a_, b_) of the one sequence, from the seed (on this rank's GPU, then to the host)
-                bi, bt = synth_sequence(n * world, a_, b_, h, w, grid, dev, seed=1234)
-                return bi.cpu().numpy(), bt.cpu().numpy()
+                def regen(a_, b_):          # frames [a_, b_) of the one sequence, from the seed (on this rank's GPU, then to the host)
+                    bi, bt = synth_sequence(n * world, a_, b_, h, w, grid, dev, seed=1234)
+                    return bi.cpu().numpy(), bt.cpu().numpy()
 
-            okb, bpairs, bmatches, whyb = check_boundaries(gm, [ranges[r_][0] for r_ in range(1, world)], regen, ssd, rsd, size, K, cfg)
-            same_rows = check_gathered_rows(gm, out["pairs_per_rank"], [pr["digest"] for pr in per_rank])
-            if not okb or not same_rows:
-                merged["bit_exact"] = False
-                merged["first_mismatch"] = merged["first_mismatch"] or whyb or "gathered rows differ from a rank's local match arrays"
-            merged.update(boundary_pairs_checked=bpairs, boundary_matches_checked=bmatches, boundaries=world - 1,
-                          gathered_rows_equal_every_ranks_local_result=same_rows, ranks_checked=world)
-            merged["pairs_checked"] += bpairs
-            merged["matches_checked"] += bmatches
-            parity = merged
-    parity["seconds"] = round(time.perf_counter() - tpar, 2)
-    parity["oracle_threads"] = ora.num_threads()
+                okb, bpairs, bmatches, whyb = check_boundaries(gm, [ranges[r_][0] for r_ in range(1, world)], regen, ssd, rsd, size, K, cfg)
+                same_rows = check_gathered_rows(gm, out["pairs_per_rank"], [pr["digest"] for pr in per_rank])
+                if not okb or not same_rows:
+                    merged["bit_exact"] = False
+                    merged["first_mismatch"] = merged["first_mismatch"] or whyb or "gathered rows differ from a rank's local match arrays"
+                merged.update(boundary_pairs_checked=bpairs, boundary_matches_checked=bmatches, boundaries=world - 1,
+                              gathered_rows_equal_every_ranks_local_result=same_rows, ranks_checked=world)
+                merged["pairs_checked"] += bpairs
+                merged["matches_checked"] += bmatches
+                parity = merged
+        parity["seconds"] = round(time.perf_counter() - tpar, 2)
+        parity["oracle_threads"] = ora.num_threads()
 
     if rank == 0:
         # per step: a sharded step extracts in two launch groups (boundary frames first), so sum the launches of a stage
@@ -816,7 +876,7 @@ def main():
                                " (FETCH_SIZE / WRITE_SIZE passes of the same command, gfx950 corrections applied)")
             except Exception:
                 traffic = traffic_src = None
-        ok = bool(parity["bit_exact"])
+        ok = parity is None or bool(parity["bit_exact"])
         rehearse = None
         if rehearsal:
             # the whole sequence in ONE process on this GPU: the gathered result of the sharded run must equal it pair for pair
@@ -832,7 +892,7 @@ def main():
                         "matches": int(one["match_count"].sum().item()), "pairs_per_rank": out["pairs_per_rank"],
                         "gather": args.gather, "records_per_rank": out.get("records_per_rank"), "rehearsal_frames_per_s": round(n * world * args.steps / dt, 1)}
             del imgs_all, toks_all, one
-        mpeak = measured_mfma_peak() if world == 1 else None
+        mpeak = measured_mfma_peak() if args.full and world == 1 else None
         res = {
             "metric": METRIC, "value": round(n * world * args.steps / dt, 2), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -852,13 +912,13 @@ def main():
             # SURVEY 8d path-level figures: authored-path FLOP (A3 + A7 + A6 + one M1 per frame) and compulsory bytes per frame
             "path_roofline": path_roofline(n * world * args.steps / dt, grid, K, pipe.selector.hidden, h, w),
             "stage_ms": stage_ms,
-            "parity": dict(parity, bit_exact=ok, **index_parity_vs_torch(grid)),
+            "parity": dict(parity, bit_exact=ok, **index_parity_vs_torch(grid)) if parity is not None else None,
             "n_ranks_seen": dist.get_world_size() if world > 1 else 1, "frame_ranges": ranges,
             "matches_per_pair": round(float(out["match_count"].float().mean().item()), 1),
         }
         if sustained is not None:
             res["sustained"] = sustained
-        if world == 1 and not args.no_vit:
+        if vit_leg is not None:
             res["with_vit"] = vit_leg
         if latency is not None:
             res["latency"] = latency
@@ -868,7 +928,7 @@ def main():
             res["with_upload"] = upload_leg
         if dir_leg is not None:
             res["tum_directory"] = dir_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             nb = min(n, 64)
             res["cpu_baseline"], cb_out = cpu_baseline(imgs[:nb].cpu().numpy(), toks[:nb].cpu().numpy(), ssd, rsd, size, K, cfg)
             # what was timed is what is checked: the timed run's own outputs against the GPU pass (frames 0..63, pairs 0..62)

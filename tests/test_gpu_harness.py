@@ -354,7 +354,7 @@ def test_two_rank_rehearsal_on_one_gpu(T):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--frames", "21",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--full", "--frames", "21",
                         "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -384,12 +384,41 @@ def test_rehearsal_gate_refuses_a_corrupted_boundary_pair(T):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--frames", "9",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--full", "--frames", "9",
                         "--steps", "1", "--warmup", "1", "--test-corrupt-gathered"], capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["value"] is None and not d["parity"]["bit_exact"]
     assert "boundary of rank 1" in d["parity"]["first_mismatch"] or "gathered rows" in d["parity"]["first_mismatch"]
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(T, tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` without --full: the line carries the headline fields and none of the
+    additional legs, and DIR holds the last timed step's arrays - equal to a pass of the pipeline over the same seeded frames."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from sslam_amd.pipeline import ExtractorConfig, SequencePipeline
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--frames", "9", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["metric"] == bench.METRIC and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(9 * 1e3 / d["ms_per_step"], rel=1e-2)
+    assert d["parity"] is None and not {"sustained", "with_vit", "bf16_mode", "with_upload", "tum_directory", "cpu_baseline"} & set(d)
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    n, h, w, size, K = bench.WORKLOADS["fr1_desk_613"]
+    imgs, toks = bench.synth_sequence(9, 0, 9, h, w, size // 16, T.device("cuda"), seed=1234)
+    ref = SequencePipeline(ExtractorConfig(input_size=size, num_keypoints=K), synth.selector_state(0), synth.refiner_state(0),
+                           device="cuda").run(imgs, toks)
+    for k in ("idx", "scores", "descriptors", "intensity", "keypoints_pixel", "matches", "quality", "match_count"):
+        assert np.array_equal(got[k], ref[k].cpu().numpy()), k
+    assert got["match_count"].sum() > 0
 
 
 _RCCL_ONE_RANK = r'''

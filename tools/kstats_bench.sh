@@ -2,7 +2,7 @@
 # per-kernel averages of one bench run (no ViT / CPU legs):  bash tools/kstats_bench.sh [extra bench args]
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/ksb && rocprofv3 --kernel-trace --stats -d /tmp/ksb -o x --output-format csv -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-vit "$@" > /dev/null 2>&1
+rm -rf /tmp/ksb && rocprofv3 --kernel-trace --stats -d /tmp/ksb -o x --output-format csv -- python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-vit "$@" > /dev/null 2>&1
 python - <<'PY'
 import csv, glob
 f = glob.glob('/tmp/ksb/**/*kernel_stats.csv', recursive=True)[0]

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 RX=${1:-sim_argmax}; TAG=${2:-pmc_one}
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --steps 2 --warmup 1 --no-vit --no-bf16 --no-cpu-baseline"
+ARGS="$ROOT/bench.py --full --steps 2 --warmup 1 --no-vit --no-bf16 --no-cpu-baseline"
 rm -rf /tmp/po1 /tmp/po2 /tmp/po3
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA SQ_INSTS_VALU \
   --kernel-trace --kernel-include-regex "$RX" -d /tmp/po1 -o x --output-format csv -- python $ARGS > /dev/null 2>&1

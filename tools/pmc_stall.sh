@@ -4,7 +4,7 @@ set -e
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 RX='gather_refine|selector_saliency|sim_argmax|refine_bf16|selector_bf16'
-ARGS="$ROOT/bench.py --steps 2 --warmup 1 --no-vit --no-cpu-baseline"
+ARGS="$ROOT/bench.py --full --steps 2 --warmup 1 --no-vit --no-cpu-baseline"
 rm -rf /tmp/pst1 /tmp/pst2
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM \
   --kernel-trace --kernel-include-regex "$RX" -d /tmp/pst1 -o x --output-format csv -- python $ARGS > /dev/null

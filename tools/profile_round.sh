@@ -13,7 +13,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 RX='selector_saliency|gather_refine|sim_argmax|bn_tokens|preprocess|select_keypoints|intensity_kernel|match_finalize|refine_bf16|selector_bf16|keys_decode'
 VRX='gemm_rt_kernel|mlp_fused_kernel|attn_kernel|im2patch|prefix_rows|ln_rows'
-BENCH="$ROOT/bench.py --steps 5 --warmup 2"
+BENCH="$ROOT/bench.py --full --steps 5 --warmup 2"
 VIT="$ROOT/tools/bench_vit.py 448 82"
 
 if [[ $PART == *a* ]]; then
@@ -84,12 +84,12 @@ python $ROOT/tools/upload_timeline.py 307 > $OUT/${TAG}_upload_timeline.txt 2>/d
 echo "[9] round-4 additions: the drop-in backbone at the reference's batch sizes, the per-frame stepper, the 4-rank rehearsal"
 python $ROOT/tools/backbone_batch_sweep.py 2>/dev/null | grep -v amdgpu > $OUT/${TAG}_backbone_batch_sweep.txt
 python $ROOT/tools/online_probe.py 2>/dev/null | grep -v amdgpu > $OUT/${TAG}_online_stepper.txt
-python $ROOT/bench.py --gpus 4 --rehearse-shared-gpu --steps 2 --warmup 1 > $OUT/${TAG}_rehearsal_4ranks.json 2>/dev/null
+python $ROOT/bench.py --full --gpus 4 --rehearse-shared-gpu --steps 2 --warmup 1 > $OUT/${TAG}_rehearsal_4ranks.json 2>/dev/null
 # (clock probes need probe builds: tools/build_variant.sh probe csrc/vit_f32.hip vit_f32.hip -DSSLAM_CLOCK_PROBE -> tools/vit_f32_probe.py;
 #  tools/build_variant.sh rtprobe csrc/vit.hip vit.hip -DSSLAM_RT_PROBE -> SSLAM_BENCH_SO=... tools/rt_probe.py 82)
 # every BASELINE configuration at its full per-GPU size (configs[2]: 2 965 frames; configs[3] / [4]: one GPU's share of the 4- / 8-GPU job)
 for wl in fr1_xyz_50 fr2_desk_1024kp synthetic_2048kp fr3_long_office_4gpu synthetic_2048kp_8gpu; do
-  python $ROOT/bench.py --steps 5 --warmup 2 --workload $wl --no-cpu-baseline --no-vit --no-directory --sustain 5 > $OUT/${TAG}_bench_$wl.json 2>/dev/null
+  python $ROOT/bench.py --full --steps 5 --warmup 2 --workload $wl --no-cpu-baseline --no-vit --no-directory --sustain 5 > $OUT/${TAG}_bench_$wl.json 2>/dev/null
 done
 fi
 echo done
