@@ -889,8 +889,10 @@ __global__ __launch_bounds__(64) void prefix_rows_kernel(const float *__restrict
 //   free), and the rescaling of O is lane-local too - no LDS broadcast of row statistics.
 // Softmax runs with a FIXED per-query shift m0 (the first tile's maximum, folded into the MFMA chain as its initial
 // accumulator: no subtraction per score): exp2(s - m0) cannot overflow unless a later score exceeds m0 by > 64 - a guard
-// (one max per two scores, lane-local) then rescales O, the row sum and the shift; that branch is taken ~never for
-// LayerNorm-ed ViT activations, but it keeps the kernel exact for any input.  VALU work per score: exp2, add, half a
+// (one max per two scores, lane-local; taken for the whole wave) then raises the shift of every query of the wave to its
+// tile maximum where that is higher, scaling its O and row sum down - never up, so any range of scores stays finite (a
+// shift lowered to a tile maximum 128 below it scaled by 2^128 = inf: NaN tokens, tests/test_gpu_vit_reference.py).  The
+// branch is taken ~never for LayerNorm-ed ViT activations.  VALU work per score: exp2, add, half a
 // convert, half a max - the kernel is VALU-bound at head dim 64 (one exp2 per 256 FLOP), so this count IS its speed.
 constexpr int AQ = 128, AKT = 64, KLD = 72;
 
@@ -997,14 +999,23 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const bf16 *__restrict__ q
 #pragma unroll
         for (int e = 0; e < 16; e++) asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mt) : "v"(st[0][e]), "v"(st[1][e]));
         if (__any(mt > 64.0f) || kt == 0) {
-            // (re)centre this query: lanes r and r + 32 hold the two key halves of the same query and must agree
-            const float d = fmaxf(mt, __shfl_xor(mt, 32));
-            const float a = __builtin_amdgcn_exp2f(-d);
-            l *= a;
+            // (re)centre this query: lanes r and r + 32 hold the two key halves of the same query and must agree.  At kt == 0
+            // the shift is set and nothing is scaled (l and O are still 0; the first tile's maximum may lie below -128, where
+            // 2^-d is inf and 0 * inf NaN).  Later the shift only ever rises: a query of the wave whose tile maximum is below its
+            // shift keeps it (d = 0, scale 1) - scaling its O and l UP by 2^-d would overflow them to inf below -128.
+            const float dq = fmaxf(mt, __shfl_xor(mt, 32));
+            const float d = kt == 0 ? dq : fmaxf(dq, 0.0f);
+            if (kt != 0) {
+                const float a = __builtin_amdgcn_exp2f(-d);
+                l *= a;
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    oacc[0][e] *= a;
+                    oacc[1][e] *= a;
+                }
+            }
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                oacc[0][e] *= a;
-                oacc[1][e] *= a;
                 negm[e] -= d;
                 st[0][e] -= d;
                 st[1][e] -= d;
