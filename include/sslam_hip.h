@@ -270,7 +270,9 @@ int sslam_vit_forward_patches(const void *patches_bf16, int n_frames, int size, 
  * as in sslam_vit_weights_t - DINOv3's construction, the 32 angles of a cell tiled twice: columns d and d + 32 of a row are equal
  * and this entry reads columns 0..31 only (a caller with other tables must not use it; sslam_amd/vit_hip.py checks).
  * Workspace: sslam_vit_f32_workspace_bytes(n_frames, size) bytes (x, LayerNorm output, q / k / v, MLP hidden: 13.7 KB per token;
- * for n_frames <= SSLAM_ATTN_KEY_SPLIT_MAX_FRAMES also the key-split attention's partials, 7.9 KB per token). */
+ * for n_frames <= SSLAM_ATTN_KEY_SPLIT_MAX_FRAMES also the key-split attention's partials, 7.9 KB per token; for 9 - 12 frames
+ * the larger need of 8 key-split frames).  It never decreases with n_frames: a buffer sized for a batch serves every smaller
+ * launch in either form.  sslam_vit_forward_f32_form checks the requested form's own need (ONE_PASS: no partials). */
 typedef struct {
     const float *ln1_g, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ls1, *ln2_g, *ln2_b, *wup, *bup, *wdown, *bdown, *ls2;
 } sslam_vit_layer_f32_t;

@@ -1013,13 +1013,25 @@ extern "C" int sslam_vit_f32_pack_linear_host(const float *w, int n_out, int k_i
     return SSLAM_OK;
 }
 
+namespace {
+// the bytes one launch of n_frames reads and writes in the given attention form (the layout of sslam_vit_forward_f32_form):
+// x, y, qkv, hidden, and for the key split its partials, ASPLIT x (O, (m, l)) per (frame, head, query)
+long long ws_need(int n_frames, int size, bool split) {
+    const long long G = size / FPATCH, T = G * G + FPREFIX, rows = (long long)n_frames * T;
+    long long b = (long long)(ws_align(rows * FD * 4) * 2 + ws_align(rows * FD * 4 * 3) + ws_align(rows * FMLP * 4));
+    if (split) b += (long long)(ws_align(ASPLIT * rows * FD * 4) + ws_align(ASPLIT * rows * FH * 2 * 4));
+    return b;
+}
+}  // namespace
+
+// Non-decreasing in n_frames, so that a buffer sized for a batch serves every smaller launch in either form: with its partials
+// (7.9 KB per token) a key-split launch of 8 frames needs more than a one-pass launch of 9-12 (13.8 KB per token), so those
+// sizes return the 8-frame need (at most 1.4x their own); from 13 frames on the one-pass need is the larger.
 extern "C" long long sslam_vit_f32_workspace_bytes(int n_frames, int size) {
     if (n_frames <= 0 || size <= 0 || size % FPATCH) return SSLAM_E_INVALID;
-    const long long G = size / FPATCH, T = G * G + FPREFIX, rows = (long long)n_frames * T;
-    long long b = (long long)(ws_align(rows * FD * 4) * 2 + ws_align(rows * FD * 4 * 3) + ws_align(rows * FMLP * 4));   // x, y, qkv, hidden
-    if (n_frames <= ASPLIT_MAX_FRAMES)           // the key-split attention's partials: ASPLIT x (O, (m, l)) per (frame, head, query)
-        b += (long long)(ws_align(ASPLIT * rows * FD * 4) + ws_align(ASPLIT * rows * FH * 2 * 4));
-    return b;
+    if (n_frames <= ASPLIT_MAX_FRAMES) return ws_need(n_frames, size, true);
+    const long long own = ws_need(n_frames, size, false), few = ws_need(ASPLIT_MAX_FRAMES, size, true);
+    return own > few ? own : few;
 }
 
 extern "C" int sslam_vit_forward_f32(const float *images_chw, int n_frames, int size, const sslam_vit_weights_f32_t *w, void *workspace,
@@ -1035,7 +1047,7 @@ extern "C" int sslam_vit_forward_f32_form(const float *images_chw, int n_frames,
     if (!images_chw || !w || !workspace || !tokens_out || n_frames <= 0 || size <= 0 || size % FPATCH) return SSLAM_E_INVALID;
     if (attention_form != SSLAM_ATTN_ONE_PASS && attention_form != SSLAM_ATTN_KEY_SPLIT) return SSLAM_E_INVALID;
     if (attention_form == SSLAM_ATTN_KEY_SPLIT && n_frames > ASPLIT_MAX_FRAMES) return SSLAM_E_INVALID;
-    if (workspace_bytes < sslam_vit_f32_workspace_bytes(n_frames, size)) return SSLAM_E_INVALID;
+    if (workspace_bytes < ws_need(n_frames, size, attention_form == SSLAM_ATTN_KEY_SPLIT)) return SSLAM_E_INVALID;   // this form's own need
     if (((uintptr_t)images_chw | (uintptr_t)workspace | (uintptr_t)tokens_out) & 15) return SSLAM_E_INVALID;
     const int G = size / FPATCH, cells = G * G, T = cells + FPREFIX;
     const long long rows = (long long)n_frames * T, prow = (long long)n_frames * cells;

@@ -17,8 +17,10 @@ kernels (a frame is 7 row tiles: most launches occupy a few dozen of the 256 CUs
 the host is already ahead of the device.  It is kept as an option because it takes the host out of the loop (0 library calls per
 frame), which matters to a caller that has other work for its CPU thread.
 
-Results are the kernels' results: bit-identical to the same frames going through `SequencePipeline.run` as one batch
-(tests/test_gpu_harness.py::test_online_stepper_*).
+Results are the kernels' results: bit-identical to the same frames going through `SequencePipeline.run` as one batch of up to 8
+frames (tests/test_gpu_harness.py::test_online_stepper_*).  A step is a batch of ONE frame, so the ViT inside runs its few-frame
+form (fp32: key-split attention; bf16: the small form) whatever sequence it steps through; a longer batch's tokens (fp32 one-pass,
+bf16 fused MLP) agree with a step's within the float64 bars, not bit for bit (test_frame_stepper_runs_the_few_frame_form).
 """
 from __future__ import annotations
 
@@ -32,7 +34,9 @@ class FrameStepper:
     def __init__(self, pipe: SequencePipeline, height: int, width: int, use_graph: bool = True, tokens_in: bool = False):
         """pipe: a SequencePipeline (with vit= unless tokens_in).  height / width: the frames' size (uint8 RGB).
         tokens_in: the caller brings the ViT's tokens with every frame (the third-party ViT stays outside).
-        use_graph=False: the same step as ordinary launches (the A/B for the graph, and the fallback while debugging)."""
+        use_graph=False: the same step as ordinary launches (the A/B for the graph, and the fallback while debugging).
+        With the ViT inside, every step runs its few-frame form (a batch of one): the tokens of SequencePipeline.run over up to
+        8 frames bit for bit, those of a longer batch within the float64 bars (module docstring)."""
         cfg = pipe.cfg
         if cfg.num_keypoints > cfg.grid ** 2:
             raise ValueError("num_keypoints > grid cells: that case reads a status word back on the host (SURVEY H6) and cannot be captured")

@@ -254,7 +254,12 @@ class SequencePipeline:
         """A0 + A1: (N, H, W, 3) uint8 -> (N, 5 + G*G, 384) fp32 tokens via the HIP ViT, `vit_chunk` frames at a time.
         Default chunk: HipViT.chunk_frames - whole rounds of the ViT's row-tile workgroups (82 frames at 448 x 448), alternating between two streams.
         batch_frames: the length of the sequence these frames are a piece of, when the caller feeds it in pieces (the streaming
-        harness): the fp32 ViT picks its attention form by the batch, so that a frame's tokens do not depend on the cuts."""
+        harness): the fp32 ViT picks its attention form by the batch, so that a frame's tokens do not depend on the cuts.
+        Routes: the bf16 ViT takes A0 as bf16 patch rows where the tiled resampler covers the frames (<= 7 horizontal taps, a
+        dword-aligned batch base), else the fp32 image, as the fp32 ViT always does - the same tokens either way.
+        Cuts: fp32 - vit_chunk and the pieces change no bit (few-frame form up to 8 frames of the BATCH, one-pass above);
+        bf16 - the form follows each LAUNCH GROUP (HipViT.forward_features), so the frames of a short last group may differ
+        from the same frames in a full group, within the bf16 bars against float64."""
         if self.vit_hip is None:
             raise lib.SslamHipError("this pipeline was built without a ViT: pass tokens, or construct it with vit=")
         if vit_chunk is None:
@@ -278,8 +283,10 @@ class SequencePipeline:
             if patches is not None:
                 self.vit_hip.forward_features(None, out=out[a:b], chunk=vit_chunk, patches=patches, size=size)
             else:
+                # only the fp32 ViT picks its form by the batch; the bf16 one picks it per launch group (HipViT.forward_features)
+                kw = dict(batch_frames=max(n, batch_frames or 0)) if self.vit_precision == "fp32" else {}
                 self.vit_hip.forward_features(self.preprocess(images_u8[a:b], reuse=self.vit_hip.n_streams < 2), out=out[a:b], chunk=vit_chunk,
-                                              batch_frames=max(n, batch_frames or 0))
+                                              **kw)
         return out
 
     def preprocess_patches(self, images_u8: torch.Tensor):

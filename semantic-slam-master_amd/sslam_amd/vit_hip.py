@@ -67,7 +67,12 @@ class HipViT:
                          patches: torch.Tensor | None = None, size: int | None = None) -> torch.Tensor:
         """(B, 3, S, S) fp32 cuda -> (B, 5 + (S/16)^2, 384) fp32 tokens (final-LayerNormed), `chunk` frames per launch group.
         patches (with size = S): the bf16 patch rows of lib.preprocess_u8_patches (B, (S/16)^2, 768) instead of the image -
-        no fp32 image, no im2patch pass, the same tokens bit for bit."""
+        no fp32 image, no im2patch pass, the same tokens bit for bit.
+        The launch form follows each LAUNCH GROUP, not the batch (HipViTF32 follows the batch): up to 8 192 token rows (10 frames
+        at 448 x 448) the small form with the two-launch MLP, above it the throughput form with the fused MLP, which sums the down
+        projection in another order.  So the frames of a short last group may differ in the last bits from the same frames in a
+        full group - within the bf16 bars against float64 (tests/test_gpu_harness.py::test_bf16_vit_form_follows_the_launch_group);
+        picking the form by the batch would need a library entry that names it."""
         if patches is not None:
             n, s = patches.shape[0], int(size)
             assert patches.is_cuda and patches.dtype == torch.bfloat16 and patches.shape[1:] == ((s // 16) ** 2, 768)
@@ -198,6 +203,7 @@ class HipViTF32:
             self._rope[g] = (cos, sin)
         self.w.rope_cos, self.w.rope_sin = self._rope[g][0].data_ptr(), self._rope[g][1].data_ptr()
         step = chunk or self.chunk_frames(s)
+        # the first group's size serves every later, shorter one in either form (the library's size never decreases with n)
         need = lib.vit_f32_workspace_bytes(min(n, step), s)
         x = images.detach().float().contiguous()
         if out is None:

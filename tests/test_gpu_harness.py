@@ -596,3 +596,205 @@ def test_online_stepper_graph_survives_the_pipeline_replacing_its_buffers(T, mod
         c = int(o["match_count"])
         assert c == int(want["match_count"][i - 1]) and T.equal(o["matches"][:c], want["matches"][i - 1][:c]), (mode, i)
     assert all(int(j[0]) == 0xA5 and int(j[-1]) == 0xA5 for j in junk), "the replay wrote into memory it no longer owns"
+
+
+# ---------------------------------------------------------------------------------------------------------------- images in
+# The code that brings frames into the HIP ViTs - SequencePipeline.tokens_from_images, the ViTs' forward_features, run_frames /
+# run_directory and FrameStepper - on every route A0 takes into A1 (the rows of tests/test_vit.py IMAGES_IN_ROWS: the bf16 ViT
+# takes bf16 patch rows at <= 7 horizontal taps and a dword-aligned frame-batch base, the fp32 image otherwise, which the fp32 ViT
+# always takes) and at the batch cuts.  References the suite already trusts: ora.resize_rgb (bit for bit), the float64 forward
+# of oracle/ora_vit.py within the BARS of test_gpu_vit_reference.py (printed with -s), the ora.* stages after the tokens (bit
+# for bit).  The rule for cuts (tokens_from_images, HipViT, FrameStepper): the fp32 ViT's form follows the
+# BATCH - no cut changes a bit, a FrameStepper step is a batch of one; the bf16 ViT's follows each LAUNCH GROUP.
+@pytest.fixture(scope="module")
+def rvit(T):
+    import foreign_vit
+    return foreign_vit.random_vit(1).cuda()
+
+
+def _vit_pipe(vit, size, K, prec):
+    from sslam_amd.pipeline import ExtractorConfig, SequencePipeline
+    return SequencePipeline(ExtractorConfig(input_size=size, num_keypoints=K), synth.selector_state(0), synth.refiner_state(0),
+                            device="cuda", vit=vit, vit_precision=prec)
+
+
+def _row_frames(T, name, n):
+    """n frames of an images-in row, on the device and on the host; the _view row: a view from frame 1 of the sequence."""
+    from test_vit import IMAGES_IN_ROWS
+    h, w = IMAGES_IN_ROWS[name][:2]
+    if name.endswith("_view"):
+        imgs = synth.image_sequence(n + 1, h, w)
+        x = T.from_numpy(imgs).cuda()[1:]
+        assert x.data_ptr() % 4 != 0              # as test_preprocess_and_intensity: this base cannot take the patch route
+        return x, imgs[1:]
+    imgs = synth.image_sequence(n, h, w)
+    return T.from_numpy(imgs).cuda(), imgs
+
+
+def _chw(T, imgs, size):
+    return T.from_numpy(np.stack([ora.resize_rgb(im, size)[1] for im in imgs]))
+
+
+def _assert_run_is_the_oracle_chain(out, tok, imgs, size, K):
+    """run()'s outputs against the ora.* chain on the same tokens: idx, descriptors, intensity, matches (i, i + 1), bit for bit."""
+    n, g = tok.shape[0], size // 16
+    feat = ora.bn_tokens(tok)[0].reshape(n, g, g, 384)
+    kp, sc, idx, _ = ora.select_keypoints(ora.selector_saliency(feat, synth.selector_state(0)), K)
+    desc = ora.refine(ora.gather(feat, kp), synth.refiner_state(0))
+    inten = np.stack([ora.intensity(imgs[i], size, ora.patch_to_pixel(kp[i])) for i in range(n)])
+    assert int(out["status"].sum()) == 0
+    assert np.array_equal(out["idx"].cpu().numpy(), idx)
+    assert np.array_equal(out["descriptors"].cpu().numpy().view(np.uint32), desc.view(np.uint32))
+    assert np.array_equal(out["intensity"].cpu().numpy().view(np.uint32), inten.view(np.uint32))
+    for p in range(n - 1):
+        mt, q = ora.match_with_quality(desc[p], desc[p + 1], sc[p], sc[p + 1], CLI["saliency_weight"], CLI["min_saliency"],
+                                       CLI["min_descriptor_sim"], inten[p], inten[p + 1], CLI["min_intensity"])
+        c = int(out["match_count"][p])
+        assert c == len(mt) and np.array_equal(out["matches"][p, :c].cpu().numpy(), mt), p
+        assert np.array_equal(out["quality"][p, :c].cpu().numpy().view(np.uint32), q.view(np.uint32)), p
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+@pytest.mark.parametrize("name", ["vga448", "vga224", "w704_224", "hd448", "tiny64", "odd224", "odd224_view"])
+def test_images_to_tokens_on_every_route(T, rvit, name, prec):
+    """A0 Pillow-exact; tokens_from_images == forward_features of A0's fp32 image bit for bit whichever route it took, within the
+    float64 bars; run() bit-exact against the oracle chain on those tokens.  The patch route launches one kernel fewer (A0 writes
+    the patch rows: no im2patch), the fallback exactly the launches it stands for."""
+    from oracle import ora_vit
+    from sslam_amd import lib
+    from test_gpu_vit_reference import _check
+    from test_vit import IMAGES_IN_ROWS
+    h, w, size, K, route, _ = IMAGES_IN_ROWS[name]
+    pipe = _vit_pipe(rvit, size, K, prec)
+    x, imgs = _row_frames(T, name, 2)
+    chw = _chw(T, imgs, size)
+    assert np.array_equal(pipe.preprocess(x).cpu().numpy().view(np.uint32), chw.numpy().view(np.uint32))
+    assert ("patch" if pipe.preprocess_patches(x) is not None else "image") == route
+    with T.no_grad():
+        n0 = lib.launch_count()
+        want = pipe.vit_hip.forward_features(pipe.preprocess(x)).clone()
+        n1 = lib.launch_count()
+        tok = pipe.tokens_from_images(x)
+        n2 = lib.launch_count()
+    assert T.equal(tok, want)
+    assert n2 - n1 == (n1 - n0) - (1 if (prec == "bf16" and route == "patch") else 0), (n2 - n1, n1 - n0)
+    ref = ora_vit.forward(rvit, chw, "bf16" if prec == "bf16" else "exact")
+    _check(f"{prec} {h}x{w} -> {size} ({route if prec == 'bf16' else 'image'})", tok, ref, "bf16" if prec == "bf16" else "f32")
+    _assert_run_is_the_oracle_chain(pipe.run(x), tok.cpu().numpy(), imgs, size, K)
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+def test_ratio_beyond_the_resampler_is_refused(T, rvit, prec):
+    """480 -> 64: the input rows one output tile needs exceed the resampler's buffer (MAXR) - SslamHipError from every entry, and
+    the ViT never runs (the caller's output stays untouched)."""
+    from sslam_amd import lib
+    from test_vit import IMAGES_IN_MAXR_ROW
+    h, w, size, K = IMAGES_IN_MAXR_ROW
+    pipe = _vit_pipe(rvit, size, K, prec)
+    x = T.from_numpy(synth.image_sequence(2, h, w)).cuda()
+    out = T.full((2, 5 + (size // 16) ** 2, 384), float("nan"), device="cuda")
+    for call in (lambda: pipe.preprocess(x), lambda: pipe.tokens_from_images(x, out=out), lambda: pipe.run(x)):
+        with pytest.raises(lib.SslamHipError, match="unsupported"):
+            call()
+    assert bool(T.isnan(out).all())
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+@pytest.mark.parametrize("name,n,chunk", [("hd448", 3, 2), ("odd224", 7, 3)])
+def test_stepper_and_streaming_harness_off_the_patch_route(T, rvit, name, n, chunk, prec):
+    """FrameStepper (graph off and on) and run_frames with the ViT inside equal a batched run() of <= 8 frames bit for bit: HD
+    frames take the fp32 image throughout, the odd frames' pieces start at unaligned bytes (chunk 3: frame 3 at 1 074 843)."""
+    from sslam_amd.harness import run_frames
+    from sslam_amd.online import FrameStepper
+    from test_vit import IMAGES_IN_ROWS
+    h, w, size, K, _, _ = IMAGES_IN_ROWS[name]
+    pipe = _vit_pipe(rvit, size, K, prec)
+    x, imgs = _row_frames(T, name, n)
+    want = {k: v.clone() for k, v in pipe.run(x).items()}
+    for use_graph in (False, True):
+        st = FrameStepper(pipe, h, w, use_graph=use_graph)
+        for i in range(n):
+            o = st.step(x[i])
+            for k in ("idx", "descriptors", "intensity", "scores"):
+                assert T.equal(o[k], want[k][i]), (use_graph, k, i)
+            if i:
+                c = int(o["match_count"])
+                assert c == int(want["match_count"][i - 1]) and T.equal(o["matches"][:c], want["matches"][i - 1][:c]), (use_graph, i)
+    assert (chunk * h * w * 3) % 4 != 0 or name == "hd448"
+    got = run_frames(pipe, n, h, w, spacings=(1,), pinned_source=T.from_numpy(imgs).pin_memory(), chunk=chunk)
+    _assert_same(T, got["frames"], want, ("idx", "descriptors", "intensity"))
+    _assert_same(T, got[1], want, ("matches", "quality", "match_count"))
+
+
+def test_fp32_vit_pipeline_does_not_depend_on_the_cuts(T, rvit, tmp_path):
+    """20 frames at G = 4 (the one-pass form): every vit_chunk, the frames fed in pieces with batch_frames, run_frames with a last
+    piece of 8 frames and run_directory with a 16-frame first chunk give the same tokens - hence run()'s results - bit for bit."""
+    from sslam_amd.harness import run_directory, run_frames
+    from test_vit import IMAGES_IN_ROWS
+    n = 20
+    h, w, size, K, _, _ = IMAGES_IN_ROWS["tiny64"]
+    pipe = _vit_pipe(rvit, size, K, "fp32")
+    x, imgs = _row_frames(T, "tiny64", n)
+    with T.no_grad():
+        cuts = {c: pipe.tokens_from_images(x, vit_chunk=c).clone() for c in (12, 9, 5, 1, None)}
+        pieces = T.empty_like(cuts[None])
+        for a, b in ((0, 7), (7, 15), (15, 20)):
+            pipe.tokens_from_images(x[a:b], out=pieces[a:b], batch_frames=n)
+    for c, t in cuts.items():
+        assert T.equal(t, cuts[None]), c
+    assert T.equal(pieces, cuts[None])
+    want = {k: v.clone() for k, v in pipe.run(x).items()}
+    _assert_run_is_the_oracle_chain(want, cuts[None].cpu().numpy(), imgs, size, K)
+    got = run_frames(pipe, n, h, w, spacings=(1,), pinned_source=T.from_numpy(imgs).pin_memory(), chunk=12)     # pieces 12 + 8
+    _assert_same(T, got["frames"], want, ("idx", "descriptors", "intensity"))
+    _assert_same(T, got[1], want, ("matches", "quality", "match_count"))
+    synth.write_tum_rgb_sequence(str(tmp_path / "seq"), imgs)
+    got = run_directory(str(tmp_path / "seq"), "", (1,), pipe=pipe, chunk=18, decode_workers=4)               # pieces 16 + 4
+    _assert_same(T, got["frames"], want, ("idx", "descriptors", "intensity"))
+    _assert_same(T, got[1], want, ("matches", "quality", "match_count"))
+
+
+def test_frame_stepper_runs_the_few_frame_form(T, rvit):
+    """Stated exception 1: a FrameStepper step is a batch of one, so the fp32 ViT runs its few-frame form whatever sequence it
+    steps through - one frame alone bit for bit, within the fp32 bars of a one-pass batch's tokens and of float64."""
+    from oracle import ora_vit
+    from sslam_amd.online import FrameStepper
+    from test_gpu_vit_reference import _check
+    from test_vit import IMAGES_IN_ROWS
+    n = 10
+    h, w, size, K, _, _ = IMAGES_IN_ROWS["tiny64"]
+    pipe = _vit_pipe(rvit, size, K, "fp32")
+    x, imgs = _row_frames(T, "tiny64", n)
+    with T.no_grad():
+        batch = pipe.tokens_from_images(x).clone()                     # 10 frames: one-pass
+    ref = ora_vit.forward(rvit, _chw(T, imgs[[0, n - 1]], size), "exact")
+    st = FrameStepper(pipe, h, w, use_graph=False)
+    for j, i in enumerate((0, n - 1)):
+        st.step(x[i])
+        tok = st.tokens.clone()
+        with T.no_grad():
+            assert T.equal(tok, pipe.tokens_from_images(x[i:i + 1]))
+        _check(f"fp32 stepper frame {i} vs the one-pass batch", tok, batch[i:i + 1].double().cpu(), "f32")
+        _check(f"fp32 stepper frame {i} vs float64", tok, ref[j:j + 1], "f32")
+
+
+def test_bf16_vit_form_follows_the_launch_group(T, rvit):
+    """Stated exception 2: 24 frames at 448 in launch groups of 20 - the first group runs the throughput form (20 x 789 token
+    rows > 8 192: fused MLP), the last 4 frames the small form (two-launch MLP).  The first group equals one 24-frame group bit
+    for bit; the short group's frames are within the bf16 bars of the float64 bf16 mode (the fused MLP sums the down projection
+    in another order, so they need not equal the 24-frame group's)."""
+    from oracle import ora_vit
+    from test_gpu_vit_reference import _check
+    from test_vit import IMAGES_IN_ROWS
+    h, w, size, K, _, _ = IMAGES_IN_ROWS["vga448"]
+    pipe = _vit_pipe(rvit, size, K, "bf16")
+    x, imgs = _row_frames(T, "vga448", 24)
+    with T.no_grad():
+        whole = pipe.tokens_from_images(x, vit_chunk=24).clone()
+        cut = pipe.tokens_from_images(x, vit_chunk=20).clone()
+    assert T.equal(cut[:20], whole[:20])
+    print(f"\n  frames 20..23: 4-frame group == 24-frame group: {T.equal(cut[20:], whole[20:])}")
+    ref = ora_vit.forward(rvit, _chw(T, imgs[[0, 23]], size), "bf16")
+    _check("bf16 448 frame 0 in a 20-frame group (throughput, fused MLP)", cut[:1], ref[:1], "bf16")
+    _check("bf16 448 frame 23 in a 4-frame group (small form)", cut[23:], ref[1:], "bf16")
+    _check("bf16 448 frame 23 in a 24-frame group (throughput, fused MLP)", whole[23:], ref[1:], "bf16")

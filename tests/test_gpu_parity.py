@@ -225,7 +225,8 @@ def test_descriptors_match_reference_golden(T, hip):
 
 
 # ---------------------------------------------------------------------------------------------------- A0 / A9
-@pytest.mark.parametrize("h,w,size", [(480, 640, 448), (480, 640, 640), (960, 1280, 960), (231, 517, 112)])
+@pytest.mark.parametrize("h,w,size", [(480, 640, 448), (480, 640, 640), (960, 1280, 960), (231, 517, 112),
+                                      (480, 640, 224), (480, 704, 224), (1080, 1920, 448), (160, 360, 64), (231, 517, 224)])
 def test_preprocess_and_intensity(T, hip, h, w, size):
     imgs = np.stack([synth.image(40 + i, h, w) for i in range(2)])
     th = tuple(dev(T, a) if isinstance(a, np.ndarray) else a for a in hip.resample_table(w, size, False))

@@ -379,3 +379,54 @@ def test_layernorm_eps_with_small_variance_rows(vit):
         got_f = _f32(one).forward_features(x)
     _check("fp32 small-variance LN", got_f, want_e, "f32")
     _check("bf16 small-variance LN", got_b, want_b, "bf16_ln")
+
+
+# ------------------------------------------------------------------------------------------------ fp32 workspace and launch groups
+@pytest.fixture(scope="module")
+def x64():
+    return _images(20, 64, 64)
+
+
+@pytest.fixture(scope="module")
+def ref64(vit, x64):
+    return ora_vit.forward(vit, x64, "exact")
+
+
+def test_fp32_workspace_for_a_batch_serves_every_smaller_launch(vit, x64):
+    """One buffer of sslam_vit_f32_workspace_bytes(12) at 64 x 64 runs every n <= 12 in each legal form (one-pass always, key
+    split up to 8 frames), each the tokens of the form's larger launch bit for bit; where that size is the form's own need (key
+    split <= 8, one-pass >= 13 frames), one byte less is SSLAM_E_INVALID - checked before anything is launched."""
+    from sslam_amd import lib
+    hv = _f32(vit)
+    N, S = 12, 64
+    with torch.no_grad():
+        one_pass = hv.forward_features(x64[:N]).clone()          # also points hv.w at the RoPE tables of G = 4
+        split = hv.forward_features(x64[:8]).clone()
+    ws = torch.empty(lib.vit_f32_workspace_bytes(N, S), dtype=torch.uint8, device="cuda")
+    for n in range(1, N + 1):
+        for form, want in ((lib.ATTN_ONE_PASS, one_pass), (lib.ATTN_KEY_SPLIT, split)):
+            if form == lib.ATTN_KEY_SPLIT and n > lib.ATTN_KEY_SPLIT_MAX_FRAMES:
+                continue
+            got = lib.vit_forward_f32(x64[:n].contiguous(), hv.w, ws, attention_form=form)
+            assert torch.equal(got, want[:n]), (n, form)
+    for n, form in ((1, lib.ATTN_KEY_SPLIT), (5, lib.ATTN_KEY_SPLIT), (8, lib.ATTN_KEY_SPLIT), (13, lib.ATTN_ONE_PASS),
+                    (20, lib.ATTN_ONE_PASS)):
+        need = lib.vit_f32_workspace_bytes(n, S)
+        buf = torch.empty(need, dtype=torch.uint8, device="cuda")
+        with pytest.raises(ValueError, match="invalid"):
+            lib.vit_forward_f32(x64[:n].contiguous(), hv.w, buf[:need - 1], attention_form=form)
+        lib.vit_forward_f32(x64[:n].contiguous(), hv.w, buf, attention_form=form)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("n,chunk", [(17, 9), (15, 9), (18, 10), (19, 11), (20, 12), (9, 8), (12, 5), (20, 1)])
+def test_fp32_tokens_do_not_depend_on_the_launch_groups(vit, x64, ref64, n, chunk):
+    """HipViTF32.forward_features in launch groups of `chunk` frames, a short last group included, gives the tokens of one
+    group bit for bit (the form follows the batch: one-pass above 8 frames in every group), within the float64 bars.  A fresh
+    instance each time: its workspace is sized from the first group, which must serve the last."""
+    hv = _f32(vit)
+    with torch.no_grad():
+        cut = hv.forward_features(x64[:n], chunk=chunk).clone()
+        whole = hv.forward_features(x64[:n], chunk=n).clone()
+    assert torch.equal(cut, whole)
+    _check(f"fp32 64x{n} in groups of {chunk}", cut, ref64[:n], "f32")

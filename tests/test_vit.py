@@ -313,3 +313,43 @@ def test_vit_weight_packs_are_permutations():
     got = np.sort(lib.pack_vit_mlp(w_up, w_down, scale))
     want = np.sort(np.concatenate([bf16_bits(w_up).ravel(), bf16_bits(w_down * scale[:, None]).ravel()]))
     assert np.array_equal(got, want)
+
+
+# the geometries A0 brings into the ViTs (tests/test_gpu_harness.py, "images in"): (H, W, S, K, the bf16 ViT's route, taps)
+IMAGES_IN_ROWS = {
+    "vga448": (480, 640, 448, 500, "patch", 5),           # the shipped geometry
+    "vga224": (480, 640, 224, 100, "patch", 7),           # exactly 7 taps: the last ratio on the patch route
+    "w704_224": (480, 704, 224, 100, "image", 9),         # the first ratio on the fp32-image fallback
+    "hd448": (1080, 1920, 448, 500, "image", 11),
+    "tiny64": (160, 360, 64, 10, "image", 13),            # G = 4: cheap to reference
+    "odd224": (231, 517, 224, 100, "patch", 7),           # 358 281-byte frames, a batch from frame 0: aligned base
+    "odd224_view": (231, 517, 224, 100, "image", 7),      # the same frames as a view from frame 1: unaligned base
+}
+IMAGES_IN_MAXR_ROW = (480, 640, 64, 10)                   # 480 / 64: 17 vertical taps, 137 input rows per 16-row tile
+
+
+def test_images_in_rows_take_the_route_they_name():
+    """Host tables (no GPU): the horizontal tap counts the pipeline uploads (lib.resample_table) follow Pillow's bilinear rule,
+    2 ceil(W / S) + 1, and put each row on the route it names (the tiled patch-row kernel takes <= 7 taps), so a row cannot drift
+    onto the other route unnoticed; the odd row's frames are not a whole number of dwords."""
+    import math
+
+    from sslam_amd import lib
+    for name, (h, w, s, k, route, taps) in IMAGES_IN_ROWS.items():
+        kh = lib.resample_table(w, s, False)[2]
+        assert kh == taps == 2 * math.ceil(w / s) + 1, name
+        assert (route == "patch") == (kh <= 7 and not name.endswith("_view")), name
+        assert k <= (s // 16) ** 2, name
+    assert (231 * 517 * 3) % 4 != 0
+    h, w, s, _ = IMAGES_IN_MAXR_ROW
+    assert lib.resample_table(h, s, False)[2] == 17
+
+
+def test_vit_f32_workspace_is_monotone_in_the_frame_count():
+    """Host entry (no GPU): sslam_vit_f32_workspace_bytes never decreases with the frame count, so a buffer sized for a batch
+    serves every smaller launch in either attention form (the key-split partials put 8 frames above 9 - 12 one-pass ones)."""
+    from sslam_amd import lib
+    for s in (64, 448, 1280):
+        b = [lib.vit_f32_workspace_bytes(n, s) for n in range(1, 41)]
+        down = [n + 2 for n in range(len(b) - 1) if b[n + 1] < b[n]]
+        assert not down, (s, down)
