@@ -307,6 +307,39 @@ int sslam_vit_forward_f32(const float *images_chw, int n_frames, int size, const
 int sslam_vit_forward_f32_form(const float *images_chw, int n_frames, int size, const sslam_vit_weights_f32_t *weights_host_struct,
                                void *workspace, long long workspace_bytes, float *tokens_out, int attention_form, void *stream);
 
+/* The bf16 forward (sslam_vit_forward / sslam_vit_forward_patches above) with its launch form named by the caller.  The unnamed
+ * entries pick by the launch's token rows (SMALL up to 8 192 rows, THROUGHPUT above) and stay exactly as they are.  form:
+ *   SSLAM_VIT_FORM_THROUGHPUT (0) 128-row GEMM workgroups over two / three / four 192-column tiles, one-pass attention, the
+ *                                 fused MLP launch when wmlp is given - at any frame count;
+ *   SSLAM_VIT_FORM_SMALL      (1) one 192-column tile per GEMM workgroup, one-pass attention, two-launch MLP - at any frame
+ *                                 count (a caller that cuts a long batch can pin the form of a short last group);
+ *   SSLAM_VIT_FORM_FEW_FRAME  (2) n_frames <= SSLAM_VIT_FEW_FRAME_MAX_FRAMES.  SMALL's QKV and up launches, and
+ *       - key-split attention: the 64-key tiles of a frame are cut into R = ceil(tiles / ceil(tiles / 4)) contiguous ranges
+ *         of ceil(tiles / 4) tiles (R <= 4; a function of the token count only), one workgroup per (frame, head, 128 queries,
+ *         range), every range starting from the one-pass shift (the maximum over key tile 0), leaves un-normalised fp32
+ *         partials (O, shift m, row sum l) in the workspace;
+ *       - merge + output projection + residual in one launch: per 32 tokens of a frame, wave h merges head h in the order
+ *         0, 1, .. with M = max m_s and weights 2^(m_s - M), normalises and rounds to bf16 once - the merged tile is the MFMA
+ *         operand of the projection as it stands - and the six waves sum K = 384 head by head into 64 output columns each;
+ *       - the down projection (K = 1536) in 32-row workgroups whose four waves take one 384-wide K chunk each, the chunks
+ *         added in LDS as ((q0 + q1) + q2) + q3, q0 starting from the bias.
+ *     Every sum has one order fixed by the token count: a frame's tokens are the same bits alone, at any position among up
+ *     to 8 frames, and in any cut of such a batch into launches that all name this form.  Against SMALL it is another summation
+ *     order of the same arithmetic (and a range's P is rounded to bf16 relative to the range's own shift).
+ * sslam_vit_workspace_bytes_form: the named form's need - THROUGHPUT / SMALL = sslam_vit_workspace_bytes, FEW_FRAME = that plus
+ * the attention partials (8.5 KB per query and range); for one form it never decreases with n_frames, so a buffer sized for a
+ * batch serves every shorter launch of it.  SSLAM_E_INVALID, before anything is launched, for an unknown form, for FEW_FRAME
+ * with n_frames > SSLAM_VIT_FEW_FRAME_MAX_FRAMES and for a workspace smaller than the form's need. */
+#define SSLAM_VIT_FORM_THROUGHPUT 0
+#define SSLAM_VIT_FORM_SMALL 1
+#define SSLAM_VIT_FORM_FEW_FRAME 2
+#define SSLAM_VIT_FEW_FRAME_MAX_FRAMES 8
+long long sslam_vit_workspace_bytes_form(int n_frames, int size, int form);
+int sslam_vit_forward_form(const float *images_chw, int n_frames, int size, const sslam_vit_weights_t *weights_host_struct,
+                           void *workspace, long long workspace_bytes, float *tokens_out, int form, void *stream);
+int sslam_vit_forward_patches_form(const void *patches_bf16, int n_frames, int size, const sslam_vit_weights_t *weights_host_struct,
+                                   void *workspace, long long workspace_bytes, float *tokens_out, int form, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

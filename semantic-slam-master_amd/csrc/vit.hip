@@ -1073,6 +1073,442 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const bf16 *__restrict__ q
     }
 }
 
+// ------------------------------------------------------------------------- few-frame form (SSLAM_VIT_FORM_FEW_FRAME)
+// For launches of <= 8 frames.  One 448 x 448 frame is 7 row tiles of 128: attn_kernel then runs 42 workgroups that each walk
+// all 13 key tiles, o_proj 14, and the down projection 14 that each walk K = 1536 in 24 groups - a few long serial chains on a
+// chip of 256 CUs.  This form cuts those chains in fixed places; every sum keeps one order that depends on T alone, so a frame's tokens
+// are the same bits alone, anywhere in a batch of <= 8, and in any cut of that batch into launches that name the form.
+//
+// Key-split attention: the 64-key tiles of a frame are cut into af_ranges(T) contiguous ranges of af_per(T) tiles (the last may
+// be shorter; fewer tiles than AF_MAX_RANGES give fewer ranges - an empty range is never launched, so no -inf shift exists).
+// attn_ff_kernel is attn_kernel over one range: same S^T / P^T / O^T layouts, the shift set from key tile 0 (the one-pass
+// shift; ranges 1.. form that one S tile first) and only ever raised.  It leaves (O, shift m, row sum l) un-normalised in fp32
+// in the ORDER ITS LANES HOLD THEM (per wave: 8 x [64 lanes][4] of O, then [64 lanes](m, l of the lane's key half)): every store,
+// and every load of the merge, is one contiguous KB per wave.  attn_ff_oproj_kernel adds the ranges in the order 0, 1, 2, ...
+// with M = max m_s and weights 2^(m_s - M) <= 1 (a range far below the maximum underflows to 0, none can overflow), normalises
+// and rounds to bf16 once, where attn_kernel does, and multiplies by the output projection in the same launch.
+#ifndef SSLAM_FF_RANGES
+#define SSLAM_FF_RANGES 4
+#endif
+constexpr int AF_MAX_RANGES = SSLAM_FF_RANGES;
+constexpr int AF_WAVE_FLOATS = 8 * 256 + 128;              // partials of one wave: O as 8 x [lane][4], then [lane](m, l)
+__host__ __device__ inline int af_per(int T) { const int nt = (T + AKT - 1) / AKT; return (nt + AF_MAX_RANGES - 1) / AF_MAX_RANGES; }
+__host__ __device__ inline int af_ranges(int T) { const int nt = (T + AKT - 1) / AKT, per = af_per(T); return (nt + per - 1) / per; }
+
+__global__ __launch_bounds__(256, 3) void attn_ff_kernel(const bf16 *__restrict__ q, const bf16 *__restrict__ k, const bf16 *__restrict__ v,
+                                                         float *__restrict__ part, int T, int n_groups) {
+    __shared__ __attribute__((aligned(16))) char att_smem[2 * AKT * KLD * 2 + 2 * AKT * VHD * 2];     // K ring 18 KB + V ring 16 KB
+    bf16 *Ks = reinterpret_cast<bf16 *>(att_smem);
+    char *Vs = att_smem + 2 * AKT * KLD * 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    // XCD-aware order as in attn_kernel: every workgroup of one (frame, head) - query tiles x key ranges - on one XCD
+    const int qtiles = (T + AQ - 1) / AQ, ns = af_ranges(T), per = af_per(T), per_grp = qtiles * ns;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int grp = (slot / per_grp) * 8 + xcd;
+    if (grp >= n_groups) return;
+    const int rem = slot - (slot / per_grp) * per_grp, qt = rem / ns, rg = rem - qt * ns;
+    const int head = grp % VH;
+    const long long f = grp / VH;
+    const long long bh = (f * VH + head) * (long long)T;
+    const int i0 = qt * AQ + wave * 32;
+    const int qi = min(i0 + r, T - 1);
+    const int ntile = (T + AKT - 1) / AKT, kt0 = rg * per, kt1 = min(kt0 + per, ntile);
+
+    bf16x8 qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++) qf[ks] = *reinterpret_cast<const bf16x8 *>(q + (bh + qi) * VHD + ks * 16 + 8 * h);
+
+    const int srow = tid >> 3, c8 = tid & 7;
+    const int vswz = 4 * ((srow >> 1) & 1);
+    u32x4 rk[2], rv[2];
+#define A_LOAD(kt)                                                                                   \
+    {                                                                                                \
+        const long long off0 = (bh + min((kt) * AKT + srow, T - 1)) * VHD + c8 * 8;                  \
+        const long long off1 = (bh + min((kt) * AKT + 32 + srow, T - 1)) * VHD + c8 * 8;             \
+        rk[0] = *reinterpret_cast<const u32x4 *>(k + off0);                                          \
+        rk[1] = *reinterpret_cast<const u32x4 *>(k + off1);                                          \
+        rv[0] = *reinterpret_cast<const u32x4 *>(v + off0);                                          \
+        rv[1] = *reinterpret_cast<const u32x4 *>(v + off1);                                          \
+    }
+#define A_STORE(buf)                                                                                 \
+    {                                                                                                \
+        *reinterpret_cast<u32x4 *>(Ks + (buf) * AKT * KLD + srow * KLD + c8 * 8) = rk[0];            \
+        *reinterpret_cast<u32x4 *>(Ks + (buf) * AKT * KLD + (32 + srow) * KLD + c8 * 8) = rk[1];     \
+        *reinterpret_cast<u32x4 *>(Vs + (buf) * AKT * 128 + srow * 128 + ((c8 ^ vswz) << 4)) = rv[0];        \
+        *reinterpret_cast<u32x4 *>(Vs + (buf) * AKT * 128 + (32 + srow) * 128 + ((c8 ^ vswz) << 4)) = rv[1]; \
+    }
+    int voff[2];
+    {
+        const int q4 = (lane >> 2) & 3, p4 = lane & 3, dl = 16 * ((lane >> 4) & 1) + 4 * p4, sw = 4 * ((q4 >> 1) & 1);
+#pragma unroll
+        for (int dt = 0; dt < 2; dt++) voff[dt] = (4 * h + q4) * 128 + ((((dl + 32 * dt) >> 3) ^ sw) << 4) + (dl & 7) * 2;
+    }
+
+    f32x16 oacc[2], negm;
+#pragma unroll
+    for (int e = 0; e < 16; e++) oacc[0][e] = oacc[1][e] = negm[e] = 0.0f;
+    float l = 0.0f;
+
+    if (rg > 0) {
+        // the shift of EVERY range starts as the one-pass shift, the maximum over key tile 0 (one extra K . Q^T tile; tile 0 is
+        // full whenever there is a second range): P = 2^(s - m) is then rounded to bf16 at the same m as in attn_kernel, and the
+        // merge's weights are 1 unless a guard trip raised a range's shift
+        A_LOAD(0);
+        A_STORE(0);
+        __syncthreads();
+        float mt = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            f32x16 s0 = negm;
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                const bf16x8 ka = *reinterpret_cast<const bf16x8 *>(Ks + (j * 32 + r) * KLD + ks * 16 + 8 * h);
+                s0 = mfma_bf16(ka, qf[ks], s0);
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++) mt = fmaxf(mt, s0[e]);
+        }
+        const float dq = fmaxf(mt, __shfl_xor(mt, 32));
+#pragma unroll
+        for (int e = 0; e < 16; e++) negm[e] = -dq;
+        __syncthreads();
+    }
+    A_LOAD(kt0);
+    A_STORE(0);
+    __syncthreads();
+    for (int kt = kt0; kt < kt1; kt++) {
+        const int cur = (kt - kt0) & 1;
+        const bool first = kt == 0;                  // range 0 sets the shift at its first tile, as attn_kernel does
+        if (kt + 1 < kt1) A_LOAD(kt + 1);
+        const bf16 *Kb = Ks + cur * AKT * KLD;
+        const char *Vb = Vs + cur * AKT * 128;
+        f32x16 st[2];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            st[j] = negm;
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                const bf16x8 ka = *reinterpret_cast<const bf16x8 *>(Kb + (j * 32 + r) * KLD + ks * 16 + 8 * h);
+                st[j] = mfma_bf16(ka, qf[ks], st[j]);
+            }
+        }
+        if (kt + 1 == ntile) {       // only the frame's last tile has keys beyond T (it still has at least one real key)
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    if (kt * AKT + j * 32 + crow(e, h) >= T) st[j][e] = -INFINITY;
+        }
+        float mt = st[0][0];
+#pragma unroll
+        for (int e = 0; e < 16; e++) asm("v_max3_f32 %0, %0, %1, %2" : "+v"(mt) : "v"(st[0][e]), "v"(st[1][e]));
+        if (__any(mt > 64.0f) || first) {
+            // attn_kernel's rule: set at key tile 0 (nothing to scale yet), afterwards the shift only ever rises (a later range
+            // starts with O = l = 0: scaling them by 2^-d, d >= 0, is harmless)
+            const float dq = fmaxf(mt, __shfl_xor(mt, 32));
+            const float d = first ? dq : fmaxf(dq, 0.0f);
+            if (!first) {
+                const float a = __builtin_amdgcn_exp2f(-d);
+                l *= a;
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    oacc[0][e] *= a;
+                    oacc[1][e] *= a;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                negm[e] -= d;
+                st[0][e] -= d;
+                st[1][e] -= d;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const float p = __builtin_amdgcn_exp2f(st[j][e]);
+                st[j][e] = p;
+                l += p;
+            }
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; s2++) {
+                bf16x8 pb;
+#pragma unroll
+                for (int e = 0; e < 8; e++) pb[e] = (bf16)st[j][8 * s2 + e];
+#pragma unroll
+                for (int dt = 0; dt < 2; dt++) {
+                    const char *vp = Vb + (32 * j + 16 * s2) * 128 + voff[dt];
+                    oacc[dt] = mfma_bf16(ld_tr2(vp, vp + 8 * 128), pb, oacc[dt]);
+                }
+            }
+        if (kt + 1 < kt1) A_STORE(cur ^ 1);
+        __syncthreads();
+    }
+#undef A_LOAD
+#undef A_STORE
+    // the partials leave as the lanes hold them: block (group, query tile, range), then wave
+    float *pw = part + (((long long)grp * qtiles + qt) * ns + rg) * (4 * AF_WAVE_FLOATS) + wave * AF_WAVE_FLOATS;
+#pragma unroll
+    for (int dt = 0; dt < 2; dt++)
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+            *reinterpret_cast<f32x4 *>(pw + ((dt * 4 + g) * 64 + lane) * 4) =
+                f32x4{oacc[dt][4 * g + 0], oacc[dt][4 * g + 1], oacc[dt][4 * g + 2], oacc[dt][4 * g + 3]};
+    *reinterpret_cast<float2 *>(pw + 8 * 256 + lane * 2) = make_float2(-negm[0], l);
+}
+
+// The merge and the output projection in ONE launch (a launch costs ~5 us here before it does anything): workgroup = 32 tokens of
+// one frame, six waves.  Wave w first merges head w (ranges 0, 1, .. in order, weights 2^(m_s - max m)) - the lanes hold O^T (d on accumulator
+// rows, the query on the lane), and registers 8 s2 .. 8 s2 + 7 of tile dt, normalised and rounded to bf16, ARE the B fragment of
+// k-step 4 w + 2 dt + s2 of the projection with the k order 8 (e >> 2) + 4 h + (e & 3), as P^T is in the attention - and leaves its
+// four fragments in LDS.  Then wave w multiplies all 24 k-steps (heads 0..5 in order) into output columns 64 w .. 64 w + 63; the
+// weights come straight from L2 out of the image gemm_rt_kernel streams, each lane taking the two 8-byte halves that match the
+// permuted k order.  Epilogue as EpiResidual: x += out (bias inside the accumulator), and the LayerNorm sums of the new rows, each
+// 192-column half added over its three waves in the order (w0 + w1) + w2.
+constexpr int FO_FRAG_BYTES = 24 * 1024;
+constexpr int FO_LDS_BYTES = FO_FRAG_BYTES + 6 * RT_STG_BYTES + 6 * 32 * 8;
+
+__global__ __launch_bounds__(384, 1) void attn_ff_oproj_kernel(const float *__restrict__ part, const bf16 *__restrict__ Wp,
+                                                               const float *__restrict__ bias, float *__restrict__ x,
+                                                               float2 *__restrict__ stats, int T) {
+    extern __shared__ __attribute__((aligned(16))) char fo_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tiles = (T + 31) / 32, qtiles = (T + AQ - 1) / AQ, ns = af_ranges(T);
+    const int f = blockIdx.x / tiles, t0 = (blockIdx.x - f * tiles) * 32;
+    const int row0 = f * T + t0, M = f * T + T;              // rows of this frame only: the tile's tail belongs to the next frame
+    char *frag = fo_smem, *stg = fo_smem + FO_FRAG_BYTES + wave * RT_STG_BYTES;
+    float2 *wst = reinterpret_cast<float2 *>(fo_smem + FO_FRAG_BYTES + 6 * RT_STG_BYTES);
+
+    // weights of output columns n0 .. n0 + 63: slices sl0, sl0 + 1 of 192-column tile nt; lane (n = r, h) takes elements 4 h .. 4 h + 3
+    // of the k-halves 0 and 1 of its row: k = 16 K + 8 (e >> 2) + 4 h + (e & 3)
+    const int n0 = 64 * wave, nt = n0 / RT_NT, sl0 = (n0 - nt * RT_NT) / 32;
+    const bf16 *wp = Wp + ((long long)nt * RT_KS * RT_SL + sl0) * 512 + r * 8 + 4 * h;
+    uint2 wl[RT_KS][2], wh[RT_KS][2];
+#pragma unroll
+    for (int K = 0; K < RT_KS / 2; K++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            wl[K][j] = *reinterpret_cast<const uint2 *>(wp + (K * RT_SL + j) * 512);
+            wh[K][j] = *reinterpret_cast<const uint2 *>(wp + (K * RT_SL + j) * 512 + 256);
+        }
+
+    // ---- merge head `wave` for tokens t0 .. t0 + 31: wave (t0 % 128) / 32 of query tile t0 / 128 in attn_ff_kernel's order
+    {
+        const float *pw = part + ((long long)(f * VH + wave) * qtiles + t0 / AQ) * ns * (4 * AF_WAVE_FLOATS) + ((t0 % AQ) / 32) * AF_WAVE_FLOATS;
+        float ms[AF_MAX_RANGES], ls[AF_MAX_RANGES];
+        float Mx = 0.0f;
+#pragma unroll
+        for (int s = 0; s < AF_MAX_RANGES; s++)
+            if (s < ns) {
+                const float2 ml = *reinterpret_cast<const float2 *>(pw + (long long)s * (4 * AF_WAVE_FLOATS) + 8 * 256 + lane * 2);
+                ms[s] = ml.x;
+                ls[s] = ml.y + __shfl_xor(ml.y, 32);
+                Mx = s == 0 ? ml.x : fmaxf(Mx, ml.x);
+            }
+        f32x4 acc[8];
+        float L = 0.0f;
+#pragma unroll
+        for (int s = 0; s < AF_MAX_RANGES; s++)
+            if (s < ns) {
+                const float wgt = __builtin_amdgcn_exp2f(ms[s] - Mx);
+                const float *ps = pw + (long long)s * (4 * AF_WAVE_FLOATS) + lane * 4;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const f32x4 ov = *reinterpret_cast<const f32x4 *>(ps + i * 256);
+                    if (s == 0) acc[i] = ov * wgt;
+                    else acc[i] = acc[i] + ov * wgt;
+                }
+                L = s == 0 ? ls[s] * wgt : L + ls[s] * wgt;
+            }
+        const float inv = 1.0f / L;
+#pragma unroll
+        for (int dt = 0; dt < 2; dt++)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; s2++) {
+                const f32x4 a0 = acc[dt * 4 + 2 * s2], a1 = acc[dt * 4 + 2 * s2 + 1];
+                const u32x4 fr = {pack_bf16x2(a0[0] * inv, a0[1] * inv), pack_bf16x2(a0[2] * inv, a0[3] * inv),
+                                  pack_bf16x2(a1[0] * inv, a1[1] * inv), pack_bf16x2(a1[2] * inv, a1[3] * inv)};
+                *reinterpret_cast<u32x4 *>(frag + ((wave * 4 + 2 * dt + s2) * 64 + lane) * 16) = fr;
+            }
+    }
+    __syncthreads();
+
+    // ---- projection: 24 k-steps x 2 slices
+#pragma unroll
+    for (int K = RT_KS / 2; K < RT_KS; K++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            wl[K][j] = *reinterpret_cast<const uint2 *>(wp + (K * RT_SL + j) * 512);
+            wh[K][j] = *reinterpret_cast<const uint2 *>(wp + (K * RT_SL + j) * 512 + 256);
+        }
+    const int q = lane >> 3, p = lane & 7;
+    f32x4 xv[2][4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+            xv[j][i] = *reinterpret_cast<const f32x4 *>(x + (long long)min(row0 + 8 * i + q, M - 1) * VD + n0 + 32 * j + 4 * p);
+    f32x16 oa[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const float4 b = *reinterpret_cast<const float4 *>(bias + n0 + 32 * j + 8 * g + 4 * h);
+            oa[j][4 * g + 0] = b.x;
+            oa[j][4 * g + 1] = b.y;
+            oa[j][4 * g + 2] = b.z;
+            oa[j][4 * g + 3] = b.w;
+        }
+#pragma unroll
+    for (int K = 0; K < RT_KS; K++) {
+        const bf16x8 bfr = *reinterpret_cast<const bf16x8 *>(frag + (K * 64 + lane) * 16);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const u32x4 wv = {wl[K][j].x, wl[K][j].y, wh[K][j].x, wh[K][j].y};
+            oa[j] = mfma_bf16(__builtin_bit_cast(bf16x8, wv), bfr, oa[j]);
+        }
+    }
+
+    // ---- residual add, LayerNorm sums of the new rows
+    float sum[4] = {0.f, 0.f, 0.f, 0.f}, sq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+            *reinterpret_cast<float4 *>(stg + r * RT_STG_ROW + 32 * g + 16 * h) =
+                make_float4(oa[j][4 * g + 0], oa[j][4 * g + 1], oa[j][4 * g + 2], oa[j][4 * g + 3]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float4 d = *reinterpret_cast<const float4 *>(stg + (8 * i + q) * RT_STG_ROW + 16 * p);
+            f32x4 v = xv[j][i];
+            v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
+            if (row0 + 8 * i + q < M) *reinterpret_cast<f32x4 *>(x + (long long)(row0 + 8 * i + q) * VD + n0 + 32 * j + 4 * p) = v;
+            sum[i] += (v.x + v.y) + (v.z + v.w);
+            sq[i] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) {
+            sum[i] += __shfl_xor(sum[i], o);
+            sq[i] += __shfl_xor(sq[i], o);
+        }
+        if (p == 0) wst[wave * 32 + 8 * i + q] = make_float2(sum[i], sq[i]);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int rr = tid & 31, hf = tid >> 5;
+        const float2 a = wst[(3 * hf) * 32 + rr], b = wst[(3 * hf + 1) * 32 + rr], c = wst[(3 * hf + 2) * 32 + rr];
+        if (row0 + rr < M) stats[2 * (long long)(row0 + rr) + hf] = make_float2((a.x + b.x) + c.x, (a.y + b.y) + c.y);
+    }
+}
+
+// Down projection (K = 1536) with K split in four fixed parts: workgroup = 32 rows x 192 columns, wave w multiplies the
+// 384-wide K chunk w (its 24 A fragments in registers, as gemm_rt_kernel keeps them) and the four partial tiles meet in LDS,
+// where wave 0 adds them as ((q0 + q1) + q2) + q3 - q0 starts from the bias - and runs the epilogue.  No counter, no atomic,
+// no memset node.  4 x as many workgroups as the 128-row form, each with a chain of 24 k-steps instead of 96 and one
+// prologue instead of four.  The waves share no weights, so there is no LDS ring and no barrier in the loop: a wave streams
+// its own 144 fragments (one contiguous KB each in the packed image) from L2 into a register ring 4 k-steps deep.
+constexpr int KS4_RED_BYTES = 3 * RT_SL * 64 * 16 * 4;                       // the partial tiles of waves 1..3
+constexpr int KS4_LDS_BYTES = 4 * RT_STG_BYTES + KS4_RED_BYTES + RT_NT * 4;
+
+template <int N>
+__device__ __forceinline__ void ks4_wait6(bf16x8 (&w)[RT_SL]) {
+    asm volatile("s_waitcnt vmcnt(%6)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]) : "n"(N) : "memory");
+}
+
+__global__ __launch_bounds__(256, 1) void gemm_ks4_kernel(ProBf16 pro, const bf16 *__restrict__ Wp, int M, EpiResidual epi) {
+    extern __shared__ __attribute__((aligned(16))) char ks4_smem[];
+    constexpr int parts = VD / RT_NT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n_tiles = (M + 31) / 32;
+    const int b16 = blockIdx.x / (8 * parts), bl = blockIdx.x % (8 * parts);
+    const int tile = b16 * 8 + (bl & 7), nt = bl >> 3;       // blocks b and b + 8 (one XCD) share the row tile
+    if (tile >= n_tiles) return;                             // padding block of the last group of 8 tiles
+    const int row0 = tile * 32;
+    char *stg = ks4_smem + wave * RT_STG_BYTES;
+    float *red = reinterpret_cast<float *>(ks4_smem + 4 * RT_STG_BYTES);
+    float *vec = reinterpret_cast<float *>(ks4_smem + 4 * RT_STG_BYTES + KS4_RED_BYTES);
+    for (int i = tid; i < RT_NT; i += 256) vec[i] = epi.bias[RT_NT * nt + i];
+
+    // the wave's weight stream: k chunk `wave` of column tile nt; fragment (ks, s) is 512 elements after (ks, s - 1)
+    const bf16 *wp = Wp + ((long long)nt * 4 + wave) * RT_KS * RT_STEP_ELEMS + lane * 8;
+    bf16x8 w[4][RT_SL];
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++)
+#pragma unroll
+        for (int s = 0; s < RT_SL; s++) rt_gload(w[ks][s], wp + (ks * RT_SL + s) * 512);
+    bf16x8 a[RT_KS];
+    pro.load(a, row0, wave, stg, nullptr, lane, M);          // ends with every load so far landed
+    __syncthreads();                                         // the bias is in LDS
+    f32x16 acc[RT_SL];
+#pragma unroll
+    for (int s = 0; s < RT_SL; s++)
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const float4 b = wave == 0 ? *reinterpret_cast<const float4 *>(vec + 32 * s + 8 * g + 4 * (lane >> 5)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            acc[s][4 * g + 0] = b.x;
+            acc[s][4 * g + 1] = b.y;
+            acc[s][4 * g + 2] = b.z;
+            acc[s][4 * g + 3] = b.w;
+        }
+    // k-step ks: its six fragments have landed once at most 6 x (younger k-steps in flight) loads are outstanding; its ring slot
+    // is refilled with k-step ks + 4 right after its MFMAs were issued (they read their operands at issue)
+#define KS4_STEP(ks)                                                                                          \
+    ks4_wait6<6 * (23 - (ks) < 3 ? 23 - (ks) : 3)>(w[(ks) & 3]);                              \
+    _Pragma("unroll") for (int s = 0; s < RT_SL; s++) acc[s] = mfma_bf16(w[(ks) & 3][s], a[ks], acc[s]);       \
+    if ((ks) + 4 < RT_KS) {                                                                                   \
+        _Pragma("unroll") for (int s = 0; s < RT_SL; s++) rt_gload(w[(ks) & 3][s], wp + (((ks) + 4) * RT_SL + s) * 512); \
+    }                                                                                                         \
+    __builtin_amdgcn_sched_barrier(0);
+#define KS4_STEP4(k) KS4_STEP(k) KS4_STEP((k) + 1) KS4_STEP((k) + 2) KS4_STEP((k) + 3)
+    KS4_STEP4(0) KS4_STEP4(4) KS4_STEP4(8) KS4_STEP4(12) KS4_STEP4(16) KS4_STEP4(20)
+#undef KS4_STEP4
+#undef KS4_STEP
+    if (wave != 0) {
+#pragma unroll
+        for (int s = 0; s < RT_SL; s++)
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+                *reinterpret_cast<f32x4 *>(red + ((((wave - 1) * RT_SL + s) * 4 + g) * 64 + lane) * 4) =
+                    f32x4{acc[s][4 * g + 0], acc[s][4 * g + 1], acc[s][4 * g + 2], acc[s][4 * g + 3]};
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // the residual rows travel while the partial tiles are added.  Plain loads, not EpiResidual::prefetch: its hand-written
+    // loads are invisible to the compiler, which under this kernel's register pressure copied and reused their destination
+    // registers before the data had landed (a reused address register: a wild load)
+    EpiResidual::State est;
+    {
+        const int q = lane >> 3, p = lane & 7;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float *px = epi.x + (long long)min(row0 + 8 * i + q, M - 1) * VD + RT_NT * nt + 4 * p;
+#pragma unroll
+            for (int s = 0; s < RT_SL; s++) est.xv[s][i] = *reinterpret_cast<const f32x4 *>(px + 32 * s);
+        }
+    }
+#pragma unroll
+    for (int pw = 0; pw < 3; pw++)                           // ((q0 + q1) + q2) + q3
+#pragma unroll
+        for (int s = 0; s < RT_SL; s++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const f32x4 p = *reinterpret_cast<const f32x4 *>(red + (((pw * RT_SL + s) * 4 + g) * 64 + lane) * 4);
+                acc[s][4 * g + 0] += p[0];
+                acc[s][4 * g + 1] += p[1];
+                acc[s][4 * g + 2] += p[2];
+                acc[s][4 * g + 3] += p[3];
+            }
+    epi.tile(acc, est, row0, nt, stg, nullptr, lane, M);
+}
+
 int g_rt_dbg = 0;
 // row-tile GEMM launch: one workgroup per (128-row tile, half of the 192-column tiles)
 template <int KC, int NTP, class Pro, class Epi>
@@ -1139,8 +1575,7 @@ extern "C" int sslam_probe_vit(unsigned long long *host_out) {
 }
 #endif
 
-extern "C" long long sslam_vit_workspace_bytes(int n_frames, int size) {
-    if (n_frames <= 0 || size <= 0 || size % VPATCH) return SSLAM_E_INVALID;
+static long long vit_base_bytes(int n_frames, int size) {
     const long long G = size / VPATCH, T = G * G + VPREFIX, rows = (long long)n_frames * T;
     size_t b = 0;
     b += ws_align(rows * VD * 4);                 // x   fp32 residual stream
@@ -1151,11 +1586,35 @@ extern "C" long long sslam_vit_workspace_bytes(int n_frames, int size) {
     return (long long)b;
 }
 
+// fp32 partials of the few-frame attention: per (frame, head, 128-query tile, key range) four waves' (O, m, l)
+static long long vit_ff_partial_bytes(int n_frames, int T) {
+    return (long long)ws_align((size_t)n_frames * VH * ((T + AQ - 1) / AQ) * af_ranges(T) * 4 * AF_WAVE_FLOATS * 4);
+}
+
+extern "C" long long sslam_vit_workspace_bytes(int n_frames, int size) {
+    if (n_frames <= 0 || size <= 0 || size % VPATCH) return SSLAM_E_INVALID;
+    return vit_base_bytes(n_frames, size);
+}
+
+extern "C" long long sslam_vit_workspace_bytes_form(int n_frames, int size, int form) {
+    if (n_frames <= 0 || size <= 0 || size % VPATCH) return SSLAM_E_INVALID;
+    if (form != SSLAM_VIT_FORM_THROUGHPUT && form != SSLAM_VIT_FORM_SMALL && form != SSLAM_VIT_FORM_FEW_FRAME) return SSLAM_E_INVALID;
+    if (form != SSLAM_VIT_FORM_FEW_FRAME) return vit_base_bytes(n_frames, size);
+    if (n_frames > SSLAM_VIT_FEW_FRAME_MAX_FRAMES) return SSLAM_E_INVALID;
+    const int G = size / VPATCH;
+    return vit_base_bytes(n_frames, size) + vit_ff_partial_bytes(n_frames, G * G + VPREFIX);
+}
+
 // images_chw (fp32 planar; patches == nullptr) or patches (bf16 rows of 768 per patch, from sslam_preprocess_u8_patches)
+// form: VIT_FORM_BY_ROWS (the unnamed entries: small up to 8 192 token rows, throughput above) or one of SSLAM_VIT_FORM_*
+constexpr int VIT_FORM_BY_ROWS = -1;
 static int vit_forward_impl(const float *images_chw, const bf16 *patches, int n_frames, int size, const sslam_vit_weights_t *w,
-                            void *workspace, long long workspace_bytes, float *tokens_out, void *stream) {
+                            void *workspace, long long workspace_bytes, float *tokens_out, void *stream, int form) {
     if ((!images_chw && !patches) || !w || !workspace || !tokens_out || n_frames <= 0 || size <= 0 || size % VPATCH) return SSLAM_E_INVALID;
-    if (workspace_bytes < sslam_vit_workspace_bytes(n_frames, size)) return SSLAM_E_INVALID;
+    {
+        const long long need = form == VIT_FORM_BY_ROWS ? sslam_vit_workspace_bytes(n_frames, size) : sslam_vit_workspace_bytes_form(n_frames, size, form);
+        if (need < 0 || workspace_bytes < need) return SSLAM_E_INVALID;      // also: unknown form, FEW_FRAME with more than 8 frames
+    }
     if (((uintptr_t)images_chw | (uintptr_t)patches | (uintptr_t)workspace | (uintptr_t)tokens_out) & 15) return SSLAM_E_INVALID;
     const int G = size / VPATCH, cells = G * G, T = cells + VPREFIX;
     const long long rows = (long long)n_frames * T, prow = (long long)n_frames * cells;
@@ -1169,7 +1628,8 @@ static int vit_forward_impl(const float *images_chw, const bf16 *patches, int n_
     bf16 *y = (bf16 *)p;              p += ws_align(rows * VD * 2);
     bf16 *q = (bf16 *)p;              bf16 *k = q + rows * VD, *v = k + rows * VD;   p += ws_align(rows * VD * 2 * 3);
     bf16 *hbuf = (bf16 *)p;          p += ws_align(rows * VMLP * 2);
-    float2 *stats = (float2 *)p;
+    float2 *stats = (float2 *)p;     p += ws_align(rows * 16);
+    float *ffpart = (float *)p;       // few-frame form only: the attention partials
 
     // patch embedding + prefix tokens
     {
@@ -1184,7 +1644,8 @@ static int vit_forward_impl(const float *images_chw, const bf16 *patches, int n_
         sslam_count_launches(1);
     }
     const float4 *st4 = (const float4 *)stats;
-    const bool small = (rows + RT_BM - 1) / RT_BM * 4 <= 256;
+    const bool few = form == SSLAM_VIT_FORM_FEW_FRAME;       // its K = 384 GEMMs are the small form's launches
+    const bool small = form == VIT_FORM_BY_ROWS ? (rows + RT_BM - 1) / RT_BM * 4 <= 256 : form != SSLAM_VIT_FORM_THROUGHPUT;
     const bool no_fused = sslam_knob(KNOB_VIT_NO_FUSED_MLP, 0) != 0;      // test-only A/B knob: the two-launch MLP     // <= 8 frames at 448 x 448: latency-shaped launches
     int rt_stop = 0;
 #ifdef SSLAM_RT_PROBE
@@ -1199,8 +1660,16 @@ static int vit_forward_impl(const float *images_chw, const bf16 *patches, int n_
         else
             launch_rt<1, 3>(ProLN{x, st4, ly.ln1_g, ly.ln1_b, 1e-5f}, (const bf16 *)ly.wqkv, rows, 3 * VD, EpiQKV{ly.bqkv, w->rope_cos, w->rope_sin, q, k, v, T, G}, st);
         if (rt_stop == 1) break;
-        hipLaunchKernelGGL(attn_kernel, dim3((unsigned)((n_frames * VH + 7) / 8 * 8 * ((T + AQ - 1) / AQ))), dim3(256), 0, st, q, k, v, y, T, n_frames * VH);
-        launch_rt<1, 1>(ProBf16{y, VD}, (const bf16 *)ly.wo, rows, VD, EpiResidual{ly.bo, x, stats}, st);
+        if (few) {
+            // key ranges, then merge + o_proj + residual in one launch
+            const int qtiles = (T + AQ - 1) / AQ;
+            hipLaunchKernelGGL(attn_ff_kernel, dim3((unsigned)((n_frames * VH + 7) / 8 * 8 * qtiles * af_ranges(T))), dim3(256), 0, st, q, k, v, ffpart, T, n_frames * VH);
+            hipLaunchKernelGGL(attn_ff_oproj_kernel, dim3((unsigned)(n_frames * ((T + 31) / 32))), dim3(384), FO_LDS_BYTES, st, ffpart,
+                               (const bf16 *)ly.wo, ly.bo, x, stats, T);
+        } else {
+            hipLaunchKernelGGL(attn_kernel, dim3((unsigned)((n_frames * VH + 7) / 8 * 8 * ((T + AQ - 1) / AQ))), dim3(256), 0, st, q, k, v, y, T, n_frames * VH);
+            launch_rt<1, 1>(ProBf16{y, VD}, (const bf16 *)ly.wo, rows, VD, EpiResidual{ly.bo, x, stats}, st);
+        }
         if (rt_stop == 2) break;
         if (ly.wmlp && !small && !no_fused) {
             // LN2 -> up -> GELU -> down -> residual in one launch: the hidden activation stays on the chip
@@ -1215,7 +1684,11 @@ static int vit_forward_impl(const float *images_chw, const bf16 *patches, int n_
         else
             launch_rt<1, 4>(ProLN{x, st4, ly.ln2_g, ly.ln2_b, 1e-5f}, (const bf16 *)ly.wup, rows, VMLP, EpiGelu{ly.bup, hbuf, VMLP}, st);
         if (rt_stop == 3) break;
-        launch_rt<4, 1>(ProBf16{hbuf, VMLP}, (const bf16 *)ly.wdown, rows, VD, EpiResidual{ly.bdown, x, stats}, st);
+        if (few)
+            hipLaunchKernelGGL(gemm_ks4_kernel, dim3((unsigned)(((rows + 31) / 32 + 7) / 8 * 8 * (VD / RT_NT))), dim3(256), KS4_LDS_BYTES, st,
+                               ProBf16{hbuf, VMLP}, (const bf16 *)ly.wdown, (int)rows, EpiResidual{ly.bdown, x, stats});
+        else
+            launch_rt<4, 1>(ProBf16{hbuf, VMLP}, (const bf16 *)ly.wdown, rows, VD, EpiResidual{ly.bdown, x, stats}, st);
         if (rt_stop == 4) break;
         sslam_count_launches(5);
     }
@@ -1228,11 +1701,27 @@ static int vit_forward_impl(const float *images_chw, const bf16 *patches, int n_
 extern "C" int sslam_vit_forward(const float *images_chw, int n_frames, int size, const sslam_vit_weights_t *w, void *workspace,
                                  long long workspace_bytes, float *tokens_out, void *stream) {
     if (!images_chw) return SSLAM_E_INVALID;
-    return vit_forward_impl(images_chw, nullptr, n_frames, size, w, workspace, workspace_bytes, tokens_out, stream);
+    return vit_forward_impl(images_chw, nullptr, n_frames, size, w, workspace, workspace_bytes, tokens_out, stream, VIT_FORM_BY_ROWS);
 }
 
 extern "C" int sslam_vit_forward_patches(const void *patches_bf16, int n_frames, int size, const sslam_vit_weights_t *w, void *workspace,
                                          long long workspace_bytes, float *tokens_out, void *stream) {
     if (!patches_bf16) return SSLAM_E_INVALID;
-    return vit_forward_impl(nullptr, (const bf16 *)patches_bf16, n_frames, size, w, workspace, workspace_bytes, tokens_out, stream);
+    return vit_forward_impl(nullptr, (const bf16 *)patches_bf16, n_frames, size, w, workspace, workspace_bytes, tokens_out, stream, VIT_FORM_BY_ROWS);
+}
+
+static bool vit_form_known(int form) {
+    return form == SSLAM_VIT_FORM_THROUGHPUT || form == SSLAM_VIT_FORM_SMALL || form == SSLAM_VIT_FORM_FEW_FRAME;
+}
+
+extern "C" int sslam_vit_forward_form(const float *images_chw, int n_frames, int size, const sslam_vit_weights_t *w, void *workspace,
+                                      long long workspace_bytes, float *tokens_out, int form, void *stream) {
+    if (!images_chw || !vit_form_known(form)) return SSLAM_E_INVALID;
+    return vit_forward_impl(images_chw, nullptr, n_frames, size, w, workspace, workspace_bytes, tokens_out, stream, form);
+}
+
+extern "C" int sslam_vit_forward_patches_form(const void *patches_bf16, int n_frames, int size, const sslam_vit_weights_t *w, void *workspace,
+                                              long long workspace_bytes, float *tokens_out, int form, void *stream) {
+    if (!patches_bf16 || !vit_form_known(form)) return SSLAM_E_INVALID;
+    return vit_forward_impl(nullptr, (const bf16 *)patches_bf16, n_frames, size, w, workspace, workspace_bytes, tokens_out, stream, form);
 }

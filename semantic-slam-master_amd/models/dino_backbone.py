@@ -29,7 +29,7 @@ from sslam_amd import lib
 
 class DinoBackbone(nn.Module):
     def __init__(self, model_name: str = "vit_small_patch16_dinov3.lvd1689m", input_size: int = 448, freeze: bool = True,
-                 dino: nn.Module | None = None, vit_precision: str = "fp32"):
+                 dino: nn.Module | None = None, vit_precision: str = "fp32", vit_form: str | None = None):
         """The first three arguments are the reference's (dino_backbone.py:25-30).  `vit_precision` says how the frozen
         ViT runs on a GPU under no_grad:
           "fp32"  (default - a script run unchanged keeps the reference's numerics) the HIP ViT-S/16 with fp32 operands on the
@@ -40,12 +40,19 @@ class DinoBackbone(nn.Module):
                   agreement with the fp32 path is MEASURED (tests/test_gpu_harness.py, bench.py
                   `with_vit.fp32_reference_numerics`: 99.8 % / 99.4 %), not bit-exact;
           "eager" the module's own torch forward (no HIP kernel for A1).
+        `vit_form`: None, or "few_frame" with vit_precision="bf16" only - batches of up to 8 frames (the reference's callers: B = 1,
+        B = 4) run the bf16 ViT's few-frame launch form (key-split attention, K-split down projection; HipViT.forward_features);
+        larger batches are untouched.
         Every entry point that needs tokens (forward(), harness.SequenceMatcher) goes through forward_tokens(), so they
         agree with each other."""
         super().__init__()
         if vit_precision not in ("bf16", "fp32", "eager"):
             raise ValueError(f"vit_precision must be 'bf16', 'fp32' or 'eager', got {vit_precision!r}")
-        self.vit_precision = vit_precision
+        if vit_form not in (None, "few_frame"):
+            raise ValueError(f"vit_form must be None or 'few_frame', got {vit_form!r}")
+        if vit_form == "few_frame" and vit_precision != "bf16":
+            raise ValueError(f"vit_form='few_frame' is a launch form of the bf16 HIP ViT, not of vit_precision={vit_precision!r}")
+        self.vit_precision, self.vit_form = vit_precision, vit_form
         self.model_name = model_name
         self.input_size = input_size
         self.patch_size = 16
@@ -109,7 +116,7 @@ class DinoBackbone(nn.Module):
         grad = self.training and not self._is_frozen()
         hv = None if (grad and torch.is_grad_enabled()) else self._hip_vit(images)
         if hv is not None:
-            return hv.forward_features(images)
+            return hv.forward_features(images, form=self.vit_form) if self.vit_precision == "bf16" else hv.forward_features(images)
         with torch.set_grad_enabled(grad):
             return self.dino.forward_features(images)
 

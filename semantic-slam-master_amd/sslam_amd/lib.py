@@ -76,6 +76,7 @@ EXPORTS = [
     "sslam_selector_saliency_ws", "sslam_sim_argmax_ws", "sslam_test_set_knob",
     "sslam_preprocess_u8_patches", "sslam_vit_forward_patches", "sslam_vit_f32_workspace_bytes", "sslam_vit_forward_f32",
     "sslam_vit_f32_pack_linear_host", "sslam_vit_forward_f32_form",
+    "sslam_vit_workspace_bytes_form", "sslam_vit_forward_form", "sslam_vit_forward_patches_form",
 ]
 
 
@@ -127,6 +128,10 @@ def lib():
         L.sslam_vit_workspace_bytes.argtypes = [i, i]
         L.sslam_vit_forward.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, p]
         L.sslam_vit_forward_patches.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, p]
+        L.sslam_vit_workspace_bytes_form.restype = C.c_longlong
+        L.sslam_vit_workspace_bytes_form.argtypes = [i, i, i]
+        L.sslam_vit_forward_form.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, i, p]
+        L.sslam_vit_forward_patches_form.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, i, p]
         L.sslam_vit_f32_workspace_bytes.restype = C.c_longlong
         L.sslam_vit_f32_workspace_bytes.argtypes = [i, i]
         L.sslam_vit_forward_f32.argtypes = [p, i, i, C.POINTER(VitWeightsF32), p, ll, p, p]
@@ -494,30 +499,48 @@ def pack_vit_mlp(w_up: np.ndarray, w_down: np.ndarray, row_scale: np.ndarray | N
     return out
 
 
-def vit_workspace_bytes(n_frames: int, size: int) -> int:
-    b = int(lib().sslam_vit_workspace_bytes(n_frames, size))
+# launch forms of the bf16 ViT that a caller can name (include/sslam_hip.h)
+VIT_FORM_THROUGHPUT, VIT_FORM_SMALL, VIT_FORM_FEW_FRAME, VIT_FEW_FRAME_MAX_FRAMES = 0, 1, 2, 8
+
+
+def vit_workspace_bytes(n_frames: int, size: int, form: int | None = None) -> int:
+    """Workspace of one bf16 ViT launch.  form None: the unnamed entries' need; VIT_FORM_*: the named form's own (FEW_FRAME adds
+    the attention partials).  ValueError for an unknown form and for FEW_FRAME with more than VIT_FEW_FRAME_MAX_FRAMES frames."""
+    if form is None:
+        b = int(lib().sslam_vit_workspace_bytes(n_frames, size))
+    else:
+        b = int(lib().sslam_vit_workspace_bytes_form(n_frames, size, int(form)))
     if b < 0:
         _check(b, "vit_workspace_bytes")
     return b
 
 
-def vit_forward_patches(patches, size: int, weights: VitWeights, workspace, out=None):
-    """patches (n, (size/16)^2, 768) bf16 from preprocess_u8_patches -> tokens (n, 5 + (size/16)^2, 384) fp32."""
+def _with_form(fn, form):
+    """The *_form entries take `form` before the trailing stream argument."""
+    return lambda *a: fn(*a[:-1], int(form), a[-1])
+
+
+def vit_forward_patches(patches, size: int, weights: VitWeights, workspace, out=None, form: int | None = None):
+    """patches (n, (size/16)^2, 768) bf16 from preprocess_u8_patches -> tokens (n, 5 + (size/16)^2, 384) fp32.
+    form: None - the library's rule by this launch's token rows; VIT_FORM_* - the caller's (sslam_vit_forward_patches_form)."""
     n = patches.shape[0]
     t = 5 + (size // 16) ** 2
     if out is None:
         out = torch.empty((n, t, C_FEAT), dtype=torch.float32, device=patches.device)
-    _run("vit_forward_patches", lib().sslam_vit_forward_patches, (patches, workspace, out,),
+    fn = lib().sslam_vit_forward_patches if form is None else _with_form(lib().sslam_vit_forward_patches_form, form)
+    _run("vit_forward_patches", fn, (patches, workspace, out,),
          _dp(patches), n, size, C.byref(weights), _dp(workspace), workspace.numel() * workspace.element_size(), _dp(out))
     return out
 
 
-def vit_forward(images_chw, weights: VitWeights, workspace, out=None):
+def vit_forward(images_chw, weights: VitWeights, workspace, out=None, form: int | None = None):
+    """form: None - the library's rule by this launch's token rows; VIT_FORM_* - the caller's (sslam_vit_forward_form)."""
     n, _, size, _ = images_chw.shape
     t = 5 + (size // 16) ** 2
     if out is None:
         out = torch.empty((n, t, C_FEAT), dtype=torch.float32, device=images_chw.device)
-    _run("vit_forward", lib().sslam_vit_forward, (images_chw, workspace, out,),
+    fn = lib().sslam_vit_forward if form is None else _with_form(lib().sslam_vit_forward_form, form)
+    _run("vit_forward", fn, (images_chw, workspace, out,),
          _dp(images_chw), n, size, C.byref(weights), _dp(workspace), workspace.numel() * workspace.element_size(),
                                    _dp(out))
     return out

@@ -21,6 +21,10 @@ Results are the kernels' results: bit-identical to the same frames going through
 frames (tests/test_gpu_harness.py::test_online_stepper_*).  A step is a batch of ONE frame, so the ViT inside runs its few-frame
 form (fp32: key-split attention; bf16: the small form) whatever sequence it steps through; a longer batch's tokens (fp32 one-pass,
 bf16 fused MLP) agree with a step's within the float64 bars, not bit for bit (test_frame_stepper_runs_the_few_frame_form).
+A pipeline built with vit_form="few_frame" steps in the bf16 ViT's FEW-FRAME form instead (key-split attention, K-split down
+projection: include/sslam_hip.h) - the stepper itself takes no argument for it, a step being a batch of one - as ordinary launches
+and from the captured graph alike (one stream, no parallel branches; the larger workspace is among the buffers the stepper holds);
+its steps equal that pipeline's run() over up to 8 frames bit for bit (tests/test_gpu_vit_few_frame.py).
 """
 from __future__ import annotations
 
@@ -36,7 +40,8 @@ class FrameStepper:
         tokens_in: the caller brings the ViT's tokens with every frame (the third-party ViT stays outside).
         use_graph=False: the same step as ordinary launches (the A/B for the graph, and the fallback while debugging).
         With the ViT inside, every step runs its few-frame form (a batch of one): the tokens of SequencePipeline.run over up to
-        8 frames bit for bit, those of a longer batch within the float64 bars (module docstring)."""
+        8 frames bit for bit, those of a longer batch within the float64 bars (module docstring).  Which few-frame form the bf16
+        ViT runs is the pipeline's choice (SequencePipeline(vit_form=...)): the small form by default, "few_frame" by name."""
         cfg = pipe.cfg
         if cfg.num_keypoints > cfg.grid ** 2:
             raise ValueError("num_keypoints > grid cells: that case reads a status word back on the host (SURVEY H6) and cannot be captured")

@@ -161,10 +161,13 @@ class ResampleTables:
 
 class SequencePipeline:
     def __init__(self, cfg: ExtractorConfig, selector_state: dict | None, refiner_state: dict | None, bn_state: dict | None = None,
-                 device="cuda", vit=None, empty_shapes: tuple | None = None, vit_precision: str = "bf16"):
+                 device="cuda", vit=None, empty_shapes: tuple | None = None, vit_precision: str = "bf16",
+                 vit_form: str | None = None):
         """vit: optional sslam_amd.vit.DinoV3ViT, or any module whose weights convert to it (vit.KEY_MAPS) - enables
         run(images, tokens=None): images -> A0 -> HIP ViT (A1) -> ...; vit_precision "bf16" (throughput form, bf16 MFMA
         operands) or "fp32" (the reference's numerics for A1: fp32 operands on the fp32 matrix pipe, csrc/vit_f32.hip)
+        vit_form: None, or "few_frame" (bf16 ViT only): batches of up to 8 frames - run() on a short sequence, every step of an
+        online.FrameStepper - take the bf16 ViT's few-frame launch form (HipViT.forward_features); larger batches are untouched.
         selector_state / refiner_state None + empty_shapes=(selector hidden, refiner blocks): uninitialised packed buffers,
         to be filled by the rank-0 weight broadcast (shard.pipeline_from_rank0)."""
         self.cfg = cfg
@@ -174,6 +177,10 @@ class SequencePipeline:
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {cfg.precision!r}")
         if vit_precision not in ("bf16", "fp32"):          # checked whether or not a ViT is given: a typo must not pass silently
             raise ValueError(f"vit_precision must be 'bf16' or 'fp32', got {vit_precision!r}")
+        if vit_form not in (None, "few_frame"):
+            raise ValueError(f"vit_form must be None or 'few_frame', got {vit_form!r}")
+        if vit_form == "few_frame" and vit_precision != "bf16":
+            raise ValueError("vit_form='few_frame' names a launch form of the bf16 ViT; the fp32 ViT already follows the batch")
         self.bf16 = cfg.precision == "bf16"
         if selector_state is None or refiner_state is None:
             if empty_shapes is None:
@@ -210,7 +217,7 @@ class SequencePipeline:
                 self.vit_hip = HipViTF32(vit, self.device)
             else:
                 self.vit_hip = HipViT(vit, self.device)
-        self.vit_precision = vit_precision
+        self.vit_precision, self.vit_form = vit_precision, vit_form
 
     def weight_tensors(self) -> list:
         """Every device buffer of packed weights / BatchNorm state, in a fixed order (6.7 MB fp32 at the shipped shapes)."""
@@ -259,7 +266,8 @@ class SequencePipeline:
         dword-aligned batch base), else the fp32 image, as the fp32 ViT always does - the same tokens either way.
         Cuts: fp32 - vit_chunk and the pieces change no bit (few-frame form up to 8 frames of the BATCH, one-pass above);
         bf16 - the form follows each LAUNCH GROUP (HipViT.forward_features), so the frames of a short last group may differ
-        from the same frames in a full group, within the bf16 bars against float64."""
+        from the same frames in a full group, within the bf16 bars against float64; with vit_form="few_frame" a batch of up to 8
+        frames runs the few-frame form in every group, and then neither vit_chunk nor the pieces change a bit."""
         if self.vit_hip is None:
             raise lib.SslamHipError("this pipeline was built without a ViT: pass tokens, or construct it with vit=")
         if vit_chunk is None:
@@ -280,11 +288,13 @@ class SequencePipeline:
             b = min(a + span, n)
             # the fp32 ViT consumes the fp32 image (its patch embedding is an fp32 contraction too); bf16: the patch rows
             patches = lib.preprocess_u8_patches(images_u8[a:b], size, th, tv) if self.vit_precision == "bf16" else None
+            whole = max(n, batch_frames or 0)
             if patches is not None:
-                self.vit_hip.forward_features(None, out=out[a:b], chunk=vit_chunk, patches=patches, size=size)
+                self.vit_hip.forward_features(None, out=out[a:b], chunk=vit_chunk, patches=patches, size=size, form=self.vit_form,
+                                              batch_frames=whole)
             else:
-                # only the fp32 ViT picks its form by the batch; the bf16 one picks it per launch group (HipViT.forward_features)
-                kw = dict(batch_frames=max(n, batch_frames or 0)) if self.vit_precision == "fp32" else {}
+                # the fp32 ViT picks its form by the batch; the bf16 one per launch group unless vit_form names one (HipViT.forward_features)
+                kw = dict(batch_frames=whole) if self.vit_precision == "fp32" else dict(form=self.vit_form, batch_frames=whole)
                 self.vit_hip.forward_features(self.preprocess(images_u8[a:b], reuse=self.vit_hip.n_streams < 2), out=out[a:b], chunk=vit_chunk,
                                               **kw)
         return out

@@ -64,7 +64,8 @@ class HipViT:
         return max(1, (506 * 128) // (5 + (size // 16) ** 2))
 
     def forward_features(self, images: torch.Tensor | None, out: torch.Tensor | None = None, chunk: int | None = None,
-                         patches: torch.Tensor | None = None, size: int | None = None) -> torch.Tensor:
+                         patches: torch.Tensor | None = None, size: int | None = None, form: str | None = None,
+                         batch_frames: int | None = None) -> torch.Tensor:
         """(B, 3, S, S) fp32 cuda -> (B, 5 + (S/16)^2, 384) fp32 tokens (final-LayerNormed), `chunk` frames per launch group.
         patches (with size = S): the bf16 patch rows of lib.preprocess_u8_patches (B, (S/16)^2, 768) instead of the image -
         no fp32 image, no im2patch pass, the same tokens bit for bit.
@@ -72,7 +73,14 @@ class HipViT:
         at 448 x 448) the small form with the two-launch MLP, above it the throughput form with the fused MLP, which sums the down
         projection in another order.  So the frames of a short last group may differ in the last bits from the same frames in a
         full group - within the bf16 bars against float64 (tests/test_gpu_harness.py::test_bf16_vit_form_follows_the_launch_group);
-        picking the form by the batch would need a library entry that names it."""
+        a caller that wants one form for every group names it.
+        form: None - the rule above, `batch_frames` accepted and ignored.  "small" / "throughput" - every launch group names that
+        form (sslam_vit_forward_form), whatever its length.  "few_frame" - if the batch (`batch_frames`, the size of
+        the batch these frames are a piece of; default: this call's frame count) has at most lib.VIT_FEW_FRAME_MAX_FRAMES frames,
+        every launch group names lib.VIT_FORM_FEW_FRAME (key-split attention, K-split down projection: include/sslam_hip.h) and a
+        frame's tokens do not depend on its position or on how the batch is cut; a larger batch runs exactly as with form=None."""
+        if form not in (None, "few_frame", "small", "throughput"):
+            raise ValueError(f"form must be None, 'few_frame', 'small' or 'throughput', got {form!r}")
         if patches is not None:
             n, s = patches.shape[0], int(size)
             assert patches.is_cuda and patches.dtype == torch.bfloat16 and patches.shape[1:] == ((s // 16) ** 2, 768)
@@ -87,16 +95,20 @@ class HipViT:
             self._rope[g] = (cos.float().contiguous(), sin.float().contiguous())
         self.w.rope_cos, self.w.rope_sin = self._rope[g][0].data_ptr(), self._rope[g][1].data_ptr()
         step = chunk or self.chunk_frames(s)
-        need = lib.vit_workspace_bytes(min(n, step), s)
+        if form == "few_frame":
+            named = lib.VIT_FORM_FEW_FRAME if max(n, batch_frames or 0) <= lib.VIT_FEW_FRAME_MAX_FRAMES else None
+        else:
+            named = {None: None, "small": lib.VIT_FORM_SMALL, "throughput": lib.VIT_FORM_THROUGHPUT}[form]
+        need = lib.vit_workspace_bytes(min(n, step), s, named)    # the first group is the largest; the need never decreases with n
         x = patches.contiguous() if patches is not None else images.detach().float().contiguous()
         if out is None:
             out = torch.empty((n, 5 + g * g, lib.C_FEAT), dtype=torch.float32, device=dev_of.device)
 
         def launch(a, ws):
             if patches is not None:
-                lib.vit_forward_patches(x[a:a + step], s, self.w, ws, out=out[a:a + step])
+                lib.vit_forward_patches(x[a:a + step], s, self.w, ws, out=out[a:a + step], form=named)
             else:
-                lib.vit_forward(x[a:a + step], self.w, ws, out=out[a:a + step])
+                lib.vit_forward(x[a:a + step], self.w, ws, out=out[a:a + step], form=named)
 
         starts = list(range(0, n, step))
         if len(starts) >= 2 and self.n_streams >= 2:

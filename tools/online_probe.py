@@ -42,8 +42,11 @@ for graph in (False, True):
         for i in range(n):
             o = st.step(imgs[i], toks[i]); int(o["match_count"]) if o["match_count"] is not None else None
     print("   ms per step (caller reads the count each frame): %.4f" % ((time.perf_counter() - t0) / 50 / n * 1e3))
-for prec in ("bf16", "fp32"):
-    pv = SequencePipeline(ExtractorConfig(), synth.selector_state(0), synth.refiner_state(0), device=dev, vit=DinoV3ViT().to(dev).eval(), vit_precision=prec)
+for prec, vit_form in (("bf16", None), ("bf16", "few_frame"), ("fp32", None)):
+    torch.manual_seed(0)
+    pv = SequencePipeline(ExtractorConfig(), synth.selector_state(0), synth.refiner_state(0), device=dev, vit=DinoV3ViT().to(dev).eval(), vit_precision=prec,
+                          vit_form=vit_form)
+    prec = prec + (" " + vit_form if vit_form else "")
     wantv = pv.run(imgs)
     outs = {}
     for graph in (False, True):
@@ -65,3 +68,26 @@ for prec in ("bf16", "fp32"):
         print("   ms per step (count read each frame): %.4f" % ((time.perf_counter() - t0) / 30 / n * 1e3))
     same = all(torch.equal(a[0][k], b[0][k]) for a, b in zip(outs[False], outs[True]) for k in ("idx", "descriptors", "intensity", "scores"))
     print("   graph == eager stepping:", same)
+
+# A/B of the bf16 ViT's forms inside the step: every stepper warm first, then five repeats per (vit_form, graph) taken alternately
+import statistics
+torch.manual_seed(0)
+dv = DinoV3ViT().to(dev).eval()
+steppers = {}
+for vit_form in (None, "few_frame"):
+    pv = SequencePipeline(ExtractorConfig(), synth.selector_state(0), synth.refiner_state(0), device=dev, vit=dv, vit_precision="bf16", vit_form=vit_form)
+    for graph in (False, True):
+        steppers[(vit_form, graph)] = FrameStepper(pv, 480, 640, use_graph=graph)
+def block(st, rounds):
+    for _ in range(rounds):
+        for i in range(n): st.step(imgs[i])
+for st in steppers.values(): block(st, 5)
+torch.cuda.synchronize()
+ms = {k: [] for k in steppers}
+for _ in range(5):
+    for k, st in steppers.items():
+        block(st, 1); torch.cuda.synchronize(); t0 = time.perf_counter()
+        block(st, 30); torch.cuda.synchronize(); ms[k].append((time.perf_counter() - t0) / 30 / n * 1e3)
+print("bf16 ViT inside the step, ms per frame (async), five alternating repeats and their median:")
+for (vit_form, graph), v in ms.items():
+    print("   vit_form %-9s graph %-5s median %.4f   repeats %s" % (vit_form, graph, statistics.median(v), " ".join("%.4f" % x for x in v)))
