@@ -8,8 +8,8 @@
  *
  * Conventions (all entries):
  *   - every pointer is a CALLER-OWNED DEVICE pointer unless the name ends in _host; the library never copies to
- *     the host and NEVER allocates or frees device memory.  The two entries whose fastest form needs scratch take it
- *     from the caller (sslam_selector_saliency_ws, sslam_sim_argmax_ws; sizes from sslam_workspace_bytes or the
+ *     the host and NEVER allocates or frees device memory.  The three entries whose fastest form needs scratch take it
+ *     from the caller (sslam_selector_saliency_ws, sslam_gather_refine_ws, sslam_sim_argmax_ws; sizes from sslam_workspace_bytes or the
  *     per-entry *_workspace_bytes); their forms without a workspace argument run a scratch-free launch shape with
  *     the same bits;
  *   - `stream` is a hipStream_t passed as void* (PyTorch: torch.cuda.current_stream().cuda_stream); calls only
@@ -48,17 +48,19 @@ long long sslam_launch_count(void);
 
 /* One caller-owned device scratch buffer (bytes, multiple of 256; 0 if none is needed) that serves every *_ws entry of
  * a pipeline step enqueued on one stream - the stages run in stream order and share it: n_frames frames of a G x G grid
- * through sslam_selector_saliency_ws, n_pairs pairs of K keypoints through sslam_sim_argmax_ws (n_pairs may be 0). */
+ * through sslam_selector_saliency_ws and, with K keypoints each, sslam_gather_refine_ws; n_pairs pairs of K keypoints through
+ * sslam_sim_argmax_ws (n_pairs may be 0). */
 long long sslam_workspace_bytes(int n_frames, int G, int K, int n_pairs);
 /* per-entry needs (what sslam_workspace_bytes takes the maximum of) */
 long long sslam_selector_saliency_workspace_bytes(int n_frames, int G);
+long long sslam_gather_refine_workspace_bytes(int n_frames, int K);
 long long sslam_sim_argmax_workspace_bytes(int n2, int n_pairs);
 
 /* TEST-ONLY: override one of the load-time knobs (name = its environment variable, e.g. "SSLAM_CONV_TAIL"); unset != 0
  * restores the value read from the environment when the library was loaded (else the built-in default).  Not thread-safe against running calls; product code never calls it.  Knobs:
  * SSLAM_M1_VARIANT, SSLAM_CONV_VARIANT, SSLAM_CONV_LATENCY_ROWS, SSLAM_CONV_LAT2_ROWS, SSLAM_CONV_NO_HALO, SSLAM_CONV_TAIL,
  * SSLAM_CONVBF_NO_HALO, SSLAM_CONVBF_TAIL, SSLAM_CONVBF_VARIANT, SSLAM_VIT_NO_FUSED_MLP, SSLAM_BN_FORM,
- * SSLAM_RT_STOP (csrc/common.h says what each selects). */
+ * SSLAM_RT_STOP, SSLAM_REFINE_DISTINCT (csrc/common.h says what each selects). */
 int sslam_test_set_knob(const char *name, long long value, int unset);
 
 /* ---- weight packing (host side, plain C++; run once per checkpoint) ------------------------------------------
@@ -165,6 +167,17 @@ int sslam_refine(const float *x, long long rows, const float *packed, int n_bloc
 /* ---- A6 + A7 fused: gather straight into the MLP's LDS tile (the pipeline's fast path). */
 int sslam_gather_refine(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
                         int n_blocks, float *desc, void *stream);
+/* The same descriptors with every DISTINCT keypoint of a frame run through the MLP once.  sslam_select_keypoints usually ends in
+ * the reference's pad (the NMS survivors, then the top raw saliencies, where the survivors re-appear: SURVEY H2), so ~7 % of a
+ * frame's keypoints repeat an earlier one; equal coordinates give equal descriptors.  A launch per frame finds, for every slot,
+ * the lowest slot of its frame with the same 64 coordinate BITS (+0.0 and -0.0 stay apart, a NaN coordinate never merges), a
+ * second packs the distinct rows of all frames into one list, the MLP kernel runs the list (its arithmetic per row is that of
+ * sslam_gather_refine, and rows are independent in it: the same bits), and a copy fills the repeated slots.  Taken for launches of
+ * more than one round of MLP workgroups (24 576 rows) with K <= 4096; smaller ones, a NULL workspace or one shorter than
+ * sslam_gather_refine_workspace_bytes (0 where the direct launch is taken) run the launch of sslam_gather_refine.
+ * After the list form the workspace holds, as int32: [f] the number of distinct keypoints of frame f, [n_frames] their sum. */
+int sslam_gather_refine_ws(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
+                           int n_blocks, float *desc, void *workspace, long long workspace_bytes, void *stream);
 
 /* ---- A6 + A7, bf16 THROUGHPUT mode (BASELINE.json configs[1]): the same gather + MLP with bf16
  * GEMM operands (v_mfma_f32_32x32x16_bf16), fp32 accumulation / residual / LayerNorm statistics / L2 normalisation;

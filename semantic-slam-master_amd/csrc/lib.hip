@@ -12,7 +12,8 @@ long long g_knob_at_load[KNOB_COUNT];   // what the environment said when the li
 const char *const kKnobNames[KNOB_COUNT] = {
     "SSLAM_M1_VARIANT",   "SSLAM_CONV_VARIANT",  "SSLAM_CONV_LATENCY_ROWS", "SSLAM_CONV_LAT2_ROWS",   "SSLAM_CONV_NO_HALO",
     "SSLAM_CONV_TAIL",    "SSLAM_CONVBF_NO_HALO", "SSLAM_CONVBF_TAIL",      "SSLAM_CONVBF_VARIANT",   "SSLAM_VIT_NO_FUSED_MLP",
-    "SSLAM_BN_FORM",      "SSLAM_VIT_F32_NO_KEY_SPLIT", "SSLAM_RT_STOP"};
+    "SSLAM_BN_FORM",      "SSLAM_VIT_F32_NO_KEY_SPLIT", "SSLAM_RT_STOP",
+    "SSLAM_REFINE_DISTINCT"};
 // the ONE place the environment is read: when the library is loaded
 struct KnobInit {
     KnobInit() {
@@ -34,7 +35,8 @@ extern "C" long long sslam_workspace_bytes(int n_frames, int G, int K, int n_pai
     if (n_frames <= 0 || G <= 0 || K <= 0 || n_pairs < 0) return SSLAM_E_INVALID;
     const long long a = sslam_selector_saliency_workspace_bytes(n_frames, G);
     const long long b = n_pairs > 0 ? sslam_sim_argmax_workspace_bytes(K, n_pairs) : 0;
-    const long long m = a > b ? a : b;
+    const long long c = sslam_gather_refine_workspace_bytes(n_frames, K);
+    const long long m = a > b ? (a > c ? a : c) : (b > c ? b : c);
     return (m + 255) & ~255LL;
 }
 

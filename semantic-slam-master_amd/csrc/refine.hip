@@ -120,6 +120,15 @@ __device__ __forceinline__ void lds_quads_done() { asm volatile("s_waitcnt lgkmc
 __device__ __forceinline__ unsigned lds_addr(const float *p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const float *)p;
 }
+// ReLU of an MFMA accumulator: ONE v_max_f32.  From `x > 0 ? x : 0` or
+// fmaxf hipcc first canonicalises the operand (v_max_f32 x, x, x - it quiets a signalling NaN, which no arithmetic result is)
+// and then takes the maximum: 96 instructions per sweep where 48 do the work, all of them issue time the matrix pipe does not
+// get.  Same bits for every input that can occur here: max(+0, -0) = +0 and max(0, quiet NaN) = 0, as the ternary gives.
+__device__ __forceinline__ float relu(float x) {
+    float y;
+    asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(x));
+    return y;
+}
 template <int I>
 __device__ __forceinline__ void store_rows_from(unsigned row_lds, const f32x16 (&v)[3]) {
     if constexpr (I < 12) {
@@ -220,20 +229,32 @@ __device__ unsigned long long g_probe_refine[8 * 4096];
 #define PRIO_GEMM() __builtin_amdgcn_s_setprio(0)
 enum { PR_GATHER = 0, PR_GEMM = 1, PR_LN = 2, PR_STORE = 3, PR_BARRIER = 4 };
 
+// WL (work list): row i of the launch is global row list[i], i < *n_list - the distinct keypoints of all frames, packed by
+// distinct_rep_kernel / distinct_list_kernel below; the grid is sized for the worst case (every row distinct) and the
+// workgroups beyond the device-side tile count leave at once.  Rows are independent in this kernel (every fma chain, row
+// statistic and norm uses one row only), so which tile a row sits in changes no bit of it.
+template <bool WL>
 __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(const float *__restrict__ feat, int G,
                                                              const float *__restrict__ kp_xy, int K,
                                                              const float *__restrict__ x_in, long long rows,
+                                                             const int *__restrict__ list, const int *__restrict__ n_list,
                                                              RefArgs args, float *__restrict__ desc) {
     __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
     float *H = smem, *scratch = smem + H_FLOATS;
     const int tid = threadIdx.x;
+    int n_tiles = gridDim.x;
+    if constexpr (WL) {
+        rows = *n_list;
+        n_tiles = (int)((rows + RM - 1) / RM);
+        if ((int)blockIdx.x >= n_tiles) return;
+    }
     PROBE_BEGIN();
     PRIO_OTHER();
     // XCD-aware order: workgroup b runs on XCD b % 8; give every XCD one contiguous range of row tiles so that the ~8
     // tiles gathering from one frame's feature map share that XCD's L2 instead of fetching the frame into all eight
     long long R0;
     {
-        const int n_tiles = gridDim.x, b = blockIdx.x, q = n_tiles / 8, rem = n_tiles % 8, x = b % 8;
+        const int b = blockIdx.x, q = n_tiles / 8, rem = n_tiles % 8, x = b % 8;
         R0 = (long long)((x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + b / 8) * RM;
     }
     const float *pk = args.packed;
@@ -249,6 +270,7 @@ __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(c
         const int row = tid >> 3, part = tid & 7;
         long long R = R0 + row;
         if (R > rows - 1) R = rows - 1;
+        if constexpr (WL) R = list[R];
         float *dst = H + row * LDH;
         if (feat) {
             const long long f = R / K;
@@ -288,7 +310,7 @@ __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(c
 #pragma unroll
     for (int t = 0; t < 3; t++)
 #pragma unroll
-        for (int e = 0; e < 16; e++) X[t][e] = acc[t][e] > 0.0f ? acc[t][e] : 0.0f;
+        for (int e = 0; e < 16; e++) X[t][e] = relu(acc[t][e]);
 
     // ---- residual blocks (descriptor_refiner.py:108-126) --------------------------------------------------------
     for (int b = 0; b < L.n_blocks; b++) {
@@ -298,7 +320,7 @@ __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(c
 #pragma unroll
         for (int t = 0; t < 3; t++)
 #pragma unroll
-            for (int e = 0; e < 16; e++) acc[t][e] = acc[t][e] > 0.0f ? acc[t][e] : 0.0f;
+            for (int e = 0; e < 16; e++) acc[t][e] = relu(acc[t][e]);
         PROBE(PR_LN, layernorm_store(H, part0, part1, pk + L.blk[b][4], pk + L.blk[b][5], tid, acc);)
         PROBE(PR_BARRIER, __syncthreads();)
         PRIO_GEMM(); PROBE(PR_GEMM, gemm_lds<3>(H, wrs, (int)L.blk[b][6] * 4, pk + L.blk[b][7], tid, acc);) PRIO_OTHER();
@@ -306,6 +328,7 @@ __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(c
         for (int t = 0; t < 3; t++)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
+                // an add's result is canonical: hipcc emits the one v_max_f32 itself here, and keeps the adds packed
                 const float v = acc[t][e] + X[t][e];
                 X[t][e] = v > 0.0f ? v : 0.0f;
             }
@@ -324,12 +347,14 @@ __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(c
         for (int e = 0; e < 16; e++) ss = __builtin_fmaf(o[0][e], o[0][e], ss);
         const float den = fmaxf(sqrtf(row_total(ss, part0, tid)), 1e-12f);
         if (R0 + r < rows) {
+            long long Ro = R0 + r;
+            if constexpr (WL) Ro = list[Ro];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 f32x4 w4;
 #pragma unroll
                 for (int i = 0; i < 4; i++) w4[i] = o[0][4 * q + i] / den;
-                *reinterpret_cast<f32x4 *>(desc + (R0 + r) * SSLAM_D + wn * 32 + 8 * q + 4 * h) = w4;
+                *reinterpret_cast<f32x4 *>(desc + Ro * SSLAM_D + wn * 32 + 8 * q + 4 * h) = w4;
             }
         }
     }
@@ -347,14 +372,175 @@ __global__ __launch_bounds__(256) void gather_kernel(const float *__restrict__ f
     *reinterpret_cast<float4 *>(out + R * SSLAM_C + c0) = blend4(t, c0);
 }
 
+// ---- distinct-row work list ------------------------------------------------------------------------------------------
+// select_keypoints almost always ends in the reference's pad (select.hip: the NMS survivors first, then the top raw
+// saliencies, among which the survivors re-appear): ~7 % of a frame's keypoints repeat an earlier one bit for bit, and
+// equal coordinates give equal taps, equal gathered rows and equal descriptors.  Three small launches around the MLP let it
+// run every distinct (x, y) of a frame once:
+//   distinct_rep_kernel   rep[R] = the lowest row of R's frame with the same 64 coordinate bits; counts[f] = distinct rows
+//   distinct_list_kernel  list = the rows with rep[R] == R, frames in order, slots ascending, all frames in ONE run (a tile
+//                         boundary per frame would give back half the gain); counts[n_frames] = their number
+//   copy_duplicates_kernel (after the MLP)  desc[R] = desc[rep[R]] where rep[R] != R
+// Workspace (int32 words): counts[n_frames + 1] | rep[rows] | list[rows], each part on a 256-byte boundary.
+constexpr int DN = 256;                     // threads of the two list kernels, one workgroup per frame
+constexpr int DISTINCT_MAX_K = 4096;        // the LDS hash table holds 2 K slots (32 KB here)
+// Up to three workgroups per CU are resident: a launch of no more than 256 x 3 tiles is ONE round with or without the
+// duplicates, and the extra launches would only add latency (single frames, the online stepper).
+constexpr long long DISTINCT_MIN_ROWS = 256 * 3 * RM + 1;
+
+__device__ __forceinline__ bool is_nan_bits(unsigned u) { return (u & 0x7fffffffu) > 0x7f800000u; }
+__device__ __forceinline__ unsigned hash_xy(unsigned x, unsigned y) {
+    unsigned h = x * 0x9e3779b1u ^ (y + 0x7f4a7c15u) * 0x85ebca6bu;
+    h ^= h >> 15;
+    h *= 0x2c1b3c6du;
+    return h ^ (h >> 13);
+}
+// sum of v over the workgroup (DN threads); `red` is an LDS array of DN / 64 ints, free again after the call
+__device__ __forceinline__ int block_sum(int v, int *red, int tid) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < DN / 64; w++) s += red[w];
+    return s;
+}
+
+// Open addressing on the coordinate BITS (+0.0 and -0.0 differ; a NaN coordinate never merges): a table slot holds a row of
+// its key, lowered to the smallest such row by atomicMin - so the result does not depend on the order of the insertions.
+__global__ __launch_bounds__(DN) void distinct_rep_kernel(const unsigned *__restrict__ kp_bits, int K, int T,
+                                                          int *__restrict__ rep, int *__restrict__ counts) {
+    extern __shared__ int tab[];            // T slots, T a power of two >= 2 K: every probe sequence meets an empty slot
+    __shared__ int red[DN / 64];
+    const int tid = threadIdx.x, f = blockIdx.x, mask = T - 1;
+    const unsigned *kp = kp_bits + 2ll * f * K;
+    for (int i = tid; i < T; i += DN) tab[i] = -1;
+    __syncthreads();
+    for (int j = tid; j < K; j += DN) {
+        const unsigned x = kp[2 * j], y = kp[2 * j + 1];
+        if (is_nan_bits(x) || is_nan_bits(y)) continue;
+        for (unsigned h = hash_xy(x, y) & mask;; h = (h + 1) & mask) {
+            const int cur = atomicCAS(&tab[h], -1, j);
+            if (cur == -1) break;
+            if (kp[2 * cur] == x && kp[2 * cur + 1] == y) {
+                atomicMin(&tab[h], j);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    int n = 0;
+    for (int j = tid; j < K; j += DN) {
+        const unsigned x = kp[2 * j], y = kp[2 * j + 1];
+        int r = j;
+        if (!(is_nan_bits(x) || is_nan_bits(y)))
+            for (unsigned h = hash_xy(x, y) & mask;; h = (h + 1) & mask) {
+                const int cur = tab[h];     // never empty before the key's own slot: the slot was on j's insertion path
+                if (cur < 0) break;
+                if (kp[2 * cur] == x && kp[2 * cur + 1] == y) {
+                    r = cur;
+                    break;
+                }
+            }
+        rep[(long long)f * K + j] = f * K + r;
+        n += r == j;
+    }
+    n = block_sum(n, red, tid);
+    if (tid == 0) counts[f] = n;
+}
+
+__global__ __launch_bounds__(DN) void distinct_list_kernel(const int *__restrict__ rep, int K, int n_frames,
+                                                           int *__restrict__ counts, int *__restrict__ list) {
+    __shared__ int red[DN / 64];
+    const int tid = threadIdx.x, f = blockIdx.x, lane = tid & 63;
+    int before = 0;                         // distinct rows of the frames in front of this one
+    for (int i = tid; i < f; i += DN) before += counts[i];
+    before = block_sum(before, red, tid);
+    // thread tid owns the slots [b, e) of the frame; exclusive scan of the per-thread counts
+    const int chunk = (K + DN - 1) / DN, b = min(tid * chunk, K), e = min(b + chunk, K), R0 = f * K;
+    int local = 0;
+    for (int j = b; j < e; j++) local += rep[R0 + j] == R0 + j;
+    int incl = local;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    __syncthreads();
+    if (lane == 63) red[tid >> 6] = incl;
+    __syncthreads();
+    int slot = before + incl - local;
+    for (int w = 0; w < (tid >> 6); w++) slot += red[w];
+    for (int j = b; j < e; j++)
+        if (rep[R0 + j] == R0 + j) list[slot++] = R0 + j;
+    if (f == n_frames - 1 && tid == DN - 1) counts[n_frames] = slot;     // the last thread of the last frame ends at the total
+}
+
+__global__ __launch_bounds__(256) void copy_duplicates_kernel(const int *__restrict__ rep, long long rows, float *desc) {
+    const long long item = (long long)blockIdx.x * 256 + threadIdx.x;   // one float4 of one row
+    const long long R = item / (SSLAM_D / 4);
+    if (R >= rows) return;
+    const long long src = rep[R];
+    if (src == R) return;
+    const int c0 = (int)(item % (SSLAM_D / 4)) * 4;
+    *reinterpret_cast<float4 *>(desc + R * SSLAM_D + c0) = *reinterpret_cast<const float4 *>(desc + src * SSLAM_D + c0);
+}
+
+struct DistinctWs {
+    long long counts, rep, list, bytes;     // byte offsets of the three parts, and the total
+};
+DistinctWs distinct_ws(int n_frames, long long rows) {
+    auto up = [](long long b) { return (b + 255) & ~255LL; };
+    DistinctWs w;
+    w.counts = 0;
+    w.rep = up(((long long)n_frames + 1) * 4);
+    w.list = w.rep + up(rows * 4);
+    w.bytes = w.list + up(rows * 4);
+    return w;
+}
+// the launch form of a (n_frames, K) call, from its shape alone; test-only knob SSLAM_REFINE_DISTINCT: 0 = direct, 1 = work list
+bool distinct_form(int n_frames, int K) {
+    const long long rows = (long long)n_frames * K;
+    if (K > DISTINCT_MAX_K || rows > 0x7fffffffLL) return false;        // rows are int32 in the list
+    const long long forced = sslam_knob(KNOB_REFINE_DISTINCT, -1);
+    return forced < 0 ? rows >= DISTINCT_MIN_ROWS : forced != 0;
+}
+
 int launch_refine(const float *feat, int G, const float *kp_xy, int K, const float *x_in, long long rows,
                   const float *packed, int n_blocks, float *desc, void *stream) {
     RefArgs a;
     a.packed = packed;
     if (sslam_refiner_layout(n_blocks, &a.lay) != SSLAM_OK) return SSLAM_E_UNSUPPORTED;
     const unsigned grid = (unsigned)((rows + RM - 1) / RM);
-    hipLaunchKernelGGL(gather_refine_kernel, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, feat, G, kp_xy, K, x_in, rows,
-                       a, desc);
+    hipLaunchKernelGGL(gather_refine_kernel<false>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, feat, G, kp_xy, K, x_in,
+                       rows, (const int *)nullptr, (const int *)nullptr, a, desc);
+    SSLAM_CHECK_LAUNCH();
+    return SSLAM_OK;
+}
+
+int launch_refine_distinct(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed, int n_blocks,
+                           float *desc, void *workspace, void *stream) {
+    RefArgs a;
+    a.packed = packed;
+    if (sslam_refiner_layout(n_blocks, &a.lay) != SSLAM_OK) return SSLAM_E_UNSUPPORTED;
+    const long long rows = (long long)n_frames * K;
+    const DistinctWs w = distinct_ws(n_frames, rows);
+    int *counts = (int *)((char *)workspace + w.counts), *rep = (int *)((char *)workspace + w.rep),
+        *list = (int *)((char *)workspace + w.list);
+    int T = 64;
+    while (T < 2 * K) T <<= 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(distinct_rep_kernel, dim3(n_frames), dim3(DN), (size_t)T * 4, st, (const unsigned *)kp_xy, K, T, rep, counts);
+    SSLAM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(distinct_list_kernel, dim3(n_frames), dim3(DN), 0, st, rep, K, n_frames, counts, list);
+    SSLAM_CHECK_LAUNCH();
+    const unsigned grid = (unsigned)((rows + RM - 1) / RM);        // worst case: the host does not know the count
+    hipLaunchKernelGGL(gather_refine_kernel<true>, dim3(grid), dim3(NTHR), 0, st, feat, G, kp_xy, K, (const float *)nullptr, rows,
+                       (const int *)list, (const int *)(counts + n_frames), a, desc);
+    SSLAM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(copy_duplicates_kernel, dim3((unsigned)((rows * (SSLAM_D / 4) + 255) / 256)), dim3(256), 0, st, rep, rows, desc);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }
@@ -420,6 +606,21 @@ extern "C" int sslam_gather_refine(const float *feat, int n_frames, int G, const
                                    int n_blocks, float *desc, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
+    return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, desc, stream);
+}
+
+extern "C" long long sslam_gather_refine_workspace_bytes(int n_frames, int K) {
+    if (n_frames <= 0 || K <= 0) return SSLAM_E_INVALID;
+    return distinct_form(n_frames, K) ? distinct_ws(n_frames, (long long)n_frames * K).bytes : 0;
+}
+
+extern "C" int sslam_gather_refine_ws(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
+                                      int n_blocks, float *desc, void *workspace, long long workspace_bytes, void *stream) {
+    if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
+    if (distinct_form(n_frames, K) && workspace && !((uintptr_t)workspace & 3) &&
+        workspace_bytes >= distinct_ws(n_frames, (long long)n_frames * K).bytes)
+        return launch_refine_distinct(feat, n_frames, G, kp_xy, K, packed, n_blocks, desc, workspace, stream);
     return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, desc, stream);
 }
 

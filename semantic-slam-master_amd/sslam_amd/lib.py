@@ -74,6 +74,7 @@ EXPORTS = [
     "sslam_bn_tokens_bf16copy", "sslam_refiner_bf16_bytes", "sslam_refiner_pack_bf16_host", "sslam_refine_bf16", "sslam_gather_refine_bf16",
     "sslam_workspace_bytes", "sslam_selector_saliency_workspace_bytes", "sslam_sim_argmax_workspace_bytes",
     "sslam_selector_saliency_ws", "sslam_sim_argmax_ws", "sslam_test_set_knob",
+    "sslam_gather_refine_ws", "sslam_gather_refine_workspace_bytes",
     "sslam_preprocess_u8_patches", "sslam_vit_forward_patches", "sslam_vit_f32_workspace_bytes", "sslam_vit_forward_f32",
     "sslam_vit_f32_pack_linear_host", "sslam_vit_forward_f32_form",
     "sslam_vit_workspace_bytes_form", "sslam_vit_forward_form", "sslam_vit_forward_patches_form",
@@ -100,7 +101,7 @@ def lib():
         L.sslam_selector_saliency.argtypes = [p, i, i, p, p, p, p, i, p, p]
         L.sslam_selector_saliency_ws.argtypes = [p, i, i, p, p, p, p, i, p, p, ll, p]
         for fn, at in ((L.sslam_workspace_bytes, [i, i, i, i]), (L.sslam_selector_saliency_workspace_bytes, [i, i]),
-                       (L.sslam_sim_argmax_workspace_bytes, [i, i])):
+                       (L.sslam_sim_argmax_workspace_bytes, [i, i]), (L.sslam_gather_refine_workspace_bytes, [i, i])):
             fn.restype, fn.argtypes = ll, at
         L.sslam_test_set_knob.argtypes = [C.c_char_p, ll, i]
         L.sslam_select_keypoints.argtypes = [p, i, i, i, i, d, p, p, p, p, p, p]
@@ -109,6 +110,7 @@ def lib():
         L.sslam_refiner_pack_host.argtypes = [p, i, p]
         L.sslam_refine.argtypes = [p, ll, p, i, p, p]
         L.sslam_gather_refine.argtypes = [p, i, i, p, i, p, i, p, p]
+        L.sslam_gather_refine_ws.argtypes = [p, i, i, p, i, p, i, p, p, ll, p]
         L.sslam_keypoint_intensity.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, i, p, p]
         L.sslam_sim_argmax.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p]
         L.sslam_sim_argmax_ws.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p, ll, p]
@@ -403,14 +405,24 @@ def refine(x, packed, n_blocks, out=None):
     return out
 
 
-def gather_refine(feat, kp, packed, n_blocks, out=None):
+def gather_refine(feat, kp, packed, n_blocks, out=None, workspace=None):
+    """workspace: optional caller-owned scratch tensor (sslam_workspace_bytes); allocated here through torch if absent and the
+    launch form needs one (the distinct-row work list of launches beyond one round of MLP workgroups).  After such a launch
+    the scratch starts with the int32 distinct-keypoint counts of the n frames and their sum (gather_refine_counts)."""
     n, g = feat.shape[0], feat.shape[1]
     K = kp.shape[1]
     if out is None:
         out = torch.empty((n, K, D_OUT), dtype=torch.float32, device=feat.device)
-    _run("gather_refine", lib().sslam_gather_refine, (feat, kp, packed, out,),
-         _dp(feat), n, g, _dp(kp), K, _dp(packed), n_blocks, _dp(out))
+    ws, wsb = _scratch(workspace, int(lib().sslam_gather_refine_workspace_bytes(n, K)), feat.device)
+    _run("gather_refine", lib().sslam_gather_refine_ws, (feat, kp, packed, out, ws),
+         _dp(feat), n, g, _dp(kp), K, _dp(packed), n_blocks, _dp(out), _dp(ws), wsb)
     return out
+
+
+def gather_refine_counts(workspace, n_frames: int):
+    """(per-frame distinct-keypoint counts, their sum) that the last work-list gather_refine over n_frames left in `workspace`."""
+    c = workspace[: 4 * (n_frames + 1)].view(torch.int32)
+    return c[:n_frames], c[n_frames]
 
 
 def gather_refine_bf16(feat, kp, packed_bf16, n_blocks, out=None):

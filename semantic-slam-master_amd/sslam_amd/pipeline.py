@@ -373,7 +373,7 @@ class SequencePipeline:
         if self.bf16:
             lib.gather_refine_bf16(feat, out["keypoints_patch"], self.refiner.packed_bf16, self.refiner.n_blocks, out=out["descriptors"])
         else:
-            lib.gather_refine(feat, out["keypoints_patch"], self.refiner.packed, self.refiner.n_blocks, out=out["descriptors"])
+            lib.gather_refine(feat, out["keypoints_patch"], self.refiner.packed, self.refiner.n_blocks, out=out["descriptors"], workspace=ws)
         if images_ready is not None:
             torch.cuda.current_stream(self.device).wait_event(images_ready)
         if images_u8 is not None and "intensity" in out:
