@@ -9,7 +9,7 @@
  * Conventions (all entries):
  *   - every pointer is a CALLER-OWNED DEVICE pointer unless the name ends in _host; the library never copies to
  *     the host and NEVER allocates or frees device memory.  The three entries whose fastest form needs scratch take it
- *     from the caller (sslam_selector_saliency_ws, sslam_gather_refine_ws, sslam_sim_argmax_ws; sizes from sslam_workspace_bytes or the
+ *     from the caller (sslam_selector_saliency_ws, sslam_gather_refine_ws, sslam_sim_argmax_ws and its pair-list form sslam_sim_argmax_pairs; sizes from sslam_workspace_bytes or the
  *     per-entry *_workspace_bytes); their forms without a workspace argument run a scratch-free launch shape with
  *     the same bits;
  *   - `stream` is a hipStream_t passed as void* (PyTorch: torch.cuda.current_stream().cuda_stream); calls only
@@ -227,6 +227,32 @@ int sslam_match_finalize(const int32_t *nn12, const float *s12, const int32_t *n
                          const float *intensity1, const float *intensity2, float w_desc, float w_sal,
                          float min_saliency, float min_sim, float min_intensity, int64_t *matches, float *quality,
                          int32_t *count, void *stream);
+
+/* ---- M1 over a PAIR LIST in device memory: the two entries above for pairs no stride can express - several spacings of an
+ * online step in one launch pair, a frame against a caller's keyframes, loop-closure candidates.
+ * bank (n_bank, K, 128) fp32, frame_stride floats between frames (alignment rules of sslam_sim_argmax_ws: a 16-byte aligned
+ * base, a stride that is a multiple of 4 floats).  pair_first / pair_second: DEVICE int32 arrays of n_pairs frame indices into
+ * the bank; pair p matches d1 = frame pair_first[p] against d2 = frame pair_second[p], n1 = n2 = K.  Any two frames make a
+ * pair: in any order, the same frame twice, a pair listed twice.  The lists are read by the kernels, never by the host: the
+ * calls only enqueue, a list may be written by earlier work of the same stream, and a captured graph replays with whatever
+ * the lists hold then.
+ * Per pair the arithmetic, the two launch forms, the rule and the knob that choose between them and the workspace
+ * (sslam_sim_argmax_workspace_bytes(K, n_pairs)) are those of sslam_sim_argmax_ws: the same bits as the strided entries on the
+ * same two frames.  Outputs as there, one row per listed pair in list order.
+ * ABSENT pairs: a pair either of whose indices lies outside [0, n_bank) - write -1 - is absent.  Its workgroups decide that
+ * from the two index words before any address is formed from them and read no bank: no index value makes the library read
+ * outside the banks described here.  An absent pair's rows: nn12 = nn21 = 0, s12 = s21 = second12 = 0.0f, count = 0, matches
+ * and quality zeroed like the slots past the count.
+ * sslam_match_finalize_pairs: scores_bank (n_bank, K) with score_stride floats between frames and intensity_bank (may be NULL)
+ * with the same stride are indexed by the same two lists. */
+int sslam_sim_argmax_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                           const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21,
+                           float *second12, void *workspace, long long workspace_bytes, void *stream);
+int sslam_match_finalize_pairs(const int32_t *nn12, const float *s12, const int32_t *nn21, int K, int n_bank,
+                               const int32_t *pair_first, const int32_t *pair_second, int n_pairs, const float *scores_bank,
+                               long long score_stride, const float *intensity_bank, float w_desc, float w_sal,
+                               float min_saliency, float min_sim, float min_intensity, int64_t *matches, float *quality,
+                               int32_t *count, void *stream);
 
 /* ---- A1: DINOv3 ViT-S/16 forward.  Replaces the third-party call
  * `self.dino.forward_features(images)` at dino_backbone.py:85 (timm model "vit_small_patch16_dinov3"): 16x16 patch

@@ -142,19 +142,46 @@ __device__ __forceinline__ void red_steps(const f32x16 (&acc)[2], int s, int nc,
     }
 }
 
+// WHICH two frames pair p matches: the last parameter of sim_argmax_kernel and match_finalize_kernel.  frames() gives the frame
+// indices that scale the strides of the descriptor / score / intensity bases, or false for an ABSENT pair, whose workgroups
+// write the fill (indices 0, similarities 0.0f, count 0, zeroed rows) and return without forming an address from the pair's
+// index words.
+struct StridedPairs {      // pair p = base + p * stride on both sides: an empty kernel argument, the code of the strided entries
+    __device__ __forceinline__ bool frames(long long p, long long &f1, long long &f2) const {
+        f1 = f2 = p;
+        return true;
+    }
+    static __device__ __forceinline__ bool unwritten(unsigned long long) { return false; }
+};
+struct ListedPairs {       // pair p = frames (first[p], second[p]) of one bank of n_bank frames; the lists live in DEVICE memory
+    const int *first, *second;
+    int n_bank;
+    __device__ __forceinline__ bool frames(long long p, long long &f1, long long &f2) const {
+        const int a = first[p], b = second[p];      // p is uniform over the workgroup: two scalar loads
+        if ((unsigned)a >= (unsigned)n_bank || (unsigned)b >= (unsigned)n_bank) return false;      // -1: the documented sentinel
+        f1 = a;
+        f2 = b;
+        return true;
+    }
+    // keys_decode_kernel: a key nobody raised above the zero fill.  Every candidate of a PRESENT pair receives keys, and none of
+    // them is 0 (the low word is ~query index, the index below 2^31), so this is an absent pair's - told without the lists
+    static __device__ __forceinline__ bool unwritten(unsigned long long key) { return key == 0ull; }
+};
+
 // ONEPASS = false: grid (query blocks, 2 directions, pairs) - S is evaluated once per direction, nothing but the outputs
 //                  is written (single pairs / small batches: twice the workgroups to spread over the CUs).
 // ONEPASS = true:  grid (query blocks, 1, pairs) - S is evaluated ONCE; the column direction (nn21) is reduced over the
 //                  32 query lanes of each half-wave by a reduce-scatter butterfly on sim_key()s and merged across waves
 //                  and workgroups with a 64-bit atomic max into `keys` (n_pairs x n2, zeroed), decoded by keys_decode_kernel.
 // SECOND: also the runner-up of the row direction (second12; the ratio-test matchers M2 / M4).
-template <bool ONEPASS, bool SECOND>
+template <bool ONEPASS, bool SECOND, class PAIRS>
 __global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restrict__ desc1, long long stride1, int n1,
                                                             const float *__restrict__ desc2, long long stride2, int n2,
                                                             int *__restrict__ nn12, float *__restrict__ s12,
                                                             int *__restrict__ nn21, float *__restrict__ s21,
                                                             float *__restrict__ second12,
-                                                            unsigned long long *__restrict__ keys, int n_pairs, int qblocks) {
+                                                            unsigned long long *__restrict__ keys, int n_pairs, int qblocks,
+                                                            PAIRS pairs) {
     __shared__ __attribute__((aligned(16))) float Cs[2 * CB * LDD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int dir = blockIdx.y;
@@ -164,8 +191,19 @@ __global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restr
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const long long pair = (long long)(slot / qblocks) * 8 + xcd;
     if (pair >= n_pairs) return;
-    const float *q = dir == 0 ? desc1 + pair * stride1 : desc2 + pair * stride2;
-    const float *c = dir == 0 ? desc2 + pair * stride2 : desc1 + pair * stride1;
+    long long f1, f2;
+    if (!pairs.frames(pair, f1, f2)) {      // the fill of this block's queries; the column direction of the single-evaluation
+        const int i = (slot % qblocks) * QB + tid;                                  // form is filled by keys_decode_kernel
+        if (tid < QB && i < (dir == 0 ? n1 : n2)) {
+            (dir == 0 ? nn12 + pair * n1 : nn21 + pair * n2)[i] = 0;
+            float *val = dir == 0 ? s12 : s21;
+            if (val) val[pair * (dir == 0 ? n1 : n2) + i] = 0.0f;
+            if (dir == 0 && second12) second12[pair * n1 + i] = 0.0f;
+        }
+        return;
+    }
+    const float *q = dir == 0 ? desc1 + f1 * stride1 : desc2 + f2 * stride2;
+    const float *c = dir == 0 ? desc2 + f2 * stride2 : desc1 + f1 * stride1;
     const int nq = dir == 0 ? n1 : n2, nc = dir == 0 ? n2 : n1;
     const int q0 = (slot % qblocks) * QB;
     if (q0 >= nq) return;
@@ -295,11 +333,17 @@ __global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restr
     }
 }
 
+template <class PAIRS>
 __global__ __launch_bounds__(256) void keys_decode_kernel(const unsigned long long *__restrict__ keys, long long n, int n1,
                                                            int *__restrict__ nn21, float *__restrict__ s21) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const unsigned long long kk = keys[i];
+    if (PAIRS::unwritten(kk)) {      // an absent pair's keys are the zero fill: not a similarity
+        nn21[i] = 0;
+        if (s21) s21[i] = 0.0f;
+        return;
+    }
     unsigned u = (unsigned)(kk >> 32);
     u ^= (u >> 31) ? 0x80000000u : 0xffffffffu;
     // with finite similarities a lane that holds a query always wins (a lane beyond the last query contributes the key of
@@ -310,6 +354,7 @@ __global__ __launch_bounds__(256) void keys_decode_kernel(const unsigned long lo
 }
 
 // one workgroup per pair: mutual check, thresholds, quality, ordered compaction (ascending idx1)
+template <class PAIRS>
 __global__ __launch_bounds__(256) void match_finalize_kernel(const int *__restrict__ nn12, const float *__restrict__ s12,
                                                               const int *__restrict__ nn21, int n1, int n2,
                                                               const float *__restrict__ sc1, long long ss1,
@@ -317,18 +362,28 @@ __global__ __launch_bounds__(256) void match_finalize_kernel(const int *__restri
                                                               const float *__restrict__ in1, const float *__restrict__ in2,
                                                               float w_desc, float w_sal, float t_sal, float t_sim,
                                                               float t_int, long long *__restrict__ matches,
-                                                              float *__restrict__ quality, int *__restrict__ count) {
+                                                              float *__restrict__ quality, int *__restrict__ count, PAIRS pairs) {
     __shared__ int wave_tot[4];
     __shared__ int running;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long p = blockIdx.x;
+    long long f1, f2;
+    if (!pairs.frames(p, f1, f2)) {      // an absent pair: no match, rows zeroed like the slots past the count below
+        if (tid == 0) count[p] = 0;
+        for (int sl = tid; sl < n1; sl += 256) {
+            matches[(p * n1 + sl) * 2] = 0;
+            matches[(p * n1 + sl) * 2 + 1] = 0;
+            quality[p * n1 + sl] = 0.f;
+        }
+        return;
+    }
     nn12 += p * n1;
     s12 += p * n1;
     nn21 += p * n2;
-    sc1 += p * ss1;
-    sc2 += p * ss2;
-    if (in1) in1 += p * ss1;
-    if (in2) in2 += p * ss2;
+    sc1 += f1 * ss1;
+    sc2 += f2 * ss2;
+    if (in1) in1 += f1 * ss1;
+    if (in2) in2 += f2 * ss2;
     matches += p * n1 * 2;
     quality += p * n1;
     if (tid == 0) running = 0;
@@ -387,11 +442,11 @@ extern "C" long long sslam_sim_argmax_workspace_bytes(int n2, int n_pairs) {
     return (long long)n_pairs * n2 * (long long)sizeof(unsigned long long);
 }
 
-extern "C" int sslam_sim_argmax_ws(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2,
-                                   int n2, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12,
-                                   void *workspace, long long workspace_bytes, void *stream) {
-    if (!desc1 || !desc2 || !nn12 || !nn21 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3) || ((uintptr_t)workspace & 7)) return SSLAM_E_INVALID;
+// both launch forms, for either way of naming the pairs (the arguments are checked by the entries)
+template <class PAIRS>
+static int launch_sim_argmax(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
+                             int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12, void *workspace,
+                             long long workspace_bytes, void *stream, PAIRS pairs) {
     if ((long long)n_pairs * ((((n1 > n2 ? n1 : n2) + QB - 1) / QB)) > 0x7ffffff0LL / 8) return SSLAM_E_UNSUPPORTED;
     // test-only knob (common.h): 0 = by batch size, 1 = S per direction (no workspace), 2 = S once + 64-bit key reduction
     const int forced = (int)sslam_knob(KNOB_M1_VARIANT, 0);
@@ -405,14 +460,14 @@ extern "C" int sslam_sim_argmax_ws(const float *desc1, long long stride1, int n1
         const int qb1 = (n1 + QB - 1) / QB;
         const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qb1), 1, 1);
         if (second12)
-            hipLaunchKernelGGL((sim_argmax_kernel<true, true>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
-                               nn21, s21, second12, keys, n_pairs, qb1);
+            hipLaunchKernelGGL((sim_argmax_kernel<true, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12,
+                               s12, nn21, s21, second12, keys, n_pairs, qb1, pairs);
         else
-            hipLaunchKernelGGL((sim_argmax_kernel<true, false>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
-                               nn21, s21, second12, keys, n_pairs, qb1);
+            hipLaunchKernelGGL((sim_argmax_kernel<true, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12,
+                               s12, nn21, s21, second12, keys, n_pairs, qb1, pairs);
         SSLAM_CHECK_LAUNCH();
         const long long n = (long long)n_pairs * n2;
-        hipLaunchKernelGGL(keys_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, n1, nn21, s21);
+        hipLaunchKernelGGL(keys_decode_kernel<PAIRS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, n1, nn21, s21);
         SSLAM_CHECK_LAUNCH();
         return SSLAM_OK;
     }
@@ -420,13 +475,33 @@ extern "C" int sslam_sim_argmax_ws(const float *desc1, long long stride1, int n1
     const int qbm = (nmax + QB - 1) / QB;
     const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qbm), 2, 1);
     if (second12)
-        hipLaunchKernelGGL((sim_argmax_kernel<false, true>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12, nn21,
-                           s21, second12, nullptr, n_pairs, qbm);
+        hipLaunchKernelGGL((sim_argmax_kernel<false, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+                           nn21, s21, second12, nullptr, n_pairs, qbm, pairs);
     else
-        hipLaunchKernelGGL((sim_argmax_kernel<false, false>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12, nn21,
-                           s21, second12, nullptr, n_pairs, qbm);
+        hipLaunchKernelGGL((sim_argmax_kernel<false, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+                           nn21, s21, second12, nullptr, n_pairs, qbm, pairs);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
+}
+
+extern "C" int sslam_sim_argmax_ws(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2,
+                                   int n2, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12,
+                                   void *workspace, long long workspace_bytes, void *stream) {
+    if (!desc1 || !desc2 || !nn12 || !nn21 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3) || ((uintptr_t)workspace & 7)) return SSLAM_E_INVALID;
+    return launch_sim_argmax(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, workspace, workspace_bytes,
+                             stream, StridedPairs{});
+}
+
+// pairs named by two DEVICE index lists into one bank: the same kernels, every pair's bases looked up by its workgroups
+extern "C" int sslam_sim_argmax_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                      const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21,
+                                      float *second12, void *workspace, long long workspace_bytes, void *stream) {
+    if (!bank || !pair_first || !pair_second || !nn12 || !nn21 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)bank & 15) || (frame_stride & 3) || ((uintptr_t)workspace & 7) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3))
+        return SSLAM_E_INVALID;
+    return launch_sim_argmax(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, nn21, s21, second12, workspace,
+                             workspace_bytes, stream, ListedPairs{pair_first, pair_second, n_bank});
 }
 
 // the form without a workspace: never allocates - the similarity matrix is evaluated once per direction
@@ -444,9 +519,26 @@ extern "C" int sslam_match_finalize(const int32_t *nn12, const float *s12, const
     if (!nn12 || !s12 || !nn21 || !scores1 || !scores2 || !matches || !quality || !count || n1 <= 0 || n2 <= 0 ||
         n_pairs <= 0)
         return SSLAM_E_INVALID;
-    hipLaunchKernelGGL(match_finalize_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, nn21, n1, n2,
+    hipLaunchKernelGGL(match_finalize_kernel<StridedPairs>, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, nn21, n1, n2,
                        scores1, sstride1, scores2, sstride2, intensity1, intensity2, w_desc, w_sal, min_saliency, min_sim,
-                       min_intensity, (long long *)matches, quality, count);
+                       min_intensity, (long long *)matches, quality, count, StridedPairs{});
+    SSLAM_CHECK_LAUNCH();
+    return SSLAM_OK;
+}
+
+extern "C" int sslam_match_finalize_pairs(const int32_t *nn12, const float *s12, const int32_t *nn21, int K, int n_bank,
+                                          const int32_t *pair_first, const int32_t *pair_second, int n_pairs, const float *scores_bank,
+                                          long long score_stride, const float *intensity_bank, float w_desc, float w_sal,
+                                          float min_saliency, float min_sim, float min_intensity, int64_t *matches, float *quality,
+                                          int32_t *count, void *stream) {
+    if (!nn12 || !s12 || !nn21 || !pair_first || !pair_second || !scores_bank || !matches || !quality || !count || K <= 0 ||
+        n_bank <= 0 || n_pairs <= 0)
+        return SSLAM_E_INVALID;
+    if (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3) return SSLAM_E_INVALID;
+    hipLaunchKernelGGL(match_finalize_kernel<ListedPairs>, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, nn21, K, K,
+                       scores_bank, score_stride, scores_bank, score_stride, intensity_bank, intensity_bank, w_desc, w_sal,
+                       min_saliency, min_sim, min_intensity, (long long *)matches, quality, count,
+                       ListedPairs{pair_first, pair_second, n_bank});
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }

@@ -78,6 +78,7 @@ EXPORTS = [
     "sslam_preprocess_u8_patches", "sslam_vit_forward_patches", "sslam_vit_f32_workspace_bytes", "sslam_vit_forward_f32",
     "sslam_vit_f32_pack_linear_host", "sslam_vit_forward_f32_form",
     "sslam_vit_workspace_bytes_form", "sslam_vit_forward_form", "sslam_vit_forward_patches_form",
+    "sslam_sim_argmax_pairs", "sslam_match_finalize_pairs",
 ]
 
 
@@ -115,6 +116,8 @@ def lib():
         L.sslam_sim_argmax.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p]
         L.sslam_sim_argmax_ws.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p, ll, p]
         L.sslam_match_finalize.argtypes = [p, p, p, i, i, i, p, ll, p, ll, p, p, f, f, f, f, f, p, p, p, p]
+        L.sslam_sim_argmax_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p, p, p, ll, p]
+        L.sslam_match_finalize_pairs.argtypes = [p, p, p, i, i, p, p, i, p, ll, p, f, f, f, f, f, p, p, p, p]
         L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
         L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
         L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
@@ -489,6 +492,89 @@ def match_finalize(nn12, s12, nn21, n1, n2, n_pairs, sc1, ss1, sc2, ss2, in1, in
                                       None if in2 is None else C.c_void_p(in2.data_ptr()),
                                       f(w_desc), f(w_sal), f(t_sal), f(t_sim), f(t_int), _dp(matches), _dp(quality),
                                       _dp(count))
+    return matches, quality, count
+
+
+def check_pair_lists(first, second, device=None) -> int:
+    """The two index lists of a pair-list call: 1-D int32 tensors of one length, contiguous, on `device` when it is given.
+    Raises ValueError, touching no device; returns the number of pairs.  The VALUES are the kernels' business (an index outside
+    the bank makes an absent pair): the host never reads them."""
+    for name, t in (("first", first), ("second", second)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"pair list `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise ValueError(f"pair list `{name}` must be int32, got {t.dtype}")
+        if t.dim() != 1:
+            raise ValueError(f"pair list `{name}` must be 1-D, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"pair list `{name}` must be contiguous")
+    if first.shape[0] != second.shape[0]:
+        raise ValueError(f"pair lists of unequal length: {first.shape[0]} and {second.shape[0]}")
+    if first.shape[0] == 0:
+        raise ValueError("empty pair list")
+    if device is not None:
+        for name, t in (("first", first), ("second", second)):
+            if t.device != device:
+                raise ValueError(f"pair list `{name}` is on {t.device}, the bank on {device}")
+    return int(first.shape[0])
+
+
+def _check_bank(name, t, tail):
+    """t: a contiguous fp32 tensor (n_bank >= 1, *tail); a tail entry given as a string stands for any size >= 1."""
+    ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 1 + len(tail) and t.is_contiguous()
+    ok = ok and all(d >= 1 for d in t.shape) and all(isinstance(w, str) or d == w for d, w in zip(t.shape[1:], tail))
+    if not ok:
+        raise ValueError(f"{name} must be a contiguous fp32 tensor of shape (n_bank, {', '.join(str(w) for w in tail)})")
+
+
+def sim_argmax_pairs(bank, first, second, want_s21=False, want_second=False, workspace=None):
+    """sslam_sim_argmax_pairs: bank (n_bank, K, 128) fp32; first / second: 1-D int32 DEVICE tensors naming, pair by pair, the
+    two frames of the bank to match (an index outside [0, n_bank), -1 by convention, makes the pair ABSENT: zero rows).
+    Returns (nn12, s12, nn21, s21, second12) with one row per listed pair, as sim_argmax does.  workspace: as there."""
+    _check_bank("bank", bank, ("K", D_OUT))
+    n_bank, k = int(bank.shape[0]), int(bank.shape[1])
+    n_pairs = check_pair_lists(first, second, bank.device)
+    dev = common_device(bank, first, second, workspace)
+    nn12 = torch.empty((n_pairs, k), dtype=torch.int32, device=dev)
+    s12 = torch.empty((n_pairs, k), dtype=torch.float32, device=dev)
+    nn21 = torch.empty((n_pairs, k), dtype=torch.int32, device=dev)
+    s21 = torch.empty((n_pairs, k), dtype=torch.float32, device=dev) if want_s21 else None
+    sec = torch.empty((n_pairs, k), dtype=torch.float32, device=dev) if want_second else None
+    ws, wsb = _scratch(workspace, int(lib().sslam_sim_argmax_workspace_bytes(k, n_pairs)), dev)
+    _run("sim_argmax_pairs", lib().sslam_sim_argmax_pairs, (bank, first, second, nn12, s12, nn21, s21, sec, ws),
+         _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(nn12), _dp(s12), _dp(nn21), _dp(s21), _dp(sec),
+         _dp(ws), wsb)
+    return nn12, s12, nn21, s21, sec
+
+
+def match_finalize_pairs(nn12, s12, nn21, first, second, scores, intensity, w_desc, w_sal, t_sal, t_sim, t_int, out=None):
+    """sslam_match_finalize_pairs: the arg-max arrays of sim_argmax_pairs over the same two lists; scores (n_bank, K) and
+    intensity (n_bank, K) or None are the banks those lists index.  out: optional (matches, quality, count) to write into."""
+    _check_bank("scores", scores, ("K",))
+    n_bank, k = int(scores.shape[0]), int(scores.shape[1])
+    if intensity is not None:
+        _check_bank("intensity", intensity, (k,))
+        if intensity.shape[0] != n_bank:
+            raise ValueError(f"intensity holds {intensity.shape[0]} frames, scores {n_bank}")
+    n_pairs = check_pair_lists(first, second, scores.device)
+    for name, t, dt in (("nn12", nn12, torch.int32), ("s12", s12, torch.float32), ("nn21", nn21, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (n_pairs, k) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {(n_pairs, k)}")
+    dev = scores.device
+    if out is not None:
+        matches, quality, count = out
+        for name, t, dt, sh in (("matches", matches, torch.int64, (n_pairs, k, 2)), ("quality", quality, torch.float32, (n_pairs, k)),
+                                ("count", count, torch.int32, (n_pairs,))):
+            if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous():
+                raise ValueError(f"out `{name}` must be a contiguous {dt} tensor of shape {sh}")
+    else:
+        matches = torch.empty((n_pairs, k, 2), dtype=torch.int64, device=dev)
+        quality = torch.empty((n_pairs, k), dtype=torch.float32, device=dev)
+        count = torch.empty((n_pairs,), dtype=torch.int32, device=dev)
+    f = C.c_float
+    _run("match_finalize_pairs", lib().sslam_match_finalize_pairs, (nn12, s12, nn21, first, second, scores, intensity, matches, quality, count),
+         _dp(nn12), _dp(s12), _dp(nn21), k, n_bank, _dp(first), _dp(second), n_pairs, _dp(scores), k, _dp(intensity),
+         f(w_desc), f(w_sal), f(t_sal), f(t_sim), f(t_int), _dp(matches), _dp(quality), _dp(count))
     return matches, quality, count
 
 

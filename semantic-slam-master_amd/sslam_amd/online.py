@@ -25,6 +25,16 @@ A pipeline built with vit_form="few_frame" steps in the bf16 ViT's FEW-FRAME for
 projection: include/sslam_hip.h) - the stepper itself takes no argument for it, a step being a batch of one - as ordinary launches
 and from the captured graph alike (one stream, no parallel branches; the larger workspace is among the buffers the stepper holds);
 its steps equal that pipeline's run() over up to 8 frames bit for bit (tests/test_gpu_vit_few_frame.py).
+
+`spacings=(1, 5, 10, 15, 20)` (any distinct positive ints) makes a step match the frame against SEVERAL earlier frames - the
+reference's own five spacings (visualize_matches_sequence.py:369), or a front end's "this frame against my last few" - still on
+static buffers and from one captured graph.  The frames live in a bank of max(spacings) + 1 slots: slot max(spacings) is the
+static slot the extraction writes, the others are a ring, frame j in slot j mod max(spacings).  The step counter t is DEVICE
+memory, and the body derives from it, with a handful of torch ops on the stream, the matcher's pair list (first[s] = the slot of
+frame t - s, or -1 while t < s: an absent pair; second = the static slot), runs ONE sslam_sim_argmax_pairs +
+sslam_match_finalize_pairs over all spacings (include/sslam_hip.h: the pair list is read by the kernels), copies the frame into
+ring slot t mod max(spacings) with a device-indexed copy and increments t.  No host value that changes between steps enters the
+body, so the replayed graph is the same step for every frame.  `spacings=None` is the one-spacing stepper above, untouched.
 """
 from __future__ import annotations
 
@@ -34,14 +44,31 @@ from . import lib
 from .pipeline import N_PREFIX, SequencePipeline
 
 
+BANK_KEYS = ("descriptors", "scores", "intensity", "keypoints_pixel")      # what an earlier frame is kept for
+
+
+def _checked_spacings(spacings) -> tuple:
+    if isinstance(spacings, (str, bytes)) or not hasattr(spacings, "__iter__"):
+        raise ValueError(f"spacings must be a sequence of distinct positive ints, got {spacings!r}")
+    sp = tuple(spacings)
+    if not sp or any(isinstance(s, bool) or not isinstance(s, int) or s < 1 for s in sp) or len(set(sp)) != len(sp):
+        raise ValueError(f"spacings must be a non-empty sequence of distinct positive ints, got {spacings!r}")
+    return sp
+
+
 class FrameStepper:
-    def __init__(self, pipe: SequencePipeline, height: int, width: int, use_graph: bool = True, tokens_in: bool = False):
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, use_graph: bool = True, tokens_in: bool = False,
+                 spacings=None):
         """pipe: a SequencePipeline (with vit= unless tokens_in).  height / width: the frames' size (uint8 RGB).
         tokens_in: the caller brings the ViT's tokens with every frame (the third-party ViT stays outside).
         use_graph=False: the same step as ordinary launches (the A/B for the graph, and the fallback while debugging).
         With the ViT inside, every step runs its few-frame form (a batch of one): the tokens of SequencePipeline.run over up to
         8 frames bit for bit, those of a longer batch within the float64 bars (module docstring).  Which few-frame form the bf16
-        ViT runs is the pipeline's choice (SequencePipeline(vit_form=...)): the small form by default, "few_frame" by name."""
+        ViT runs is the pipeline's choice (SequencePipeline(vit_form=...)): the small form by default, "few_frame" by name.
+        spacings: None - match against the previous frame (above); a sequence of distinct positive ints - match every frame
+        against the frames that many steps back, all in one launch pair (module docstring; step() says what comes back)."""
+        if spacings is not None:
+            spacings = _checked_spacings(spacings)       # before anything is allocated
         cfg = pipe.cfg
         if cfg.num_keypoints > cfg.grid ** 2:
             raise ValueError("num_keypoints > grid cells: that case reads a status word back on the host (SURVEY H6) and cannot be captured")
@@ -52,26 +79,72 @@ class FrameStepper:
         dev, K = self.device, cfg.num_keypoints
         self.image = torch.zeros((1, height, width, 3), dtype=torch.uint8, device=dev)
         self.tokens = torch.zeros((1, N_PREFIX + cfg.grid ** 2, lib.C_FEAT), dtype=torch.float32, device=dev)
+        self.spacings = spacings
+        self.n_frames = 0
+        self._graph = None
+        self._aux = None
+        self._held = None
+        if spacings is not None:
+            self._init_bank(spacings)
+            return
         # slot 0: the previous frame, slot 1: this frame - the matcher's pair (0, 1) without any concatenation
         self.pair = pipe.alloc_extract(2, True)
         for v in self.pair.values():
             v.zero_()
         self.cur = {k: v[1:2] for k, v in self.pair.items()}
         self.m = pipe.alloc_match(1, K)
-        self.n_frames = 0
-        self._graph = None
-        self._aux = None
-        self._held = None
+
+    def _init_bank(self, spacings: tuple) -> None:
+        pipe, dev = self.pipe, self.device
+        ring = self.ring = max(spacings)
+        one = pipe.alloc_extract(1, True)
+        for v in one.values():
+            v.zero_()
+        # slots 0 .. ring - 1: frame j in slot j mod ring; slot `ring`: the static slot of the frame being extracted
+        self.bank = {k: torch.zeros((ring + 1,) + tuple(one[k].shape[1:]), dtype=one[k].dtype, device=dev) for k in BANK_KEYS}
+        self._ring = {k: v[:ring] for k, v in self.bank.items()}
+        self.cur = {k: (self.bank[k][ring:ring + 1] if k in BANK_KEYS else v) for k, v in one.items()}
+        self.m = pipe.alloc_match(len(spacings), self.cfg.num_keypoints)
+        i64 = dict(dtype=torch.int64, device=dev)
+        self._t = torch.zeros((1,), **i64)                                   # the step counter: frames since reset()
+        self._sp = torch.tensor(spacings, **i64)
+        self._back, self._back_slot, self._first64 = (torch.zeros((len(spacings),), **i64) for _ in range(3))
+        self._seen = torch.zeros((len(spacings),), dtype=torch.bool, device=dev)
+        self._absent = torch.full((len(spacings),), -1, **i64)
+        self._slot = torch.zeros((1,), **i64)
+        self.first_slot = torch.full((len(spacings),), -1, dtype=torch.int32, device=dev)      # the matcher's pair lists
+        self.second_slot = torch.full((len(spacings),), ring, dtype=torch.int32, device=dev)
 
     # the captured region: only launches on the current stream, static buffers on both sides
     def _body(self) -> None:
         p = self.pipe
+        if self.spacings is not None:
+            return self._body_spacings()
         if not self.tokens_in:
             p.tokens_from_images(self.image, out=self.tokens)
         p.extract(self.tokens, self.image, out=self.cur)
         self._aux = p.match(self.pair["descriptors"], self.pair["scores"], self.pair["intensity"], spacing=1, out=self.m)
         for k in ("descriptors", "scores", "intensity", "keypoints_pixel"):      # this frame becomes the previous one
             self.pair[k][0].copy_(self.pair[k][1])
+
+    def _body_spacings(self) -> None:
+        p, ring = self.pipe, self.ring
+        if not self.tokens_in:
+            p.tokens_from_images(self.image, out=self.tokens)
+        p.extract(self.tokens, self.image, out=self.cur)
+        # the pair list from the device's own counter t: frame t - s sits in ring slot (t - s) mod ring once t >= s, else -1
+        torch.sub(self._t, self._sp, out=self._back)
+        torch.ge(self._back, 0, out=self._seen)
+        torch.remainder(self._back, ring, out=self._back_slot)
+        torch.where(self._seen, self._back_slot, self._absent, out=self._first64)
+        self.first_slot.copy_(self._first64)
+        self._aux = p.match_pairs(self.bank["descriptors"], self.bank["scores"], self.bank["intensity"], first=self.first_slot,
+                                  second=self.second_slot, out=self.m)
+        # this frame takes the ring slot of frame t - ring, which no spacing reaches any more
+        torch.remainder(self._t, ring, out=self._slot)
+        for k in BANK_KEYS:
+            self._ring[k].index_copy_(0, self._slot, self.cur[k])
+        self._t.add_(1)
 
     def _capture(self) -> None:
         # warm-up outside the capture: resampling tables, RoPE tables, workspaces and the ViT's buffers are created on first use
@@ -82,11 +155,13 @@ class FrameStepper:
                 self._body()
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
+        if self.spacings is not None:
+            self._t.zero_()                      # the warm-up passes counted as frames: the first real frame is frame 0
         # The graph bakes in the ADDRESSES of buffers the stepper does not own: the pipeline's scratch, the ViT's workspaces, the
         # resampling and RoPE tables.  Their owners grow them by replacement (a later, larger pipe.run / tokens_from_images drops
         # the old tensor), which would leave the graph reading and writing freed memory.  The stepper therefore keeps its own
         # reference to every one of them from the warm-up on: a replaced buffer stays alive - and exclusively the graph's - for
-        # as long as the graph does.
+        # as long as the graph does.  (The bank, the counter and the pair lists of the multi-spacing step are the stepper's own.)
         self._held = self._external_buffers()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -111,7 +186,10 @@ class FrameStepper:
         """image_u8: (H, W, 3) or (1, H, W, 3) uint8, on the device or in host memory (pinned: the copy is asynchronous).
         tokens: (T, 384) / (1, T, 384) fp32 when the stepper was built with tokens_in.  Returns this frame's saliency /
         keypoints_pixel / scores / idx / descriptors / intensity (views of static buffers, (K, ...) without the batch axis) and,
-        from the second frame on, matches (K, 2) int64 / quality (K,) / match_count against the previous frame (None before)."""
+        from the second frame on, matches (K, 2) int64 / quality (K,) / match_count against the previous frame (None before).
+        With spacings: matches (S, K, 2) / quality (S, K) / match_count (S,), one row per spacing in the order given (views of
+        static buffers; a spacing that reaches back before the first frame has count 0 and zero rows), and pair_first: a host
+        list of the global index of each row's first frame, -1 where there is none yet.  The second frame is this one."""
         if self.use_graph and self._graph is None:
             self._capture()                      # runs the body on whatever the buffers hold; the first real frame has no previous one
         self.image.copy_(image_u8.reshape(self.image.shape), non_blocking=True)
@@ -126,11 +204,26 @@ class FrameStepper:
         first = self.n_frames == 0
         self.n_frames += 1
         out = {k: v[0] for k, v in self.cur.items()}
+        if self.spacings is not None:
+            t = self.n_frames - 1
+            out.update(matches=self.m["matches"], quality=self.m["quality"], match_count=self.m["match_count"],
+                       pair_first=[t - s if t >= s else -1 for s in self.spacings])
+            return out
         out["matches"] = None if first else self.m["matches"][0]
         out["quality"] = None if first else self.m["quality"][0]
         out["match_count"] = None if first else self.m["match_count"][0]
         return out
 
     def reset(self) -> None:
-        """Forget the previous frame (the next step returns no matches)."""
+        """Forget the previous frame (the next step returns no matches); with spacings: every earlier frame - the device's
+        counter is zeroed here, outside the graph."""
         self.n_frames = 0
+        if self.spacings is not None:
+            self._t.zero_()
+
+    def frame(self, index: int) -> dict:
+        """With spacings: the bank rows (descriptors, scores, intensity, keypoints_pixel) of the frame with global index `index`,
+        one of the last max(spacings) stepped - what a pair_first entry names."""
+        if self.spacings is None or not max(0, self.n_frames - self.ring) <= index < self.n_frames:
+            raise ValueError(f"frame {index} is not in the bank")
+        return {k: v[index % self.ring] for k, v in self.bank.items()}

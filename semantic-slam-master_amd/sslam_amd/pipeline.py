@@ -57,6 +57,16 @@ def _np(v):
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
 
+def _host_pair_list(name: str, t):
+    """A host sequence of frame indices as an int32 tensor (tensors pass through: lib.check_pair_lists judges them)."""
+    if isinstance(t, torch.Tensor):
+        return t
+    a = np.asarray(t)
+    if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < -2 ** 31 or int(a.max()) > 2 ** 31 - 1)):
+        raise ValueError(f"pair list `{name}` must hold 32-bit integers, got {a.dtype}")
+    return torch.from_numpy(a.astype(np.int32))
+
+
 REFINER_ORDER_HEAD = ["input_proj.weight", "input_proj.bias"]
 REFINER_ORDER_BLOCK = ["norm1.weight", "norm1.bias", "fc1.weight", "fc1.bias", "norm2.weight", "norm2.bias",
                        "fc2.weight", "fc2.bias"]
@@ -415,6 +425,39 @@ class SequencePipeline:
                                out=(res["matches"][a:a + m], res["quality"][a:a + m], res["match_count"][a:a + m]))
             aux.append((nn12, nn21, s12))
         for i, key in enumerate(("nn12", "nn21", "sim")):       # the arg-max arrays (diagnostics): one launch in practice
+            res[key] = aux[0][i] if len(aux) == 1 else torch.cat([x[i] for x in aux])
+        return res
+
+    def match_pairs(self, desc, scores, intensity=None, first=None, second=None, out: dict | None = None) -> dict:
+        """M1 for a LIST of pairs of the bank desc (N, K, 128) / scores (N, K) / intensity (N, K): row p matches frame first[p]
+        against frame second[p] - any two frames, in any order, as often as listed; an index outside [0, N) (-1 by convention)
+        makes the pair absent: count 0, zero rows.  first / second: 1-D int32 device tensors (they may be written by earlier work
+        of the stream: nothing here reads them on the host), or host sequences of ints, uploaded once.
+        Returns match()'s dictionary with one row per listed pair, in list order; per pair the same bits as match() on the same
+        two frames.  out: alloc_match buffers (or row slices of them) to write into."""
+        cfg = self.cfg
+        if first is None or second is None:
+            raise ValueError("match_pairs needs both pair lists, first= and second=")
+        if desc.dim() != 3 or scores.dim() != 2 or tuple(scores.shape) != tuple(desc.shape[:2]):
+            raise ValueError(f"desc (N, K, {lib.D_OUT}) and scores (N, K) expected, got {tuple(desc.shape)} and {tuple(scores.shape)}")
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)             # a malformed list is refused before anything is uploaded
+        first, second = (t if t.is_cuda else t.to(desc.device) for t in (first, second))
+        lib.check_pair_lists(first, second, desc.device)
+        k = desc.shape[1]
+        use_int = cfg.use_intensity and intensity is not None
+        res = dict(out) if out is not None else self.alloc_match(n_pairs, k)
+        aux = []
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match() cuts
+            m = min(MAX_PAIRS_PER_LAUNCH, n_pairs - a)
+            f, s = first[a:a + m], second[a:a + m]
+            nn12, s12, nn21, _, _ = lib.sim_argmax_pairs(desc, f, s, workspace=self.workspace(0, m))
+            lib.match_finalize_pairs(nn12, s12, nn21, f, s, scores, intensity if use_int else None,
+                                     1.0 - cfg.saliency_weight, cfg.saliency_weight, cfg.min_saliency,
+                                     cfg.min_descriptor_sim, cfg.min_intensity,
+                                     out=(res["matches"][a:a + m], res["quality"][a:a + m], res["match_count"][a:a + m]))
+            aux.append((nn12, nn21, s12))
+        for i, key in enumerate(("nn12", "nn21", "sim")):
             res[key] = aux[0][i] if len(aux) == 1 else torch.cat([x[i] for x in aux])
         return res
 

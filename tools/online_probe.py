@@ -13,6 +13,66 @@ n = 6
 imgs = torch.from_numpy(synth.image_sequence(n)).to(dev)
 toks = torch.from_numpy(synth.token_sequence(n, 28)).to(dev)
 pipe = SequencePipeline(ExtractorConfig(), synth.selector_state(0), synth.refiner_state(0), device=dev)
+
+
+def multi_spacing_leg(reps=60):
+    """The pair-list matcher and FrameStepper(spacings=...).  Table 1: the 612 consecutive pairs of the 613-frame workload through
+    match(spacing=1) and through match_pairs(first = arange, second = arange + 1), alternating, one device-event timing per call.
+    Table 2: ms per frame, tokens in, of the five reference spacings - StreamingSequence in ring mode pushed one frame at a time,
+    the multi-spacing stepper as launches and from its graph - beside the one-spacing stepper; every caller warm and in its steady
+    state (all spacings present), a pass of 27 frames per timing, taken alternately.  Medians; clocks as found."""
+    import statistics
+    from sslam_amd.harness import StreamingSequence
+    med = statistics.median
+    sp = (1, 5, 10, 15, 20)
+    big = pipe.extract(torch.from_numpy(synth.token_sequence(613, 28)).to(dev))
+    d, sc = big["descriptors"], big["scores"]
+    first = torch.arange(612, dtype=torch.int32, device=dev)
+    second = first + 1
+    calls = {"match(spacing=1)": lambda: pipe.match(d, sc, None, spacing=1),
+             "match_pairs(arange, arange + 1)": lambda: pipe.match_pairs(d, sc, None, first=first, second=second)}
+    a, b = calls.values()
+    assert all(torch.equal(x, y) for x, y in zip(a().values(), b().values())), "the two calls must give the same rows"
+    ms = {k: [] for k in calls}
+    for r in range(5 + reps):
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+            if r >= 5: ms[k].append(e0.elapsed_time(e1))
+    print("612 pairs of 500 x 500 x 128 (613 frames), sim_argmax + finalize, ms per call over %d alternating calls:" % reps)
+    for k, v in ms.items():
+        print("   %-34s median %.4f   min %.4f   max %.4f" % (k, med(v), min(v), max(v)))
+    del big, d, sc
+
+    m = 27
+    im, tk = torch.from_numpy(synth.image_sequence(m)).to(dev), torch.from_numpy(synth.token_sequence(m, 28)).to(dev)
+    ring = StreamingSequence(pipe, sp)
+    callers = {"StreamingSequence ring, one frame per push (5 launch pairs)": lambda i: ring.push(tk[i:i + 1], im[i:i + 1])}
+    for graph in (False, True):
+        multi = FrameStepper(pipe, 480, 640, use_graph=graph, tokens_in=True, spacings=sp)
+        one = FrameStepper(pipe, 480, 640, use_graph=graph, tokens_in=True)
+        callers["FrameStepper spacings=%s graph %s" % (sp, graph)] = lambda i, st=multi: st.step(im[i], tk[i])
+        callers["FrameStepper one spacing graph %s" % graph] = lambda i, st=one: st.step(im[i], tk[i])
+    launches = {}
+    for k, fn in callers.items():
+        for _ in range(3):
+            for i in range(m): fn(i)
+        n0 = lib.launch_count(); fn(0); launches[k] = lib.launch_count() - n0
+    torch.cuda.synchronize()
+    ms = {k: [] for k in callers}
+    for _ in range(reps):
+        for k, fn in callers.items():
+            t0 = time.perf_counter()
+            for i in range(m): fn(i)
+            torch.cuda.synchronize(); ms[k].append((time.perf_counter() - t0) / m * 1e3)
+    print("ms per frame, tokens in, steady state, %d alternating passes of %d frames:" % (reps, m))
+    for k, v in ms.items():
+        print("   %-62s median %.4f   min %.4f   max %.4f   library calls per frame %d" % (k, med(v), min(v), max(v), launches[k]))
+
+
+if "--multi-spacing" in sys.argv:          # this leg alone
+    multi_spacing_leg()
+    sys.exit(0)
 want = pipe.run(imgs, tokens=toks)
 def run_stepper(st, with_tokens):
     res = []
@@ -91,3 +151,4 @@ for _ in range(5):
 print("bf16 ViT inside the step, ms per frame (async), five alternating repeats and their median:")
 for (vit_form, graph), v in ms.items():
     print("   vit_form %-9s graph %-5s median %.4f   repeats %s" % (vit_form, graph, statistics.median(v), " ".join("%.4f" % x for x in v)))
+multi_spacing_leg()
