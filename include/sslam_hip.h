@@ -131,6 +131,10 @@ int sslam_bn_tokens_bf16copy(const float *tokens, int n_frames, int tokens_per_f
 int sslam_pack_conv3x3_bf16_host(const float *w_host, int hs, void *out_bf16_host);
 int sslam_selector_saliency_bf16(const void *feat_bf16, int n_frames, int G, const void *w1_packed_bf16, const float *b1,
                                  const float *w2, const float *b2, int hs, float *sal, void *stream);
+/* Which kernel sslam_selector_saliency_bf16 launches for this shape (host only, no GPU work; the entry itself dispatches on
+ * it): 5..8 = the halo form with that many 64-row groups of the image in LDS, 0 = the stage form (hs != 256, or a grid whose
+ * halo image needs more than 8 groups - G = 128 upwards - and would not fit the LDS).  < 0: invalid arguments. */
+int sslam_selector_bf16_halo_groups(int n_frames, int G, int hs);
 
 /* ---- A4 + A5 (+ A8): NMS + percentile threshold + branchy top-k.  Replaces KeypointSelector.select_keypoints /
  * _apply_nms, keypoint_selector.py:69-226, and DinoBackbone.patch_to_pixel, dino_backbone.py:154-165.

@@ -394,6 +394,17 @@ extern "C" int sslam_pack_conv3x3_bf16_host(const float *w, int hs, void *out_bf
     return SSLAM_OK;
 }
 
+// The dispatch of sslam_selector_saliency_bf16 under the present knobs: the 64-row groups of the halo image (5..8) if the halo
+// form runs, 0 if the stage form does.  Instantiated for 5..8: the two image buffers of 9 x 64 rows would be 165 888 bytes,
+// above the 163 840 bytes of LDS a workgroup can have (such a launch fails), so grids from G = 128 upwards take the stage form.
+extern "C" int sslam_selector_bf16_halo_groups(int n_frames, int G, int hs) {
+    if (n_frames <= 0 || G <= 0) return SSLAM_E_INVALID;
+    const long long rows = (long long)n_frames * G * G;
+    if (hs != 256 || sslam_knob(KNOB_CONVBF_NO_HALO, 0) || rows >= (1LL << 31) / 2) return 0;
+    const int np = std::max(5, (halo_rows(G, rows) + 63) / 64);
+    return np <= 8 ? np : 0;
+}
+
 extern "C" int sslam_selector_saliency_bf16(const void *feat_bf16, int n_frames, int G, const void *w1_packed_bf16,
                                             const float *b1, const float *w2, const float *b2, int hs, float *sal, void *stream) {
     if (!feat_bf16 || !w1_packed_bf16 || !b1 || !w2 || !b2 || !sal || n_frames <= 0 || G <= 0) return SSLAM_E_INVALID;
@@ -401,9 +412,9 @@ extern "C" int sslam_selector_saliency_bf16(const void *feat_bf16, int n_frames,
     const long long rows = (long long)n_frames * G * G;
     if (rows * (long long)(SSLAM_C * 2) > 0xffffffffLL) return SSLAM_E_UNSUPPORTED;   // one buffer descriptor spans the bf16 feature map
     hipStream_t st = (hipStream_t)stream;
-    if (hs == 256 && !sslam_knob(KNOB_CONVBF_NO_HALO, 0)) {
-        const int np = std::max(5, (halo_rows(G, rows) + 63) / 64);      // instantiated for 5..10 x 64 image rows
-        if (np <= 10 && rows < (1LL << 31) / 2) {
+    {
+        const int np = sslam_selector_bf16_halo_groups(n_frames, G, hs);
+        if (np > 0) {
             const int n_tiles = (int)((rows + 255) / 256);
             const int round = (int)sslam_knob(KNOB_CONVBF_TAIL, 256);           // round size in tiles (one workgroup per CU); 0: all big
             const int n_big = round > 0 && n_tiles > round ? n_tiles / round * round : n_tiles;
@@ -413,8 +424,6 @@ extern "C" int sslam_selector_saliency_bf16(const void *feat_bf16, int n_frames,
     hipLaunchKernelGGL((selector_bf16_halo_kernel<NP_>), dim3(n_big + n_small), dim3(512), lds, st, (const bf16 *)feat_bf16, (int)rows, G, \
                        (const bf16 *)w1_packed_bf16, b1, w2, b2, sal, n_big)
             switch (np) {
-                case 10: HALO(10); break;
-                case 9: HALO(9); break;
                 case 8: HALO(8); break;
                 case 7: HALO(7); break;
                 case 6: HALO(6); break;

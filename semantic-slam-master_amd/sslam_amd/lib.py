@@ -78,7 +78,7 @@ EXPORTS = [
     "sslam_preprocess_u8_patches", "sslam_vit_forward_patches", "sslam_vit_f32_workspace_bytes", "sslam_vit_forward_f32",
     "sslam_vit_f32_pack_linear_host", "sslam_vit_forward_f32_form",
     "sslam_vit_workspace_bytes_form", "sslam_vit_forward_form", "sslam_vit_forward_patches_form",
-    "sslam_sim_argmax_pairs", "sslam_match_finalize_pairs",
+    "sslam_sim_argmax_pairs", "sslam_match_finalize_pairs", "sslam_selector_bf16_halo_groups",
 ]
 
 
@@ -121,6 +121,7 @@ def lib():
         L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
         L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
         L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
+        L.sslam_selector_bf16_halo_groups.argtypes = [i, i, i]
         L.sslam_bn_tokens_bf16copy.argtypes = [p, i, i, i, i, p, p, p, p, i, f, p, p, p, p, p]
         L.sslam_refiner_bf16_bytes.restype = C.c_longlong
         L.sslam_refiner_bf16_bytes.argtypes = [i]
@@ -369,6 +370,15 @@ def selector_saliency_bf16(feat_bf16, w1p_bf16, b1, w2, b2, hs, out=None):
     _run("selector_saliency_bf16", lib().sslam_selector_saliency_bf16, (feat_bf16, w1p_bf16, b1, w2, b2, out,),
          _dp(feat_bf16), n, g, _dp(w1p_bf16), _dp(b1), _dp(w2), _dp(b2), hs, _dp(out))
     return out
+
+
+def selector_bf16_halo_groups(n_frames: int, G: int, hs: int = 256) -> int:
+    """The kernel selector_saliency_bf16 launches for this shape under the present knobs: 5..8 = halo form with that many
+    64-row image groups, 0 = stage form (include/sslam_hip.h)."""
+    np_ = int(lib().sslam_selector_bf16_halo_groups(n_frames, G, hs))
+    if np_ < 0:
+        _check(np_, "selector_bf16_halo_groups")
+    return np_
 
 
 def select_keypoints(sal, K, radius=2, pct=0.5, want_idx=True, want_pixel=True, out=None):
