@@ -258,6 +258,44 @@ int sslam_match_finalize_pairs(const int32_t *nn12, const float *s12, const int3
                                float min_saliency, float min_sim, float min_intensity, int64_t *matches, float *quality,
                                int32_t *count, void *stream);
 
+/* ---- M2 / M4 / M5: the sibling matchers' rules on the device - the finalize stage of sslam_match_finalize[_pairs] with another
+ * rule, given nn12 / s12 / second12 / nn21 of sslam_sim_argmax[_pairs] (strided form: n_pairs-strided arrays, pair p's rows at
+ * p*n1 resp. p*n2; pair-list form: n1 = n2 = K, the two DEVICE lists of sslam_sim_argmax_pairs over a bank of n_bank frames decide
+ * only whether a pair is absent).  One workgroup per pair; outputs per pair as there: matches (n1 rows of 2 int64 (idx1, idx2),
+ * ascending idx1), value (n1 fp32), count (1 int32); slots past the count are zeroed; an absent pair has count 0 and zero rows.
+ * For row i with j = nn12[i] (a j outside [0, n2) is never used: the row is not kept):
+ *   SSLAM_RULE_RATIO_BEST   M2, MatchVisualizer.find_matches, visualize_matches.py:102-124 (mutual :114, ratio test :117-121):
+ *                           keep iff nn21[j] == i and s12[i] > max(second12[i], -1) * param; value = s12[i] (the original
+ *                           writes -1 over the winner and takes the row's max, so with n2 == 1 the runner-up is -1);
+ *   SSLAM_RULE_RATIO_SECOND M4, find_mutual_nearest_neighbors, test/test_descriptor_quality.py:97-142 (mutual :126, ratio
+ *                           :129-131, distance :140): keep iff nn21[j] == i and second12[i] / (s12[i] + 1e-8f) < param, the add
+ *                           and the divide each rounded to fp32 once; value = 1.0f - s12[i].  n2 < 2: SSLAM_E_INVALID before
+ *                           anything is launched (the original's np.sort(...)[:, 1] raises);
+ *   SSLAM_RULE_TRACKED      M5, the tracking count of track_frame_sequence, test/test_tracking.py:158-161: keep iff
+ *                           s12[i] > param - no mutual check; nn21 and second12 are not read and may be NULL; value = s12[i];
+ *                           count is the original's `matches`.
+ * param (ratio_thresh / ratio_threshold / match_threshold) is fp32: the originals compare fp32 arrays with a Python scalar,
+ * which numpy rounds to fp32 first.  Every comparison is false on a NaN: such a row is not kept.
+ * SSLAM_E_INVALID, before anything is launched: a NULL nn12 / s12 / matches / value / count, an unknown rule, NULL second12 or
+ * nn21 where the rule reads them, NULL or misaligned pair lists, non-positive sizes. */
+#define SSLAM_RULE_RATIO_BEST 1
+#define SSLAM_RULE_RATIO_SECOND 2
+#define SSLAM_RULE_TRACKED 3
+int sslam_match_finalize_rule(const int32_t *nn12, const float *s12, const float *second12, const int32_t *nn21, int n1, int n2,
+                              int n_pairs, int rule, float param, int64_t *matches, float *value, int32_t *count, void *stream);
+int sslam_match_finalize_rule_pairs(const int32_t *nn12, const float *s12, const float *second12, const int32_t *nn21, int K,
+                                    int n_bank, const int32_t *pair_first, const int32_t *pair_second, int n_pairs, int rule,
+                                    float param, int64_t *matches, float *value, int32_t *count, void *stream);
+
+/* ---- The row direction alone, for callers that need no nn21 (SSLAM_RULE_TRACKED; test/test_tracking.py:159-160 takes only
+ * sim_matrix.max(axis=1)): nn12, s12 (may be NULL) and second12 (may be NULL) of sslam_sim_argmax resp. sslam_sim_argmax_pairs -
+ * the same bits as those entries write in either of their launch forms - from ONE launch of the row direction of the two-pass
+ * form, half its work; no workspace.  Arguments, alignment rules and absent pairs (nn12 = 0, s12 = second12 = 0.0f) as there. */
+int sslam_sim_argmax_rows(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                          int n_pairs, int32_t *nn12, float *s12, float *second12, void *stream);
+int sslam_sim_argmax_rows_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, float *second12, void *stream);
+
 /* ---- A1: DINOv3 ViT-S/16 forward.  Replaces the third-party call
  * `self.dino.forward_features(images)` at dino_backbone.py:85 (timm model "vit_small_patch16_dinov3"): 16x16 patch
  * embedding, [CLS] + 4 register tokens, 12 pre-LN blocks (6 heads x 64, q/v/proj bias, axial RoPE theta 100 on the

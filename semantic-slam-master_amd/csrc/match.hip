@@ -4,6 +4,10 @@
 // SequenceMatcher.match_with_quality (reference semantic-slam/visualize_matches_sequence.py:138-197) and the sibling
 // matchers (visualize_matches.py:105-109, train.py:423-425, test/test_descriptor_quality.py:116-123,
 // test/test_tracking.py:159-160).
+// The sibling matchers M2 / M4 / M5 have their rules on the device too: match_finalize_rule_kernel (the ratio tests of
+// visualize_matches.py:102-124 and test/test_descriptor_quality.py:97-142, the tracking count of test/test_tracking.py:158-161)
+// is M1's finalize stage with another predicate, on the same arg-max arrays plus the row runner-up; M5 reads no column direction
+// and takes the rows-only launch (sslam_sim_argmax_rows[_pairs]: the two-pass form's direction 0 alone, grid y = 1).
 //
 // sim_argmax: grid (query blocks of 128, direction, pair).  Direction 0 finds for every row of d1 its best row of
 // d2 (nn12), direction 1 swaps the roles (nn21): S[i][j] and S^T[j][i] are the same fma chain (a*b commutes), so
@@ -432,6 +436,93 @@ __global__ __launch_bounds__(256) void match_finalize_kernel(const int *__restri
     }
 }
 
+// The sibling matchers' rules on the same arg-max arrays (+ the row runner-up): one workgroup per pair, the ordered compaction,
+// the count and the zeroed tail of match_finalize_kernel, so the arrays are a pure function of the inputs here too.
+//   SSLAM_RULE_RATIO_BEST   (M2) MatchVisualizer.find_matches, visualize_matches.py:102-124
+//   SSLAM_RULE_RATIO_SECOND (M4) find_mutual_nearest_neighbors, test/test_descriptor_quality.py:97-142
+//   SSLAM_RULE_TRACKED      (M5) track_frame_sequence, test/test_tracking.py:158-161 (reads neither nn21 nor second12)
+// `rule` is uniform over the launch.  Every comparison is false on a NaN, so such a row is not kept.
+template <class PAIRS>
+__global__ __launch_bounds__(256) void match_finalize_rule_kernel(const int *__restrict__ nn12, const float *__restrict__ s12,
+                                                                   const float *__restrict__ second12, const int *__restrict__ nn21,
+                                                                   int n1, int n2, int rule, float param,
+                                                                   long long *__restrict__ matches, float *__restrict__ value,
+                                                                   int *__restrict__ count, PAIRS pairs) {
+    __shared__ int wave_tot[4];
+    __shared__ int running;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long p = blockIdx.x;
+    long long f1, f2;
+    if (!pairs.frames(p, f1, f2)) {      // an absent pair: count 0, rows zeroed like the slots past the count below
+        if (tid == 0) count[p] = 0;
+        for (int sl = tid; sl < n1; sl += 256) {
+            matches[(p * n1 + sl) * 2] = 0;
+            matches[(p * n1 + sl) * 2 + 1] = 0;
+            value[p * n1 + sl] = 0.f;
+        }
+        return;
+    }
+    nn12 += p * n1;
+    s12 += p * n1;
+    if (second12) second12 += p * n1;
+    if (nn21) nn21 += p * n2;
+    matches += p * n1 * 2;
+    value += p * n1;
+    if (tid == 0) running = 0;
+    __syncthreads();
+    for (int base = 0; base < n1; base += 256) {
+        const int i = base + tid;
+        bool ok = false;
+        int j = 0;
+        float val = 0.f;
+        if (i < n1) {
+            j = nn12[i];
+            if ((unsigned)j < (unsigned)n2) {                                  // arrays not from sslam_sim_argmax: never index outside
+                const float best = s12[i];
+                if (rule == SSLAM_RULE_TRACKED) {
+                    ok = best > param;                                          // test_tracking.py:160
+                    val = best;
+                } else if (nn21[j] == i) {                                      // visualize_matches.py:114, test_descriptor_quality.py:126
+                    const float sec = second12[i];
+                    if (rule == SSLAM_RULE_RATIO_BEST) {
+                        // the original writes -1 over the winner and takes the row's max: never below -1 (-inf here if n2 == 1)
+                        ok = best > fmaxf(sec, -1.0f) * param;                  // visualize_matches.py:117-121
+                        val = best;
+                    } else {
+                        ok = __fdiv_rn(sec, __fadd_rn(best, 1e-8f)) < param;    // test_descriptor_quality.py:129-131
+                        val = __fsub_rn(1.0f, best);                            // :140
+                    }
+                }
+            }
+        }
+        int inc = ok ? 1 : 0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(inc, off);
+            if (lane >= off) inc += t;
+        }
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        int off0 = running;
+        for (int w = 0; w < wave; w++) off0 += wave_tot[w];
+        if (ok) {
+            const int slot = off0 + inc - 1;      // < n1: at most one slot per row
+            matches[2 * slot] = i;
+            matches[2 * slot + 1] = j;
+            value[slot] = val;
+        }
+        __syncthreads();
+        if (tid == 0) running += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+        __syncthreads();
+    }
+    if (tid == 0) count[p] = running;
+    for (int sl = running + tid; sl < n1; sl += 256) {
+        matches[2 * sl] = 0;
+        matches[2 * sl + 1] = 0;
+        value[sl] = 0.f;
+    }
+}
+
 }  // namespace
 
 // scratch of the single-evaluation form: one 64-bit (value, ~index) key per (pair, candidate)
@@ -539,6 +630,73 @@ extern "C" int sslam_match_finalize_pairs(const int32_t *nn12, const float *s12,
                        scores_bank, score_stride, scores_bank, score_stride, intensity_bank, intensity_bank, w_desc, w_sal,
                        min_saliency, min_sim, min_intensity, (long long *)matches, quality, count,
                        ListedPairs{pair_first, pair_second, n_bank});
+    SSLAM_CHECK_LAUNCH();
+    return SSLAM_OK;
+}
+
+// ---- rows-only similarity: the row direction of the two-pass form as a launch of its own (grid y = 1: direction 0 only) - the
+// same kernel, so the same bits as the row outputs of sslam_sim_argmax[_pairs] in either of its forms; no workspace
+template <class PAIRS>
+static int launch_sim_argmax_rows(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
+                                  int32_t *nn12, float *s12, float *second12, void *stream, PAIRS pairs) {
+    const int qb1 = (n1 + QB - 1) / QB;
+    if ((long long)n_pairs * qb1 > 0x7ffffff0LL / 8) return SSLAM_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qb1), 1, 1);
+    hipStream_t st = (hipStream_t)stream;
+    if (second12)
+        hipLaunchKernelGGL((sim_argmax_kernel<false, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+                           nullptr, nullptr, second12, nullptr, n_pairs, qb1, pairs);
+    else
+        hipLaunchKernelGGL((sim_argmax_kernel<false, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+                           nullptr, nullptr, second12, nullptr, n_pairs, qb1, pairs);
+    SSLAM_CHECK_LAUNCH();
+    return SSLAM_OK;
+}
+
+extern "C" int sslam_sim_argmax_rows(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                                     int n_pairs, int32_t *nn12, float *s12, float *second12, void *stream) {
+    if (!desc1 || !desc2 || !nn12 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3)) return SSLAM_E_INVALID;
+    return launch_sim_argmax_rows(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, stream, StridedPairs{});
+}
+
+extern "C" int sslam_sim_argmax_rows_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                           const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, float *second12,
+                                           void *stream) {
+    if (!bank || !pair_first || !pair_second || !nn12 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)bank & 15) || (frame_stride & 3) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3)) return SSLAM_E_INVALID;
+    return launch_sim_argmax_rows(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, second12, stream,
+                                  ListedPairs{pair_first, pair_second, n_bank});
+}
+
+// what both rule entries refuse before anything is launched: an unknown rule, M4 on fewer than two candidates (the reference's
+// np.sort(...)[:, 1] raises there), a NULL array the rule reads
+static bool rule_args_ok(const int32_t *nn12, const float *s12, const float *second12, const int32_t *nn21, int n1, int n2, int n_pairs,
+                         int rule, const int64_t *matches, const float *value, const int32_t *count) {
+    if (!nn12 || !s12 || !matches || !value || !count || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return false;
+    if (rule != SSLAM_RULE_RATIO_BEST && rule != SSLAM_RULE_RATIO_SECOND && rule != SSLAM_RULE_TRACKED) return false;
+    if (rule != SSLAM_RULE_TRACKED && (!second12 || !nn21)) return false;
+    return rule != SSLAM_RULE_RATIO_SECOND || n2 >= 2;
+}
+
+extern "C" int sslam_match_finalize_rule(const int32_t *nn12, const float *s12, const float *second12, const int32_t *nn21, int n1,
+                                         int n2, int n_pairs, int rule, float param, int64_t *matches, float *value, int32_t *count,
+                                         void *stream) {
+    if (!rule_args_ok(nn12, s12, second12, nn21, n1, n2, n_pairs, rule, matches, value, count)) return SSLAM_E_INVALID;
+    hipLaunchKernelGGL(match_finalize_rule_kernel<StridedPairs>, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, second12, nn21,
+                       n1, n2, rule, param, (long long *)matches, value, count, StridedPairs{});
+    SSLAM_CHECK_LAUNCH();
+    return SSLAM_OK;
+}
+
+extern "C" int sslam_match_finalize_rule_pairs(const int32_t *nn12, const float *s12, const float *second12, const int32_t *nn21, int K,
+                                               int n_bank, const int32_t *pair_first, const int32_t *pair_second, int n_pairs, int rule,
+                                               float param, int64_t *matches, float *value, int32_t *count, void *stream) {
+    if (!rule_args_ok(nn12, s12, second12, nn21, K, K, n_pairs, rule, matches, value, count) || !pair_first || !pair_second || n_bank <= 0)
+        return SSLAM_E_INVALID;
+    if (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3) return SSLAM_E_INVALID;
+    hipLaunchKernelGGL(match_finalize_rule_kernel<ListedPairs>, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, second12, nn21,
+                       K, K, rule, param, (long long *)matches, value, count, ListedPairs{pair_first, pair_second, n_bank});
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }

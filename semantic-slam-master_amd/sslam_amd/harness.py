@@ -65,10 +65,13 @@ class StreamingSequence:
     The reference's process_spacing (visualize_matches_sequence.py:298-300) visits only i = 0, s, 2s, ... and stops
     after `max_pairs` pairs: `reference_pairs()` selects those rows from the result."""
 
-    def __init__(self, pipe: SequencePipeline, spacings=(1, 5, 10, 15, 20)):
+    def __init__(self, pipe: SequencePipeline, spacings=(1, 5, 10, 15, 20), rule=None):
+        """rule: None - M1; a pipeline.MatchRule - every spacing under M2 / M4 / M5 instead, in both storage modes: the match
+        dicts then hold what SequencePipeline.match(rule=) returns (`value` in place of `quality`)."""
         self.pipe, self.spacings = pipe, tuple(int(s) for s in spacings)
         if not self.spacings or min(self.spacings) < 1:
             raise ValueError("spacings must be positive")
+        self._rule_kw = {} if rule is None else {"rule": rule}       # rule=None: the pipeline is called exactly as before
         self.reset()
 
     def reset(self, capacity: int | None = None):
@@ -87,7 +90,7 @@ class StreamingSequence:
             self._store = pipe.alloc_extract(self.capacity, images_u8 is not None)
             for s in self.spacings:
                 if self.capacity > s:
-                    self._pairs[s] = pipe.alloc_match(self.capacity - s)
+                    self._pairs[s] = pipe.alloc_match(self.capacity - s, **self._rule_kw)
         st = self._store
         pipe.extract(tokens, images_u8, out={k: v[n0:n0 + m] for k, v in st.items()}, images_ready=images_ready)
         res = {"frames": {k: v[n0:n0 + m] for k, v in st.items()}}
@@ -98,7 +101,7 @@ class StreamingSequence:
                 continue
             mm = pipe.match(st["descriptors"][lo:lo + cnt + s], st["scores"][lo:lo + cnt + s],
                             st["intensity"][lo:lo + cnt + s] if "intensity" in st else None, spacing=s,
-                            out={k: v[lo:lo + cnt] for k, v in self._pairs[s].items()})
+                            out={k: v[lo:lo + cnt] for k, v in self._pairs[s].items()}, **self._rule_kw)
             mm["first"] = torch.arange(lo, lo + cnt, dtype=torch.int64, device=tokens.device)
             res[s] = mm
         self.n_seen += m
@@ -137,7 +140,7 @@ class StreamingSequence:
                 continue
             a = lo - base
             sub = {k: v[a:a + cnt + s] for k, v in cat.items()}
-            mm = self.pipe.match(sub["descriptors"], sub["scores"], sub.get("intensity"), spacing=s)
+            mm = self.pipe.match(sub["descriptors"], sub["scores"], sub.get("intensity"), spacing=s, **self._rule_kw)
             mm["first"] = torch.arange(lo, lo + cnt, dtype=torch.int64, device=tokens.device)
             res[s] = mm
         keep = max(self.spacings)
@@ -359,11 +362,12 @@ def _push_vit_groups(pipe: SequencePipeline, seq: "StreamingSequence", feeder: "
 
 def run_frames(pipe: SequencePipeline, n: int, h: int, w: int, spacings=(1,), tokens: torch.Tensor | None = None, fill=None,
                pinned_source: torch.Tensor | None = None, chunk: int | None = None, first_chunk: int | None = None,
-               preprocess_too: bool = False, feeder_kw: dict | None = None) -> dict:
+               preprocess_too: bool = False, feeder_kw: dict | None = None, rule=None) -> dict:
     """Host-resident frames -> matches, with the upload of chunk i + 1 overlapping the compute of chunk i.
     tokens: device-resident ViT tokens of the n frames (tokens-in mode); None: the pipeline's HIP ViT computes them
     (pipe built with vit=).  preprocess_too: in tokens-in mode also run A0 on every chunk (the ViT input a real backbone would
-    consume; bench.py counts it in `value`).  Returns StreamingSequence.result() (sequence-sized buffers, written in place)."""
+    consume; bench.py counts it in `value`).  rule: StreamingSequence's.
+    Returns StreamingSequence.result() (sequence-sized buffers, written in place)."""
     if tokens is None and pipe.vit_hip is None:
         raise ValueError("tokens, or a pipeline built with vit=, required")
     if chunk is None:
@@ -375,7 +379,7 @@ def run_frames(pipe: SequencePipeline, n: int, h: int, w: int, spacings=(1,), to
             chunk = pipe.vit_hip.chunk_frames(pipe.cfg.input_size)
         else:
             chunk = max(1, min(pipe.launch_group(), max((n + 1) // 2, (1024 * 128) // pipe.cfg.grid ** 2)))
-    seq = StreamingSequence(pipe, spacings)
+    seq = StreamingSequence(pipe, spacings, rule=rule)
     seq.reset(capacity=n)
     feeder = FrameFeeder(n, h, w, pipe.device, chunk_bounds(n, chunk, first_chunk), fill=fill, pinned_source=pinned_source,
                          **(feeder_kw or {}))
@@ -393,7 +397,7 @@ def run_frames(pipe: SequencePipeline, n: int, h: int, w: int, spacings=(1,), to
 def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pipe: SequencePipeline | None = None,
                   selector_state: dict | None = None, refiner_state: dict | None = None, cfg: ExtractorConfig | None = None,
                   vit=None, tokens_fn=None, max_frames: int | None = None, chunk: int | None = None,
-                  decode_workers: int | None = None, device="cuda") -> dict:
+                  decode_workers: int | None = None, device="cuda", rule=None) -> dict:
     """A TUM RGB-D sequence directory -> matches for every requested spacing: the batched counterpart of the reference's
     main() -> process_spacing() -> extract(path) -> match loop (visualize_matches_sequence.py:272-357, 360-448) over the
     directory layout of data/tum_dataset.py:210-224 (rgb/*.png sorted by name).
@@ -401,7 +405,8 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     TUMSequence lists the frames; a thread pool decodes the PNGs of chunk i + 1 (PIL, 'RGB' as at :71) into a pinned
     staging buffer while chunk i is uploaded on a side stream and extracted + matched on the compute stream.
     Tokens come from the HIP ViT (`vit`: an sslam_amd.vit.DinoV3ViT holding the weights) or from `tokens_fn(a, b) ->
-    (b - a, 5 + G^2, 384) device tensor` (any other backbone).  Returns StreamingSequence.result() plus 'files'."""
+    (b - a, 5 + G^2, 384) device tensor` (any other backbone).  rule: StreamingSequence's.
+    Returns StreamingSequence.result() plus 'files'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
 
@@ -433,7 +438,7 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
 
     if chunk is None:
         chunk = pipe.vit_hip.chunk_frames(pipe.cfg.input_size) if tokens_fn is None else 64
-    seq = StreamingSequence(pipe, spacings)
+    seq = StreamingSequence(pipe, spacings, rule=rule)
     seq.reset(capacity=n)
     try:
         with torch.no_grad():

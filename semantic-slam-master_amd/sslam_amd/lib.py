@@ -79,6 +79,7 @@ EXPORTS = [
     "sslam_vit_f32_pack_linear_host", "sslam_vit_forward_f32_form",
     "sslam_vit_workspace_bytes_form", "sslam_vit_forward_form", "sslam_vit_forward_patches_form",
     "sslam_sim_argmax_pairs", "sslam_match_finalize_pairs", "sslam_selector_bf16_halo_groups",
+    "sslam_match_finalize_rule", "sslam_match_finalize_rule_pairs", "sslam_sim_argmax_rows", "sslam_sim_argmax_rows_pairs",
 ]
 
 
@@ -118,6 +119,10 @@ def lib():
         L.sslam_match_finalize.argtypes = [p, p, p, i, i, i, p, ll, p, ll, p, p, f, f, f, f, f, p, p, p, p]
         L.sslam_sim_argmax_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p, p, p, ll, p]
         L.sslam_match_finalize_pairs.argtypes = [p, p, p, i, i, p, p, i, p, ll, p, f, f, f, f, f, p, p, p, p]
+        L.sslam_match_finalize_rule.argtypes = [p, p, p, p, i, i, i, i, f, p, p, p, p]
+        L.sslam_match_finalize_rule_pairs.argtypes = [p, p, p, p, i, i, p, p, i, i, f, p, p, p, p]
+        L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
+        L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
         L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
         L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
         L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
@@ -586,6 +591,99 @@ def match_finalize_pairs(nn12, s12, nn21, first, second, scores, intensity, w_de
          _dp(nn12), _dp(s12), _dp(nn21), k, n_bank, _dp(first), _dp(second), n_pairs, _dp(scores), k, _dp(intensity),
          f(w_desc), f(w_sal), f(t_sal), f(t_sim), f(t_int), _dp(matches), _dp(quality), _dp(count))
     return matches, quality, count
+
+
+# rules of the sibling matchers the finalize stage can apply in place of M1's (include/sslam_hip.h)
+RULE_RATIO_BEST, RULE_RATIO_SECOND, RULE_TRACKED = 1, 2, 3
+
+
+def _check_arrays(shape, *named):
+    """named: (name, tensor or None, dtype); every tensor given must be contiguous, of that dtype and of `shape`."""
+    for name, t, dt in named:
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
+
+
+def _rows_out(out, n_pairs, n1, want_second, dev):
+    if out is None:
+        return (torch.empty((n_pairs, n1), dtype=torch.int32, device=dev), torch.empty((n_pairs, n1), dtype=torch.float32, device=dev),
+                torch.empty((n_pairs, n1), dtype=torch.float32, device=dev) if want_second else None)
+    nn12, s12, sec = out
+    if nn12 is None:
+        raise ValueError("out `nn12` is required")
+    _check_arrays((n_pairs, n1), ("out `nn12`", nn12, torch.int32), ("out `s12`", s12, torch.float32), ("out `second12`", sec, torch.float32))
+    return nn12, s12, sec
+
+
+def sim_argmax_rows(d1, stride1, n1, d2, stride2, n2, n_pairs, want_second=False, out=None):
+    """sslam_sim_argmax_rows: the row direction of sim_argmax alone - one launch, no workspace, the same bits.
+    Returns (nn12, s12, second12 or None).  out: optional (nn12, s12, second12 or None) tensors to write into."""
+    nn12, s12, sec = _rows_out(out, n_pairs, n1, want_second, d1.device)
+    _run("sim_argmax_rows", lib().sslam_sim_argmax_rows, (nn12, s12, sec, d1, d2),
+         C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs, _dp(nn12), _dp(s12), _dp(sec))
+    return nn12, s12, sec
+
+
+def sim_argmax_rows_pairs(bank, first, second, want_second=False, out=None):
+    """sslam_sim_argmax_rows_pairs: the row direction of sim_argmax_pairs alone (bank and lists as there).
+    Returns (nn12, s12, second12 or None), one row per listed pair.  out: optional tensors to write into, as sim_argmax_rows."""
+    _check_bank("bank", bank, ("K", D_OUT))
+    n_bank, k = int(bank.shape[0]), int(bank.shape[1])
+    n_pairs = check_pair_lists(first, second, bank.device)
+    dev = common_device(bank, first, second)
+    nn12, s12, sec = _rows_out(out, n_pairs, k, want_second, dev)
+    _run("sim_argmax_rows_pairs", lib().sslam_sim_argmax_rows_pairs, (bank, first, second, nn12, s12, sec),
+         _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(nn12), _dp(s12), _dp(sec))
+    return nn12, s12, sec
+
+
+def _check_rule_arrays(rule, n_pairs, n1, n2, nn12, s12, second12, nn21):
+    """The arg-max arrays a rule's finalize kernel reads, row for row: a short or mistyped one would be read past its end."""
+    for name, t in (("nn12", nn12), ("s12", s12)) + ((("second12", second12), ("nn21", nn21)) if int(rule) != RULE_TRACKED else ()):
+        if t is None:
+            raise ValueError(f"{name} is required by this rule")
+    _check_arrays((n_pairs, n1), ("nn12", nn12, torch.int32), ("s12", s12, torch.float32), ("second12", second12, torch.float32))
+    _check_arrays((n_pairs, n2), ("nn21", nn21, torch.int32))
+
+
+def _rule_out(out, n_pairs, n1, dev):
+    if out is not None:
+        matches, value, count = out
+        for name, t, dt, sh in (("matches", matches, torch.int64, (n_pairs, n1, 2)), ("value", value, torch.float32, (n_pairs, n1)),
+                                ("count", count, torch.int32, (n_pairs,))):
+            if t is None:
+                raise ValueError(f"out `{name}` is required")
+            _check_arrays(sh, (f"out `{name}`", t, dt))
+        return matches, value, count
+    return (torch.empty((n_pairs, n1, 2), dtype=torch.int64, device=dev), torch.empty((n_pairs, n1), dtype=torch.float32, device=dev),
+            torch.empty((n_pairs,), dtype=torch.int32, device=dev))
+
+
+def match_finalize_rule(nn12, s12, second12, nn21, n1, n2, n_pairs, rule, param, out=None):
+    """sslam_match_finalize_rule: rule RULE_RATIO_BEST (M2) / RULE_RATIO_SECOND (M4) / RULE_TRACKED (M5) with its fp32 parameter
+    on the arg-max arrays of sim_argmax (want_second=True) - or of sim_argmax_rows for RULE_TRACKED, which reads neither second12
+    nor nn21 (pass None).  Returns (matches, value, count); out: optional tensors of those shapes to write into."""
+    _check_rule_arrays(rule, n_pairs, n1, n2, nn12, s12, second12, nn21)
+    matches, value, count = _rule_out(out, n_pairs, n1, nn12.device)
+    _run("match_finalize_rule", lib().sslam_match_finalize_rule, (nn12, s12, second12, nn21, matches, value, count),
+         _dp(nn12), _dp(s12), _dp(second12), _dp(nn21), n1, n2, n_pairs, int(rule), C.c_float(param), _dp(matches), _dp(value),
+         _dp(count))
+    return matches, value, count
+
+
+def match_finalize_rule_pairs(nn12, s12, second12, nn21, first, second, n_bank, rule, param, out=None):
+    """sslam_match_finalize_rule_pairs: match_finalize_rule on the arrays of sim_argmax_pairs / sim_argmax_rows_pairs over the
+    same two lists into a bank of n_bank frames (the lists only tell which pairs are absent: count 0, zero rows)."""
+    n_pairs = check_pair_lists(first, second, nn12.device if isinstance(nn12, torch.Tensor) else None)
+    if not isinstance(nn12, torch.Tensor) or nn12.dim() != 2 or nn12.shape[0] != n_pairs:
+        raise ValueError(f"nn12 must be a tensor of shape ({n_pairs}, K)")
+    k = int(nn12.shape[1])
+    _check_rule_arrays(rule, n_pairs, k, k, nn12, s12, second12, nn21)
+    matches, value, count = _rule_out(out, n_pairs, k, nn12.device)
+    _run("match_finalize_rule_pairs", lib().sslam_match_finalize_rule_pairs, (nn12, s12, second12, nn21, first, second, matches, value, count),
+         _dp(nn12), _dp(s12), _dp(second12), _dp(nn21), k, int(n_bank), _dp(first), _dp(second), n_pairs, int(rule), C.c_float(param),
+         _dp(matches), _dp(value), _dp(count))
+    return matches, value, count
 
 
 def pack_vit_linear(w: np.ndarray) -> np.ndarray:

@@ -41,7 +41,7 @@ from __future__ import annotations
 import torch
 
 from . import lib
-from .pipeline import N_PREFIX, SequencePipeline
+from .pipeline import N_PREFIX, SequencePipeline, _checked_rule
 
 
 BANK_KEYS = ("descriptors", "scores", "intensity", "keypoints_pixel")      # what an earlier frame is kept for
@@ -57,6 +57,9 @@ def _checked_spacings(spacings) -> tuple:
 
 
 class FrameStepper:
+    rule = None         # M1.  Only RuleFrameStepper (below) sets a pipeline.MatchRule, in its constructor; with None every call
+                        # this class makes into the pipeline is the call it made before rules existed (_rule_kw)
+
     def __init__(self, pipe: SequencePipeline, height: int, width: int, use_graph: bool = True, tokens_in: bool = False,
                  spacings=None):
         """pipe: a SequencePipeline (with vit= unless tokens_in).  height / width: the frames' size (uint8 RGB).
@@ -66,7 +69,8 @@ class FrameStepper:
         8 frames bit for bit, those of a longer batch within the float64 bars (module docstring).  Which few-frame form the bf16
         ViT runs is the pipeline's choice (SequencePipeline(vit_form=...)): the small form by default, "few_frame" by name.
         spacings: None - match against the previous frame (above); a sequence of distinct positive ints - match every frame
-        against the frames that many steps back, all in one launch pair (module docstring; step() says what comes back)."""
+        against the frames that many steps back, all in one launch pair (module docstring; step() says what comes back).
+        The matcher is M1; the class attribute `rule` is set only by the subclass RuleFrameStepper."""
         if spacings is not None:
             spacings = _checked_spacings(spacings)       # before anything is allocated
         cfg = pipe.cfg
@@ -92,7 +96,12 @@ class FrameStepper:
         for v in self.pair.values():
             v.zero_()
         self.cur = {k: v[1:2] for k, v in self.pair.items()}
-        self.m = pipe.alloc_match(1, K)
+        self.m = pipe.alloc_match(1, K, **self._rule_kw())
+
+    def _rule_kw(self) -> dict:
+        """rule None adds no argument to a pipeline call (harness.StreamingSequence's convention: a pipeline that knows no `rule`
+        still serves the stepper without one)."""
+        return {} if self.rule is None else {"rule": self.rule}
 
     def _init_bank(self, spacings: tuple) -> None:
         pipe, dev = self.pipe, self.device
@@ -104,7 +113,7 @@ class FrameStepper:
         self.bank = {k: torch.zeros((ring + 1,) + tuple(one[k].shape[1:]), dtype=one[k].dtype, device=dev) for k in BANK_KEYS}
         self._ring = {k: v[:ring] for k, v in self.bank.items()}
         self.cur = {k: (self.bank[k][ring:ring + 1] if k in BANK_KEYS else v) for k, v in one.items()}
-        self.m = pipe.alloc_match(len(spacings), self.cfg.num_keypoints)
+        self.m = pipe.alloc_match(len(spacings), self.cfg.num_keypoints, **self._rule_kw())
         i64 = dict(dtype=torch.int64, device=dev)
         self._t = torch.zeros((1,), **i64)                                   # the step counter: frames since reset()
         self._sp = torch.tensor(spacings, **i64)
@@ -123,7 +132,8 @@ class FrameStepper:
         if not self.tokens_in:
             p.tokens_from_images(self.image, out=self.tokens)
         p.extract(self.tokens, self.image, out=self.cur)
-        self._aux = p.match(self.pair["descriptors"], self.pair["scores"], self.pair["intensity"], spacing=1, out=self.m)
+        self._aux = p.match(self.pair["descriptors"], self.pair["scores"], self.pair["intensity"], spacing=1, out=self.m,
+                            **self._rule_kw())
         for k in ("descriptors", "scores", "intensity", "keypoints_pixel"):      # this frame becomes the previous one
             self.pair[k][0].copy_(self.pair[k][1])
 
@@ -139,7 +149,7 @@ class FrameStepper:
         torch.where(self._seen, self._back_slot, self._absent, out=self._first64)
         self.first_slot.copy_(self._first64)
         self._aux = p.match_pairs(self.bank["descriptors"], self.bank["scores"], self.bank["intensity"], first=self.first_slot,
-                                  second=self.second_slot, out=self.m)
+                                  second=self.second_slot, out=self.m, **self._rule_kw())
         # this frame takes the ring slot of frame t - ring, which no spacing reaches any more
         torch.remainder(self._t, ring, out=self._slot)
         for k in BANK_KEYS:
@@ -189,7 +199,8 @@ class FrameStepper:
         from the second frame on, matches (K, 2) int64 / quality (K,) / match_count against the previous frame (None before).
         With spacings: matches (S, K, 2) / quality (S, K) / match_count (S,), one row per spacing in the order given (views of
         static buffers; a spacing that reaches back before the first frame has count 0 and zero rows), and pair_first: a host
-        list of the global index of each row's first frame, -1 where there is none yet.  The second frame is this one."""
+        list of the global index of each row's first frame, -1 where there is none yet.  The second frame is this one.
+        Under a rule (RuleFrameStepper) `value` takes the place of `quality` everywhere above."""
         if self.use_graph and self._graph is None:
             self._capture()                      # runs the body on whatever the buffers hold; the first real frame has no previous one
         self.image.copy_(image_u8.reshape(self.image.shape), non_blocking=True)
@@ -204,13 +215,15 @@ class FrameStepper:
         first = self.n_frames == 0
         self.n_frames += 1
         out = {k: v[0] for k, v in self.cur.items()}
+        val = "quality" if self.rule is None else "value"
         if self.spacings is not None:
             t = self.n_frames - 1
-            out.update(matches=self.m["matches"], quality=self.m["quality"], match_count=self.m["match_count"],
+            out.update(matches=self.m["matches"], match_count=self.m["match_count"],
                        pair_first=[t - s if t >= s else -1 for s in self.spacings])
+            out[val] = self.m[val]
             return out
         out["matches"] = None if first else self.m["matches"][0]
-        out["quality"] = None if first else self.m["quality"][0]
+        out[val] = None if first else self.m[val][0]
         out["match_count"] = None if first else self.m["match_count"][0]
         return out
 
@@ -227,3 +240,18 @@ class FrameStepper:
         if self.spacings is None or not max(0, self.n_frames - self.ring) <= index < self.n_frames:
             raise ValueError(f"frame {index} is not in the bank")
         return {k: v[index % self.ring] for k, v in self.bank.items()}
+
+
+class RuleFrameStepper(FrameStepper):
+    """FrameStepper whose matcher stage applies a pipeline.MatchRule - the ratio tests M2 / M4, or M5's tracking count, which is
+    the loop of test/test_tracking.py:146-178 as it stands: keep the previous descriptors, count the rows whose best similarity
+    exceeds 0.8.  Same step, same buffers, one-spacing body and spacings= body, ordinary launches and the captured graph: the
+    rule's finalize kernel stands where M1's stood (and, for tracked, the rows-only similarity launch where the two-direction one
+    stood) on the same one stream - no parallel branches, no host value entering the body; rule and threshold are baked in like
+    the M1 thresholds are.  step() returns `value` in place of `quality`.
+    A class of its own, since FrameStepper's constructor signature is pinned by its tests; rule=None is FrameStepper."""
+
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, use_graph: bool = True, tokens_in: bool = False,
+                 spacings=None, rule=None):
+        self.rule = _checked_rule(rule, pipe.cfg.num_keypoints)      # before anything is allocated
+        super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=spacings)

@@ -10,6 +10,8 @@ PyTorch is plumbing only (device buffers, streams); all arithmetic runs in libss
 """
 from __future__ import annotations
 
+import math
+import numbers
 from dataclasses import dataclass
 
 import numpy as np
@@ -51,6 +53,60 @@ class ExtractorConfig:
         """Frames per launch group: chunk_frames, but never more than one 32-bit buffer descriptor can span (the saliency CNN
         addresses the fp32 feature map through a single descriptor: < 4 GiB per launch; 2 965 frames at G = 40 are 7.3 GB)."""
         return max(1, min(self.chunk_frames, (2 ** 32 - 1) // (self.grid ** 2 * 384 * 4)))
+
+
+@dataclass(frozen=True)
+class MatchRule:
+    """One of the reference's sibling matchers as the rule of the matcher stage (`rule=` of SequencePipeline.match / match_pairs,
+    harness.StreamingSequence, online.RuleFrameStepper; include/sslam_hip.h states each rule).  `param` is the threshold rounded
+    to fp32 once, as a Python float: the reference compares fp32 arrays with a Python scalar, which numpy rounds to fp32 first.
+    Built by the three constructors, whose names and defaults are the reference's arguments."""
+    kind: int
+    param: float
+
+    @staticmethod
+    def _fp32(name: str, v) -> float:
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        with np.errstate(over="ignore"):
+            r = float(np.float32(v))
+        if not math.isfinite(r):
+            raise ValueError(f"{name} = {v!r} is not finite in fp32")
+        return r
+
+    @classmethod
+    def ratio(cls, ratio_thresh: float = 0.8) -> "MatchRule":
+        """M2, MatchVisualizer.find_matches (visualize_matches.py:102-124): mutual nearest neighbours whose similarity exceeds
+        ratio_thresh times the row's runner-up; `value` is the similarity."""
+        return cls(lib.RULE_RATIO_BEST, cls._fp32("ratio_thresh", ratio_thresh))
+
+    @classmethod
+    def mnn_ratio(cls, ratio_threshold: float = 0.9) -> "MatchRule":
+        """M4, find_mutual_nearest_neighbors (test/test_descriptor_quality.py:97-142): mutual nearest neighbours with
+        runner-up / (best + 1e-8) below ratio_threshold; `value` is the cosine DISTANCE 1 - similarity."""
+        return cls(lib.RULE_RATIO_SECOND, cls._fp32("ratio_threshold", ratio_threshold))
+
+    @classmethod
+    def tracked(cls, match_threshold: float = 0.8) -> "MatchRule":
+        """M5, the tracking count (test/test_tracking.py:158-161): rows whose best similarity exceeds match_threshold, no mutual
+        check - `match_count` is the reference's count, `matches` row (i, nn12[i]), `value` the similarity.  Reads the row
+        direction only: the matcher takes the rows-only similarity launch."""
+        return cls(lib.RULE_TRACKED, cls._fp32("match_threshold", match_threshold))
+
+    def __post_init__(self):
+        if self.kind not in (lib.RULE_RATIO_BEST, lib.RULE_RATIO_SECOND, lib.RULE_TRACKED):
+            raise ValueError(f"unknown rule kind {self.kind!r}")
+        if self._fp32("param", self.param) != self.param:
+            raise ValueError(f"param {self.param!r} is not an fp32 value: use the constructors")
+
+
+def _checked_rule(rule, k: int):
+    """rule=: None or a MatchRule; M4 on fewer than two candidates raises what the reference's np.sort(...)[:, 1] raises."""
+    if rule is not None and not isinstance(rule, MatchRule):
+        raise ValueError(f"rule must be None or a MatchRule, got {type(rule).__name__}")
+    if rule is not None and rule.kind == lib.RULE_RATIO_SECOND and k < 2:
+        raise IndexError(f"index 1 is out of bounds for axis 1 with size {k}")
+    return rule
 
 
 def _np(v):
@@ -391,26 +447,74 @@ class SequencePipeline:
             th, tv = self.tables.get(h, w, cfg.input_size, True)
             lib.keypoint_intensity(images_u8, cfg.input_size, th, tv, out["keypoints_pixel"], out=out["intensity"])
 
-    def alloc_match(self, n_pairs: int, k: int | None = None) -> dict:
-        """Output buffers of match() for n_pairs pairs (fixed capacity K per pair + device-side count)."""
+    def alloc_match(self, n_pairs: int, k: int | None = None, rule: MatchRule | None = None) -> dict:
+        """Output buffers of match() for n_pairs pairs (fixed capacity K per pair + device-side count).
+        rule: the buffers of match(rule=...): `value` in place of `quality` (a distance must not pass for a quality)."""
         k = self.cfg.num_keypoints if k is None else k
         dev = self.device
-        return dict(matches=torch.empty((n_pairs, k, 2), dtype=torch.int64, device=dev),
-                    quality=torch.empty((n_pairs, k), dtype=torch.float32, device=dev),
-                    match_count=torch.empty((n_pairs,), dtype=torch.int32, device=dev))
+        return {"matches": torch.empty((n_pairs, k, 2), dtype=torch.int64, device=dev),
+                ("quality" if rule is None else "value"): torch.empty((n_pairs, k), dtype=torch.float32, device=dev),
+                "match_count": torch.empty((n_pairs,), dtype=torch.int32, device=dev)}
 
-    def match(self, desc, scores, intensity=None, spacing: int | None = None, out: dict | None = None) -> dict:
+    @staticmethod
+    def _rule_result(res: dict, aux: list) -> dict:
+        """The arg-max arrays a rule's launches produced (nn12, sim; second and nn21 where the rule reads them), beside its outputs."""
+        for key in aux[0]:
+            res[key] = aux[0][key] if len(aux) == 1 else torch.cat([x[key] for x in aux])
+        return res
+
+    def _match_rule(self, rule: MatchRule, desc, sp: int, res: dict) -> dict:
+        """match() under a rule: the same cuts, the rule's finalize entry; RULE_TRACKED takes the rows-only similarity launch."""
+        n, k = desc.shape[0], desc.shape[1]
+        n_pairs, aux = n - sp, []
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):
+            m = min(MAX_PAIRS_PER_LAUNCH, n_pairs - a)
+            d1, d2 = desc[a:a + m], desc[a + sp:a + sp + m]
+            if rule.kind == lib.RULE_TRACKED:
+                nn12, s12, sec = lib.sim_argmax_rows(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m)
+                nn21 = None
+            else:
+                nn12, s12, nn21, _, sec = lib.sim_argmax(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, want_second=True,
+                                                         workspace=self.workspace(0, m))
+            lib.match_finalize_rule(nn12, s12, sec, nn21, k, k, m, rule.kind, rule.param,
+                                    out=(res["matches"][a:a + m], res["value"][a:a + m], res["match_count"][a:a + m]))
+            aux.append({key: t for key, t in (("nn12", nn12), ("sim", s12), ("second", sec), ("nn21", nn21)) if t is not None})
+        return self._rule_result(res, aux)
+
+    def _match_pairs_rule(self, rule: MatchRule, desc, first, second, n_pairs: int, res: dict) -> dict:
+        aux = []
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):
+            m = min(MAX_PAIRS_PER_LAUNCH, n_pairs - a)
+            f, s = first[a:a + m], second[a:a + m]
+            if rule.kind == lib.RULE_TRACKED:
+                nn12, s12, sec = lib.sim_argmax_rows_pairs(desc, f, s)
+                nn21 = None
+            else:
+                nn12, s12, nn21, _, sec = lib.sim_argmax_pairs(desc, f, s, want_second=True, workspace=self.workspace(0, m))
+            lib.match_finalize_rule_pairs(nn12, s12, sec, nn21, f, s, desc.shape[0], rule.kind, rule.param,
+                                          out=(res["matches"][a:a + m], res["value"][a:a + m], res["match_count"][a:a + m]))
+            aux.append({key: t for key, t in (("nn12", nn12), ("sim", s12), ("second", sec), ("nn21", nn21)) if t is not None})
+        return self._rule_result(res, aux)
+
+    def match(self, desc, scores, intensity=None, spacing: int | None = None, out: dict | None = None,
+              rule: MatchRule | None = None) -> dict:
         """M1 for all pairs (i, i + spacing) inside the batch.  desc (N, K, 128), scores (N, K), intensity (N, K).
-        out: row slices of alloc_match buffers to write into (the streaming scheduler passes slices of sequence-sized ones)."""
+        out: row slices of alloc_match buffers to write into (the streaming scheduler passes slices of sequence-sized ones).
+        rule: a MatchRule - the same pairs under M2 / M4 / M5 instead (scores, intensity and the M1 thresholds are not read).
+        Returns matches, match_count and `value` (similarity; distance 1 - similarity under mnn_ratio) - no `quality` key - with
+        nn12 and sim, and second and nn21 under the two ratio rules (tracked computes neither); out: alloc_match(rule=) buffers."""
         cfg = self.cfg
         sp = cfg.spacing if spacing is None else spacing
         n, k = desc.shape[0], desc.shape[1]
+        rule = _checked_rule(rule, k)
         n_pairs = n - sp
         if n_pairs <= 0:
             z = torch.zeros
-            return dict(matches=z((0, k, 2), dtype=torch.int64, device=desc.device),
-                        quality=z((0, k), dtype=torch.float32, device=desc.device),
-                        match_count=z((0,), dtype=torch.int32, device=desc.device))
+            return {"matches": z((0, k, 2), dtype=torch.int64, device=desc.device),
+                    ("quality" if rule is None else "value"): z((0, k), dtype=torch.float32, device=desc.device),
+                    "match_count": z((0,), dtype=torch.int32, device=desc.device)}
+        if rule is not None:
+            return self._match_rule(rule, desc, sp, dict(out) if out is not None else self.alloc_match(n_pairs, k, rule))
         use_int = cfg.use_intensity and intensity is not None
         res = dict(out) if out is not None else self.alloc_match(n_pairs, k)
         aux = []
@@ -428,23 +532,29 @@ class SequencePipeline:
             res[key] = aux[0][i] if len(aux) == 1 else torch.cat([x[i] for x in aux])
         return res
 
-    def match_pairs(self, desc, scores, intensity=None, first=None, second=None, out: dict | None = None) -> dict:
+    def match_pairs(self, desc, scores, intensity=None, first=None, second=None, out: dict | None = None,
+                    rule: MatchRule | None = None) -> dict:
         """M1 for a LIST of pairs of the bank desc (N, K, 128) / scores (N, K) / intensity (N, K): row p matches frame first[p]
         against frame second[p] - any two frames, in any order, as often as listed; an index outside [0, N) (-1 by convention)
         makes the pair absent: count 0, zero rows.  first / second: 1-D int32 device tensors (they may be written by earlier work
         of the stream: nothing here reads them on the host), or host sequences of ints, uploaded once.
         Returns match()'s dictionary with one row per listed pair, in list order; per pair the same bits as match() on the same
-        two frames.  out: alloc_match buffers (or row slices of them) to write into."""
+        two frames.  out: alloc_match buffers (or row slices of them) to write into.
+        rule: a MatchRule - the listed pairs under M2 / M4 / M5, returning what match(rule=) returns."""
         cfg = self.cfg
         if first is None or second is None:
             raise ValueError("match_pairs needs both pair lists, first= and second=")
         if desc.dim() != 3 or scores.dim() != 2 or tuple(scores.shape) != tuple(desc.shape[:2]):
             raise ValueError(f"desc (N, K, {lib.D_OUT}) and scores (N, K) expected, got {tuple(desc.shape)} and {tuple(scores.shape)}")
+        rule = _checked_rule(rule, desc.shape[1])
         first, second = _host_pair_list("first", first), _host_pair_list("second", second)
         n_pairs = lib.check_pair_lists(first, second)             # a malformed list is refused before anything is uploaded
         first, second = (t if t.is_cuda else t.to(desc.device) for t in (first, second))
         lib.check_pair_lists(first, second, desc.device)
         k = desc.shape[1]
+        if rule is not None:
+            return self._match_pairs_rule(rule, desc, first, second, n_pairs,
+                                          dict(out) if out is not None else self.alloc_match(n_pairs, k, rule))
         use_int = cfg.use_intensity and intensity is not None
         res = dict(out) if out is not None else self.alloc_match(n_pairs, k)
         aux = []

@@ -177,6 +177,10 @@ class ShardedSequenceRunner:
     are written straight into block-sized buffers - no concatenation of the boundary group and the rest.
     match_fn(desc, scores, intensity, spacing) -> dict with 'matches' (p, K, 2) int64, 'quality' (p, K), 'match_count' (p,)
     Both run on this rank's device; in production they are SequencePipeline.extract / .match.
+    A pipeline.MatchRule (M2 / M4 / M5) needs nothing added here, match_fn being any callable: pass
+    `lambda d, s, i, sp: pipe.match(d, s, i, sp, rule=rule)`.  That dict has 'value' where M1's has 'quality', and the gathers
+    ship the array NAMED 'quality': a callable whose result is gathered also sets m["quality"] = m["value"] (all_quality is
+    then the rule's value).
     Pair numbers in the gathered records are the SEQUENCE's pair numbers: every rank sends local pair indices and rank 0
     adds the exclusive prefix sum of the ranks' pair counts (from the size exchange) - callers pass no offset."""
 
