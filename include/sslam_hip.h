@@ -421,6 +421,75 @@ int sslam_vit_forward_form(const float *images_chw, int n_frames, int size, cons
 int sslam_vit_forward_patches_form(const void *patches_bf16, int n_frames, int size, const sslam_vit_weights_t *weights_host_struct,
                                    void *workspace, long long workspace_bytes, float *tokens_out, int form, void *stream);
 
+/* ---- Checkpoint validation: the forward of the trainer's losses under no_grad (train.py:451-499 validate -> :292-408
+ * _forward_pass; losses/self_supervised.py), as per-frame and per-pair statistics a host function composes into the seven
+ * loss terms and five batch metrics for any batch size (sslam_amd/validation.py states the composition).  Forward only.
+ * Every sum below has one order fixed by the shapes alone: a frame's or a pair's results are the same bits in any launch.
+ *
+ * sslam_row_lse / sslam_row_lse_pairs: for every row i of frame a against all rows j of frame b, with
+ *   x_ij = clamp(s_ij / temperature, -50, 50) (self_supervised.py:58-59; s_ij the similarity bits of sslam_sim_argmax):
+ *     ce[pair, i]  = log sum_j exp(x_ij - max_j x_ij)       the row's cross-entropy against its nearest neighbour (:62)
+ *     lse[pair, i] = max_j x_ij + ce[pair, i]               = log sum_j exp(x_ij)
+ *     s00[pair]    = s_00                                   (the target of the trainer's zero-padded match rows, train.py:445)
+ *   s12 (n_pairs, n1) must be the row maxima of the same pairs, as sslam_sim_argmax / sslam_sim_argmax_rows (and their _pairs
+ *   forms) write them: the kernel sums exp(x_ij - clamp(s12_i / temperature)) in one pass.  Each of lse, ce, s00 may be NULL
+ *   (lse and ce not both).  Pairs are named as in sslam_sim_argmax_rows / sslam_sim_argmax_rows_pairs (strides in floats; an
+ *   index outside [0, n_bank), -1 by convention, is an absent pair: zero rows, s00 = 0).  temperature > 0, finite.
+ *   The K x K logits are never written to memory; exp and log are the library's canonical fmaf-only forms. */
+int sslam_row_lse(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
+                  const float *s12, float temperature, float *lse, float *ce, float *s00, void *stream);
+int sslam_row_lse_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                        const int32_t *pair_second, int n_pairs, const float *s12, float temperature, float *lse, float *ce,
+                        float *s00, void *stream);
+/* sslam_edge_pool: the image side of EdgeAwarenessLoss.forward (self_supervised.py:248-260) in one pass over the fp32
+ * normalised image (n, 3, size, size) that sslam_preprocess_u8 writes, size % 16 == 0 (else SSLAM_E_UNSUPPORTED):
+ *   gray = 0.299 c0 + 0.587 c1 + 0.114 c2; 3 x 3 Sobel x and y with ZERO padding at the border; mag = sqrt(gx^2 + gy^2 + 1e-8);
+ *   pooled (n, size/16, size/16) = the 16 x 16 block means of mag (what adaptive_avg_pool2d gives at this size, before the
+ *   reference's division by the batch maximum: a positive factor the host applies); edge_max (n) = the frame's maximum of mag.
+ * images_chw 16-byte aligned.  No scratch: the maximum is an integer atomic max on the bits of the positive magnitudes. */
+int sslam_edge_pool(const float *images_chw, int n_frames, int size, float *pooled, float *edge_max, void *stream);
+/* sslam_val_frame_stats: one row of SSLAM_VAL_FRAME_STATS floats per frame from its saliency map (n, G, G):
+ *   SAL_MEAN, SAL_VAR (biased, :196), SAL_MAX, SAL_DX = sum |s[y][x+1] - s[y][x]|, SAL_DY = sum |s[y+1][x] - s[y][x]| (:300-301),
+ *   SAL_HIGH = number of cells > 0.6 (:309), SAL_SS = sum (s - mean)^2;
+ *   with pooled / edge_max of sslam_edge_pool (both or neither; without them the EDGE slots are 0): EDGE_MEAN = mean P,
+ *   EDGE_A = sum (P - mean P)(s - mean s), EDGE_E = sum (P - mean P)^2 (:270-275), EDGE_MAX = edge_max;
+ *   with descriptors (n, K, 128) (or NULL): desc_mean (n, 128) the mean over the K rows per dimension, desc_m2 (n, 128) the sum
+ *   of squares about it (two passes) - frames combine by the pairwise update of mean and M2 (:102-109). */
+#define SSLAM_VAL_FRAME_STATS 12
+#define SSLAM_VAL_SAL_MEAN 0
+#define SSLAM_VAL_SAL_VAR 1
+#define SSLAM_VAL_SAL_MAX 2
+#define SSLAM_VAL_SAL_DX 3
+#define SSLAM_VAL_SAL_DY 4
+#define SSLAM_VAL_SAL_HIGH 5
+#define SSLAM_VAL_SAL_SS 6
+#define SSLAM_VAL_EDGE_A 7
+#define SSLAM_VAL_EDGE_E 8
+#define SSLAM_VAL_EDGE_MEAN 9
+#define SSLAM_VAL_EDGE_MAX 10
+int sslam_val_frame_stats(const float *saliency, const float *pooled, const float *edge_max, const float *descriptors, int n_frames,
+                          int G, int K, float *stats, float *desc_mean, float *desc_m2, void *stream);
+/* sslam_val_pair_stats / sslam_val_pair_stats_pairs: one row of SSLAM_VAL_PAIR_STATS floats per pair (a, b):
+ *   PAIR_REPEAT  = mean (s_a - s_b)^2 over the G x G cells (RepeatabilityLoss, :180-182);
+ *   PAIR_MATCHES = number of rows i with nn21[nn12[i]] == i, the mutual nearest neighbours of _find_matches (train.py:423-428;
+ *                  no thresholds), also as an integer in n_matches (n_pairs);
+ *   PAIR_CE_SUM  = sum of ce[i] over those rows;
+ *   PAIR_PAD_CE  = lse_0 - x_00 = ce[0] + (clamp(s12[0] / T) - clamp(s00 / T)): a zero-padded match row.
+ * nn12, nn21, s12 from sslam_sim_argmax[_pairs], ce and s00 from sslam_row_lse[_pairs] over the same pairs; the strided form
+ * takes frame p of saliency1 and of saliency2 (n_pairs, G, G each), the listed form a bank (n_bank, G, G) and the two lists
+ * (an absent pair: a zero row, n_matches 0). */
+#define SSLAM_VAL_PAIR_STATS 4
+#define SSLAM_VAL_PAIR_REPEAT 0
+#define SSLAM_VAL_PAIR_CE_SUM 1
+#define SSLAM_VAL_PAIR_PAD_CE 2
+#define SSLAM_VAL_PAIR_MATCHES 3
+int sslam_val_pair_stats(const float *saliency1, const float *saliency2, int G, const int32_t *nn12, const int32_t *nn21,
+                         const float *s12, const float *ce, const float *s00, int n1, int n2, int n_pairs, float temperature,
+                         float *stats, int32_t *n_matches, void *stream);
+int sslam_val_pair_stats_pairs(const float *saliency_bank, int G, int n_bank, const int32_t *pair_first, const int32_t *pair_second,
+                               const int32_t *nn12, const int32_t *nn21, const float *s12, const float *ce, const float *s00, int K,
+                               int n_pairs, float temperature, float *stats, int32_t *n_matches, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

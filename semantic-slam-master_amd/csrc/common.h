@@ -93,6 +93,28 @@ __device__ __forceinline__ float sslam_expf(float x) {
     int ni = (int)n;
     return e * __int_as_float((ni + 127) << 23);
 }
+// canonical natural logarithm of a positive normal x, fmaf only: x = 2^e * m with m in [sqrt(1/2), sqrt(2)),
+// log(m) = f - f^2/2 + f^3 P(f) at f = m - 1 (the degree-8 polynomial of Cephes' logf), e * log(2) added in two parts
+__device__ __forceinline__ float sslam_logf(float x) {
+    const int ix = __float_as_int(x);
+    const int e = (ix - 0x3f3504f3) >> 23;          // 0x3f3504f3 = sqrt(1/2)
+    const float f = __int_as_float(ix - (e << 23)) - 1.0f;
+    const float fe = (float)e;
+    float p = 7.0376836292e-2f;
+    p = __builtin_fmaf(p, f, -1.1514610310e-1f);
+    p = __builtin_fmaf(p, f, 1.1676998740e-1f);
+    p = __builtin_fmaf(p, f, -1.2420140846e-1f);
+    p = __builtin_fmaf(p, f, 1.4249322787e-1f);
+    p = __builtin_fmaf(p, f, -1.6668057665e-1f);
+    p = __builtin_fmaf(p, f, 2.0000714765e-1f);
+    p = __builtin_fmaf(p, f, -2.4999993993e-1f);
+    p = __builtin_fmaf(p, f, 3.3333331174e-1f);
+    const float z = f * f;
+    float y = (p * f) * z;
+    y = __builtin_fmaf(fe, -2.12194440e-4f, y);
+    y = __builtin_fmaf(-0.5f, z, y);
+    return __builtin_fmaf(fe, 0.693359375f, f + y);
+}
 __device__ __forceinline__ float sslam_sigmoid(float x) { return 1.0f / (1.0f + sslam_expf(-x)); }
 
 // 8 consecutive logical k values (two float4 loads) -> the two float4 of the KP8 image

@@ -80,6 +80,8 @@ EXPORTS = [
     "sslam_vit_workspace_bytes_form", "sslam_vit_forward_form", "sslam_vit_forward_patches_form",
     "sslam_sim_argmax_pairs", "sslam_match_finalize_pairs", "sslam_selector_bf16_halo_groups",
     "sslam_match_finalize_rule", "sslam_match_finalize_rule_pairs", "sslam_sim_argmax_rows", "sslam_sim_argmax_rows_pairs",
+    "sslam_row_lse", "sslam_row_lse_pairs", "sslam_edge_pool", "sslam_val_frame_stats", "sslam_val_pair_stats",
+    "sslam_val_pair_stats_pairs",
 ]
 
 
@@ -123,6 +125,12 @@ def lib():
         L.sslam_match_finalize_rule_pairs.argtypes = [p, p, p, p, i, i, p, p, i, i, f, p, p, p, p]
         L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
         L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
+        L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
+        L.sslam_row_lse_pairs.argtypes = [p, ll, i, i, p, p, i, p, f, p, p, p, p]
+        L.sslam_edge_pool.argtypes = [p, i, i, p, p, p]
+        L.sslam_val_frame_stats.argtypes = [p, p, p, p, i, i, i, p, p, p, p]
+        L.sslam_val_pair_stats.argtypes = [p, p, i, p, p, p, p, p, i, i, i, f, p, p, p]
+        L.sslam_val_pair_stats_pairs.argtypes = [p, i, i, p, p, p, p, p, p, p, i, i, f, p, p, p]
         L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
         L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
         L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
@@ -684,6 +692,142 @@ def match_finalize_rule_pairs(nn12, s12, second12, nn21, first, second, n_bank, 
          _dp(nn12), _dp(s12), _dp(second12), _dp(nn21), k, int(n_bank), _dp(first), _dp(second), n_pairs, int(rule), C.c_float(param),
          _dp(matches), _dp(value), _dp(count))
     return matches, value, count
+
+
+# ------------------------------------------------------------------------------------------------ validation stage
+# slots of a sslam_val_frame_stats / sslam_val_pair_stats row (include/sslam_hip.h)
+VAL_FRAME_STATS, VAL_PAIR_STATS = 12, 4
+VAL_FRAME_SLOTS = dict(sal_mean=0, sal_var=1, sal_max=2, sal_dx=3, sal_dy=4, sal_high=5, sal_ss=6, edge_a=7, edge_e=8, edge_mean=9,
+                       edge_max=10)
+VAL_PAIR_SLOTS = dict(repeat=0, ce_sum=1, pad_ce=2, matches=3)
+
+
+def check_temperature(temperature) -> float:
+    """The InfoNCE temperature as the fp32 value the kernels divide by: a finite number above zero, else ValueError."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.floating, np.integer)):
+        raise ValueError(f"temperature must be a number, got {temperature!r}")
+    t = float(np.float32(temperature))
+    if not (t > 0.0 and np.isfinite(t)):
+        raise ValueError(f"temperature must be finite and positive, got {temperature!r}")
+    return t
+
+
+def _lse_out(n_pairs, n1, dev):
+    f32 = dict(dtype=torch.float32, device=dev)
+    return torch.empty((n_pairs, n1), **f32), torch.empty((n_pairs, n1), **f32), torch.empty((n_pairs,), **f32)
+
+
+def row_lse(d1, stride1, n1, d2, stride2, n2, n_pairs, s12, temperature=0.1):
+    """sslam_row_lse: (lse, ce, s00) of the rows of frame p of d1 against frame p of d2; s12 (n_pairs, n1): the row maxima that
+    sim_argmax / sim_argmax_rows wrote for the same pairs."""
+    t = check_temperature(temperature)
+    _check_arrays((n_pairs, n1), ("s12", s12, torch.float32))
+    lse, ce, s00 = _lse_out(n_pairs, n1, d1.device)
+    _run("row_lse", lib().sslam_row_lse, (d1, d2, s12, lse, ce, s00),
+         C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs, _dp(s12), C.c_float(t), _dp(lse),
+         _dp(ce), _dp(s00))
+    return lse, ce, s00
+
+
+def row_lse_pairs(bank, first, second, s12, temperature=0.1):
+    """sslam_row_lse_pairs: row_lse for the listed pairs of bank (n_bank, K, 128); lists as sim_argmax_pairs takes them."""
+    t = check_temperature(temperature)
+    _check_bank("bank", bank, ("K", D_OUT))
+    n_bank, k = int(bank.shape[0]), int(bank.shape[1])
+    n_pairs = check_pair_lists(first, second, bank.device)
+    _check_arrays((n_pairs, k), ("s12", s12, torch.float32))
+    lse, ce, s00 = _lse_out(n_pairs, k, bank.device)
+    _run("row_lse_pairs", lib().sslam_row_lse_pairs, (bank, first, second, s12, lse, ce, s00),
+         _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(s12), C.c_float(t), _dp(lse), _dp(ce), _dp(s00))
+    return lse, ce, s00
+
+
+def edge_pool(images_chw, out=None):
+    """sslam_edge_pool: fp32 (n, 3, S, S) -> (pooled (n, S/16, S/16), edge_max (n,)).  out: optional tensors to write into."""
+    if (not isinstance(images_chw, torch.Tensor) or images_chw.dtype != torch.float32 or images_chw.dim() != 4 or images_chw.shape[1] != 3
+            or images_chw.shape[2] != images_chw.shape[3] or images_chw.shape[2] % 16 or not images_chw.is_contiguous()):
+        raise ValueError("images must be a contiguous fp32 tensor of shape (n, 3, S, S) with S a multiple of 16")
+    n, s = int(images_chw.shape[0]), int(images_chw.shape[2])
+    g = s // 16
+    if out is None:
+        out = (torch.empty((n, g, g), dtype=torch.float32, device=images_chw.device),
+               torch.empty((n,), dtype=torch.float32, device=images_chw.device))
+    pooled, emax = out
+    _check_arrays((n, g, g), ("out `pooled`", pooled, torch.float32))
+    _check_arrays((n,), ("out `edge_max`", emax, torch.float32))
+    _run("edge_pool", lib().sslam_edge_pool, (images_chw, pooled, emax), _dp(images_chw), n, s, _dp(pooled), _dp(emax))
+    return pooled, emax
+
+
+def val_frame_stats(saliency, pooled=None, edge_max=None, descriptors=None):
+    """sslam_val_frame_stats: saliency (n, G, G) [+ pooled, edge_max of edge_pool] [+ descriptors (n, K, 128)] ->
+    (stats (n, VAL_FRAME_STATS), desc_mean (n, 128) or None, desc_m2 (n, 128) or None)."""
+    if not isinstance(saliency, torch.Tensor) or saliency.dim() != 3 or saliency.shape[1] != saliency.shape[2]:
+        raise ValueError("saliency must be a tensor of shape (n, G, G)")
+    n, g = int(saliency.shape[0]), int(saliency.shape[1])
+    _check_arrays((n, g, g), ("saliency", saliency, torch.float32), ("pooled", pooled, torch.float32))
+    _check_arrays((n,), ("edge_max", edge_max, torch.float32))
+    if (pooled is None) != (edge_max is None):
+        raise ValueError("pooled and edge_max come together")
+    dev, k, dm, d2 = saliency.device, 0, None, None
+    if descriptors is not None:
+        _check_bank("descriptors", descriptors, ("K", D_OUT))
+        if descriptors.shape[0] != n:
+            raise ValueError(f"descriptors hold {descriptors.shape[0]} frames, saliency {n}")
+        k = int(descriptors.shape[1])
+        dm, d2 = (torch.empty((n, D_OUT), dtype=torch.float32, device=dev) for _ in range(2))
+    stats = torch.empty((n, VAL_FRAME_STATS), dtype=torch.float32, device=dev)
+    _run("val_frame_stats", lib().sslam_val_frame_stats, (saliency, pooled, edge_max, descriptors, stats),
+         _dp(saliency), _dp(pooled), _dp(edge_max), _dp(descriptors), n, g, k, _dp(stats), _dp(dm), _dp(d2))
+    return stats, dm, d2
+
+
+def _pair_stats_arrays(n_pairs, n1, n2, nn12, nn21, s12, ce, s00):
+    for name, t in (("nn12", nn12), ("nn21", nn21), ("s12", s12), ("ce", ce), ("s00", s00)):
+        if t is None:
+            raise ValueError(f"{name} is required")
+    _check_arrays((n_pairs, n1), ("nn12", nn12, torch.int32), ("s12", s12, torch.float32), ("ce", ce, torch.float32))
+    _check_arrays((n_pairs, n2), ("nn21", nn21, torch.int32))
+    _check_arrays((n_pairs,), ("s00", s00, torch.float32))
+
+
+def val_pair_stats(sal1, sal2, nn12, nn21, s12, ce, s00, temperature=0.1):
+    """sslam_val_pair_stats: pair p = frame p of sal1 and of sal2 (n_pairs, G, G each; row slices of one saliency tensor do).
+    Returns (stats (n_pairs, VAL_PAIR_STATS), n_matches (n_pairs,) int32)."""
+    t = check_temperature(temperature)
+    if not isinstance(sal1, torch.Tensor) or sal1.dim() != 3 or sal1.shape[1] != sal1.shape[2]:
+        raise ValueError("saliency must be a tensor of shape (n_pairs, G, G)")
+    n_pairs, g = int(sal1.shape[0]), int(sal1.shape[1])
+    _check_arrays((n_pairs, g, g), ("saliency1", sal1, torch.float32), ("saliency2", sal2, torch.float32))
+    if not isinstance(nn12, torch.Tensor) or not isinstance(nn21, torch.Tensor) or nn12.dim() != 2 or nn21.dim() != 2:
+        raise ValueError("nn12 (n_pairs, n1) and nn21 (n_pairs, n2) tensors expected")
+    n1, n2 = int(nn12.shape[1]), int(nn21.shape[1])
+    _pair_stats_arrays(n_pairs, n1, n2, nn12, nn21, s12, ce, s00)
+    stats = torch.empty((n_pairs, VAL_PAIR_STATS), dtype=torch.float32, device=sal1.device)
+    cnt = torch.empty((n_pairs,), dtype=torch.int32, device=sal1.device)
+    _run("val_pair_stats", lib().sslam_val_pair_stats, (sal1, sal2, nn12, nn21, s12, ce, s00, stats, cnt),
+         _dp(sal1), _dp(sal2), g, _dp(nn12), _dp(nn21), _dp(s12), _dp(ce), _dp(s00), n1, n2, n_pairs, C.c_float(t), _dp(stats), _dp(cnt))
+    return stats, cnt
+
+
+def val_pair_stats_pairs(saliency, first, second, nn12, nn21, s12, ce, s00, temperature=0.1):
+    """sslam_val_pair_stats_pairs: the listed pairs of the bank saliency (n_bank, G, G)."""
+    t = check_temperature(temperature)
+    if not isinstance(saliency, torch.Tensor) or saliency.dim() != 3 or saliency.shape[1] != saliency.shape[2]:
+        raise ValueError("saliency must be a tensor of shape (n_bank, G, G)")
+    n_bank, g = int(saliency.shape[0]), int(saliency.shape[1])
+    _check_arrays((n_bank, g, g), ("saliency", saliency, torch.float32))
+    n_pairs = check_pair_lists(first, second, saliency.device)
+    if not isinstance(nn12, torch.Tensor) or nn12.dim() != 2:
+        raise ValueError("nn12 (n_pairs, K) tensor expected")
+    k = int(nn12.shape[1])
+    _pair_stats_arrays(n_pairs, k, k, nn12, nn21, s12, ce, s00)
+    stats = torch.empty((n_pairs, VAL_PAIR_STATS), dtype=torch.float32, device=saliency.device)
+    cnt = torch.empty((n_pairs,), dtype=torch.int32, device=saliency.device)
+    _run("val_pair_stats_pairs", lib().sslam_val_pair_stats_pairs, (saliency, first, second, nn12, nn21, s12, ce, s00, stats, cnt),
+         _dp(saliency), g, n_bank, _dp(first), _dp(second), _dp(nn12), _dp(nn21), _dp(s12), _dp(ce), _dp(s00), k, n_pairs,
+         C.c_float(t), _dp(stats), _dp(cnt))
+    return stats, cnt
 
 
 def pack_vit_linear(w: np.ndarray) -> np.ndarray:

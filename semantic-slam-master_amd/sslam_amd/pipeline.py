@@ -571,6 +571,88 @@ class SequencePipeline:
             res[key] = aux[0][i] if len(aux) == 1 else torch.cat([x[i] for x in aux])
         return res
 
+    def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
+                         temperature: float = 0.1) -> dict:
+        """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
+        together the trainer's seven loss terms and five metrics (train.py:292-408 under no_grad), for the N frames `out` holds
+        (what extract() / run() returned: saliency (N, G, G), descriptors (N, K, 128)) and the pairs (i, i + spacing) - or the
+        listed pairs first / second, as match_pairs takes them (1-D int32 device tensors or host sequences; -1 = absent pair:
+        zero rows, which compose refuses).
+        images: (N, H, W, 3) uint8 - resampled here by A0 into the fp32 ViT input, a launch group at a time - or that fp32
+        image itself, (N, 3, S, S) with S = input_size.
+        Only launches on the current stream (a fixed number for given shapes), no host read-back: capturable.
+        Returns device tensors: per frame sal_mean, sal_var, sal_max, sal_dx, sal_dy, sal_high, sal_ss, edge_a, edge_e,
+        edge_mean, edge_max (N,), desc_mean, desc_m2 (N, 128), pooled (N, G, G); per pair first, second (int32), repeat,
+        ce_sum, pad_ce (P,), n_matches (P,) int32, lse, ce, sim (P, K), nn12, nn21 (P, K) int32; and the numbers grid,
+        num_keypoints, temperature."""
+        cfg = self.cfg
+        t = lib.check_temperature(temperature)
+        sal, desc = out["saliency"], out["descriptors"]
+        n, k, g = int(desc.shape[0]), int(desc.shape[1]), cfg.grid
+        if tuple(sal.shape) != (n, g, g):
+            raise ValueError(f"saliency {tuple(sal.shape)} does not go with {n} frames of a {g} x {g} grid")
+        listed = first is not None or second is not None
+        if listed:
+            if first is None or second is None:
+                raise ValueError("validation_stats needs both pair lists, first= and second=")
+            if spacing is not None:
+                raise ValueError("give spacing= or the two pair lists, not both")
+            first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+            n_pairs = lib.check_pair_lists(first, second)
+        else:
+            sp = cfg.spacing if spacing is None else spacing
+            if isinstance(sp, bool) or not isinstance(sp, numbers.Integral) or sp < 1:
+                raise ValueError(f"spacing must be an integer >= 1, got {sp!r}")
+            n_pairs = n - int(sp)
+            if n_pairs <= 0:
+                raise ValueError(f"{n} frames hold no pair at spacing {sp}")
+        if not isinstance(images, torch.Tensor) or images.shape[0] != n:
+            raise ValueError(f"images must be a tensor of the same {n} frames")
+        if images.dtype == torch.uint8:
+            if images.dim() != 4 or images.shape[3] != 3:
+                raise ValueError("uint8 images must have shape (N, H, W, 3)")
+        elif images.dtype != torch.float32 or tuple(images.shape[1:]) != (3, cfg.input_size, cfg.input_size):
+            raise ValueError(f"images must be uint8 (N, H, W, 3) or fp32 (N, 3, {cfg.input_size}, {cfg.input_size})")
+        dev = desc.device
+        # ---- per frame: Sobel / pool over the fp32 image, then one workgroup per frame
+        pooled = torch.empty((n, g, g), dtype=torch.float32, device=dev)
+        emax = torch.empty((n,), dtype=torch.float32, device=dev)
+        step = self.launch_group()
+        for a in range(0, n, step):
+            b = min(a + step, n)
+            img = self.preprocess(images[a:b], reuse=True) if images.dtype == torch.uint8 else images[a:b]
+            lib.edge_pool(img, out=(pooled[a:b], emax[a:b]))
+        fstats, dmean, dm2 = lib.val_frame_stats(sal, pooled, emax, desc)
+        res = {key: fstats[:, slot] for key, slot in lib.VAL_FRAME_SLOTS.items()}
+        res.update(desc_mean=dmean, desc_m2=dm2, pooled=pooled)
+        # ---- per pair: the arg-max launch gives the row maxima the log-sum-exp launch starts from
+        if listed:
+            first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
+            lib.check_pair_lists(first, second, dev)
+        else:
+            first = torch.arange(n_pairs, dtype=torch.int32, device=dev)
+            second = first + int(sp)
+        parts = []
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match() cuts
+            m = min(MAX_PAIRS_PER_LAUNCH, n_pairs - a)
+            if listed:
+                f, s = first[a:a + m], second[a:a + m]
+                nn12, s12, nn21, _, _ = lib.sim_argmax_pairs(desc, f, s, workspace=self.workspace(0, m))
+                lse, ce, s00 = lib.row_lse_pairs(desc, f, s, s12, t)
+                pstats, cnt = lib.val_pair_stats_pairs(sal, f, s, nn12, nn21, s12, ce, s00, t)
+            else:
+                d1, d2 = desc[a:a + m], desc[a + sp:a + sp + m]
+                nn12, s12, nn21, _, _ = lib.sim_argmax(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, workspace=self.workspace(0, m))
+                lse, ce, s00 = lib.row_lse(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, s12, t)
+                pstats, cnt = lib.val_pair_stats(sal[a:a + m], sal[a + sp:a + sp + m], nn12, nn21, s12, ce, s00, t)
+            parts.append(dict(pstats=pstats, n_matches=cnt, lse=lse, ce=ce, sim=s12, nn12=nn12, nn21=nn21))
+        cat = {key: parts[0][key] if len(parts) == 1 else torch.cat([x[key] for x in parts]) for key in parts[0]}
+        pstats = cat.pop("pstats")
+        res.update(cat)
+        res.update({key: pstats[:, slot] for key, slot in lib.VAL_PAIR_SLOTS.items() if key != "matches"})
+        res.update(first=first, second=second, grid=g, num_keypoints=k, temperature=t)
+        return res
+
     def run(self, images_u8: torch.Tensor | None, tokens: torch.Tensor | None = None, with_preprocess: bool = False) -> dict:
         """One pass of the hot path over a frame sequence: extract every frame once, match (i, i+spacing).
         tokens=None: compute them from the images with the HIP ViT (A0 + A1)."""
