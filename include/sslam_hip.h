@@ -99,7 +99,11 @@ int sslam_preprocess_u8_patches(const uint8_t *img, int n, int h, int w, int siz
  * dino_backbone.py:91-106.  tokens (n_frames, tokens_per_frame, 384); statistics over `group` consecutive frames
  * (group = 1 reproduces per-frame B=1 calls).  train != 0: batch statistics, also written to
  * out_mean / out_var (n_frames/group, 384; biased variance); train == 0: run_mean / run_var are used.
- * out_feat (n_frames, cells, 384) with cells = tokens_per_frame - n_prefix. */
+ * out_feat (n_frames, cells, 384) with cells = tokens_per_frame - n_prefix.
+ * Pinned bit for bit to the oracle (tests/test_gpu_trained_ranges.py) in both modes, for n_prefix 0 / 1 / 5, another eps, one cell
+ * past each launch-form boundary (784, 1 600, 3 600 cells) and on degenerate channels: a constant channel has batch variance
+ * exactly 0 and is scaled by 1/sqrtf(eps) (output beta' + x*alpha, exactly 0 under gamma 1, beta 0); a channel whose spread is
+ * far below its mean (1e4 +- 1e-3) is ill-conditioned in fp32 - finite and equal to the oracle, not close to float64. */
 int sslam_bn_tokens(const float *tokens, int n_frames, int tokens_per_frame, int n_prefix, int group,
                     const float *gamma, const float *beta, const float *run_mean, const float *run_var, int train,
                     float eps, float *out_feat, float *out_mean, float *out_var, void *stream);
@@ -111,7 +115,11 @@ int sslam_bn_tokens(const float *tokens, int n_frames, int tokens_per_frame, int
  * and the stage form of the 128-row throughput kernel, and two latency forms for few frames.  The second latency form
  * (two workgroups per 32-cell tile; up to six 28x28 frames) needs 16 bytes of scratch per cell: the _ws entry takes it from
  * the caller (workspace_bytes >= sslam_selector_saliency_workspace_bytes; workspace may be NULL: then, and in the entry
- * without a workspace, the 8-wave latency form runs instead). */
+ * without a workspace, the 8-wave latency form runs instead).  G up to 64 is tested in every form.
+ * The sigmoid is 1 / (1 + e) with e the canonical exp of -logit (argument clamped to [-87, 88], oracle ora_expf), for every
+ * finite logit: exactly 1.0f from about 17 upwards, and from -88 downwards ONE value, 1 / (1 + exp(88)) = 6.0546e-39
+ * (bits 0x0041edc4) - a SUBNORMAL, never 0: saliency is strictly positive, and the kernels rely on fp32 denormals not being
+ * flushed.  NaN / Inf logits are outside the contract. */
 int sslam_selector_saliency(const float *feat, int n_frames, int G, const float *w1_packed, const float *b1,
                             const float *w2, const float *b2, int hs, float *sal, void *stream);
 int sslam_selector_saliency_ws(const float *feat, int n_frames, int G, const float *w1_packed, const float *b1,
@@ -155,7 +163,11 @@ int sslam_gather(const float *feat, int n_frames, int G, const float *kp_xy, int
 /* ---- A7: descriptor MLP.  Replaces DescriptorRefiner.forward / ResidualBlock.forward,
  * descriptor_refiner.py:58-126.  Refiner weights are passed as ONE packed device buffer laid out by
  * sslam_refiner_pack_host (offsets in floats are returned by sslam_refiner_layout).
- * x (rows, 384) -> desc (rows, 128). */
+ * x (rows, 384) -> desc (rows, 128).  0 <= n_blocks <= 8, every depth bit-identical to the oracle (tests at 0, 1, 2, 3, 8).
+ * Finite inputs give finite descriptors: a row whose hidden activations are all equal (all dead, for one) passes LayerNorm as
+ * (0 * 1/sqrtf(1e-5f)) * gamma + beta = beta; the output is v / max(sqrtf(sum v^2), 1e-12f) with the correctly rounded divide,
+ * so a zero output stays +0, a norm below 1e-12 (squares that underflow or are subnormal) divides by 1e-12, and a sum of
+ * squares that overflows to +inf gives 0 - as F.normalize does in fp32. */
 typedef struct {
     int n_blocks;          /* residual blocks (num_layers - 2; 2 in the shipped config) */
     long long total;       /* floats in the packed buffer */

@@ -23,7 +23,8 @@ def oracle_block(imgs: np.ndarray, toks: np.ndarray, ssd: dict, rsd: dict, size:
     feat = ora.bn_tokens(toks, train=cfg.bn_train_mode, eps=cfg.bn_eps)[0].reshape(n, grid, grid, 384)   # A2
     sal = ora.selector_saliency(feat, ssd)                                                 # A3
     kp, sc, idx, _ = ora.select_keypoints(sal, K, cfg.nms_radius, cfg.min_score_percentile)   # A4 / A5
-    desc = ora.refine(ora.gather(feat, kp), rsd)                                           # A6 / A7
+    n_blocks = len({k.split(".")[1] for k in rsd if k.startswith("residual_blocks.")})    # as pipeline.refiner_weight_list
+    desc = ora.refine(ora.gather(feat, kp), rsd, n_blocks)                                 # A6 / A7
     del feat
     inten = np.stack([ora.intensity(imgs[i], size, ora.patch_to_pixel(kp[i])) for i in range(n)])   # A8 / A9
     matches, quality = [], []
