@@ -447,7 +447,9 @@ int sslam_vit_forward_patches_form(const void *patches_bf16, int n_frames, int s
  *   forms) write them: the kernel sums exp(x_ij - clamp(s12_i / temperature)) in one pass.  Each of lse, ce, s00 may be NULL
  *   (lse and ce not both).  Pairs are named as in sslam_sim_argmax_rows / sslam_sim_argmax_rows_pairs (strides in floats; an
  *   index outside [0, n_bank), -1 by convention, is an absent pair: zero rows, s00 = 0).  temperature > 0, finite.
- *   The K x K logits are never written to memory; exp and log are the library's canonical fmaf-only forms. */
+ *   The K x K logits are never written to memory; exp and log are the library's canonical fmaf-only forms.
+ *   Tested (tests/test_gpu_validation_edges.py) with both clamp arms reached in every row, n1 != n2, stride1 = 0, 9 and 17
+ *   pairs of two query blocks each, every NULL combination of the outputs, and outputs lying between sentinel rows. */
 int sslam_row_lse(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
                   const float *s12, float temperature, float *lse, float *ce, float *s00, void *stream);
 int sslam_row_lse_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
@@ -458,7 +460,9 @@ int sslam_row_lse_pairs(const float *bank, long long frame_stride, int n_bank, i
  *   gray = 0.299 c0 + 0.587 c1 + 0.114 c2; 3 x 3 Sobel x and y with ZERO padding at the border; mag = sqrt(gx^2 + gy^2 + 1e-8);
  *   pooled (n, size/16, size/16) = the 16 x 16 block means of mag (what adaptive_avg_pool2d gives at this size, before the
  *   reference's division by the batch maximum: a positive factor the host applies); edge_max (n) = the frame's maximum of mag.
- * images_chw 16-byte aligned.  No scratch: the maximum is an integer atomic max on the bits of the positive magnitudes. */
+ * images_chw 16-byte aligned.  No scratch: the maximum is an integer atomic max on the bits of the positive magnitudes.
+ * Tested (tests/test_gpu_validation_edges.py) at sizes 512, 544, 1024 and 1040 - one to three column segments of 512 pixels, the
+ * last 32 or 16 wide - where a cell's block mean has the same bits wherever the cell lies in a segment. */
 int sslam_edge_pool(const float *images_chw, int n_frames, int size, float *pooled, float *edge_max, void *stream);
 /* sslam_val_frame_stats: one row of SSLAM_VAL_FRAME_STATS floats per frame from its saliency map (n, G, G):
  *   SAL_MEAN, SAL_VAR (biased, :196), SAL_MAX, SAL_DX = sum |s[y][x+1] - s[y][x]|, SAL_DY = sum |s[y+1][x] - s[y][x]| (:300-301),

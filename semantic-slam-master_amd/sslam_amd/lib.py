@@ -712,31 +712,38 @@ def check_temperature(temperature) -> float:
     return t
 
 
-def _lse_out(n_pairs, n1, dev):
+def _lse_out(n_pairs, n1, dev, out=None):
     f32 = dict(dtype=torch.float32, device=dev)
-    return torch.empty((n_pairs, n1), **f32), torch.empty((n_pairs, n1), **f32), torch.empty((n_pairs,), **f32)
+    if out is None:
+        return torch.empty((n_pairs, n1), **f32), torch.empty((n_pairs, n1), **f32), torch.empty((n_pairs,), **f32)
+    lse, ce, s00 = out
+    _check_arrays((n_pairs, n1), ("out `lse`", lse, torch.float32), ("out `ce`", ce, torch.float32))
+    _check_arrays((n_pairs,), ("out `s00`", s00, torch.float32))
+    return lse, ce, s00
 
 
-def row_lse(d1, stride1, n1, d2, stride2, n2, n_pairs, s12, temperature=0.1):
+def row_lse(d1, stride1, n1, d2, stride2, n2, n_pairs, s12, temperature=0.1, out=None):
     """sslam_row_lse: (lse, ce, s00) of the rows of frame p of d1 against frame p of d2; s12 (n_pairs, n1): the row maxima that
-    sim_argmax / sim_argmax_rows wrote for the same pairs."""
+    sim_argmax / sim_argmax_rows wrote for the same pairs.  out: optional (lse, ce, s00) to write into; an entry given as None
+    is not computed (the entry's NULL; lse and ce not both: ValueError) and comes back as None."""
     t = check_temperature(temperature)
     _check_arrays((n_pairs, n1), ("s12", s12, torch.float32))
-    lse, ce, s00 = _lse_out(n_pairs, n1, d1.device)
+    lse, ce, s00 = _lse_out(n_pairs, n1, d1.device, out)
     _run("row_lse", lib().sslam_row_lse, (d1, d2, s12, lse, ce, s00),
          C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs, _dp(s12), C.c_float(t), _dp(lse),
          _dp(ce), _dp(s00))
     return lse, ce, s00
 
 
-def row_lse_pairs(bank, first, second, s12, temperature=0.1):
-    """sslam_row_lse_pairs: row_lse for the listed pairs of bank (n_bank, K, 128); lists as sim_argmax_pairs takes them."""
+def row_lse_pairs(bank, first, second, s12, temperature=0.1, out=None):
+    """sslam_row_lse_pairs: row_lse for the listed pairs of bank (n_bank, K, 128); lists as sim_argmax_pairs takes them;
+    out as row_lse takes it."""
     t = check_temperature(temperature)
     _check_bank("bank", bank, ("K", D_OUT))
     n_bank, k = int(bank.shape[0]), int(bank.shape[1])
     n_pairs = check_pair_lists(first, second, bank.device)
     _check_arrays((n_pairs, k), ("s12", s12, torch.float32))
-    lse, ce, s00 = _lse_out(n_pairs, k, bank.device)
+    lse, ce, s00 = _lse_out(n_pairs, k, bank.device, out)
     _run("row_lse_pairs", lib().sslam_row_lse_pairs, (bank, first, second, s12, lse, ce, s00),
          _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(s12), C.c_float(t), _dp(lse), _dp(ce), _dp(s00))
     return lse, ce, s00

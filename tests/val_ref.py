@@ -90,6 +90,38 @@ def frame_stats(sal, img=None, desc=None):
     return out
 
 
+def sobel_magnitude(img):
+    """img (3, S, S) -> the (S, S) Sobel magnitude that sobel_pool pools: where the frame maximum sits."""
+    c = f64(img)
+    gray = 0.299 * c[0] + 0.587 * c[1] + 0.114 * c[2]
+    s = gray.shape[0]
+    p = np.zeros((s + 2, s + 2))
+    p[1:-1, 1:-1] = gray
+    gx = (p[:-2, 2:] - p[:-2, :-2]) + 2.0 * (p[1:-1, 2:] - p[1:-1, :-2]) + (p[2:, 2:] - p[2:, :-2])
+    gy = (p[2:, :-2] - p[:-2, :-2]) + 2.0 * (p[2:, 1:-1] - p[:-2, 1:-1]) + (p[2:, 2:] - p[:-2, 2:])
+    return np.sqrt(gx * gx + gy * gy + 1e-8)
+
+
+def mutual_rows(nn12, nn21):
+    """The mask of the rows i with 0 <= nn12[i] < len(nn21) and nn21[nn12[i]] == i, for ANY two integer arrays (n1,), (n2,):
+    an index outside the second side names no row and is not mutual."""
+    nn12, nn21 = np.asarray(nn12, np.int64), np.asarray(nn21, np.int64)
+    ok = (nn12 >= 0) & (nn12 < len(nn21))
+    mask = np.zeros(len(nn12), bool)
+    idx = np.nonzero(ok)[0]
+    mask[idx] = nn21[nn12[idx]] == idx
+    return mask
+
+
+def pair_sums(ce, nn12, nn21, s12_0, s00, temperature):
+    """What val_pair_stats sums for one pair from given arrays: n_matches and ce_sum over mutual_rows(nn12, nn21), and
+    pad_ce = ce[0] + (clamp(s12[0] / T) - clamp(s00 / T)) - in float64, for hand-made index arrays as for the device's own."""
+    mask = mutual_rows(nn12, nn21)
+    t = float(temperature)
+    pad = float(f64(ce)[0] + (np.clip(float(s12_0) / t, -50.0, 50.0) - np.clip(float(s00) / t, -50.0, 50.0)))
+    return dict(n_matches=int(mask.sum()), ce_sum=float(f64(ce)[mask].sum()), pad_ce=pad, mask=mask)
+
+
 # ----------------------------------------------------------------------------------------------------------- composition
 def batch_terms(sal1, sal2, images, d1, d2, temperature=0.1, weights=WEIGHTS, targets=TARGETS):
     """One batch as the trainer sees it: sal1, sal2 (B, G, G), images (B, 3, S, S), d1, d2 (B, K, 128) -> the seven terms,
