@@ -38,7 +38,7 @@ extern "C" {
 
 #define SSLAM_C 384   /* backbone embed dim (ViT-S/16), dino_backbone.py:50 */
 #define SSLAM_HID 384 /* refiner hidden dim, configs/train_config.yaml:13 */
-#define SSLAM_D 128   /* descriptor dim, configs/train_config.yaml:12 */
+#define SSLAM_D 128   /* descriptor dim, configs/train_config.yaml:12: the default width; the _d entries also take 256 */
 
 /* library version (major*10000 + minor*100 + patch) and the gfx target it was compiled for */
 int sslam_version(void);
@@ -505,6 +505,48 @@ int sslam_val_pair_stats(const float *saliency1, const float *saliency2, int G, 
 int sslam_val_pair_stats_pairs(const float *saliency_bank, int G, int n_bank, const int32_t *pair_first, const int32_t *pair_second,
                                const int32_t *nn12, const int32_t *nn21, const float *s12, const float *ce, const float *s00, int K,
                                int n_pairs, float temperature, float *stats, int32_t *n_matches, void *stream);
+
+/* ---- Descriptor width 128 or 256.  SSLAM_D above is the DEFAULT width, the one every entry without a width argument works at
+ * (each of them is its _d form with d = SSLAM_D).  The _d entries below take the width as `int d`, the last argument before
+ * `stream` (before the output pointer in the two host-side packers): d = 128 runs the very kernels of the unsuffixed entry,
+ * d = 256 their second instantiation - the refiner's output projection over two 32-column tiles per wave (output_proj.weight
+ * (256, 384); column layout wave*64 + 32*t + crow(e, h); the L2 norm one fma chain over the lane's 32 outputs in (t, e) order,
+ * then the same row tree), descriptors / banks with rows of 256 floats, and every similarity ONE fma chain over k = 0 .. 255
+ * ascending - bit-identical to the oracle at that width (ora_refine(d_out = 256), ora_sim_argmax(d = 256)).
+ * Any other d: SSLAM_E_UNSUPPORTED before anything is launched; NULL / misaligned / non-positive arguments: SSLAM_E_INVALID as in
+ * the unsuffixed entry (the refiner's _d entries also want `desc` 16-byte aligned).  Strides stay explicit, in floats.  Outputs,
+ * workspace sizes (sslam_sim_argmax_workspace_bytes, sslam_gather_refine_workspace_bytes: neither depends on d), absent pairs and
+ * launch forms are those of the unsuffixed entries.  The packed refiner buffer of width d holds sslam_refiner_layout_d(...).total
+ * floats: the layout of sslam_refiner_layout with out_w (d x 384, packed) and out_b (d) at the end.
+ * sslam_val_frame_stats_d: descriptors (n, K, d) -> desc_mean / desc_m2 (n, d); at 256 one thread per dimension sums the K rows in
+ * increasing index (at 128: two row-parity half-sums).  The bf16 throughput entries have no 256 form. */
+int sslam_refiner_layout_d(int n_blocks, int d, sslam_refiner_layout_t *layout_host);
+int sslam_refiner_pack_host_d(const float *const *w_host, int n_blocks, int d, float *out_host);
+int sslam_refine_d(const float *x, long long rows, const float *packed, int n_blocks, float *desc, int d, void *stream);
+int sslam_gather_refine_d(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed, int n_blocks,
+                          float *desc, int d, void *stream);
+int sslam_gather_refine_ws_d(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed, int n_blocks,
+                             float *desc, void *workspace, long long workspace_bytes, int d, void *stream);
+int sslam_sim_argmax_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
+                       int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12, int d, void *stream);
+int sslam_sim_argmax_ws_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
+                          int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12, void *workspace,
+                          long long workspace_bytes, int d, void *stream);
+int sslam_sim_argmax_pairs_d(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                             const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21,
+                             float *second12, void *workspace, long long workspace_bytes, int d, void *stream);
+int sslam_sim_argmax_rows_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                            int n_pairs, int32_t *nn12, float *s12, float *second12, int d, void *stream);
+int sslam_sim_argmax_rows_pairs_d(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                  const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, float *second12, int d,
+                                  void *stream);
+int sslam_row_lse_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
+                    const float *s12, float temperature, float *lse, float *ce, float *s00, int d, void *stream);
+int sslam_row_lse_pairs_d(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                          const int32_t *pair_second, int n_pairs, const float *s12, float temperature, float *lse, float *ce,
+                          float *s00, int d, void *stream);
+int sslam_val_frame_stats_d(const float *saliency, const float *pooled, const float *edge_max, const float *descriptors,
+                            int n_frames, int G, int K, float *stats, float *desc_mean, float *desc_m2, int d, void *stream);
 
 #ifdef __cplusplus
 }

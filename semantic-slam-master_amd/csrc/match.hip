@@ -30,22 +30,23 @@ namespace {
 constexpr int QB = 128;            // queries per workgroup (32 per wave)
 constexpr int CB = 64;             // candidates per stage (two MFMA tiles per wave)
 constexpr int NTM = 256;           // threads per workgroup
-constexpr int LDD = SSLAM_D + 4;   // 132-float rows: 528 B = 33 x 16 B -> conflict-free b128 fragment reads
+// LDS rows are D + 4 floats (132 at D = 128: 528 B = 33 x 16 B; 260 at D = 256: 65 x 16 B) -> conflict-free b128 fragment reads
 
-// rows x 128 floats -> KP8 image, split into a load half (global -> registers) and a store half (registers -> LDS)
+// rows x D floats -> KP8 image, split into a load half (global -> registers) and a store half (registers -> LDS)
 // so that the next candidate tile is in flight while the current one is multiplied.
 // rows beyond n_valid are zero (they are masked out of the arg-max anyway)
-template <int ROWS>
+template <int ROWS, int D>
 struct Stager {
-    static constexpr int ITEMS = ROWS * 16 / NTM;
+    static constexpr int GL = D == 128 ? 4 : 5, GM = D / 8 - 1, LDD = D + 4;      // D / 8 groups of 8 floats per row
+    static constexpr int ITEMS = ROWS * (D / 8) / NTM;
     float4 lo[ITEMS], hi[ITEMS];
     bool ok[ITEMS];         // rows beyond n_valid are zeroed at store time: nothing waits for the loads before the MFMAs
     __device__ __forceinline__ void load(const float *__restrict__ src, int first, int n_valid, int tid) {
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
-            const int it = tid + NTM * i, row = it >> 4, g = it & 15;
+            const int it = tid + NTM * i, row = it >> GL, g = it & GM;
             ok[i] = first + row < n_valid;
-            const float4 *p = reinterpret_cast<const float4 *>(src + (long long)(ok[i] ? first + row : 0) * SSLAM_D + 8 * g);
+            const float4 *p = reinterpret_cast<const float4 *>(src + (long long)(ok[i] ? first + row : 0) * D + 8 * g);
             lo[i] = p[0];
             hi[i] = p[1];
         }
@@ -53,7 +54,7 @@ struct Stager {
     __device__ __forceinline__ void store(float *dst, int tid) const {
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
-            const int it = tid + NTM * i, row = it >> 4, g = it & 15;
+            const int it = tid + NTM * i, row = it >> GL, g = it & GM;
             float4 ev, od;
             const bool k = ok[i];
             kp8_split(make_float4(k ? lo[i].x : 0.f, k ? lo[i].y : 0.f, k ? lo[i].z : 0.f, k ? lo[i].w : 0.f),
@@ -178,14 +179,18 @@ struct ListedPairs {       // pair p = frames (first[p], second[p]) of one bank 
 //                  32 query lanes of each half-wave by a reduce-scatter butterfly on sim_key()s and merged across waves
 //                  and workgroups with a 64-bit atomic max into `keys` (n_pairs x n2, zeroed), decoded by keys_decode_kernel.
 // SECOND: also the runner-up of the row direction (second12; the ratio-test matchers M2 / M4).
-template <bool ONEPASS, bool SECOND, class PAIRS>
-__global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restrict__ desc1, long long stride1, int n1,
+// D = 128: two workgroups per CU (2 x 33 KB of candidate tiles each, 64 query registers).  D = 256: the same stage of 64
+// candidates is 2 x 65 KB and the wave's queries are 128 registers - one workgroup per CU; every output is still one fma chain
+// over k = 0 .. D - 1 ascending, the MFMA steps of a stage in increasing k-group.
+template <int D, bool ONEPASS, bool SECOND, class PAIRS>
+__global__ __launch_bounds__(NTM, D == 128 ? 2 : 1) void sim_argmax_kernel(const float *__restrict__ desc1, long long stride1, int n1,
                                                             const float *__restrict__ desc2, long long stride2, int n2,
                                                             int *__restrict__ nn12, float *__restrict__ s12,
                                                             int *__restrict__ nn21, float *__restrict__ s21,
                                                             float *__restrict__ second12,
                                                             unsigned long long *__restrict__ keys, int n_pairs, int qblocks,
                                                             PAIRS pairs) {
+    constexpr int LDD = D + 4;
     __shared__ __attribute__((aligned(16))) float Cs[2 * CB * LDD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int dir = blockIdx.y;
@@ -215,19 +220,19 @@ __global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restr
     float *o_val = dir == 0 ? (s12 ? s12 + pair * n1 : nullptr) : (s21 ? s21 + pair * n2 : nullptr);
     float *o_sec = (dir == 0 && second12) ? second12 + pair * n1 : nullptr;
 
-    Stager<CB> sc;
+    Stager<CB, D> sc;
     sc.load(c, 0, nc, tid);
-    // this lane's query as the B operand of all 64 MFMA steps: step i multiplies k = 2 i + h
+    // this lane's query as the B operand of all D / 2 MFMA steps: step i multiplies k = 2 i + h
     const int qi = q0 + wave * 32 + r;
     const bool qok = qi < nq;
-    float qreg[SSLAM_D / 2];
+    float qreg[D / 2];
     {
         // rows beyond nq re-read row 0 and are multiplied by 0 (finite data; exact for the valid rows): a select on qok around
         // the loads makes hipcc branch around EACH load and wait for it - 32 serial memory round trips in the prologue
-        const float4 *qp = reinterpret_cast<const float4 *>(q + (long long)(qok ? qi : 0) * SSLAM_D);
+        const float4 *qp = reinterpret_cast<const float4 *>(q + (long long)(qok ? qi : 0) * D);
         const float qm = qok ? 1.0f : 0.0f;
 #pragma unroll
-        for (int i = 0; i < SSLAM_D / 4; i++) {
+        for (int i = 0; i < D / 4; i++) {
             const float4 v = qp[i];
             qreg[2 * i] = (h ? v.y : v.x) * qm;
             qreg[2 * i + 1] = (h ? v.w : v.z) * qm;
@@ -273,7 +278,7 @@ __global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restr
     {
         const float *A = Cs + r * LDD + 4 * h;
 #pragma unroll
-        for (int g = 0; g < SSLAM_D / 8; g++) M1_MMA(g, A, held)
+        for (int g = 0; g < D / 8; g++) M1_MMA(g, A, held)
     }
     if (nstage > 1) {
         sc.load(c, CB, nc, tid);
@@ -289,8 +294,9 @@ __global__ __launch_bounds__(NTM, 2) void sim_argmax_kernel(const float *__restr
         int jj[2] = {0, 0};
 #pragma unroll
         for (int e = 0; e < 16; e++) acc[0][e] = acc[1][e] = 0.0f;
+        /* a slot = D / 128 k-groups in increasing k (one at D = 128), then 3 micro-steps of the held stage */
 #define M1_SLOT(g_)                                                                                                   \
-        M1_MMA(g_, A, acc)                                                                                            \
+        _Pragma("unroll") for (int u = 0; u < D / 128; u++) M1_MMA((D / 128) * (g_) + u, A, acc)                       \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
         red_steps<3 * (g_), 3, ONEPASS, false, SECOND>(held, s - 1, nc, r, h, qoff, nqi, rb, kq, kk, jj);                              \
         __builtin_amdgcn_sched_barrier(0);
@@ -534,7 +540,7 @@ extern "C" long long sslam_sim_argmax_workspace_bytes(int n2, int n_pairs) {
 }
 
 // both launch forms, for either way of naming the pairs (the arguments are checked by the entries)
-template <class PAIRS>
+template <int D, class PAIRS>
 static int launch_sim_argmax(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
                              int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12, void *workspace,
                              long long workspace_bytes, void *stream, PAIRS pairs) {
@@ -551,10 +557,10 @@ static int launch_sim_argmax(const float *desc1, long long stride1, int n1, cons
         const int qb1 = (n1 + QB - 1) / QB;
         const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qb1), 1, 1);
         if (second12)
-            hipLaunchKernelGGL((sim_argmax_kernel<true, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12,
+            hipLaunchKernelGGL((sim_argmax_kernel<D, true, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12,
                                s12, nn21, s21, second12, keys, n_pairs, qb1, pairs);
         else
-            hipLaunchKernelGGL((sim_argmax_kernel<true, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12,
+            hipLaunchKernelGGL((sim_argmax_kernel<D, true, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12,
                                s12, nn21, s21, second12, keys, n_pairs, qb1, pairs);
         SSLAM_CHECK_LAUNCH();
         const long long n = (long long)n_pairs * n2;
@@ -566,40 +572,68 @@ static int launch_sim_argmax(const float *desc1, long long stride1, int n1, cons
     const int qbm = (nmax + QB - 1) / QB;
     const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qbm), 2, 1);
     if (second12)
-        hipLaunchKernelGGL((sim_argmax_kernel<false, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+        hipLaunchKernelGGL((sim_argmax_kernel<D, false, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
                            nn21, s21, second12, nullptr, n_pairs, qbm, pairs);
     else
-        hipLaunchKernelGGL((sim_argmax_kernel<false, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+        hipLaunchKernelGGL((sim_argmax_kernel<D, false, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
                            nn21, s21, second12, nullptr, n_pairs, qbm, pairs);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }
 
+// the width-taking entries: d = 128 or 256 picks the kernels' instantiation; any other width is refused before a launch
+#define SSLAM_BY_WIDTH(d_, call128_, call256_) ((d_) == 128 ? (call128_) : (d_) == 256 ? (call256_) : SSLAM_E_UNSUPPORTED)
+
+extern "C" int sslam_sim_argmax_ws_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2,
+                                     int n2, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12,
+                                     void *workspace, long long workspace_bytes, int d, void *stream) {
+    if (!desc1 || !desc2 || !nn12 || !nn21 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3) || ((uintptr_t)workspace & 7)) return SSLAM_E_INVALID;
+    return SSLAM_BY_WIDTH(d,
+                          launch_sim_argmax<128>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, workspace,
+                                                 workspace_bytes, stream, StridedPairs{}),
+                          launch_sim_argmax<256>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, workspace,
+                                                 workspace_bytes, stream, StridedPairs{}));
+}
 extern "C" int sslam_sim_argmax_ws(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2,
                                    int n2, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12,
                                    void *workspace, long long workspace_bytes, void *stream) {
-    if (!desc1 || !desc2 || !nn12 || !nn21 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3) || ((uintptr_t)workspace & 7)) return SSLAM_E_INVALID;
-    return launch_sim_argmax(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, workspace, workspace_bytes,
-                             stream, StridedPairs{});
+    return sslam_sim_argmax_ws_d(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, workspace,
+                                 workspace_bytes, SSLAM_D, stream);
 }
 
 // pairs named by two DEVICE index lists into one bank: the same kernels, every pair's bases looked up by its workgroups
-extern "C" int sslam_sim_argmax_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
-                                      const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21,
-                                      float *second12, void *workspace, long long workspace_bytes, void *stream) {
+extern "C" int sslam_sim_argmax_pairs_d(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                        const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21,
+                                        float *second12, void *workspace, long long workspace_bytes, int d, void *stream) {
     if (!bank || !pair_first || !pair_second || !nn12 || !nn21 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)bank & 15) || (frame_stride & 3) || ((uintptr_t)workspace & 7) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3))
         return SSLAM_E_INVALID;
-    return launch_sim_argmax(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, nn21, s21, second12, workspace,
-                             workspace_bytes, stream, ListedPairs{pair_first, pair_second, n_bank});
+    const ListedPairs lp{pair_first, pair_second, n_bank};
+    return SSLAM_BY_WIDTH(d,
+                          launch_sim_argmax<128>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, nn21, s21, second12,
+                                                 workspace, workspace_bytes, stream, lp),
+                          launch_sim_argmax<256>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, nn21, s21, second12,
+                                                 workspace, workspace_bytes, stream, lp));
+}
+extern "C" int sslam_sim_argmax_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                      const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21,
+                                      float *second12, void *workspace, long long workspace_bytes, void *stream) {
+    return sslam_sim_argmax_pairs_d(bank, frame_stride, n_bank, K, pair_first, pair_second, n_pairs, nn12, s12, nn21, s21, second12,
+                                    workspace, workspace_bytes, SSLAM_D, stream);
 }
 
 // the form without a workspace: never allocates - the similarity matrix is evaluated once per direction
+extern "C" int sslam_sim_argmax_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2,
+                                  int n2, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12,
+                                  int d, void *stream) {
+    return sslam_sim_argmax_ws_d(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, nullptr, 0, d, stream);
+}
 extern "C" int sslam_sim_argmax(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2,
                                 int n2, int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12,
                                 void *stream) {
-    return sslam_sim_argmax_ws(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, nullptr, 0, stream);
+    return sslam_sim_argmax_ws_d(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, nullptr, 0, SSLAM_D,
+                                 stream);
 }
 
 extern "C" int sslam_match_finalize(const int32_t *nn12, const float *s12, const int32_t *nn21, int n1, int n2, int n_pairs,
@@ -636,7 +670,7 @@ extern "C" int sslam_match_finalize_pairs(const int32_t *nn12, const float *s12,
 
 // ---- rows-only similarity: the row direction of the two-pass form as a launch of its own (grid y = 1: direction 0 only) - the
 // same kernel, so the same bits as the row outputs of sslam_sim_argmax[_pairs] in either of its forms; no workspace
-template <class PAIRS>
+template <int D, class PAIRS>
 static int launch_sim_argmax_rows(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
                                   int32_t *nn12, float *s12, float *second12, void *stream, PAIRS pairs) {
     const int qb1 = (n1 + QB - 1) / QB;
@@ -644,29 +678,43 @@ static int launch_sim_argmax_rows(const float *desc1, long long stride1, int n1,
     const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qb1), 1, 1);
     hipStream_t st = (hipStream_t)stream;
     if (second12)
-        hipLaunchKernelGGL((sim_argmax_kernel<false, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+        hipLaunchKernelGGL((sim_argmax_kernel<D, false, true, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
                            nullptr, nullptr, second12, nullptr, n_pairs, qb1, pairs);
     else
-        hipLaunchKernelGGL((sim_argmax_kernel<false, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
+        hipLaunchKernelGGL((sim_argmax_kernel<D, false, false, PAIRS>), grid, dim3(NTM), 0, st, desc1, stride1, n1, desc2, stride2, n2, nn12, s12,
                            nullptr, nullptr, second12, nullptr, n_pairs, qb1, pairs);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }
 
-extern "C" int sslam_sim_argmax_rows(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
-                                     int n_pairs, int32_t *nn12, float *s12, float *second12, void *stream) {
+extern "C" int sslam_sim_argmax_rows_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                                       int n_pairs, int32_t *nn12, float *s12, float *second12, int d, void *stream) {
     if (!desc1 || !desc2 || !nn12 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3)) return SSLAM_E_INVALID;
-    return launch_sim_argmax_rows(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, stream, StridedPairs{});
+    return SSLAM_BY_WIDTH(d,
+                          launch_sim_argmax_rows<128>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, stream, StridedPairs{}),
+                          launch_sim_argmax_rows<256>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, stream, StridedPairs{}));
+}
+extern "C" int sslam_sim_argmax_rows(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                                     int n_pairs, int32_t *nn12, float *s12, float *second12, void *stream) {
+    return sslam_sim_argmax_rows_d(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, SSLAM_D, stream);
 }
 
+extern "C" int sslam_sim_argmax_rows_pairs_d(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                             const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, float *second12,
+                                             int d, void *stream) {
+    if (!bank || !pair_first || !pair_second || !nn12 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)bank & 15) || (frame_stride & 3) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3)) return SSLAM_E_INVALID;
+    const ListedPairs lp{pair_first, pair_second, n_bank};
+    return SSLAM_BY_WIDTH(d,
+                          launch_sim_argmax_rows<128>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, second12, stream, lp),
+                          launch_sim_argmax_rows<256>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, second12, stream, lp));
+}
 extern "C" int sslam_sim_argmax_rows_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
                                            const int32_t *pair_second, int n_pairs, int32_t *nn12, float *s12, float *second12,
                                            void *stream) {
-    if (!bank || !pair_first || !pair_second || !nn12 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)bank & 15) || (frame_stride & 3) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3)) return SSLAM_E_INVALID;
-    return launch_sim_argmax_rows(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, second12, stream,
-                                  ListedPairs{pair_first, pair_second, n_bank});
+    return sslam_sim_argmax_rows_pairs_d(bank, frame_stride, n_bank, K, pair_first, pair_second, n_pairs, nn12, s12, second12, SSLAM_D,
+                                         stream);
 }
 
 // what both rule entries refuse before anything is launched: an unknown rule, M4 on fewer than two candidates (the reference's

@@ -233,7 +233,8 @@ enum { PR_GATHER = 0, PR_GEMM = 1, PR_LN = 2, PR_STORE = 3, PR_BARRIER = 4 };
 // distinct_rep_kernel / distinct_list_kernel below; the grid is sized for the worst case (every row distinct) and the
 // workgroups beyond the device-side tile count leave at once.  Rows are independent in this kernel (every fma chain, row
 // statistic and norm uses one row only), so which tile a row sits in changes no bit of it.
-template <bool WL>
+// NT: 32-column tiles of the output projection per wave = descriptor width / 128 (1 or 2).
+template <bool WL, int NT>
 __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(const float *__restrict__ feat, int G,
                                                              const float *__restrict__ kp_xy, int K,
                                                              const float *__restrict__ x_in, long long rows,
@@ -338,24 +339,29 @@ __global__ __launch_bounds__(NTHR, WMR == 1 ? 3 : 2) void gather_refine_kernel(c
     PROBE(PR_BARRIER, __syncthreads();)
 
     // ---- output_proj + L2 normalise (:83-86; F.normalize eps 1e-12) --------------------------------------------
-    f32x16 o[1];
-    PRIO_GEMM(); PROBE(PR_GEMM, gemm_lds<1>(H, wrs, (int)L.out_w * 4, pk + L.out_b, tid, o);) PRIO_OTHER();
+    // wave wn owns the columns wn * 32 NT + 32 t + crow(e, h); the lane's share of the L2 sum is one fma chain in (t, e) order
+    f32x16 o[NT];
+    PRIO_GEMM(); PROBE(PR_GEMM, gemm_lds<NT>(H, wrs, (int)L.out_w * 4, pk + L.out_b, tid, o);) PRIO_OTHER();
     {
         const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5, wn = wave & 3;
         float ss = 0.0f;
 #pragma unroll
-        for (int e = 0; e < 16; e++) ss = __builtin_fmaf(o[0][e], o[0][e], ss);
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) ss = __builtin_fmaf(o[t][e], o[t][e], ss);
         const float den = fmaxf(sqrtf(row_total(ss, part0, tid)), 1e-12f);
         if (R0 + r < rows) {
             long long Ro = R0 + r;
             if constexpr (WL) Ro = list[Ro];
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                f32x4 w4;
+            for (int t = 0; t < NT; t++)
 #pragma unroll
-                for (int i = 0; i < 4; i++) w4[i] = o[0][4 * q + i] / den;
-                *reinterpret_cast<f32x4 *>(desc + Ro * SSLAM_D + wn * 32 + 8 * q + 4 * h) = w4;
-            }
+                for (int q = 0; q < 4; q++) {
+                    f32x4 w4;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) w4[i] = o[t][4 * q + i] / den;
+                    *reinterpret_cast<f32x4 *>(desc + Ro * (128 * NT) + wn * 32 * NT + 32 * t + 8 * q + 4 * h) = w4;
+                }
         }
     }
     PROBE_END();
@@ -478,14 +484,15 @@ __global__ __launch_bounds__(DN) void distinct_list_kernel(const int *__restrict
     if (f == n_frames - 1 && tid == DN - 1) counts[n_frames] = slot;     // the last thread of the last frame ends at the total
 }
 
+template <int D>
 __global__ __launch_bounds__(256) void copy_duplicates_kernel(const int *__restrict__ rep, long long rows, float *desc) {
     const long long item = (long long)blockIdx.x * 256 + threadIdx.x;   // one float4 of one row
-    const long long R = item / (SSLAM_D / 4);
+    const long long R = item / (D / 4);
     if (R >= rows) return;
     const long long src = rep[R];
     if (src == R) return;
-    const int c0 = (int)(item % (SSLAM_D / 4)) * 4;
-    *reinterpret_cast<float4 *>(desc + R * SSLAM_D + c0) = *reinterpret_cast<const float4 *>(desc + src * SSLAM_D + c0);
+    const int c0 = (int)(item % (D / 4)) * 4;
+    *reinterpret_cast<float4 *>(desc + R * D + c0) = *reinterpret_cast<const float4 *>(desc + src * D + c0);
 }
 
 struct DistinctWs {
@@ -508,23 +515,28 @@ bool distinct_form(int n_frames, int K) {
     return forced < 0 ? rows >= DISTINCT_MIN_ROWS : forced != 0;
 }
 
+// d: the descriptor width, 128 or 256 (checked by the entries)
 int launch_refine(const float *feat, int G, const float *kp_xy, int K, const float *x_in, long long rows,
-                  const float *packed, int n_blocks, float *desc, void *stream) {
+                  const float *packed, int n_blocks, int d, float *desc, void *stream) {
     RefArgs a;
     a.packed = packed;
-    if (sslam_refiner_layout(n_blocks, &a.lay) != SSLAM_OK) return SSLAM_E_UNSUPPORTED;
+    if (sslam_refiner_layout_d(n_blocks, d, &a.lay) != SSLAM_OK) return SSLAM_E_UNSUPPORTED;
     const unsigned grid = (unsigned)((rows + RM - 1) / RM);
-    hipLaunchKernelGGL(gather_refine_kernel<false>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, feat, G, kp_xy, K, x_in,
-                       rows, (const int *)nullptr, (const int *)nullptr, a, desc);
+    if (d == 128)
+        hipLaunchKernelGGL((gather_refine_kernel<false, 1>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, feat, G, kp_xy, K, x_in,
+                           rows, (const int *)nullptr, (const int *)nullptr, a, desc);
+    else
+        hipLaunchKernelGGL((gather_refine_kernel<false, 2>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, feat, G, kp_xy, K, x_in,
+                           rows, (const int *)nullptr, (const int *)nullptr, a, desc);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }
 
 int launch_refine_distinct(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed, int n_blocks,
-                           float *desc, void *workspace, void *stream) {
+                           int d, float *desc, void *workspace, void *stream) {
     RefArgs a;
     a.packed = packed;
-    if (sslam_refiner_layout(n_blocks, &a.lay) != SSLAM_OK) return SSLAM_E_UNSUPPORTED;
+    if (sslam_refiner_layout_d(n_blocks, d, &a.lay) != SSLAM_OK) return SSLAM_E_UNSUPPORTED;
     const long long rows = (long long)n_frames * K;
     const DistinctWs w = distinct_ws(n_frames, rows);
     int *counts = (int *)((char *)workspace + w.counts), *rep = (int *)((char *)workspace + w.rep),
@@ -537,18 +549,29 @@ int launch_refine_distinct(const float *feat, int n_frames, int G, const float *
     hipLaunchKernelGGL(distinct_list_kernel, dim3(n_frames), dim3(DN), 0, st, rep, K, n_frames, counts, list);
     SSLAM_CHECK_LAUNCH();
     const unsigned grid = (unsigned)((rows + RM - 1) / RM);        // worst case: the host does not know the count
-    hipLaunchKernelGGL(gather_refine_kernel<true>, dim3(grid), dim3(NTHR), 0, st, feat, G, kp_xy, K, (const float *)nullptr, rows,
-                       (const int *)list, (const int *)(counts + n_frames), a, desc);
+    if (d == 128)
+        hipLaunchKernelGGL((gather_refine_kernel<true, 1>), dim3(grid), dim3(NTHR), 0, st, feat, G, kp_xy, K, (const float *)nullptr, rows,
+                           (const int *)list, (const int *)(counts + n_frames), a, desc);
+    else
+        hipLaunchKernelGGL((gather_refine_kernel<true, 2>), dim3(grid), dim3(NTHR), 0, st, feat, G, kp_xy, K, (const float *)nullptr, rows,
+                           (const int *)list, (const int *)(counts + n_frames), a, desc);
     SSLAM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(copy_duplicates_kernel, dim3((unsigned)((rows * (SSLAM_D / 4) + 255) / 256)), dim3(256), 0, st, rep, rows, desc);
+    const dim3 cgrid((unsigned)((rows * (d / 4) + 255) / 256));
+    if (d == 128)
+        hipLaunchKernelGGL(copy_duplicates_kernel<128>, cgrid, dim3(256), 0, st, rep, rows, desc);
+    else
+        hipLaunchKernelGGL(copy_duplicates_kernel<256>, cgrid, dim3(256), 0, st, rep, rows, desc);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }
 
 }  // namespace
 
-extern "C" int sslam_refiner_layout(int n_blocks, sslam_refiner_layout_t *L) {
+static bool width_ok(int d) { return d == 128 || d == 256; }
+
+extern "C" int sslam_refiner_layout_d(int n_blocks, int d, sslam_refiner_layout_t *L) {
     if (!L || n_blocks < 0 || n_blocks > 8) return SSLAM_E_INVALID;
+    if (!width_ok(d)) return SSLAM_E_UNSUPPORTED;
     long long off = 0;
     auto take = [&](long long n) { const long long o = off; off += n; return o; };
     L->n_blocks = n_blocks;
@@ -562,11 +585,12 @@ extern "C" int sslam_refiner_layout(int n_blocks, sslam_refiner_layout_t *L) {
         L->blk[b][4] = take(HID); L->blk[b][5] = take(HID);
         L->blk[b][6] = take((long long)HID * HID); L->blk[b][7] = take(HID);
     }
-    L->out_w = take((long long)SSLAM_D * HID);
-    L->out_b = take(SSLAM_D);
+    L->out_w = take((long long)d * HID);
+    L->out_b = take(d);
     L->total = off;
     return SSLAM_OK;
 }
+extern "C" int sslam_refiner_layout(int n_blocks, sslam_refiner_layout_t *L) { return sslam_refiner_layout_d(n_blocks, SSLAM_D, L); }
 
 // w (n_out, k_in) -> [k-group = k/8][n][8 floats in KP8 order]: the MFMA B-fragment order
 extern "C" int sslam_pack_linear_host(const float *w, int n_out, int k_in, float *out) {
@@ -577,9 +601,10 @@ extern "C" int sslam_pack_linear_host(const float *w, int n_out, int k_in, float
     return SSLAM_OK;
 }
 
-extern "C" int sslam_refiner_pack_host(const float *const *w, int n_blocks, float *out) {
+extern "C" int sslam_refiner_pack_host_d(const float *const *w, int n_blocks, int d, float *out) {
     sslam_refiner_layout_t L;
-    if (!w || !out || sslam_refiner_layout(n_blocks, &L) != SSLAM_OK) return SSLAM_E_INVALID;
+    if (!w || !out) return SSLAM_E_INVALID;
+    if (const int rc = sslam_refiner_layout_d(n_blocks, d, &L)) return rc;
     auto cp = [&](long long off, const float *src, int n) { for (int i = 0; i < n; i++) out[off + i] = src[i]; };
     sslam_pack_linear_host(w[0], HID, SSLAM_C, out + L.in_w);
     cp(L.in_b, w[1], HID);
@@ -591,22 +616,39 @@ extern "C" int sslam_refiner_pack_host(const float *const *w, int n_blocks, floa
         sslam_pack_linear_host(p[6], HID, HID, out + L.blk[b][6]); cp(L.blk[b][7], p[7], HID);
     }
     const float *const *po = w + 2 + 8 * n_blocks;
-    sslam_pack_linear_host(po[0], SSLAM_D, HID, out + L.out_w);
-    cp(L.out_b, po[1], SSLAM_D);
+    sslam_pack_linear_host(po[0], d, HID, out + L.out_w);
+    cp(L.out_b, po[1], d);
     return SSLAM_OK;
 }
+extern "C" int sslam_refiner_pack_host(const float *const *w, int n_blocks, float *out) {
+    // as before the width-taking entry: every failure of the layout is SSLAM_E_INVALID here
+    return sslam_refiner_pack_host_d(w, n_blocks, SSLAM_D, out) == SSLAM_OK ? SSLAM_OK : SSLAM_E_INVALID;
+}
 
+extern "C" int sslam_refine_d(const float *x, long long rows, const float *packed, int n_blocks, float *desc, int d, void *stream) {
+    if (!x || !packed || !desc || rows <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;
+    if (!width_ok(d)) return SSLAM_E_UNSUPPORTED;
+    return launch_refine(nullptr, 0, nullptr, 1, x, rows, packed, n_blocks, d, desc, stream);
+}
 extern "C" int sslam_refine(const float *x, long long rows, const float *packed, int n_blocks, float *desc, void *stream) {
     if (!x || !packed || !desc || rows <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)x | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
-    return launch_refine(nullptr, 0, nullptr, 1, x, rows, packed, n_blocks, desc, stream);
+    return launch_refine(nullptr, 0, nullptr, 1, x, rows, packed, n_blocks, SSLAM_D, desc, stream);
 }
 
+extern "C" int sslam_gather_refine_d(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
+                                     int n_blocks, float *desc, int d, void *stream) {
+    if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;
+    if (!width_ok(d)) return SSLAM_E_UNSUPPORTED;
+    return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, d, desc, stream);
+}
 extern "C" int sslam_gather_refine(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
                                    int n_blocks, float *desc, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
-    return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, desc, stream);
+    return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, SSLAM_D, desc, stream);
 }
 
 extern "C" long long sslam_gather_refine_workspace_bytes(int n_frames, int K) {
@@ -614,14 +656,26 @@ extern "C" long long sslam_gather_refine_workspace_bytes(int n_frames, int K) {
     return distinct_form(n_frames, K) ? distinct_ws(n_frames, (long long)n_frames * K).bytes : 0;
 }
 
+static int gather_refine_ws(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed, int n_blocks,
+                            int d, float *desc, void *workspace, long long workspace_bytes, void *stream) {
+    if (distinct_form(n_frames, K) && workspace && !((uintptr_t)workspace & 3) &&
+        workspace_bytes >= distinct_ws(n_frames, (long long)n_frames * K).bytes)
+        return launch_refine_distinct(feat, n_frames, G, kp_xy, K, packed, n_blocks, d, desc, workspace, stream);
+    return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, d, desc, stream);
+}
+// the workspace (sslam_gather_refine_workspace_bytes) does not depend on the width: it holds row indices only
+extern "C" int sslam_gather_refine_ws_d(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
+                                        int n_blocks, float *desc, void *workspace, long long workspace_bytes, int d, void *stream) {
+    if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;
+    if (!width_ok(d)) return SSLAM_E_UNSUPPORTED;
+    return gather_refine_ws(feat, n_frames, G, kp_xy, K, packed, n_blocks, d, desc, workspace, workspace_bytes, stream);
+}
 extern "C" int sslam_gather_refine_ws(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
                                       int n_blocks, float *desc, void *workspace, long long workspace_bytes, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
-    if (distinct_form(n_frames, K) && workspace && !((uintptr_t)workspace & 3) &&
-        workspace_bytes >= distinct_ws(n_frames, (long long)n_frames * K).bytes)
-        return launch_refine_distinct(feat, n_frames, G, kp_xy, K, packed, n_blocks, desc, workspace, stream);
-    return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, desc, stream);
+    return gather_refine_ws(feat, n_frames, G, kp_xy, K, packed, n_blocks, SSLAM_D, desc, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sslam_gather(const float *feat, int n_frames, int G, const float *kp_xy, int K, float *out, void *stream) {

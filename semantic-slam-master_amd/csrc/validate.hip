@@ -26,21 +26,22 @@ namespace {
 constexpr int QB = 128;            // queries per workgroup (32 per wave)
 constexpr int CB = 64;             // candidates per stage (two MFMA tiles per wave)
 constexpr int NTM = 256;           // threads per workgroup
-constexpr int LDD = SSLAM_D + 4;   // 132-float rows: conflict-free b128 fragment reads
+// LDS rows are D + 4 floats (132 / 260): conflict-free b128 fragment reads
 
-// rows x 128 floats -> KP8 image in LDS; load half (global -> registers) and store half (registers -> LDS), so that the next
+// rows x D floats -> KP8 image in LDS; load half (global -> registers) and store half (registers -> LDS), so that the next
 // candidate tile is in flight during the MFMAs.  Rows beyond n_valid re-read row 0 and are stored as zeros.
-template <int ROWS>
+template <int ROWS, int D>
 struct Stager {
-    static constexpr int ITEMS = ROWS * 16 / NTM;
+    static constexpr int GL = D == 128 ? 4 : 5, GM = D / 8 - 1, LDD = D + 4;      // D / 8 groups of 8 floats per row
+    static constexpr int ITEMS = ROWS * (D / 8) / NTM;
     float4 lo[ITEMS], hi[ITEMS];
     bool ok[ITEMS];
     __device__ __forceinline__ void load(const float *__restrict__ src, int first, int n_valid, int tid) {
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
-            const int it = tid + NTM * i, row = it >> 4, g = it & 15;
+            const int it = tid + NTM * i, row = it >> GL, g = it & GM;
             ok[i] = first + row < n_valid;
-            const float4 *p = reinterpret_cast<const float4 *>(src + (long long)(ok[i] ? first + row : 0) * SSLAM_D + 8 * g);
+            const float4 *p = reinterpret_cast<const float4 *>(src + (long long)(ok[i] ? first + row : 0) * D + 8 * g);
             lo[i] = p[0];
             hi[i] = p[1];
         }
@@ -48,7 +49,7 @@ struct Stager {
     __device__ __forceinline__ void store(float *dst, int tid) const {
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
-            const int it = tid + NTM * i, row = it >> 4, g = it & 15;
+            const int it = tid + NTM * i, row = it >> GL, g = it & GM;
             float4 ev, od;
             const bool k = ok[i];
             kp8_split(make_float4(k ? lo[i].x : 0.f, k ? lo[i].y : 0.f, k ? lo[i].z : 0.f, k ? lo[i].w : 0.f),
@@ -82,13 +83,15 @@ __device__ __forceinline__ float logit(float s, float temperature) {      // sel
     return fminf(fmaxf(s / temperature, -50.0f), 50.0f);
 }
 
-// grid: (pair, query block) in the XCD-aware order of sim_argmax_kernel; 4 waves x 32 queries
-template <class PAIRS>
-__global__ __launch_bounds__(NTM, 2) void row_lse_kernel(const float *__restrict__ desc1, long long stride1, int n1,
+// grid: (pair, query block) in the XCD-aware order of sim_argmax_kernel; 4 waves x 32 queries.  D = 256: the stage of 64 candidates
+// is 2 x 65 KB of LDS and the queries 128 registers - one workgroup per CU, as in sim_argmax_kernel
+template <int D, class PAIRS>
+__global__ __launch_bounds__(NTM, D == 128 ? 2 : 1) void row_lse_kernel(const float *__restrict__ desc1, long long stride1, int n1,
                                                          const float *__restrict__ desc2, long long stride2, int n2,
                                                          const float *__restrict__ s12, float temperature,
                                                          float *__restrict__ lse, float *__restrict__ ce,
                                                          float *__restrict__ s00, int n_pairs, int qblocks, PAIRS pairs) {
+    constexpr int LDD = D + 4;
     __shared__ __attribute__((aligned(16))) float Cs[2 * CB * LDD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -108,16 +111,16 @@ __global__ __launch_bounds__(NTM, 2) void row_lse_kernel(const float *__restrict
     const float *q = desc1 + f1 * stride1, *c = desc2 + f2 * stride2;
     const int nq = n1, nc = n2;
 
-    Stager<CB> sc;
+    Stager<CB, D> sc;
     sc.load(c, 0, nc, tid);
     const int qi = q0 + wave * 32 + r;
     const bool qok = qi < nq;
-    float qreg[SSLAM_D / 2];      // this lane's query as the B operand of all 64 MFMA steps: step i multiplies k = 2 i + h
+    float qreg[D / 2];      // this lane's query as the B operand of all D / 2 MFMA steps: step i multiplies k = 2 i + h
     {
-        const float4 *qp = reinterpret_cast<const float4 *>(q + (long long)(qok ? qi : 0) * SSLAM_D);
+        const float4 *qp = reinterpret_cast<const float4 *>(q + (long long)(qok ? qi : 0) * D);
         const float qm = qok ? 1.0f : 0.0f;
 #pragma unroll
-        for (int i = 0; i < SSLAM_D / 4; i++) {
+        for (int i = 0; i < D / 4; i++) {
             const float4 v = qp[i];
             qreg[2 * i] = (h ? v.y : v.x) * qm;
             qreg[2 * i + 1] = (h ? v.w : v.z) * qm;
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(NTM, 2) void row_lse_kernel(const float *__restrict
 #pragma unroll
         for (int e = 0; e < 16; e++) acc[0][e] = acc[1][e] = 0.0f;
 #pragma unroll
-        for (int g = 0; g < SSLAM_D / 8; g++) {
+        for (int g = 0; g < D / 8; g++) {
             // KP8 image: the float4 at 8 g + 4 h holds k = 8 g + 2 st + h, st = 0..3 -> MFMA step 4 g + st
             const f32x4 a0 = *reinterpret_cast<const f32x4 *>(A + 8 * g);
             const f32x4 a1 = *reinterpret_cast<const f32x4 *>(A + 32 * LDD + 8 * g);
@@ -263,7 +266,9 @@ __device__ __forceinline__ float block_max(float v, float *red, int tid) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// one workgroup per frame; stats row: SSLAM_VAL_* slots of include/sslam_hip.h
+// one workgroup per frame; stats row: SSLAM_VAL_* slots of include/sslam_hip.h.  D: the descriptor width (128: two row-parity
+// half-sums per dimension on the 256 threads; 256: one thread per dimension, all rows in increasing index)
+template <int D>
 __global__ __launch_bounds__(256) void val_frame_stats_kernel(const float *__restrict__ sal, const float *__restrict__ pooled,
                                                               const float *__restrict__ edge_max, const float *__restrict__ desc,
                                                               int G, int K, float *__restrict__ stats,
@@ -334,25 +339,26 @@ __global__ __launch_bounds__(256) void val_frame_stats_kernel(const float *__res
         for (int i = SSLAM_VAL_EDGE_MAX + 1; i < SSLAM_VAL_FRAME_STATS; i++) o[i] = 0.0f;
     }
     if (desc) {      // per dimension: mean, then the centred sum of squares; thread = (row parity, dimension)
-        const float *d = desc + f * (long long)K * SSLAM_D;
-        const int dim = tid & (SSLAM_D - 1), par = tid >> 7;
+        constexpr int NPAR = 256 / D;      // row classes per dimension: 2 or 1
+        const float *d = desc + f * (long long)K * D;
+        const int dim = tid & (D - 1), par = tid >> (D == 128 ? 7 : 8);
         float t = 0.f;
-        for (int k = par; k < K; k += 2) t = t + d[(long long)k * SSLAM_D + dim];
+        for (int k = par; k < K; k += NPAR) t = t + d[(long long)k * D + dim];
         __syncthreads();
         part[tid] = t;
         __syncthreads();
-        const float mean = (part[dim] + part[dim + SSLAM_D]) / (float)K;
+        const float mean = (NPAR == 2 ? part[dim] + part[dim + (NPAR == 2 ? D : 0)] : part[dim]) / (float)K;
         float q = 0.f;
-        for (int k = par; k < K; k += 2) {
-            const float c = d[(long long)k * SSLAM_D + dim] - mean;
+        for (int k = par; k < K; k += NPAR) {
+            const float c = d[(long long)k * D + dim] - mean;
             q = q + c * c;
         }
         __syncthreads();
         part[tid] = q;
         __syncthreads();
         if (par == 0) {
-            desc_mean[f * SSLAM_D + dim] = mean;
-            desc_m2[f * SSLAM_D + dim] = part[dim] + part[dim + SSLAM_D];
+            desc_mean[f * D + dim] = mean;
+            desc_m2[f * D + dim] = NPAR == 2 ? part[dim] + part[dim + (NPAR == 2 ? D : 0)] : part[dim];
         }
     }
 }
@@ -405,13 +411,13 @@ __global__ __launch_bounds__(256) void val_pair_stats_kernel(const float *__rest
     }
 }
 
-template <class PAIRS>
+template <int D, class PAIRS>
 int launch_row_lse(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2, int n_pairs,
                    const float *s12, float temperature, float *lse, float *ce, float *s00, void *stream, PAIRS pairs) {
     const int qb1 = (n1 + QB - 1) / QB;
     if ((long long)n_pairs * qb1 > 0x7ffffff0LL / 8) return SSLAM_E_UNSUPPORTED;
     const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8 * qb1), 1, 1);
-    hipLaunchKernelGGL(row_lse_kernel<PAIRS>, grid, dim3(NTM), 0, (hipStream_t)stream, desc1, stride1, n1, desc2, stride2, n2, s12,
+    hipLaunchKernelGGL((row_lse_kernel<D, PAIRS>), grid, dim3(NTM), 0, (hipStream_t)stream, desc1, stride1, n1, desc2, stride2, n2, s12,
                        temperature, lse, ce, s00, n_pairs, qb1, pairs);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
@@ -421,23 +427,39 @@ bool temperature_ok(float t) { return t > 0.0f && t < INFINITY; }
 
 }  // namespace
 
-extern "C" int sslam_row_lse(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
-                             int n_pairs, const float *s12, float temperature, float *lse, float *ce, float *s00, void *stream) {
+#define SSLAM_BY_WIDTH(d_, call128_, call256_) ((d_) == 128 ? (call128_) : (d_) == 256 ? (call256_) : SSLAM_E_UNSUPPORTED)
+
+extern "C" int sslam_row_lse_d(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                               int n_pairs, const float *s12, float temperature, float *lse, float *ce, float *s00, int d, void *stream) {
     if (!desc1 || !desc2 || !s12 || (!lse && !ce) || n1 <= 0 || n2 <= 0 || n_pairs <= 0 || !temperature_ok(temperature))
         return SSLAM_E_INVALID;
     if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3)) return SSLAM_E_INVALID;
-    return launch_row_lse(desc1, stride1, n1, desc2, stride2, n2, n_pairs, s12, temperature, lse, ce, s00, stream, StridedPairs{});
+    return SSLAM_BY_WIDTH(d,
+                          launch_row_lse<128>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, s12, temperature, lse, ce, s00, stream, StridedPairs{}),
+                          launch_row_lse<256>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, s12, temperature, lse, ce, s00, stream, StridedPairs{}));
+}
+extern "C" int sslam_row_lse(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
+                             int n_pairs, const float *s12, float temperature, float *lse, float *ce, float *s00, void *stream) {
+    return sslam_row_lse_d(desc1, stride1, n1, desc2, stride2, n2, n_pairs, s12, temperature, lse, ce, s00, SSLAM_D, stream);
 }
 
-extern "C" int sslam_row_lse_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
-                                   const int32_t *pair_second, int n_pairs, const float *s12, float temperature, float *lse,
-                                   float *ce, float *s00, void *stream) {
+extern "C" int sslam_row_lse_pairs_d(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                     const int32_t *pair_second, int n_pairs, const float *s12, float temperature, float *lse,
+                                     float *ce, float *s00, int d, void *stream) {
     if (!bank || !pair_first || !pair_second || !s12 || (!lse && !ce) || n_bank <= 0 || K <= 0 || n_pairs <= 0 ||
         !temperature_ok(temperature))
         return SSLAM_E_INVALID;
     if (((uintptr_t)bank & 15) || (frame_stride & 3) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3)) return SSLAM_E_INVALID;
-    return launch_row_lse(bank, frame_stride, K, bank, frame_stride, K, n_pairs, s12, temperature, lse, ce, s00, stream,
-                          ListedPairs{pair_first, pair_second, n_bank});
+    const ListedPairs lp{pair_first, pair_second, n_bank};
+    return SSLAM_BY_WIDTH(d,
+                          launch_row_lse<128>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, s12, temperature, lse, ce, s00, stream, lp),
+                          launch_row_lse<256>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, s12, temperature, lse, ce, s00, stream, lp));
+}
+extern "C" int sslam_row_lse_pairs(const float *bank, long long frame_stride, int n_bank, int K, const int32_t *pair_first,
+                                   const int32_t *pair_second, int n_pairs, const float *s12, float temperature, float *lse,
+                                   float *ce, float *s00, void *stream) {
+    return sslam_row_lse_pairs_d(bank, frame_stride, n_bank, K, pair_first, pair_second, n_pairs, s12, temperature, lse, ce, s00, SSLAM_D,
+                                 stream);
 }
 
 extern "C" int sslam_edge_pool(const float *images_chw, int n_frames, int size, float *pooled, float *edge_max, void *stream) {
@@ -454,15 +476,24 @@ extern "C" int sslam_edge_pool(const float *images_chw, int n_frames, int size, 
     return SSLAM_OK;
 }
 
-extern "C" int sslam_val_frame_stats(const float *saliency, const float *pooled, const float *edge_max, const float *descriptors,
-                                     int n_frames, int G, int K, float *stats, float *desc_mean, float *desc_m2, void *stream) {
+extern "C" int sslam_val_frame_stats_d(const float *saliency, const float *pooled, const float *edge_max, const float *descriptors,
+                                       int n_frames, int G, int K, float *stats, float *desc_mean, float *desc_m2, int d, void *stream) {
     if (!saliency || !stats || n_frames <= 0 || G <= 0 || G > 4096) return SSLAM_E_INVALID;
     if ((pooled != nullptr) != (edge_max != nullptr)) return SSLAM_E_INVALID;
     if (descriptors && (!desc_mean || !desc_m2 || K <= 0)) return SSLAM_E_INVALID;
-    hipLaunchKernelGGL(val_frame_stats_kernel, dim3((unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, saliency, pooled, edge_max,
-                       descriptors, G, K, stats, desc_mean, desc_m2);
+    if (d != 128 && d != 256) return SSLAM_E_UNSUPPORTED;
+    if (d == 128)
+        hipLaunchKernelGGL(val_frame_stats_kernel<128>, dim3((unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, saliency, pooled,
+                           edge_max, descriptors, G, K, stats, desc_mean, desc_m2);
+    else
+        hipLaunchKernelGGL(val_frame_stats_kernel<256>, dim3((unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, saliency, pooled,
+                           edge_max, descriptors, G, K, stats, desc_mean, desc_m2);
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
+}
+extern "C" int sslam_val_frame_stats(const float *saliency, const float *pooled, const float *edge_max, const float *descriptors,
+                                     int n_frames, int G, int K, float *stats, float *desc_mean, float *desc_m2, void *stream) {
+    return sslam_val_frame_stats_d(saliency, pooled, edge_max, descriptors, n_frames, G, K, stats, desc_mean, desc_m2, SSLAM_D, stream);
 }
 
 static bool pair_stats_args_ok(const float *saliency, int G, const int32_t *nn12, const int32_t *nn21, const float *s12, const float *ce,

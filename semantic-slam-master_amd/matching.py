@@ -30,8 +30,9 @@ def _dev(a, dtype=torch.float32):
 
 def _argmax(desc1, desc2, want_second=False):
     d1, d2 = _dev(desc1), _dev(desc2)
-    if d1.shape[1] != lib.D_OUT or d2.shape[1] != lib.D_OUT:
-        raise lib.SslamHipError("descriptor dimension must be 128")
+    if d1.dim() != 2 or d2.dim() != 2 or d1.shape[1] not in lib.WIDTHS or d2.shape[1] != d1.shape[1]:
+        raise lib.SslamHipError(f"descriptor dimension must be one of {lib.WIDTHS}, the same on both sides; got shapes "
+                                f"{tuple(d1.shape)} and {tuple(d2.shape)}")
     n, m = d1.shape[0], d2.shape[0]
     return (n, m) + lib.sim_argmax(d1, 0, n, d2, 0, m, 1, want_s21=False, want_second=want_second)
 
@@ -84,9 +85,12 @@ def find_mutual_nearest_neighbors(desc1, desc2, ratio_threshold: float = 0.9):
 def find_matches_batched(desc1: torch.Tensor, desc2: torch.Tensor) -> torch.Tensor:
     """M3.  (B, N, D) x 2 on the device -> (B, Mmax, 2) int64 mutual-NN pairs, zero-padded to the longest;
     all-empty -> zeros(B, 1, 2) (train.py:439-440).  The padding rows are (0, 0), as in the original."""
-    B, N, _ = desc1.shape
+    B, N, D = desc1.shape
     d1, d2 = _dev(desc1), _dev(desc2)
-    nn12, s12, nn21, _, _ = lib.sim_argmax(d1, N * lib.D_OUT, N, d2, N * lib.D_OUT, N, B)
+    if D not in lib.WIDTHS or tuple(d2.shape) != (B, N, D):
+        raise lib.SslamHipError(f"descriptor dimension must be one of {lib.WIDTHS}, the same on both sides; got shapes "
+                                f"{tuple(d1.shape)} and {tuple(d2.shape)}")
+    nn12, s12, nn21, _, _ = lib.sim_argmax(d1, N * D, N, d2, N * D, N, B)
     ones = torch.ones((B, N), dtype=torch.float32, device=d1.device)
     mt, _, cnt = lib.match_finalize(nn12, s12, nn21, N, N, B, ones, N, ones, N, None, None, 1.0, 0.0, -1e30, -1e30, -1e30)
     mmax = int(cnt.max().item())

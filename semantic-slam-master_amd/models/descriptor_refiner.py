@@ -63,13 +63,13 @@ class DescriptorRefiner(nn.Module):
         return self._packed
 
     def _hip_ok(self, x: torch.Tensor) -> bool:
-        """HIP path only for 384 -> 384 -> 128 (any other dims the reference accepts, descriptor_refiner.py:22-45, run
+        """HIP path only for 384 -> 384 -> 128 | 256 (any other dims the reference accepts, descriptor_refiner.py:22-45, run
         as eager torch ops) and when weights and input share a GPU."""
         w_in, w_out = self.input_proj.weight, self.output_proj.weight
         if not PackedRefiner.supported(w_in.shape[1], w_in.shape[0], w_out.shape[0], len(self.residual_blocks)):
             if not self._warned:
                 warnings.warn(f"DescriptorRefiner: {w_in.shape[1]} -> {w_in.shape[0]} -> {w_out.shape[0]} is outside the HIP "
-                              f"kernel's shape (384 -> 384 -> 128); using the eager torch path")
+                              f"kernel's shapes (384 -> 384 -> 128 | 256); using the eager torch path")
                 self._warned = True
             return False
         return w_in.device == x.device

@@ -20,6 +20,7 @@ OK, E_INVALID, E_UNSUPPORTED, E_LAUNCH = 0, -1, -2, -3
 _ERR = {E_INVALID: "invalid argument", E_UNSUPPORTED: "unsupported shape", E_LAUNCH: "kernel launch failed"}
 
 C_FEAT, HID, D_OUT = 384, 384, 128
+WIDTHS = (128, 256)     # descriptor widths the kernels are built for; D_OUT is the default (include/sslam_hip.h, the _d entries)
 MAX_TAPS = 32
 
 
@@ -82,6 +83,9 @@ EXPORTS = [
     "sslam_match_finalize_rule", "sslam_match_finalize_rule_pairs", "sslam_sim_argmax_rows", "sslam_sim_argmax_rows_pairs",
     "sslam_row_lse", "sslam_row_lse_pairs", "sslam_edge_pool", "sslam_val_frame_stats", "sslam_val_pair_stats",
     "sslam_val_pair_stats_pairs",
+    "sslam_refiner_layout_d", "sslam_refiner_pack_host_d", "sslam_refine_d", "sslam_gather_refine_d", "sslam_gather_refine_ws_d",
+    "sslam_sim_argmax_d", "sslam_sim_argmax_ws_d", "sslam_sim_argmax_pairs_d", "sslam_sim_argmax_rows_d",
+    "sslam_sim_argmax_rows_pairs_d", "sslam_row_lse_d", "sslam_row_lse_pairs_d", "sslam_val_frame_stats_d",
 ]
 
 
@@ -131,6 +135,13 @@ def lib():
         L.sslam_val_frame_stats.argtypes = [p, p, p, p, i, i, i, p, p, p, p]
         L.sslam_val_pair_stats.argtypes = [p, p, i, p, p, p, p, p, i, i, i, f, p, p, p]
         L.sslam_val_pair_stats_pairs.argtypes = [p, i, i, p, p, p, p, p, p, p, i, i, f, p, p, p]
+        # the width-taking forms: `int d` in front of the stream (of the output pointer in the host-side packers)
+        L.sslam_refiner_layout_d.argtypes = [i, i, C.POINTER(RefinerLayout)]
+        L.sslam_refiner_pack_host_d.argtypes = [p, i, i, p]
+        for name in ("refine", "gather_refine", "gather_refine_ws", "sim_argmax", "sim_argmax_ws", "sim_argmax_pairs", "sim_argmax_rows",
+                     "sim_argmax_rows_pairs", "row_lse", "row_lse_pairs", "val_frame_stats"):
+            at = getattr(L, "sslam_" + name).argtypes
+            getattr(L, f"sslam_{name}_d").argtypes = at[:-1] + [i, at[-1]]
         L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
         L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
         L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
@@ -202,6 +213,39 @@ def _dp(t):
     return C.c_void_p(t.data_ptr())
 
 
+def check_width(d, what: str = "descriptor width") -> int:
+    """d if the kernels are built for it (WIDTHS), else ValueError naming them."""
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or int(d) not in WIDTHS:
+        raise ValueError(f"{what} must be one of {WIDTHS}, got {d!r}")
+    return int(d)
+
+
+def _operand_width(*named) -> int:
+    """The one width of a call's descriptor operands ((name, tensor) pairs): the last dimension of each; a 1-D buffer stands for
+    rows of the default width.  Unequal or unsupported widths: ValueError."""
+    d = None
+    for name, t in named:
+        w = check_width(int(t.shape[-1]) if t.dim() >= 2 else D_OUT, f"the width of {name}")
+        if d is not None and w != d:
+            raise ValueError(f"descriptor operands of unequal width: {d} and {w}")
+        d = w
+    return d
+
+
+_PACKED_WIDTH = {}      # (floats, n_blocks) -> width: refine / gather_refine ask on every call
+
+
+def packed_refiner_width(packed, n_blocks: int) -> int:
+    """The output width a packed refiner buffer was laid out for, from its length (refiner_layout(n_blocks, d).total)."""
+    n = int(packed.numel())
+    key = (n, int(n_blocks))
+    if key not in _PACKED_WIDTH:
+        _PACKED_WIDTH[key] = next((d for d in WIDTHS if n == int(refiner_layout(n_blocks, d).total)), None)
+    if _PACKED_WIDTH[key] is not None:
+        return _PACKED_WIDTH[key]
+    raise ValueError(f"a packed refiner buffer of {n} floats fits no supported output width {WIDTHS} at {n_blocks} blocks")
+
+
 def launch_count() -> int:
     return int(lib().sslam_launch_count())
 
@@ -252,20 +296,25 @@ def pack_conv3x3(w: np.ndarray) -> np.ndarray:
     return out
 
 
-def refiner_layout(n_blocks: int) -> RefinerLayout:
+def refiner_layout(n_blocks: int, d: int = D_OUT) -> RefinerLayout:
+    """Offsets (floats) of the packed refiner buffer for output width d (128 or 256)."""
     lay = RefinerLayout()
-    _check(lib().sslam_refiner_layout(n_blocks, C.byref(lay)), "refiner_layout")
+    _check(lib().sslam_refiner_layout_d(n_blocks, check_width(d, "refiner output width"), C.byref(lay)), "refiner_layout")
     return lay
 
 
 def pack_refiner(weights: list, n_blocks: int) -> np.ndarray:
-    """weights: 4 + 8*n_blocks fp32 arrays in state_dict order (input_proj, blocks, output_proj)."""
+    """weights: 4 + 8*n_blocks fp32 arrays in state_dict order (input_proj, blocks, output_proj); the output width is the
+    row count of output_proj.weight (128 or 256)."""
     ws = [np.ascontiguousarray(w, np.float32) for w in weights]
     assert len(ws) == 4 + 8 * n_blocks
-    lay = refiner_layout(n_blocks)
+    d = check_width(int(ws[-2].shape[0]), "refiner output width")
+    if ws[-2].shape != (d, HID) or ws[-1].shape != (d,):
+        raise ValueError(f"output_proj of shapes {ws[-2].shape}, {ws[-1].shape}: ({d}, {HID}) and ({d},) expected")
+    lay = refiner_layout(n_blocks, d)
     out = np.empty(lay.total, np.float32)
     arr = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-    _check(lib().sslam_refiner_pack_host(arr, n_blocks, out.ctypes.data), "refiner_pack")
+    _check(lib().sslam_refiner_pack_host_d(arr, n_blocks, d, out.ctypes.data), "refiner_pack")
     return out
 
 
@@ -423,11 +472,15 @@ def gather(feat, kp, out=None):
 
 
 def refine(x, packed, n_blocks, out=None):
+    """x (..., 384) -> descriptors (..., d), d the output width `packed` was laid out for (pack_refiner)."""
     rows = x.numel() // C_FEAT
+    d = packed_refiner_width(packed, n_blocks)
     if out is None:
-        out = torch.empty(x.shape[:-1] + (D_OUT,), dtype=torch.float32, device=x.device)
-    _run("refine", lib().sslam_refine, (x, packed, out,),
-         _dp(x), rows, _dp(packed), n_blocks, _dp(out))
+        out = torch.empty(x.shape[:-1] + (d,), dtype=torch.float32, device=x.device)
+    elif out.numel() != rows * d:
+        raise ValueError(f"out holds {out.numel()} floats, {rows} rows of width {d} expected")
+    _run("refine", lib().sslam_refine_d, (x, packed, out,),
+         _dp(x), rows, _dp(packed), n_blocks, _dp(out), d)
     return out
 
 
@@ -437,11 +490,14 @@ def gather_refine(feat, kp, packed, n_blocks, out=None, workspace=None):
     the scratch starts with the int32 distinct-keypoint counts of the n frames and their sum (gather_refine_counts)."""
     n, g = feat.shape[0], feat.shape[1]
     K = kp.shape[1]
+    d = packed_refiner_width(packed, n_blocks)
     if out is None:
-        out = torch.empty((n, K, D_OUT), dtype=torch.float32, device=feat.device)
+        out = torch.empty((n, K, d), dtype=torch.float32, device=feat.device)
+    elif out.numel() != n * K * d:
+        raise ValueError(f"out holds {out.numel()} floats, ({n}, {K}, {d}) expected")
     ws, wsb = _scratch(workspace, int(lib().sslam_gather_refine_workspace_bytes(n, K)), feat.device)
-    _run("gather_refine", lib().sslam_gather_refine_ws, (feat, kp, packed, out, ws),
-         _dp(feat), n, g, _dp(kp), K, _dp(packed), n_blocks, _dp(out), _dp(ws), wsb)
+    _run("gather_refine", lib().sslam_gather_refine_ws_d, (feat, kp, packed, out, ws),
+         _dp(feat), n, g, _dp(kp), K, _dp(packed), n_blocks, _dp(out), _dp(ws), wsb, d)
     return out
 
 
@@ -486,15 +542,16 @@ def sim_argmax(d1, stride1, n1, d2, stride2, n2, n_pairs, want_s21=False, want_s
     """workspace: optional caller-owned scratch tensor (sslam_workspace_bytes); batched calls without one get a torch
     allocation of n_pairs * n2 * 8 bytes here - the library itself never allocates."""
     dev = d1.device
+    d = _operand_width(("d1", d1), ("d2", d2))
     nn12 = torch.empty((n_pairs, n1), dtype=torch.int32, device=dev)
     s12 = torch.empty((n_pairs, n1), dtype=torch.float32, device=dev)
     nn21 = torch.empty((n_pairs, n2), dtype=torch.int32, device=dev)
     s21 = torch.empty((n_pairs, n2), dtype=torch.float32, device=dev) if want_s21 else None
     sec = torch.empty((n_pairs, n1), dtype=torch.float32, device=dev) if want_second else None
     ws, wsb = _scratch(workspace, int(lib().sslam_sim_argmax_workspace_bytes(n2, n_pairs)), dev)
-    _run("sim_argmax", lib().sslam_sim_argmax_ws, (nn12, s12, nn21, s21, sec, d1, d2, ws),
+    _run("sim_argmax", lib().sslam_sim_argmax_ws_d, (nn12, s12, nn21, s21, sec, d1, d2, ws),
          C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs,
-                                  _dp(nn12), _dp(s12), _dp(nn21), _dp(s21), _dp(sec), _dp(ws), wsb)
+                                  _dp(nn12), _dp(s12), _dp(nn21), _dp(s21), _dp(sec), _dp(ws), wsb, d)
     return nn12, s12, nn21, s21, sec
 
 
@@ -543,18 +600,21 @@ def check_pair_lists(first, second, device=None) -> int:
 
 
 def _check_bank(name, t, tail):
-    """t: a contiguous fp32 tensor (n_bank >= 1, *tail); a tail entry given as a string stands for any size >= 1."""
+    """t: a contiguous fp32 tensor (n_bank >= 1, *tail); a tail entry given as a string stands for any size >= 1, one given as a
+    tuple for any of its sizes (the descriptor widths)."""
+    fits = lambda d, w: isinstance(w, str) or (d in w if isinstance(w, tuple) else d == w)
     ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 1 + len(tail) and t.is_contiguous()
-    ok = ok and all(d >= 1 for d in t.shape) and all(isinstance(w, str) or d == w for d, w in zip(t.shape[1:], tail))
+    ok = ok and all(d >= 1 for d in t.shape) and all(fits(d, w) for d, w in zip(t.shape[1:], tail))
     if not ok:
-        raise ValueError(f"{name} must be a contiguous fp32 tensor of shape (n_bank, {', '.join(str(w) for w in tail)})")
+        shape = ", ".join(" | ".join(str(x) for x in w) if isinstance(w, tuple) else str(w) for w in tail)
+        raise ValueError(f"{name} must be a contiguous fp32 tensor of shape (n_bank, {shape})")
 
 
 def sim_argmax_pairs(bank, first, second, want_s21=False, want_second=False, workspace=None):
-    """sslam_sim_argmax_pairs: bank (n_bank, K, 128) fp32; first / second: 1-D int32 DEVICE tensors naming, pair by pair, the
+    """sslam_sim_argmax_pairs: bank (n_bank, K, 128 | 256) fp32; first / second: 1-D int32 DEVICE tensors naming, pair by pair, the
     two frames of the bank to match (an index outside [0, n_bank), -1 by convention, makes the pair ABSENT: zero rows).
     Returns (nn12, s12, nn21, s21, second12) with one row per listed pair, as sim_argmax does.  workspace: as there."""
-    _check_bank("bank", bank, ("K", D_OUT))
+    _check_bank("bank", bank, ("K", WIDTHS))
     n_bank, k = int(bank.shape[0]), int(bank.shape[1])
     n_pairs = check_pair_lists(first, second, bank.device)
     dev = common_device(bank, first, second, workspace)
@@ -564,9 +624,10 @@ def sim_argmax_pairs(bank, first, second, want_s21=False, want_second=False, wor
     s21 = torch.empty((n_pairs, k), dtype=torch.float32, device=dev) if want_s21 else None
     sec = torch.empty((n_pairs, k), dtype=torch.float32, device=dev) if want_second else None
     ws, wsb = _scratch(workspace, int(lib().sslam_sim_argmax_workspace_bytes(k, n_pairs)), dev)
-    _run("sim_argmax_pairs", lib().sslam_sim_argmax_pairs, (bank, first, second, nn12, s12, nn21, s21, sec, ws),
-         _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(nn12), _dp(s12), _dp(nn21), _dp(s21), _dp(sec),
-         _dp(ws), wsb)
+    d = int(bank.shape[2])
+    _run("sim_argmax_pairs", lib().sslam_sim_argmax_pairs_d, (bank, first, second, nn12, s12, nn21, s21, sec, ws),
+         _dp(bank), k * d, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(nn12), _dp(s12), _dp(nn21), _dp(s21), _dp(sec),
+         _dp(ws), wsb, d)
     return nn12, s12, nn21, s21, sec
 
 
@@ -627,21 +688,23 @@ def sim_argmax_rows(d1, stride1, n1, d2, stride2, n2, n_pairs, want_second=False
     """sslam_sim_argmax_rows: the row direction of sim_argmax alone - one launch, no workspace, the same bits.
     Returns (nn12, s12, second12 or None).  out: optional (nn12, s12, second12 or None) tensors to write into."""
     nn12, s12, sec = _rows_out(out, n_pairs, n1, want_second, d1.device)
-    _run("sim_argmax_rows", lib().sslam_sim_argmax_rows, (nn12, s12, sec, d1, d2),
-         C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs, _dp(nn12), _dp(s12), _dp(sec))
+    d = _operand_width(("d1", d1), ("d2", d2))
+    _run("sim_argmax_rows", lib().sslam_sim_argmax_rows_d, (nn12, s12, sec, d1, d2),
+         C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs, _dp(nn12), _dp(s12), _dp(sec), d)
     return nn12, s12, sec
 
 
 def sim_argmax_rows_pairs(bank, first, second, want_second=False, out=None):
     """sslam_sim_argmax_rows_pairs: the row direction of sim_argmax_pairs alone (bank and lists as there).
     Returns (nn12, s12, second12 or None), one row per listed pair.  out: optional tensors to write into, as sim_argmax_rows."""
-    _check_bank("bank", bank, ("K", D_OUT))
+    _check_bank("bank", bank, ("K", WIDTHS))
     n_bank, k = int(bank.shape[0]), int(bank.shape[1])
     n_pairs = check_pair_lists(first, second, bank.device)
     dev = common_device(bank, first, second)
     nn12, s12, sec = _rows_out(out, n_pairs, k, want_second, dev)
-    _run("sim_argmax_rows_pairs", lib().sslam_sim_argmax_rows_pairs, (bank, first, second, nn12, s12, sec),
-         _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(nn12), _dp(s12), _dp(sec))
+    d = int(bank.shape[2])
+    _run("sim_argmax_rows_pairs", lib().sslam_sim_argmax_rows_pairs_d, (bank, first, second, nn12, s12, sec),
+         _dp(bank), k * d, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(nn12), _dp(s12), _dp(sec), d)
     return nn12, s12, sec
 
 
@@ -729,23 +792,25 @@ def row_lse(d1, stride1, n1, d2, stride2, n2, n_pairs, s12, temperature=0.1, out
     t = check_temperature(temperature)
     _check_arrays((n_pairs, n1), ("s12", s12, torch.float32))
     lse, ce, s00 = _lse_out(n_pairs, n1, d1.device, out)
-    _run("row_lse", lib().sslam_row_lse, (d1, d2, s12, lse, ce, s00),
+    d = _operand_width(("d1", d1), ("d2", d2))
+    _run("row_lse", lib().sslam_row_lse_d, (d1, d2, s12, lse, ce, s00),
          C.c_void_p(d1.data_ptr()), stride1, n1, C.c_void_p(d2.data_ptr()), stride2, n2, n_pairs, _dp(s12), C.c_float(t), _dp(lse),
-         _dp(ce), _dp(s00))
+         _dp(ce), _dp(s00), d)
     return lse, ce, s00
 
 
 def row_lse_pairs(bank, first, second, s12, temperature=0.1, out=None):
-    """sslam_row_lse_pairs: row_lse for the listed pairs of bank (n_bank, K, 128); lists as sim_argmax_pairs takes them;
+    """sslam_row_lse_pairs: row_lse for the listed pairs of bank (n_bank, K, 128 | 256); lists as sim_argmax_pairs takes them;
     out as row_lse takes it."""
     t = check_temperature(temperature)
-    _check_bank("bank", bank, ("K", D_OUT))
+    _check_bank("bank", bank, ("K", WIDTHS))
     n_bank, k = int(bank.shape[0]), int(bank.shape[1])
     n_pairs = check_pair_lists(first, second, bank.device)
     _check_arrays((n_pairs, k), ("s12", s12, torch.float32))
     lse, ce, s00 = _lse_out(n_pairs, k, bank.device, out)
-    _run("row_lse_pairs", lib().sslam_row_lse_pairs, (bank, first, second, s12, lse, ce, s00),
-         _dp(bank), k * D_OUT, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(s12), C.c_float(t), _dp(lse), _dp(ce), _dp(s00))
+    d = int(bank.shape[2])
+    _run("row_lse_pairs", lib().sslam_row_lse_pairs_d, (bank, first, second, s12, lse, ce, s00),
+         _dp(bank), k * d, n_bank, k, _dp(first), _dp(second), n_pairs, _dp(s12), C.c_float(t), _dp(lse), _dp(ce), _dp(s00), d)
     return lse, ce, s00
 
 
@@ -767,8 +832,8 @@ def edge_pool(images_chw, out=None):
 
 
 def val_frame_stats(saliency, pooled=None, edge_max=None, descriptors=None):
-    """sslam_val_frame_stats: saliency (n, G, G) [+ pooled, edge_max of edge_pool] [+ descriptors (n, K, 128)] ->
-    (stats (n, VAL_FRAME_STATS), desc_mean (n, 128) or None, desc_m2 (n, 128) or None)."""
+    """sslam_val_frame_stats: saliency (n, G, G) [+ pooled, edge_max of edge_pool] [+ descriptors (n, K, d), d = 128 | 256] ->
+    (stats (n, VAL_FRAME_STATS), desc_mean (n, d) or None, desc_m2 (n, d) or None)."""
     if not isinstance(saliency, torch.Tensor) or saliency.dim() != 3 or saliency.shape[1] != saliency.shape[2]:
         raise ValueError("saliency must be a tensor of shape (n, G, G)")
     n, g = int(saliency.shape[0]), int(saliency.shape[1])
@@ -776,16 +841,17 @@ def val_frame_stats(saliency, pooled=None, edge_max=None, descriptors=None):
     _check_arrays((n,), ("edge_max", edge_max, torch.float32))
     if (pooled is None) != (edge_max is None):
         raise ValueError("pooled and edge_max come together")
-    dev, k, dm, d2 = saliency.device, 0, None, None
+    dev, k, dm, d2, width = saliency.device, 0, None, None, D_OUT
     if descriptors is not None:
-        _check_bank("descriptors", descriptors, ("K", D_OUT))
+        _check_bank("descriptors", descriptors, ("K", WIDTHS))
         if descriptors.shape[0] != n:
             raise ValueError(f"descriptors hold {descriptors.shape[0]} frames, saliency {n}")
         k = int(descriptors.shape[1])
-        dm, d2 = (torch.empty((n, D_OUT), dtype=torch.float32, device=dev) for _ in range(2))
+        width = int(descriptors.shape[2])
+        dm, d2 = (torch.empty((n, width), dtype=torch.float32, device=dev) for _ in range(2))
     stats = torch.empty((n, VAL_FRAME_STATS), dtype=torch.float32, device=dev)
-    _run("val_frame_stats", lib().sslam_val_frame_stats, (saliency, pooled, edge_max, descriptors, stats),
-         _dp(saliency), _dp(pooled), _dp(edge_max), _dp(descriptors), n, g, k, _dp(stats), _dp(dm), _dp(d2))
+    _run("val_frame_stats", lib().sslam_val_frame_stats_d, (saliency, pooled, edge_max, descriptors, stats),
+         _dp(saliency), _dp(pooled), _dp(edge_max), _dp(descriptors), n, g, k, _dp(stats), _dp(dm), _dp(d2), width)
     return stats, dm, d2
 
 

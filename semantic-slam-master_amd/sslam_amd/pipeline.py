@@ -183,22 +183,31 @@ class PackedRefiner:
 
     @staticmethod
     def supported(input_dim: int, hidden_dim: int, output_dim: int, n_blocks: int) -> bool:
-        """Shapes the fused descriptor-MLP kernel is built for: 384 -> 384 -> 128 with up to 8 residual blocks."""
-        return (input_dim, hidden_dim, output_dim) == (lib.C_FEAT, lib.HID, lib.D_OUT) and 0 <= n_blocks <= 8
+        """Shapes the fused descriptor-MLP kernel is built for: 384 -> 384 -> 128 | 256 with up to 8 residual blocks."""
+        return (input_dim, hidden_dim) == (lib.C_FEAT, lib.HID) and output_dim in lib.WIDTHS and 0 <= n_blocks <= 8
 
     def __init__(self, sd: dict, device, bf16: bool = False):
         ws, self.n_blocks = refiner_weight_list(sd)
-        if ws[0].shape != (lib.HID, lib.C_FEAT) or ws[-2].shape != (lib.D_OUT, lib.HID):
-            raise lib.SslamHipError("refiner shape unsupported by the HIP kernels (384 -> 384 -> 128)")
+        self.output_dim = int(ws[-2].shape[0]) if ws[-2].ndim == 2 else -1
+        if ws[0].shape != (lib.HID, lib.C_FEAT) or self.output_dim not in lib.WIDTHS or ws[-2].shape != (self.output_dim, lib.HID):
+            raise lib.SslamHipError("refiner shape unsupported by the HIP kernels (384 -> 384 -> 128 | 256)")
+        if bf16 and self.output_dim != lib.D_OUT:
+            raise lib.SslamHipError(f"precision='bf16' has no {self.output_dim}-wide refiner: the bf16 descriptor MLP is built for "
+                                    f"output width {lib.D_OUT} only (use precision='fp32')")
         self.packed = torch.from_numpy(lib.pack_refiner(ws, self.n_blocks)).to(device)
         self.packed_bf16 = torch.from_numpy(lib.pack_refiner_bf16(ws, self.n_blocks)).to(device) if bf16 else None
 
     @classmethod
-    def empty(cls, n_blocks: int, device, bf16: bool = False) -> "PackedRefiner":
-        """Uninitialised packed buffers for `n_blocks` residual blocks (receiving side of the weight broadcast)."""
+    def empty(cls, n_blocks: int, device, bf16: bool = False, output_dim: int = lib.D_OUT) -> "PackedRefiner":
+        """Uninitialised packed buffers for `n_blocks` residual blocks and descriptors of width `output_dim` (receiving side of
+        the weight broadcast)."""
         self = cls.__new__(cls)
         self.n_blocks = int(n_blocks)
-        self.packed = torch.empty(int(lib.refiner_layout(n_blocks).total), dtype=torch.float32, device=device)
+        self.output_dim = lib.check_width(output_dim, "refiner output width")
+        if bf16 and self.output_dim != lib.D_OUT:
+            raise lib.SslamHipError(f"precision='bf16' has no {self.output_dim}-wide refiner: the bf16 descriptor MLP is built for "
+                                    f"output width {lib.D_OUT} only (use precision='fp32')")
+        self.packed = torch.empty(int(lib.refiner_layout(n_blocks, self.output_dim).total), dtype=torch.float32, device=device)
         self.packed_bf16 = (torch.empty(int(lib.lib().sslam_refiner_bf16_bytes(n_blocks)), dtype=torch.uint8, device=device)
                             if bf16 else None)
         return self
@@ -234,8 +243,10 @@ class SequencePipeline:
         operands) or "fp32" (the reference's numerics for A1: fp32 operands on the fp32 matrix pipe, csrc/vit_f32.hip)
         vit_form: None, or "few_frame" (bf16 ViT only): batches of up to 8 frames - run() on a short sequence, every step of an
         online.FrameStepper - take the bf16 ViT's few-frame launch form (HipViT.forward_features); larger batches are untouched.
-        selector_state / refiner_state None + empty_shapes=(selector hidden, refiner blocks): uninitialised packed buffers,
-        to be filled by the rank-0 weight broadcast (shard.pipeline_from_rank0)."""
+        selector_state / refiner_state None + empty_shapes=(selector hidden, refiner blocks[, descriptor width = 128]):
+        uninitialised packed buffers, to be filled by the rank-0 weight broadcast (shard.pipeline_from_rank0).
+        descriptor_dim: the refiner's output width (128 or 256), from its state or from empty_shapes; every descriptor buffer,
+        bank and matcher launch of this pipeline follows it.  precision="bf16" with a 256-wide refiner raises SslamHipError."""
         self.cfg = cfg
         self.device = torch.device(device)
         lib.lib()   # fail loudly if the HIP library is not built
@@ -250,9 +261,10 @@ class SequencePipeline:
         self.bf16 = cfg.precision == "bf16"
         if selector_state is None or refiner_state is None:
             if empty_shapes is None:
-                raise ValueError("state dicts or empty_shapes=(hidden, n_blocks) required")
+                raise ValueError("state dicts or empty_shapes=(hidden, n_blocks[, descriptor width]) required")
             self.selector = PackedSelector.empty(empty_shapes[0], self.device, self.bf16)
-            self.refiner = PackedRefiner.empty(empty_shapes[1], self.device, self.bf16)
+            self.refiner = PackedRefiner.empty(empty_shapes[1], self.device, self.bf16,
+                                               output_dim=empty_shapes[2] if len(empty_shapes) > 2 else lib.D_OUT)
         else:
             self.selector = PackedSelector(selector_state, self.device, self.bf16)
             self.refiner = PackedRefiner(refiner_state, self.device, self.bf16)
@@ -284,6 +296,11 @@ class SequencePipeline:
             else:
                 self.vit_hip = HipViT(vit, self.device)
         self.vit_precision, self.vit_form = vit_precision, vit_form
+
+    @property
+    def descriptor_dim(self) -> int:
+        """The refiner's output width (128 or 256): the width of every descriptor buffer, bank and matcher launch here."""
+        return int(getattr(getattr(self, "refiner", None), "output_dim", lib.D_OUT))
 
     def weight_tensors(self) -> list:
         """Every device buffer of packed weights / BatchNorm state, in a fixed order (6.7 MB fp32 at the shipped shapes)."""
@@ -397,7 +414,7 @@ class SequencePipeline:
         f32 = dict(dtype=torch.float32, device=dev)
         out = dict(saliency=torch.empty((n, g, g), **f32), keypoints_patch=torch.empty((n, K, 2), **f32),
                    keypoints_pixel=torch.empty((n, K, 2), **f32), scores=torch.empty((n, K), **f32),
-                   idx=torch.empty((n, K), dtype=torch.int32, device=dev), descriptors=torch.empty((n, K, lib.D_OUT), **f32),
+                   idx=torch.empty((n, K), dtype=torch.int32, device=dev), descriptors=torch.empty((n, K, self.descriptor_dim), **f32),
                    status=torch.empty((n,), dtype=torch.int32, device=dev))
         if with_intensity:
             out["intensity"] = torch.empty((n, K), **f32)
@@ -456,6 +473,12 @@ class SequencePipeline:
                 ("quality" if rule is None else "value"): torch.empty((n_pairs, k), dtype=torch.float32, device=dev),
                 "match_count": torch.empty((n_pairs,), dtype=torch.int32, device=dev)}
 
+    def _desc_width(self, desc) -> int:
+        """The width of a (N, K, width) descriptor tensor handed to the matcher: this pipeline's descriptor_dim."""
+        if desc.dim() != 3 or int(desc.shape[2]) != self.descriptor_dim:
+            raise ValueError(f"desc (N, K, {self.descriptor_dim}) expected, got {tuple(desc.shape)}")
+        return self.descriptor_dim
+
     @staticmethod
     def _rule_result(res: dict, aux: list) -> dict:
         """The arg-max arrays a rule's launches produced (nn12, sim; second and nn21 where the rule reads them), beside its outputs."""
@@ -465,16 +488,16 @@ class SequencePipeline:
 
     def _match_rule(self, rule: MatchRule, desc, sp: int, res: dict) -> dict:
         """match() under a rule: the same cuts, the rule's finalize entry; RULE_TRACKED takes the rows-only similarity launch."""
-        n, k = desc.shape[0], desc.shape[1]
+        n, k, dw = desc.shape[0], desc.shape[1], self._desc_width(desc)
         n_pairs, aux = n - sp, []
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):
             m = min(MAX_PAIRS_PER_LAUNCH, n_pairs - a)
             d1, d2 = desc[a:a + m], desc[a + sp:a + sp + m]
             if rule.kind == lib.RULE_TRACKED:
-                nn12, s12, sec = lib.sim_argmax_rows(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m)
+                nn12, s12, sec = lib.sim_argmax_rows(d1, k * dw, k, d2, k * dw, k, m)
                 nn21 = None
             else:
-                nn12, s12, nn21, _, sec = lib.sim_argmax(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, want_second=True,
+                nn12, s12, nn21, _, sec = lib.sim_argmax(d1, k * dw, k, d2, k * dw, k, m, want_second=True,
                                                          workspace=self.workspace(0, m))
             lib.match_finalize_rule(nn12, s12, sec, nn21, k, k, m, rule.kind, rule.param,
                                     out=(res["matches"][a:a + m], res["value"][a:a + m], res["match_count"][a:a + m]))
@@ -498,14 +521,14 @@ class SequencePipeline:
 
     def match(self, desc, scores, intensity=None, spacing: int | None = None, out: dict | None = None,
               rule: MatchRule | None = None) -> dict:
-        """M1 for all pairs (i, i + spacing) inside the batch.  desc (N, K, 128), scores (N, K), intensity (N, K).
+        """M1 for all pairs (i, i + spacing) inside the batch.  desc (N, K, descriptor_dim), scores (N, K), intensity (N, K).
         out: row slices of alloc_match buffers to write into (the streaming scheduler passes slices of sequence-sized ones).
         rule: a MatchRule - the same pairs under M2 / M4 / M5 instead (scores, intensity and the M1 thresholds are not read).
         Returns matches, match_count and `value` (similarity; distance 1 - similarity under mnn_ratio) - no `quality` key - with
         nn12 and sim, and second and nn21 under the two ratio rules (tracked computes neither); out: alloc_match(rule=) buffers."""
         cfg = self.cfg
         sp = cfg.spacing if spacing is None else spacing
-        n, k = desc.shape[0], desc.shape[1]
+        n, k, dw = desc.shape[0], desc.shape[1], self._desc_width(desc)
         rule = _checked_rule(rule, k)
         n_pairs = n - sp
         if n_pairs <= 0:
@@ -521,7 +544,7 @@ class SequencePipeline:
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # the pair index is a 16-bit grid dimension
             m = min(MAX_PAIRS_PER_LAUNCH, n_pairs - a)
             d1, d2 = desc[a:a + m], desc[a + sp:a + sp + m]
-            nn12, s12, nn21, _, _ = lib.sim_argmax(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, workspace=self.workspace(0, m))
+            nn12, s12, nn21, _, _ = lib.sim_argmax(d1, k * dw, k, d2, k * dw, k, m, workspace=self.workspace(0, m))
             lib.match_finalize(nn12, s12, nn21, k, k, m, scores[a:], k, scores[a + sp:], k,
                                intensity[a:] if use_int else None, intensity[a + sp:] if use_int else None,
                                1.0 - cfg.saliency_weight, cfg.saliency_weight, cfg.min_saliency,
@@ -534,7 +557,7 @@ class SequencePipeline:
 
     def match_pairs(self, desc, scores, intensity=None, first=None, second=None, out: dict | None = None,
                     rule: MatchRule | None = None) -> dict:
-        """M1 for a LIST of pairs of the bank desc (N, K, 128) / scores (N, K) / intensity (N, K): row p matches frame first[p]
+        """M1 for a LIST of pairs of the bank desc (N, K, descriptor_dim) / scores (N, K) / intensity (N, K): row p matches frame first[p]
         against frame second[p] - any two frames, in any order, as often as listed; an index outside [0, N) (-1 by convention)
         makes the pair absent: count 0, zero rows.  first / second: 1-D int32 device tensors (they may be written by earlier work
         of the stream: nothing here reads them on the host), or host sequences of ints, uploaded once.
@@ -544,8 +567,9 @@ class SequencePipeline:
         cfg = self.cfg
         if first is None or second is None:
             raise ValueError("match_pairs needs both pair lists, first= and second=")
-        if desc.dim() != 3 or scores.dim() != 2 or tuple(scores.shape) != tuple(desc.shape[:2]):
-            raise ValueError(f"desc (N, K, {lib.D_OUT}) and scores (N, K) expected, got {tuple(desc.shape)} and {tuple(scores.shape)}")
+        if desc.dim() != 3 or scores.dim() != 2 or tuple(scores.shape) != tuple(desc.shape[:2]) or desc.shape[2] != self.descriptor_dim:
+            raise ValueError(f"desc (N, K, {self.descriptor_dim}) and scores (N, K) expected, got {tuple(desc.shape)} and "
+                             f"{tuple(scores.shape)}")
         rule = _checked_rule(rule, desc.shape[1])
         first, second = _host_pair_list("first", first), _host_pair_list("second", second)
         n_pairs = lib.check_pair_lists(first, second)             # a malformed list is refused before anything is uploaded
@@ -575,20 +599,20 @@ class SequencePipeline:
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
         together the trainer's seven loss terms and five metrics (train.py:292-408 under no_grad), for the N frames `out` holds
-        (what extract() / run() returned: saliency (N, G, G), descriptors (N, K, 128)) and the pairs (i, i + spacing) - or the
+        (what extract() / run() returned: saliency (N, G, G), descriptors (N, K, descriptor_dim)) and the pairs (i, i + spacing) - or the
         listed pairs first / second, as match_pairs takes them (1-D int32 device tensors or host sequences; -1 = absent pair:
         zero rows, which compose refuses).
         images: (N, H, W, 3) uint8 - resampled here by A0 into the fp32 ViT input, a launch group at a time - or that fp32
         image itself, (N, 3, S, S) with S = input_size.
         Only launches on the current stream (a fixed number for given shapes), no host read-back: capturable.
         Returns device tensors: per frame sal_mean, sal_var, sal_max, sal_dx, sal_dy, sal_high, sal_ss, edge_a, edge_e,
-        edge_mean, edge_max (N,), desc_mean, desc_m2 (N, 128), pooled (N, G, G); per pair first, second (int32), repeat,
+        edge_mean, edge_max (N,), desc_mean, desc_m2 (N, descriptor_dim), pooled (N, G, G); per pair first, second (int32), repeat,
         ce_sum, pad_ce (P,), n_matches (P,) int32, lse, ce, sim (P, K), nn12, nn21 (P, K) int32; and the numbers grid,
         num_keypoints, temperature."""
         cfg = self.cfg
         t = lib.check_temperature(temperature)
         sal, desc = out["saliency"], out["descriptors"]
-        n, k, g = int(desc.shape[0]), int(desc.shape[1]), cfg.grid
+        n, k, g, dw = int(desc.shape[0]), int(desc.shape[1]), cfg.grid, self._desc_width(desc)
         if tuple(sal.shape) != (n, g, g):
             raise ValueError(f"saliency {tuple(sal.shape)} does not go with {n} frames of a {g} x {g} grid")
         listed = first is not None or second is not None
@@ -642,8 +666,8 @@ class SequencePipeline:
                 pstats, cnt = lib.val_pair_stats_pairs(sal, f, s, nn12, nn21, s12, ce, s00, t)
             else:
                 d1, d2 = desc[a:a + m], desc[a + sp:a + sp + m]
-                nn12, s12, nn21, _, _ = lib.sim_argmax(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, workspace=self.workspace(0, m))
-                lse, ce, s00 = lib.row_lse(d1, k * lib.D_OUT, k, d2, k * lib.D_OUT, k, m, s12, t)
+                nn12, s12, nn21, _, _ = lib.sim_argmax(d1, k * dw, k, d2, k * dw, k, m, workspace=self.workspace(0, m))
+                lse, ce, s00 = lib.row_lse(d1, k * dw, k, d2, k * dw, k, m, s12, t)
                 pstats, cnt = lib.val_pair_stats(sal[a:a + m], sal[a + sp:a + sp + m], nn12, nn21, s12, ce, s00, t)
             parts.append(dict(pstats=pstats, n_matches=cnt, lse=lse, ce=ce, sim=s12, nn12=nn12, nn21=nn21))
         cat = {key: parts[0][key] if len(parts) == 1 else torch.cat([x[key] for x in parts]) for key in parts[0]}

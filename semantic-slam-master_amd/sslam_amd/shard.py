@@ -92,30 +92,48 @@ def broadcast_weights(tensors: list, src: int = 0, group=None):
         _broadcast(t, src, group)
 
 
+HEADER_WORDS = 4
+
+
+def weights_header(selector_state: dict, refiner_state: dict) -> list:
+    """The int64 words that go ahead of the weight broadcast: selector hidden width, refiner residual blocks, 1 (a header that
+    was never sent stays all zero), descriptor width (the rows of output_proj.weight)."""
+    from .pipeline import refiner_weight_list
+    ws, n_blocks = refiner_weight_list(refiner_state)
+    return [int(tuple(selector_state["conv.0.weight"].shape)[0]), int(n_blocks), 1, int(ws[-2].shape[0])]
+
+
+def header_shapes(head) -> tuple:
+    """A received header -> SequencePipeline's empty_shapes = (selector hidden, refiner blocks, descriptor width)."""
+    if len(head) != HEADER_WORDS:
+        raise RuntimeError(f"weight broadcast header of {len(head)} words, {HEADER_WORDS} expected")
+    hidden, n_blocks, ok, width = (int(v) for v in head)
+    if not ok:
+        raise RuntimeError("weight broadcast header missing")
+    return hidden, n_blocks, width
+
+
 def pipeline_from_rank0(cfg, selector_state: dict | None, refiner_state: dict | None, device, bn_state: dict | None = None,
                         src: int = 0, group=None):
     """rank `src` alone reads the checkpoint and packs the weights into kernel order; the other ranks
     (selector_state = refiner_state = None) allocate the packed buffers uninitialised and receive them by broadcast
-    (RCCL over xGMI on the GPUs; gloo in the CPU tests).  A three-number header (selector hidden width, residual blocks,
-    BatchNorm-state flag) travels first so that the receivers can size their buffers.  Returns this rank's SequencePipeline."""
-    from .pipeline import SequencePipeline, refiner_weight_list
+    (RCCL over xGMI on the GPUs; gloo in the CPU tests).  A four-number header (weights_header: selector hidden width, residual
+    blocks, header flag, descriptor width) travels first so that the receivers can size their buffers.  Returns this rank's
+    SequencePipeline."""
+    from .pipeline import SequencePipeline
     rank = dist.get_rank(group)
     dev = torch.device(device)
-    head = torch.zeros(3, dtype=torch.int64, device=dev)
+    head = torch.zeros(HEADER_WORDS, dtype=torch.int64, device=dev)
     if rank == src:
         if selector_state is None or refiner_state is None:
             raise ValueError(f"rank {src} must hold the state dicts")
-        head[0] = int(tuple(selector_state["conv.0.weight"].shape)[0])
-        head[1] = refiner_weight_list(refiner_state)[1]
-        head[2] = 1
+        head.copy_(torch.tensor(weights_header(selector_state, refiner_state), dtype=torch.int64))
     _broadcast(head, src, group)
-    hidden, n_blocks, ok = (int(v) for v in head.tolist())
-    if not ok:
-        raise RuntimeError("weight broadcast header missing")
+    shapes = header_shapes(head.tolist())
     if rank == src:
         pipe = SequencePipeline(cfg, selector_state, refiner_state, bn_state, device=dev)
     else:
-        pipe = SequencePipeline(cfg, None, None, None, device=dev, empty_shapes=(hidden, n_blocks))
+        pipe = SequencePipeline(cfg, None, None, None, device=dev, empty_shapes=shapes)
     broadcast_weights(pipe.weight_tensors(), src=src, group=group)
     return pipe
 

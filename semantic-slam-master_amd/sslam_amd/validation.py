@@ -19,7 +19,7 @@ function in float64 - puts them together for any batch size:
     desc        mean_b (ce_sum_b + (Mmax - n_b) pad_ce_b) / Mmax,  Mmax = max_b n_b: the trainer zero-pads the match lists
                 to the longest of the batch (train.py:437-447) and the loss counts the (0, 0) rows as matches
   metrics       num_matches = Mmax, mean_saliency, max_saliency, saliency_variance (np.var over the batch),
-                descriptor_variance (np.var over all B K 128 elements)
+                descriptor_variance (np.var over all B K D elements, D = the descriptor width of the statistics: 128 or 256)
 
 The reference's branch for a batch without any match (train.py:439-440, self_supervised.py:71) is not built: the global
 maximum of a similarity matrix of finite descriptors is always a mutual nearest neighbour, so every pair has n >= 1.
