@@ -548,6 +548,28 @@ int sslam_row_lse_pairs_d(const float *bank, long long frame_stride, int n_bank,
 int sslam_val_frame_stats_d(const float *saliency, const float *pooled, const float *edge_max, const float *descriptors,
                             int n_frames, int G, int K, float *stats, float *desc_mean, float *desc_m2, int d, void *stream);
 
+/* ---- Rank a match list by its value and keep the best `best` rows of every pair: what the reference's callers do with a
+ * matcher's list (visualize_matches_sequence.py:224-225: np.argsort(-match_quality)[:max_matches], max_matches 50 from the command
+ * line, 100 by default; visualize_matches.py:150-151: sorted(matches, key=similarity, reverse=True)[:max_matches]).
+ * matches (n_pairs, n1, 2), value (n_pairs, n1), count (n_pairs): the outputs of sslam_match_finalize[_pairs] (value = quality) or
+ * sslam_match_finalize_rule[_pairs]; only the first count[p] rows of a pair are read, count[p] clamped to [0, n1] (the arrays need
+ * not come from those entries; an absent pair carries count 0).
+ * THE ORDER: better value first, equal values in ascending input slot (for a finalize entry's list: ascending idx1).  Better is
+ * LARGER with ascending = 0 and SMALLER with ascending = 1 (SSLAM_RULE_RATIO_SECOND's value is a cosine distance).  -0.0f and
+ * +0.0f are equal; NaN rows come last in either direction, in slot order (numpy's order).  This is the reference's stable M2
+ * order, and one of the orders its M1 argsort may return - the only one wherever the values are pairwise distinct.
+ * With kept = min(count[p], best): out_matches (n_pairs, best, 2), out_value (n_pairs, best) and out_slot (n_pairs, best; may be
+ * NULL) hold in rows 0 .. kept - 1 the kept rows, their values (the input's bits) and the input slot each came from, so that a
+ * caller can gather other per-match arrays; rows kept .. best - 1 are zero; out_count[p] = kept.  The outputs are a function of the
+ * inputs alone.  One launch (one 256-thread workgroup per pair, the pair on the grid's x dimension: any n_pairs), no atomics, no
+ * scratch, no allocation, no host read: capturable.
+ * SSLAM_E_INVALID: a NULL pointer other than out_slot; n1, n_pairs or best <= 0; best > n1; ascending not 0 or 1; an output that
+ * starts where an input starts.  SSLAM_E_UNSUPPORTED: n1 > SSLAM_RANK_MAX_N1 (the keys of a pair live in 32 KB of LDS).  Every
+ * refusal comes before anything is launched.  The entry reads no descriptors: it takes no width and has no _pairs form. */
+#define SSLAM_RANK_MAX_N1 4096
+int sslam_match_rank(const int64_t *matches, const float *value, const int32_t *count, int n1, int n_pairs, int best, int ascending,
+                     int64_t *out_matches, float *out_value, int32_t *out_count, int32_t *out_slot, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,9 @@ return types, running on the HIP kernels sslam_sim_argmax / sslam_match_finalize
                                                                              test/test_descriptor_quality.py:97-142
     M5  count_tracked                  track_frame_sequence                  test/test_tracking.py:158-161
 
+and of the step their callers take next, best_matches (visualize_matches.py:150-151, visualize_matches_sequence.py:224-225: the
+max_matches best rows of a list), on sslam_match_rank.
+
 numpy in -> numpy out like the originals (they pull descriptors to the host first); torch CUDA tensors are accepted
 too and then nothing leaves the device except the result.  There is no CPU implementation here: without the GPU
 library these functions raise.
@@ -106,3 +109,24 @@ def count_tracked(desc_prev, desc_curr, match_threshold: float = 0.8) -> int:
     """M5.  Number of rows of desc_prev whose best similarity in desc_curr exceeds the threshold."""
     _, _, _, s12, _, _, _ = _argmax(desc_prev, desc_curr)
     return int((s12[0] > match_threshold).sum().item())
+
+
+def best_matches(matches, values, max_matches: int = 100, ascending: bool = False):
+    """The callers' step after a matcher (visualize_matches.py:131 max_matches=100, :150-151; visualize_matches_sequence.py:224-225):
+    the max_matches best rows of ONE pair's list, better value first - larger, or smaller with ascending=True (M4's distances) -
+    and equal values in the list's own order: the reference's stable sort, on the device (sslam_match_rank).
+    matches (n, 2) integers, values (n,): numpy arrays or tensors.  Returns (matches (min(n, max_matches), 2) int64, values fp32),
+    numpy for numpy input, device tensors for tensors."""
+    as_numpy = not isinstance(matches, torch.Tensor)
+    if isinstance(max_matches, bool) or not isinstance(max_matches, (int, np.integer)) or max_matches < 1:
+        raise ValueError(f"max_matches must be a positive int, got {max_matches!r}")
+    mt, v = _dev(matches, torch.int64), _dev(values)
+    if mt.dim() != 2 or mt.shape[1] != 2 or v.dim() != 1 or v.shape[0] != mt.shape[0]:
+        raise ValueError(f"matches (n, 2) and values (n,) expected, got {tuple(mt.shape)} and {tuple(v.shape)}")
+    n = int(mt.shape[0])
+    if n == 0:
+        return (mt.cpu().numpy(), v.cpu().numpy()) if as_numpy else (mt, v)
+    keep = min(n, int(max_matches))
+    count = torch.full((1,), n, dtype=torch.int32, device=mt.device)
+    om, ov, _, _ = lib.match_rank(mt[None], v[None], count, keep, ascending=bool(ascending), want_slot=False)
+    return (om[0].cpu().numpy(), ov[0].cpu().numpy()) if as_numpy else (om[0], ov[0])

@@ -165,6 +165,13 @@ class StreamingSequence:
         return idx if max_pairs is None else idx[:max_pairs]
 
 
+def rank_result(pipe: SequencePipeline, result: dict, best, rule=None) -> dict:
+    """The `best` best matches of every pair of a StreamingSequence.result() / run() / run_frames / run_directory result:
+    {spacing: SequencePipeline.rank_matches of that spacing's match dict} - one rank launch per spacing over all its pairs,
+    nothing read on the host.  rule: the rule the result was matched under (None: M1)."""
+    return {s: pipe.rank_matches(mm, best, rule=rule) for s, mm in result.items() if s != "frames" and isinstance(mm, dict)}
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Host -> device feed.  The reference loads and uploads one frame at a time, synchronously
 # (visualize_matches_sequence.py:71-72).  Here chunk i + 1 is produced on the host (PNG decode on a thread pool, or a slice

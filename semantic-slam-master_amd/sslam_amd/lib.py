@@ -86,6 +86,7 @@ EXPORTS = [
     "sslam_refiner_layout_d", "sslam_refiner_pack_host_d", "sslam_refine_d", "sslam_gather_refine_d", "sslam_gather_refine_ws_d",
     "sslam_sim_argmax_d", "sslam_sim_argmax_ws_d", "sslam_sim_argmax_pairs_d", "sslam_sim_argmax_rows_d",
     "sslam_sim_argmax_rows_pairs_d", "sslam_row_lse_d", "sslam_row_lse_pairs_d", "sslam_val_frame_stats_d",
+    "sslam_match_rank",
 ]
 
 
@@ -127,6 +128,7 @@ def lib():
         L.sslam_match_finalize_pairs.argtypes = [p, p, p, i, i, p, p, i, p, ll, p, f, f, f, f, f, p, p, p, p]
         L.sslam_match_finalize_rule.argtypes = [p, p, p, p, i, i, i, i, f, p, p, p, p]
         L.sslam_match_finalize_rule_pairs.argtypes = [p, p, p, p, i, i, p, p, i, i, f, p, p, p, p]
+        L.sslam_match_rank.argtypes = [p, p, p, i, i, i, i, p, p, p, p, p]
         L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
         L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
         L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
@@ -755,6 +757,58 @@ def match_finalize_rule_pairs(nn12, s12, second12, nn21, first, second, n_bank, 
          _dp(nn12), _dp(s12), _dp(second12), _dp(nn21), k, int(n_bank), _dp(first), _dp(second), n_pairs, int(rule), C.c_float(param),
          _dp(matches), _dp(value), _dp(count))
     return matches, value, count
+
+
+RANK_MAX_N1 = 4096      # SSLAM_RANK_MAX_N1: the longest list sslam_match_rank ranks (a pair's keys live in LDS)
+
+
+def check_best(best, n1: int) -> int:
+    """`best` of a rank call as an int in [1, n1] (None: all n1 rows), else ValueError - before any device work."""
+    if best is None:
+        return int(n1)
+    if isinstance(best, bool) or not isinstance(best, (int, np.integer)) or not 1 <= int(best) <= int(n1):
+        raise ValueError(f"best must be None or an int in [1, {int(n1)}], got {best!r}")
+    return int(best)
+
+
+def match_rank(matches, value, count, best=None, ascending=False, out=None, want_slot=True):
+    """sslam_match_rank: the `best` best rows of every pair's match list, better value first (larger; smaller with ascending=True:
+    a cosine distance), equal values in ascending input slot, NaN rows last (include/sslam_hip.h states the order).
+    matches (P, n1, 2) int64, value (P, n1) fp32, count (P,) int32: what a finalize entry wrote.  best=None ranks all n1 rows.
+    Returns (matches (P, best, 2), value (P, best), count (P,) = min(count, best), slot (P, best) int32 or None): rows past the
+    count are zero; slot names the input row each kept row came from.  out: optional tensors of those shapes to write into (slot
+    None, or want_slot=False, for no slot array).  One launch, no host read."""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or matches.shape[0] < 1 or matches.shape[1] < 1:
+        raise ValueError("matches must be a tensor of shape (n_pairs >= 1, n1 >= 1, 2)")
+    n_pairs, n1 = int(matches.shape[0]), int(matches.shape[1])
+    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+    for name, t in (("value", value), ("count", count)):
+        if t is None:
+            raise ValueError(f"{name} is required")
+    _check_arrays((n_pairs, n1), ("value", value, torch.float32))
+    _check_arrays((n_pairs,), ("count", count, torch.int32))
+    best = check_best(best, n1)
+    if not isinstance(ascending, (bool, np.bool_)):
+        raise ValueError(f"ascending must be a bool, got {ascending!r}")
+    if n1 > RANK_MAX_N1:
+        raise SslamHipError(f"match_rank: lists of {n1} rows; at most {RANK_MAX_N1} are ranked on the device")
+    dev = matches.device
+    if out is not None:
+        o_m, o_v, o_c, o_s = out
+        for name, t in (("matches", o_m), ("value", o_v), ("count", o_c)):
+            if t is None:
+                raise ValueError(f"out `{name}` is required")
+        _check_arrays((n_pairs, best, 2), ("out `matches`", o_m, torch.int64))
+        _check_arrays((n_pairs, best), ("out `value`", o_v, torch.float32), ("out `slot`", o_s, torch.int32))
+        _check_arrays((n_pairs,), ("out `count`", o_c, torch.int32))
+    else:
+        o_m = torch.empty((n_pairs, best, 2), dtype=torch.int64, device=dev)
+        o_v = torch.empty((n_pairs, best), dtype=torch.float32, device=dev)
+        o_c = torch.empty((n_pairs,), dtype=torch.int32, device=dev)
+        o_s = torch.empty((n_pairs, best), dtype=torch.int32, device=dev) if want_slot else None
+    _run("match_rank", lib().sslam_match_rank, (matches, value, count, o_m, o_v, o_c, o_s),
+         _dp(matches), _dp(value), _dp(count), n1, n_pairs, best, int(ascending), _dp(o_m), _dp(o_v), _dp(o_c), _dp(o_s))
+    return o_m, o_v, o_c, o_s
 
 
 # ------------------------------------------------------------------------------------------------ validation stage

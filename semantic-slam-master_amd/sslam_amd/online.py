@@ -103,6 +103,9 @@ class FrameStepper:
         still serves the stepper without one)."""
         return {} if self.rule is None else {"rule": self.rule}
 
+    def _after_match(self) -> None:
+        """What a subclass enqueues behind the matcher's finalize launch, on the same stream (RankedFrameStepper: the rank launch)."""
+
     def _init_bank(self, spacings: tuple) -> None:
         pipe, dev = self.pipe, self.device
         ring = self.ring = max(spacings)
@@ -134,6 +137,7 @@ class FrameStepper:
         p.extract(self.tokens, self.image, out=self.cur)
         self._aux = p.match(self.pair["descriptors"], self.pair["scores"], self.pair["intensity"], spacing=1, out=self.m,
                             **self._rule_kw())
+        self._after_match()
         for k in ("descriptors", "scores", "intensity", "keypoints_pixel"):      # this frame becomes the previous one
             self.pair[k][0].copy_(self.pair[k][1])
 
@@ -150,6 +154,7 @@ class FrameStepper:
         self.first_slot.copy_(self._first64)
         self._aux = p.match_pairs(self.bank["descriptors"], self.bank["scores"], self.bank["intensity"], first=self.first_slot,
                                   second=self.second_slot, out=self.m, **self._rule_kw())
+        self._after_match()
         # this frame takes the ring slot of frame t - ring, which no spacing reaches any more
         torch.remainder(self._t, ring, out=self._slot)
         for k in BANK_KEYS:
@@ -255,3 +260,34 @@ class RuleFrameStepper(FrameStepper):
                  spacings=None, rule=None):
         self.rule = _checked_rule(rule, pipe.cfg.num_keypoints)      # before anything is allocated
         super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=spacings)
+
+
+class RankedFrameStepper(RuleFrameStepper):
+    """RuleFrameStepper whose step also ranks: behind the finalize launch, on the same one stream, sslam_match_rank keeps the
+    `best` best matches of every pair of the step (visualize_matches_sequence.py:224-225; best=50 is that script's --max_matches
+    default) - in the one-spacing body and the spacings= body, as ordinary launches and inside the captured graph, where the
+    count stays a device value that nothing reads on the host.  step() returns what the parent returns, untouched, plus "best":
+    matches (best, 2) / quality | value (best,) / match_count / slot (best,) - with spacings (S, best, 2) / (S, best) / (S,) /
+    (S, best) - as views of static buffers (None before the second frame of the one-spacing stepper); rows past the count are
+    zero, slot is the row of the step's own match arrays each kept row came from.  rule=None ranks M1's quality; under
+    MatchRule.mnn_ratio the smaller distance is the better one (SequencePipeline.rank_matches)."""
+
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, use_graph: bool = True, tokens_in: bool = False,
+                 spacings=None, rule=None, best: int = 50):
+        self.best = lib.check_best(best, pipe.cfg.num_keypoints)      # before anything is allocated
+        super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=spacings, rule=rule)
+        self.ranked = pipe.alloc_ranked(1 if self.spacings is None else len(self.spacings), self.best, self.cfg.num_keypoints,
+                                        rule=self.rule)
+
+    def _after_match(self) -> None:
+        self.pipe.rank_matches(self.m, self.best, rule=self.rule, out=self.ranked)
+
+    @torch.no_grad()
+    def step(self, image_u8: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
+        first = self.n_frames == 0
+        out = super().step(image_u8, tokens)
+        if self.spacings is not None:
+            out["best"] = dict(self.ranked)
+        else:
+            out["best"] = None if first else {k: v[0] for k, v in self.ranked.items()}
+        return out

@@ -595,6 +595,49 @@ class SequencePipeline:
             res[key] = aux[0][i] if len(aux) == 1 else torch.cat([x[i] for x in aux])
         return res
 
+    def alloc_ranked(self, n_pairs: int, best: int, k: int | None = None, rule: MatchRule | None = None) -> dict:
+        """Output buffers of rank_matches() for n_pairs pairs: the `best` best rows of lists of capacity k (num_keypoints by
+        default).  rule: as in alloc_match - `value` in place of `quality`."""
+        k = self.cfg.num_keypoints if k is None else k
+        best = lib.check_best(best, k)
+        _checked_rule(rule, k)
+        dev = self.device
+        return {"matches": torch.empty((n_pairs, best, 2), dtype=torch.int64, device=dev),
+                ("quality" if rule is None else "value"): torch.empty((n_pairs, best), dtype=torch.float32, device=dev),
+                "match_count": torch.empty((n_pairs,), dtype=torch.int32, device=dev),
+                "slot": torch.empty((n_pairs, best), dtype=torch.int32, device=dev)}
+
+    def rank_matches(self, m: dict, best: int | None = None, rule: MatchRule | None = None, out: dict | None = None) -> dict:
+        """The stage after the matcher, as the reference's callers have it (visualize_matches_sequence.py:224-225,
+        visualize_matches.py:150-151): every pair's `best` best matches, better first, equal values in the list's own order
+        (ascending idx1) - one launch, nothing read on the host.  m: what match() / match_pairs() returned (or alloc_match buffers
+        they wrote): matches, match_count and `quality` (M1) or `value` (a rule).  rule: the rule m was matched under - better is
+        SMALLER exactly under MatchRule.mnn_ratio, whose value is a distance; None for M1.  best=None ranks whole lists.
+        Returns matches (P, best, 2), quality | value (P, best), match_count (P,) = min(count, best) and slot (P, best) int32, the
+        row of m each kept row came from; rows past the count are zero.  out: alloc_ranked buffers (or row slices of them).
+        m itself is left as it is."""
+        val = "quality" if rule is None else "value"
+        if not isinstance(m, dict) or any(key not in m for key in ("matches", "match_count")):
+            raise ValueError("rank_matches takes the dictionary match() / match_pairs() returned")
+        matches = m["matches"]
+        if not isinstance(matches, torch.Tensor) or matches.dim() != 3:
+            raise ValueError("matches (P, K, 2) expected")
+        k = int(matches.shape[1])
+        best = lib.check_best(best, k)                              # a bad best, a bad rule: before any device work
+        rule = _checked_rule(rule, k)
+        if val not in m:
+            raise ValueError(f"this match dictionary holds no `{val}`: " +
+                             ("pass the rule it was matched under" if rule is None else "it was not matched under a rule"))
+        n_pairs = int(matches.shape[0])
+        res = dict(out) if out is not None else self.alloc_ranked(n_pairs, best, k, rule)
+        if val not in res or any(key not in res for key in ("matches", "match_count")):
+            raise ValueError(f"out must hold matches, {val} and match_count (alloc_ranked with the same rule)")
+        if n_pairs == 0:
+            return res
+        lib.match_rank(matches, m[val], m["match_count"], best, ascending=rule is not None and rule.kind == lib.RULE_RATIO_SECOND,
+                       out=(res["matches"], res[val], res["match_count"], res.get("slot")))
+        return res
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
