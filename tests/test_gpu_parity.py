@@ -252,7 +252,8 @@ def test_preprocess_and_intensity(T, hip, h, w, size):
         view = raw[off:off + imgs.size].view(imgs.shape)
         view.copy_(dev(T, imgs))
         assert view.data_ptr() % 4 == off
-        assert_bits(hip.preprocess_u8(view, size, th, tv).cpu().numpy(), out, "preprocess, unaligned base")
+        into = T.full(out.shape, 0x7FC0DEAD, dtype=T.int32, device="cuda").view(T.float32)      # not a freed block that holds `out`
+        assert_bits(hip.preprocess_u8(view, size, th, tv, out=into).cpu().numpy(), out, "preprocess, unaligned base")
     th = tuple(dev(T, a) if isinstance(a, np.ndarray) else a for a in hip.resample_table(w, size, True))
     tv = tuple(dev(T, a) if isinstance(a, np.ndarray) else a for a in hip.resample_table(h, size, True))
     rng = np.random.Generator(np.random.PCG64(size))
