@@ -150,7 +150,10 @@ int sslam_selector_bf16_halo_groups(int n_frames, int G, int hs);
  * idx (n_frames, K) int32 flat cell index (may be NULL); kp_pixel (n_frames, K, 2) = kp*16+8 (may be NULL);
  * status (n_frames) int32: 0 ok, 1 = the reference's torch.topk would raise (K exceeds the cells).
  * No host synchronisation: the whole data-dependent control flow runs on the device, one workgroup per frame.
- * G*G <= 4096, K <= 4096, 0 <= nms_radius <= 8. */
+ * G*G <= 4096, K <= 4096, 0 <= nms_radius <= 8.
+ * Tested over that whole range (tests/test_gpu_select_range.py): every radius 0..8 - windows wider than the grid included - on
+ * grids from 1 x 1 to 64 x 64, every arm of the control flow at each radius 5..8, K beyond the cells, idx / kp_pixel NULL, and the
+ * reference's own output at radius 4..8 (tests/golden/select_range.npz). */
 int sslam_select_keypoints(const float *sal, int n_frames, int G, int K, int nms_radius, double min_score_percentile,
                            float *kp_xy, float *scores, int32_t *idx, float *kp_pixel, int32_t *status,
                            void *stream);
@@ -227,7 +230,10 @@ int sslam_keypoint_intensity(const uint8_t *img, int n, int h, int w, int size, 
  * without a workspace evaluate it once per direction and need no scratch.  Same bits either way.
  * Precondition: finite descriptors (the refiner's L2-normalised rows are).  With NaN / Inf in the inputs the VALUES and the
  * choice among candidates are unspecified (torch.argmax would return the first NaN), but every index written stays inside
- * [0, n2) resp. [0, n1), so sslam_match_finalize and the sibling matchers never index out of range. */
+ * [0, n2) resp. [0, n1), so sslam_match_finalize and the sibling matchers never index out of range.
+ * Tested bit for bit where no similarity is positive (tests/test_gpu_sim_signs.py): all-negative and mixed-sign sets, the winner in
+ * the last stage of candidates, rows and columns of exact zeros, in both forms and at both widths; the same file sets every
+ * threshold of sslam_match_finalize and sslam_match_finalize_rule to the value compared and one ulp either side of it. */
 int sslam_sim_argmax(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,
                      int n_pairs, int32_t *nn12, float *s12, int32_t *nn21, float *s21, float *second12, void *stream);
 int sslam_sim_argmax_ws(const float *desc1, long long stride1, int n1, const float *desc2, long long stride2, int n2,

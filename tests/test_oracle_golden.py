@@ -411,6 +411,27 @@ def test_select_wide_vs_reference():
     assert raised < int(g["count"]) // 2
 
 
+def test_select_range_vs_reference():
+    """70 tie-free maps at nms_radius 4..8 on grids of 1, 2, 3, 5, 9, 17 and 28 cells a side (windows wider than the grid, one cell,
+    K = n): the oracle's indices and score bits equal what the reference's KeypointSelector.select_keypoints returned
+    (tests/golden/make_golden_select_range.py).  The stored maps are those of select_range_cases.golden_case."""
+    import select_range_cases as sc
+    g = gold("select_range")
+    assert int(g["count"]) == sc.GOLDEN_COUNT
+    seen = set()
+    for s in range(sc.GOLDEN_COUNT):
+        m, (G, K, radius), pct = g[f"s{s}_map"], (int(v) for v in g["g_k_radius"][s]), float(g["pct"][s])
+        want_m, want_K, want_r, want_p = sc.golden_case(s)
+        assert np.array_equal(m.view(np.uint32), want_m.view(np.uint32)) and (K, radius, pct) == (want_K, want_r, want_p), s
+        assert m.shape == (G, G) and K <= G * G
+        kp, scores, idx, st = ora.select_keypoints(m, K, radius, pct)
+        assert st[0] == 0, s
+        assert np.array_equal(idx[0], g[f"s{s}_idx"].astype(np.int32)), (s, G, K, radius, pct)
+        assert np.array_equal(scores[0].view(np.uint32), g[f"s{s}_scores"].view(np.uint32)), (s, G, K, radius, pct)
+        seen.add((G, radius))
+    assert seen == {(G, r) for G in sc.GOLDEN_GRIDS for r in sc.GOLDEN_RADII}
+
+
 def test_match_wide_vs_reference():
     """32 random descriptor pairs (ragged sizes, duplicated rows = exact ties, random thresholds, with and without the
     intensity test): match pairs equal the reference's SequenceMatcher.match_with_quality, quality within 1e-6."""
