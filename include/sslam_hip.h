@@ -576,6 +576,49 @@ int sslam_val_frame_stats_d(const float *saliency, const float *pooled, const fl
 int sslam_match_rank(const int64_t *matches, const float *value, const int32_t *count, int n1, int n_pairs, int best, int ascending,
                      int64_t *out_matches, float *out_value, int32_t *out_count, int32_t *out_slot, void *stream);
 
+/* ---- Score a sequence against its poses: the reference's two headline quality scores, per listed frame pair.
+ * sslam_pose_nn_pairs: RepeatabilityTester.compute_repeatability (test/test_repeatability.py:79-128) and
+ * DescriptorQualityTester.compute_ground_truth_matches (test/test_descriptor_quality.py:144-185).
+ *   kp_bank (n_bank, K, 2) fp32 pixel (x, y), what sslam_select_keypoints writes as keypoints_pixel; 8-byte aligned.  Of a pair
+ *   (a, b) = (pair_first[p], pair_second[p]) - int32 DEVICE lists as in sslam_sim_argmax_pairs, an index outside [0, n_bank),
+ *   -1 by convention, an ABSENT pair - the first n1 rows of frame a are the queries and the first n2 rows of frame b the
+ *   candidates (n1, n2 <= K; a sequence passes n1 = n2 = K, a caller with two sets of unequal size a two-frame bank with K the
+ *   larger).  H: (n_pairs, 9) float64 row-major homographies frame a -> frame b, or NULL for the raw coordinates.
+ *   Per row i, all in float64, every product and sum rounded once (no contraction):
+ *     X = (h00*x + h01*y) + h02, Y and W likewise from rows 1 and 2; the warped point is (X / W, Y / W);
+ *     the distance to candidate j is sqrt(dx*dx + dy*dy); the nearest candidate is the LOWEST index among equal distances
+ *     (numpy's argmin; duplicate keypoints of frame b tie exactly).
+ *   Outputs, capacity n1 per pair as sslam_match_finalize has it:
+ *     gt_matches (n_pairs, n1, 2) int64  rows (i, argmin) with distance < threshold, ascending in i; zero rows past the count;
+ *     gt_count   (n_pairs) int32         their number = the reference's `repeatable` count;
+ *     gt_of_row  (n_pairs, n1) int32     the argmin of row i, or -1 where the row is not within the threshold;
+ *     dist_sum   (n_pairs) float64       the sum of the n1 nearest distances (the thread's rows ascending, lanes by xor 32 .. 1,
+ *                                        waves in order: one order per n1), the reference's mean times n1;
+ *     dist_median (n_pairs) float64      np.median of them: the mean of the two middle values of the sorted distances.
+ *   An absent pair: zero rows, count 0, sum and median 0, gt_of_row -1 in every row (no row has a ground-truth partner).
+ *   A row whose W is exactly 0 has an infinite distance: it is not within any threshold, and the pair's dist_sum is infinite, as
+ *   numpy's.  Non-finite entries of H, NaN keypoints and 0 / 0 (W and X or Y both zero) are outside the contract, as NaN
+ *   descriptors are for the matchers: the outputs stay inside their arrays and are otherwise unspecified.
+ *   One launch, one workgroup per pair (frame b's points, then the sorted distances, in LDS); no atomics, no scratch, no
+ *   allocation, no host read: capturable.
+ * sslam_match_score_pairs: evaluate_matches (test/test_descriptor_quality.py:187-231) on a match list (matches (n_pairs, n1, 2),
+ *   value (n_pairs, n1), count (n_pairs)) as sslam_match_finalize_rule[_pairs] writes it, against gt_of_row / gt_count of the
+ *   entry above over the same pairs (count clamped to [0, n1]; an idx1 outside [0, n1) is a false positive):
+ *     tp = rows with gt_of_row[idx1] == idx2, fp = count - tp, fn = gt_count - tp (n_pairs int32 each);
+ *     value_sum (n_pairs) float64 = the sum of the first count values (M4: cosine distances), in one fixed order.
+ *   PRECONDITION: idx1 is unique within the match list, as it is in gt_matches (both hold one row per query at most); then
+ *   tp / fp / fn are the sizes of the reference's set intersection and differences.  One launch, capturable.
+ * SSLAM_E_INVALID: a NULL pointer other than H; a non-positive size; n1 or n2 above K; a threshold that is negative, NaN or
+ * infinite; a misaligned kp_bank, H or pair list.  SSLAM_E_UNSUPPORTED: K (n1 for the score entry) above SSLAM_EVAL_MAX_K.
+ * Every refusal comes before anything is launched. */
+#define SSLAM_EVAL_MAX_K 4096
+int sslam_pose_nn_pairs(const float *kp_bank, int n_bank, int K, int n1, int n2, const int32_t *pair_first,
+                        const int32_t *pair_second, int n_pairs, const double *H, double threshold, int64_t *gt_matches,
+                        int32_t *gt_count, int32_t *gt_of_row, double *dist_sum, double *dist_median, void *stream);
+int sslam_match_score_pairs(const int64_t *matches, const float *value, const int32_t *count, const int32_t *gt_of_row,
+                            const int32_t *gt_count, int n1, int n_pairs, int32_t *tp, int32_t *fp, int32_t *fn,
+                            double *value_sum, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

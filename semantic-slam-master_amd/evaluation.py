@@ -1,0 +1,90 @@
+"""Home of the reference's three pose-based scoring functions, with their original signatures, return types and dictionary
+keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (csrc/evaluate.hip):
+
+    compute_repeatability          RepeatabilityTester.compute_repeatability              test/test_repeatability.py:79-128
+    compute_ground_truth_matches   DescriptorQualityTester.compute_ground_truth_matches   test/test_descriptor_quality.py:144-185
+    evaluate_matches               DescriptorQualityTester.evaluate_matches               test/test_descriptor_quality.py:187-231
+
+numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
+result.  There is no CPU implementation here: without the GPU library these functions raise.
+
+The two keypoint sets may differ in size: they go to the device as a two-frame bank (2, max(N, M), 2), zero rows behind the
+shorter set, and the entry is told how many rows of each frame count (its n1 / n2 arguments), so the padding is never read.
+Keypoints are taken as float32 - what every extractor here and in the reference returns - and all arithmetic is float64,
+also with H=None, where the original stays in float32 (its distances differ from these by float32 rounding, ~1e-7 relative).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from sslam_amd import lib
+from sslam_amd.evaluation import match_metrics
+
+
+def _dev(a, dtype):
+    if isinstance(a, torch.Tensor):
+        return a.detach().to("cuda", dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype).contiguous()
+
+
+def _pose_nn(kpts1, kpts2, H, threshold):
+    k1, k2 = _dev(kpts1, torch.float32), _dev(kpts2, torch.float32)
+    if k1.dim() != 2 or k2.dim() != 2 or k1.shape[1] != 2 or k2.shape[1] != 2 or k1.shape[0] < 1 or k2.shape[0] < 1:
+        raise ValueError(f"keypoints (N >= 1, 2) and (M >= 1, 2) expected, got {tuple(k1.shape)} and {tuple(k2.shape)}")
+    n, m = int(k1.shape[0]), int(k2.shape[0])
+    bank = torch.zeros((2, max(n, m), 2), dtype=torch.float32, device=k1.device)
+    bank[0, :n], bank[1, :m] = k1, k2
+    if H is not None:
+        H = _dev(H, torch.float64)
+        if tuple(H.shape) != (3, 3):
+            raise ValueError(f"H (3, 3) expected, got {tuple(H.shape)}")
+        H = H.reshape(1, 9)
+    first = torch.zeros((1,), dtype=torch.int32, device=k1.device)
+    return n, lib.pose_nn_pairs(bank, first, first + 1, H, threshold, n1=n, n2=m)
+
+
+def compute_repeatability(kpts1, kpts2, H=None, threshold: float = 3.0) -> dict:
+    """Repeatability of kpts1 (N, 2) in kpts2 (M, 2) under the homography H (3, 3) frame 1 -> frame 2, or the raw coordinates.
+    Returns the original's dictionary: repeatability, repeatable_count, total_keypoints, mean_nn_distance, median_nn_distance."""
+    n, (_, cnt, _, dsum, dmed) = _pose_nn(kpts1, kpts2, H, threshold)
+    c, s, med = torch.stack([cnt.to(torch.float64), dsum, dmed]).reshape(3).tolist()      # one read-back
+    repeatable = np.int64(c)
+    return {"repeatability": repeatable / n, "repeatable_count": repeatable, "total_keypoints": n,
+            "mean_nn_distance": np.float64(s) / n, "median_nn_distance": np.float64(med)}
+
+
+def compute_ground_truth_matches(kpts1, kpts2, H, threshold: float = 3.0):
+    """Ground-truth matches (K, 2) int64 [idx1, idx2]: the rows of kpts1 whose warp lands within `threshold` pixels of a point of
+    kpts2, with the nearest such point (the lowest index among equally near ones).  numpy for numpy input, a device tensor else."""
+    if H is None:
+        raise ValueError("compute_ground_truth_matches needs the homography H")
+    _, (gt, cnt, _, _, _) = _pose_nn(kpts1, kpts2, H, threshold)
+    out = gt[0, :int(cnt.item())]
+    return out if isinstance(kpts1, torch.Tensor) else out.cpu().numpy()
+
+
+def evaluate_matches(pred_matches, gt_matches, num_kpts1: int, num_kpts2: int) -> dict:
+    """Predicted matches (P, 2) against ground-truth matches (G, 2).  Returns the original's dictionary: tp, fp, fn, precision,
+    recall, f1, inlier_ratio, num_pred_matches, num_gt_matches.
+    Both lists must hold every idx1 at most once, within [0, num_kpts1) - as every matcher here and
+    compute_ground_truth_matches write them; the counts are then the sizes of the original's set intersection and differences."""
+    n1 = int(num_kpts1)
+    pm, gm = _dev(pred_matches, torch.int64).reshape(-1, 2), _dev(gt_matches, torch.int64).reshape(-1, 2)
+    n_pred, n_gt = int(pm.shape[0]), int(gm.shape[0])
+    if n1 < 1 or n_pred > n1 or n_gt > n1:
+        raise ValueError(f"lists of {n_pred} and {n_gt} rows cannot hold every idx1 of {n1} keypoints at most once")
+    dev = pm.device
+    matches = torch.zeros((1, n1, 2), dtype=torch.int64, device=dev)
+    matches[0, :n_pred] = pm
+    gt_of_row = torch.full((1, n1), -1, dtype=torch.int32, device=dev)
+    if n_gt:
+        if int(gm[:, 0].min()) < 0 or int(gm[:, 0].max()) >= n1:
+            raise ValueError(f"gt_matches names a keypoint outside [0, {n1})")
+        gt_of_row[0, gm[:, 0]] = gm[:, 1].to(torch.int32)
+    value = torch.zeros((1, n1), dtype=torch.float32, device=dev)
+    count = torch.full((1,), n_pred, dtype=torch.int32, device=dev)
+    gt_count = torch.full((1,), n_gt, dtype=torch.int32, device=dev)
+    tp, fp, fn, _ = lib.match_score_pairs(matches, value, count, gt_of_row, gt_count)
+    tp, fp, fn = torch.stack([tp, fp, fn]).reshape(3).tolist()
+    return match_metrics(tp, fp, fn, n_pred, n_gt)

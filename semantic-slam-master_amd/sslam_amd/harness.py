@@ -404,7 +404,7 @@ def run_frames(pipe: SequencePipeline, n: int, h: int, w: int, spacings=(1,), to
 def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pipe: SequencePipeline | None = None,
                   selector_state: dict | None = None, refiner_state: dict | None = None, cfg: ExtractorConfig | None = None,
                   vit=None, tokens_fn=None, max_frames: int | None = None, chunk: int | None = None,
-                  decode_workers: int | None = None, device="cuda", rule=None) -> dict:
+                  decode_workers: int | None = None, device="cuda", evaluate: dict | None = None, rule=None) -> dict:
     """A TUM RGB-D sequence directory -> matches for every requested spacing: the batched counterpart of the reference's
     main() -> process_spacing() -> extract(path) -> match loop (visualize_matches_sequence.py:272-357, 360-448) over the
     directory layout of data/tum_dataset.py:210-224 (rgb/*.png sorted by name).
@@ -413,13 +413,28 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     staging buffer while chunk i is uploaded on a side stream and extracted + matched on the compute stream.
     Tokens come from the HIP ViT (`vit`: an sslam_amd.vit.DinoV3ViT holding the weights) or from `tokens_fn(a, b) ->
     (b - a, 5 + G^2, 384) device tensor` (any other backbone).  rule: StreamingSequence's.
-    Returns StreamingSequence.result() plus 'files'."""
+    evaluate: None, or a dict of evaluation.evaluate_result's keyword arguments (num_pairs, use_pose, threshold; also
+    ratio_threshold, the M4 ratio when no rule is given) - the sequence is then matched under MatchRule.mnn_ratio (a rule given
+    beside it must be one) and scored against the poses of groundtruth.txt: the result gains 'evaluation', {spacing:
+    {'repeatability': ..., 'descriptor_quality': ...}} for every spacing that has a pair.
+    Returns StreamingSequence.result() plus 'files' and 'timestamps'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
 
     from PIL import Image
 
     from .tum import TUMSequence
+    if evaluate is not None:
+        from . import evaluation
+        from .pipeline import MatchRule
+        evaluate = dict(evaluate)
+        if "spacing" in evaluate:
+            raise ValueError("evaluate= scores every spacing of spacings=: it takes no spacing of its own")
+        ratio = evaluate.pop("ratio_threshold", None)
+        if rule is None:
+            rule = MatchRule.mnn_ratio(0.9 if ratio is None else ratio)
+        elif not isinstance(rule, MatchRule) or rule.kind != lib.RULE_RATIO_SECOND or ratio is not None:
+            raise ValueError("evaluate= scores M4 lists: leave rule= out (ratio_threshold names the ratio) or pass a MatchRule.mnn_ratio")
     tum = TUMSequence(root, sequence, max_frames=max_frames)
     n = len(tum)
     if n == 0:
@@ -460,4 +475,7 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     res = seq.result()
     res["files"] = list(tum.rgb_files)
     res["timestamps"] = list(tum.timestamps)
+    if evaluate is not None:
+        res["evaluation"] = {s: evaluation.evaluate_result(pipe, res, tum.poses, spacing=s, sequence=sequence, **evaluate)
+                             for s in seq.spacings if s in res}
     return res

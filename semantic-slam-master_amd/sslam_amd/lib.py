@@ -86,7 +86,7 @@ EXPORTS = [
     "sslam_refiner_layout_d", "sslam_refiner_pack_host_d", "sslam_refine_d", "sslam_gather_refine_d", "sslam_gather_refine_ws_d",
     "sslam_sim_argmax_d", "sslam_sim_argmax_ws_d", "sslam_sim_argmax_pairs_d", "sslam_sim_argmax_rows_d",
     "sslam_sim_argmax_rows_pairs_d", "sslam_row_lse_d", "sslam_row_lse_pairs_d", "sslam_val_frame_stats_d",
-    "sslam_match_rank",
+    "sslam_match_rank", "sslam_pose_nn_pairs", "sslam_match_score_pairs",
 ]
 
 
@@ -129,6 +129,8 @@ def lib():
         L.sslam_match_finalize_rule.argtypes = [p, p, p, p, i, i, i, i, f, p, p, p, p]
         L.sslam_match_finalize_rule_pairs.argtypes = [p, p, p, p, i, i, p, p, i, i, f, p, p, p, p]
         L.sslam_match_rank.argtypes = [p, p, p, i, i, i, i, p, p, p, p, p]
+        L.sslam_pose_nn_pairs.argtypes = [p, i, i, i, i, p, p, i, p, d, p, p, p, p, p, p]
+        L.sslam_match_score_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p]
         L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
         L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
         L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
@@ -809,6 +811,96 @@ def match_rank(matches, value, count, best=None, ascending=False, out=None, want
     _run("match_rank", lib().sslam_match_rank, (matches, value, count, o_m, o_v, o_c, o_s),
          _dp(matches), _dp(value), _dp(count), n1, n_pairs, best, int(ascending), _dp(o_m), _dp(o_v), _dp(o_c), _dp(o_s))
     return o_m, o_v, o_c, o_s
+
+
+# ------------------------------------------------------------------------------------------------ pose-based scoring
+EVAL_MAX_K = 4096       # SSLAM_EVAL_MAX_K: the most keypoints per frame sslam_pose_nn_pairs searches (a pair's distances live in LDS)
+POSE_SCORE_KEYS = ("gt_matches", "gt_count", "gt_of_row", "dist_sum", "dist_median")
+MATCH_SCORE_KEYS = ("tp", "fp", "fn", "value_sum")
+
+
+def check_threshold(threshold) -> float:
+    """The pixel threshold of pose_nn_pairs as a float: finite and >= 0, else ValueError - before any device work."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating, np.integer)):
+        raise ValueError(f"threshold must be a number, got {threshold!r}")
+    t = float(threshold)
+    if not (np.isfinite(t) and t >= 0.0):
+        raise ValueError(f"threshold must be finite and >= 0, got {threshold!r}")
+    return t
+
+
+def pose_score_shapes(n_pairs: int, n1: int) -> dict:
+    """name -> (shape, dtype) of the outputs of pose_nn_pairs and match_score_pairs for n_pairs pairs of n1 query rows."""
+    return {"gt_matches": ((n_pairs, n1, 2), torch.int64), "gt_count": ((n_pairs,), torch.int32),
+            "gt_of_row": ((n_pairs, n1), torch.int32), "dist_sum": ((n_pairs,), torch.float64),
+            "dist_median": ((n_pairs,), torch.float64), "tp": ((n_pairs,), torch.int32), "fp": ((n_pairs,), torch.int32),
+            "fn": ((n_pairs,), torch.int32), "value_sum": ((n_pairs,), torch.float64)}
+
+
+def _score_out(out, keys, n_pairs, n1, dev=None):
+    """The output tensors of a scoring call: `out` checked against the shapes (no device needed), or fresh ones on dev."""
+    shapes = pose_score_shapes(n_pairs, n1)
+    if out is None:
+        return [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in keys]
+    if len(out) != len(keys):
+        raise ValueError(f"out must hold {len(keys)} tensors: {', '.join(keys)}")
+    for key, t in zip(keys, out):
+        if t is None:
+            raise ValueError(f"out `{key}` is required")
+        _check_arrays(shapes[key][0], (f"out `{key}`", t, shapes[key][1]))
+    return list(out)
+
+
+def pose_nn_pairs(kp_bank, first, second, H=None, threshold=3.0, n1=None, n2=None, out=None):
+    """sslam_pose_nn_pairs: kp_bank (n_bank, K, 2) fp32 pixel keypoints; first / second: 1-D int32 DEVICE lists naming each pair's
+    two frames (-1 = absent pair); H (n_pairs, 9) or (n_pairs, 3, 3) float64 device tensor of homographies first -> second, or None
+    for the raw coordinates.  n1 / n2: the rows of the first / second frame that count (K by default).
+    Returns (gt_matches (P, n1, 2) int64, gt_count (P,) int32, gt_of_row (P, n1) int32, dist_sum (P,) float64, dist_median (P,)
+    float64) - include/sslam_hip.h states them; out: optional tensors of those shapes to write into.  One launch, no host read."""
+    _check_bank("kp_bank", kp_bank, ("K", 2))
+    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
+    n_pairs = check_pair_lists(first, second, kp_bank.device)
+    n1, n2 = (k if v is None else v for v in (n1, n2))
+    for name, v in (("n1", n1), ("n2", n2)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= k:
+            raise ValueError(f"{name} must be an int in [1, {k}], got {v!r}")
+    n1, n2 = int(n1), int(n2)
+    t = check_threshold(threshold)
+    if H is not None:
+        if not isinstance(H, torch.Tensor) or H.dtype != torch.float64 or not H.is_contiguous() or \
+                tuple(H.shape) not in ((n_pairs, 9), (n_pairs, 3, 3)):
+            raise ValueError(f"H must be a contiguous float64 tensor of shape ({n_pairs}, 9) or ({n_pairs}, 3, 3)")
+    if k > EVAL_MAX_K:
+        raise SslamHipError(f"pose_nn_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are searched on the device")
+    o = None if out is None else _score_out(out, POSE_SCORE_KEYS, n_pairs, n1)
+    dev = common_device(kp_bank, first, second, H)
+    o = _score_out(None, POSE_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
+    _run("pose_nn_pairs", lib().sslam_pose_nn_pairs, (kp_bank, first, second, H, *o),
+         _dp(kp_bank), n_bank, k, n1, n2, _dp(first), _dp(second), n_pairs, _dp(H), C.c_double(t), *(_dp(x) for x in o))
+    return tuple(o)
+
+
+def match_score_pairs(matches, value, count, gt_of_row, gt_count, out=None):
+    """sslam_match_score_pairs: a match list (matches (P, n1, 2) int64, value (P, n1) fp32, count (P,) int32, as a finalize entry
+    wrote it; idx1 unique within a pair) against gt_of_row (P, n1) / gt_count (P,) of pose_nn_pairs over the same pairs.
+    Returns (tp, fp, fn (P,) int32, value_sum (P,) float64); out: optional tensors of those shapes.  One launch, no host read."""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or matches.shape[0] < 1 or matches.shape[1] < 1:
+        raise ValueError("matches must be a tensor of shape (n_pairs >= 1, n1 >= 1, 2)")
+    n_pairs, n1 = int(matches.shape[0]), int(matches.shape[1])
+    for name, t in (("value", value), ("count", count), ("gt_of_row", gt_of_row), ("gt_count", gt_count)):
+        if t is None:
+            raise ValueError(f"{name} is required")
+    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+    _check_arrays((n_pairs, n1), ("value", value, torch.float32), ("gt_of_row", gt_of_row, torch.int32))
+    _check_arrays((n_pairs,), ("count", count, torch.int32), ("gt_count", gt_count, torch.int32))
+    if n1 > EVAL_MAX_K:
+        raise SslamHipError(f"match_score_pairs: lists of {n1} rows; at most {EVAL_MAX_K} are scored on the device")
+    o = None if out is None else _score_out(out, MATCH_SCORE_KEYS, n_pairs, n1)
+    dev = common_device(matches, value, count, gt_of_row, gt_count)
+    o = _score_out(None, MATCH_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
+    _run("match_score_pairs", lib().sslam_match_score_pairs, (matches, value, count, gt_of_row, gt_count, *o),
+         _dp(matches), _dp(value), _dp(count), _dp(gt_of_row), _dp(gt_count), n1, n_pairs, *(_dp(x) for x in o))
+    return tuple(o)
 
 
 # ------------------------------------------------------------------------------------------------ validation stage

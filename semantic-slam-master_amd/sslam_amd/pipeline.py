@@ -638,6 +638,61 @@ class SequencePipeline:
                        out=(res["matches"], res[val], res["match_count"], res.get("slot")))
         return res
 
+    def alloc_pose_scores(self, n_pairs: int, k: int | None = None, with_matches: bool = True) -> dict:
+        """Output buffers of pose_scores() for n_pairs pairs of k keypoints (num_keypoints by default); with_matches: also the
+        tp / fp / fn / value_sum a match list is scored into."""
+        k = self.cfg.num_keypoints if k is None else k
+        keys = lib.POSE_SCORE_KEYS + (lib.MATCH_SCORE_KEYS if with_matches else ())
+        shapes = lib.pose_score_shapes(n_pairs, k)
+        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in keys}
+
+    def pose_scores(self, keypoints_pixel, first, second, H, threshold: float = 3.0, matches: dict | None = None,
+                    out: dict | None = None) -> dict:
+        """The scoring stage (csrc/evaluate.hip): for every listed pair of the bank keypoints_pixel (N, K, 2) - what extract()
+        returns under that name - warp frame first[p]'s keypoints by H[p], find the nearest keypoint of frame second[p] and keep the
+        rows nearer than `threshold` pixels: the reference's repeatability count and its ground-truth matches
+        (test/test_repeatability.py:79-128, test/test_descriptor_quality.py:144-185).
+        first / second: as match_pairs takes them (1-D int32 device tensors or host sequences; -1 = absent pair).  H: (P, 3, 3) or
+        (P, 9) float64, a device tensor or a host array (uploaded once), or None for the raw coordinates.
+        matches: what match_pairs(rule=MatchRule.mnn_ratio()) returned for the same lists (matches, value, match_count) - then the
+        list of every pair is scored against the ground truth as evaluate_matches does (:187-231).
+        Returns device tensors, one row per listed pair: gt_matches (P, K, 2) int64, gt_count (P,) int32 (= the repeatable count),
+        gt_of_row (P, K) int32, dist_sum, dist_median (P,) float64, and with matches tp, fp, fn (P,) int32, value_sum (P,) float64.
+        out: alloc_pose_scores buffers (or row slices of them).  Two launches per 65 535 pairs, nothing read on the host."""
+        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
+            raise ValueError("keypoints_pixel (N, K, 2) expected")
+        if first is None or second is None:
+            raise ValueError("pose_scores needs both pair lists, first= and second=")
+        t = lib.check_threshold(threshold)
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)
+        dev, k = keypoints_pixel.device, int(keypoints_pixel.shape[1])
+        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
+        lib.check_pair_lists(first, second, dev)
+        if H is not None:
+            if not isinstance(H, torch.Tensor):
+                H = torch.from_numpy(np.ascontiguousarray(np.asarray(H, dtype=np.float64)))
+            if H.dtype != torch.float64 or tuple(H.shape) not in ((n_pairs, 9), (n_pairs, 3, 3)):
+                raise ValueError(f"H must be float64 of shape ({n_pairs}, 3, 3) or ({n_pairs}, 9), got {H.dtype} {tuple(H.shape)}")
+            H = H.to(dev).contiguous()
+        if matches is not None:
+            if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "value", "match_count")):
+                raise ValueError("matches must be the dictionary match_pairs(rule=...) returned: matches, value, match_count")
+            if tuple(matches["matches"].shape) != (n_pairs, k, 2):
+                raise ValueError(f"matches holds {tuple(matches['matches'].shape)}, the pair lists ask for {(n_pairs, k, 2)}")
+        keys = lib.POSE_SCORE_KEYS + (lib.MATCH_SCORE_KEYS if matches is not None else ())
+        res = dict(out) if out is not None else self.alloc_pose_scores(n_pairs, k, matches is not None)
+        if any(key not in res for key in keys):
+            raise ValueError(f"out must hold {', '.join(keys)} (alloc_pose_scores)")
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
+            b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
+            lib.pose_nn_pairs(keypoints_pixel, first[a:b], second[a:b], None if H is None else H[a:b], t,
+                              out=tuple(res[key][a:b] for key in lib.POSE_SCORE_KEYS))
+            if matches is not None:
+                lib.match_score_pairs(matches["matches"][a:b], matches["value"][a:b], matches["match_count"][a:b],
+                                      res["gt_of_row"][a:b], res["gt_count"][a:b], out=tuple(res[key][a:b] for key in lib.MATCH_SCORE_KEYS))
+        return res
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
