@@ -619,6 +619,57 @@ int sslam_match_score_pairs(const int64_t *matches, const float *value, const in
                             const int32_t *gt_count, int n1, int n_pairs, int32_t *tp, int32_t *fp, int32_t *fn,
                             double *value_sum, void *stream);
 
+/* ---- The same scores against a translation-aware ground truth: depth and the full relative pose (csrc/evaluate_depth.hip).
+ * The entries above keep the reference's ground truth, H = K R K^-1 with the translation dropped; these use the D of RGB-D:
+ * back-project a keypoint with its depth, move it by [R | t], project it into the other frame.  All arithmetic is float64, every
+ * product, quotient and sum rounded once in the order written (no contraction).  Each entry is one launch that only enqueues:
+ * no atomics, no scratch, no allocation, no host read (capturable); every refusal comes before anything is launched.
+ * sslam_keypoint_depth: the depth sibling of sslam_keypoint_intensity, per frame at extraction time.
+ *   depth (n, h, w) uint16, TUM's raw values; kp_pixel (n, K, 2) fp32 (x, y), 8-byte aligned; scale_x, scale_y take keypoint
+ *   units to depth pixels (w / input_size and h / input_size for a pipeline's keypoints, 1 for the reference's convention).
+ *     u = (double)x * scale_x, c = floor(u + 0.5); v = (double)y * scale_y, r = floor(v + 0.5);
+ *   kp_depth (n, K) int32 = depth[frame][r][c], or -1 where 0 <= c < w && 0 <= r < h is false - judged on the DOUBLES, before
+ *   any conversion to an integer, so a NaN or a huge coordinate gives -1.  A raw 0 stays 0: TUM's "no measurement".
+ * sslam_pose_depth_nn_pairs: sslam_pose_nn_pairs with the warp replaced.  kp_bank, n_bank, K, n1, n2, the pair lists and the
+ *   threshold are as there; kp_depth_bank (n_bank, K) int32 is what the entry above wrote for the same bank; T (n_pairs, 12)
+ *   float64 row-major [R | t] takes camera-a coordinates to camera-b coordinates in metres (8-byte aligned, never NULL).
+ *   For row i of frame a with raw depth d:
+ *     u = x*scale_x, v = y*scale_y, z = d / depth_scale;
+ *     X = ((u - cx) * z) / fx, Y = ((v - cy) * z) / fy, Z = z;
+ *     X' = ((r00*X + r01*Y) + r02*Z) + t0, Y' and Z' likewise from rows 1 and 2;
+ *     u' = (fx * X') / Z' + cx, v' = (fy * Y') / Z' + cy;  the warped keypoint is (u' / scale_x, v' / scale_y);
+ *   from there the search of sslam_pose_nn_pairs bit for bit: sqrt(dx*dx + dy*dy), the LOWEST index among equal distances, the
+ *   threshold in keypoint units.  A row HAS NO GROUND TRUTH when d <= 0 (no measurement, or -1 from outside the image), when
+ *   Z' > 0 is false (a NaN gives false), or when -0.5 <= u' < view_w - 0.5 && -0.5 <= v' < view_h - 0.5 is false (the
+ *   projection is outside frame b's view, view_w x view_h depth pixels).
+ *   Outputs as sslam_pose_nn_pairs, with:
+ *     gt_of_row   the argmin, -1 for a row with ground truth but no keypoint within the threshold, -2 for a row without one;
+ *     valid_count (n_pairs) int32  the rows with ground truth; gt_matches and gt_count range over those rows only;
+ *     dist_sum    the fixed-order sum of the valid rows' nearest distances (the order of sslam_pose_nn_pairs, an invalid row
+ *                 adding +0.0);
+ *     dist_median the median over the valid rows: the others sort as +inf, and it is (dist[(v-1)>>1] + dist[v>>1]) / 2 with
+ *                 v = valid_count, 0.0 when v == 0.
+ *   An absent pair: the absent pair's rows of sslam_pose_nn_pairs (gt_of_row -1), valid_count 0.
+ *   There is no occlusion test against frame b's depth.  Non-finite entries of T and NaN keypoints in a row that passes the
+ *   three tests are outside the contract, as for the entry above.
+ * sslam_match_score_known_pairs: sslam_match_score_pairs that knows about -2.  unknown (n_pairs) int32 = the listed rows whose
+ *   gt_of_row[idx1] == -2: such a match cannot be called wrong, so it is no false positive.  tp as before,
+ *   fp = count - tp - unknown, fn = gt_count - tp; value_sum over ALL listed rows in the existing order; an idx1 outside [0, n1)
+ *   stays a false positive.  With no -2 present tp / fp / fn / value_sum are those of sslam_match_score_pairs bit for bit.
+ * SSLAM_E_INVALID: a NULL pointer (T included); a non-positive size; n1 or n2 above K; a threshold that is negative, NaN or
+ * infinite; fx, fy, depth_scale, scale_x, scale_y, view_w or view_h not finite and positive; cx or cy not finite; a misaligned
+ * pointer.  SSLAM_E_UNSUPPORTED: K (n1 for the score entry) above SSLAM_EVAL_MAX_K; n * K above 2^31 - 1 in the gather. */
+int sslam_keypoint_depth(const uint16_t *depth, int n, int h, int w, const float *kp_pixel, int K, double scale_x, double scale_y,
+                         int32_t *kp_depth, void *stream);
+int sslam_pose_depth_nn_pairs(const float *kp_bank, const int32_t *kp_depth_bank, int n_bank, int K, int n1, int n2,
+                              const int32_t *pair_first, const int32_t *pair_second, int n_pairs, const double *T, double fx, double fy,
+                              double cx, double cy, double depth_scale, double scale_x, double scale_y, double view_w, double view_h,
+                              double threshold, int64_t *gt_matches, int32_t *gt_count, int32_t *gt_of_row, int32_t *valid_count,
+                              double *dist_sum, double *dist_median, void *stream);
+int sslam_match_score_known_pairs(const int64_t *matches, const float *value, const int32_t *count, const int32_t *gt_of_row,
+                                  const int32_t *gt_count, int n1, int n_pairs, int32_t *tp, int32_t *fp, int32_t *fn, int32_t *unknown,
+                                  double *value_sum, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

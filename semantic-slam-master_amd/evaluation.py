@@ -5,6 +5,9 @@ keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (
     compute_ground_truth_matches   DescriptorQualityTester.compute_ground_truth_matches   test/test_descriptor_quality.py:144-185
     evaluate_matches               DescriptorQualityTester.evaluate_matches               test/test_descriptor_quality.py:187-231
 
+Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate_depth.hip):
+compute_repeatability_depth and compute_ground_truth_matches_depth.
+
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
 result.  There is no CPU implementation here: without the GPU library these functions raise.
 
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 from sslam_amd import lib
-from sslam_amd.evaluation import match_metrics
+from sslam_amd.evaluation import check_depth_size, match_metrics
 
 
 def _dev(a, dtype):
@@ -60,6 +63,50 @@ def compute_ground_truth_matches(kpts1, kpts2, H, threshold: float = 3.0):
     if H is None:
         raise ValueError("compute_ground_truth_matches needs the homography H")
     _, (gt, cnt, _, _, _) = _pose_nn(kpts1, kpts2, H, threshold)
+    out = gt[0, :int(cnt.item())]
+    return out if isinstance(kpts1, torch.Tensor) else out.cpu().numpy()
+
+
+def _pose_depth_nn(kpts1, kpts2, depth1, T_rel, camera, threshold):
+    lib.check_camera(camera)                                 # the camera and the depth image are judged before any device work
+    if isinstance(depth1, np.ndarray):
+        depth1 = torch.from_numpy(np.ascontiguousarray(depth1))
+    if not isinstance(depth1, torch.Tensor) or depth1.dtype != torch.uint16 or depth1.dim() != 2:
+        raise ValueError("depth1 (h, w) uint16 expected: frame 1's raw depth image")
+    check_depth_size(depth1.shape[1], depth1.shape[0], camera)   # a camera that is not this image's would score against another view
+    k1, k2 = _dev(kpts1, torch.float32), _dev(kpts2, torch.float32)
+    if k1.dim() != 2 or k2.dim() != 2 or k1.shape[1] != 2 or k2.shape[1] != 2 or k1.shape[0] < 1 or k2.shape[0] < 1:
+        raise ValueError(f"keypoints (N >= 1, 2) and (M >= 1, 2) expected, got {tuple(k1.shape)} and {tuple(k2.shape)}")
+    T = _dev(T_rel, torch.float64)
+    if tuple(T.shape) not in ((4, 4), (3, 4)):
+        raise ValueError(f"T_rel (4, 4) or (3, 4) expected, got {tuple(T.shape)}")
+    n, m = int(k1.shape[0]), int(k2.shape[0])
+    bank = torch.zeros((2, max(n, m), 2), dtype=torch.float32, device=k1.device)
+    bank[0, :n], bank[1, :m] = k1, k2
+    kp_depth = torch.full((2, max(n, m)), -1, dtype=torch.int32, device=k1.device)
+    lib.keypoint_depth(depth1.to(k1.device).contiguous()[None], bank[:1], out=kp_depth[:1])      # pixel units: scale 1
+    first = torch.zeros((1,), dtype=torch.int32, device=k1.device)
+    return n, lib.pose_depth_nn_pairs(bank, kp_depth, first, first + 1, T[:3].contiguous().reshape(1, 12), camera, threshold=threshold,
+                                      n1=n, n2=m)
+
+
+def compute_repeatability_depth(kpts1, kpts2, depth1, T_rel, camera, threshold: float = 3.0) -> dict:
+    """compute_repeatability against the depth ground truth: kpts1 (N, 2) and kpts2 (M, 2) in the pixels of the depth image
+    depth1 (h, w) uint16 of frame 1 (the reference's convention: scale 1), T_rel (4, 4) from camera 1 to camera 2
+    (sslam_amd.evaluation.relative_transform), camera an sslam_amd.evaluation.Camera.  Returns compute_repeatability's dictionary
+    plus valid_keypoints: repeatability and mean_nn_distance are over the keypoints that HAVE a ground truth (a depth
+    measurement, in front of camera 2, inside its view), 0.0 when there is none."""
+    n, (_, cnt, _, valid, dsum, dmed) = _pose_depth_nn(kpts1, kpts2, depth1, T_rel, camera, threshold)
+    c, v, s, med = torch.stack([cnt.to(torch.float64), valid.to(torch.float64), dsum, dmed]).reshape(4).tolist()      # one read-back
+    repeatable, v = np.int64(c), np.int64(v)
+    return {"repeatability": repeatable / v if v > 0 else 0.0, "repeatable_count": repeatable, "total_keypoints": n,
+            "valid_keypoints": v, "mean_nn_distance": np.float64(s) / v if v > 0 else 0.0, "median_nn_distance": np.float64(med)}
+
+
+def compute_ground_truth_matches_depth(kpts1, kpts2, depth1, T_rel, camera, threshold: float = 3.0):
+    """compute_ground_truth_matches against the depth ground truth (arguments as compute_repeatability_depth): (K, 2) int64
+    [idx1, idx2].  numpy for numpy keypoints, a device tensor else."""
+    _, (gt, cnt, _, _, _, _) = _pose_depth_nn(kpts1, kpts2, depth1, T_rel, camera, threshold)
     out = gt[0, :int(cnt.item())]
     return out if isinstance(kpts1, torch.Tensor) else out.cpu().numpy()
 

@@ -416,7 +416,9 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     evaluate: None, or a dict of evaluation.evaluate_result's keyword arguments (num_pairs, use_pose, threshold; also
     ratio_threshold, the M4 ratio when no rule is given) - the sequence is then matched under MatchRule.mnn_ratio (a rule given
     beside it must be one) and scored against the poses of groundtruth.txt: the result gains 'evaluation', {spacing:
-    {'repeatability': ..., 'descriptor_quality': ...}} for every spacing that has a pair.
+    {'repeatability': ..., 'descriptor_quality': ...}} for every spacing that has a pair.  A key "depth": True reads the
+    sequence's depth PNGs as well (TUMSequence.load_depth_raw) and scores against the translation-aware ground truth
+    (evaluate_result's depth=) with tum.camera_for(sequence), or with the Camera given under "camera".
     Returns StreamingSequence.result() plus 'files' and 'timestamps'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -431,6 +433,11 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
         if "spacing" in evaluate:
             raise ValueError("evaluate= scores every spacing of spacings=: it takes no spacing of its own")
         ratio = evaluate.pop("ratio_threshold", None)
+        with_depth = evaluate.pop("depth", False)
+        if not isinstance(with_depth, bool):
+            raise ValueError('evaluate["depth"] is a flag, True or False: the images are read from the sequence directory')
+        if not with_depth and "camera" in evaluate:
+            raise ValueError('evaluate["camera"] describes the depth images: it needs "depth": True')
         if rule is None:
             rule = MatchRule.mnn_ratio(0.9 if ratio is None else ratio)
         elif not isinstance(rule, MatchRule) or rule.kind != lib.RULE_RATIO_SECOND or ratio is not None:
@@ -439,6 +446,15 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     n = len(tum)
     if n == 0:
         raise ValueError(f"no rgb frames under {tum.rgb_dir}")
+    if evaluate is not None and with_depth:                  # what the depth scoring needs is judged before the sequence is run
+        from .tum import camera_for
+        if not tum.depth_files:
+            raise ValueError(f'evaluate["depth"]: no depth images under {tum.depth_dir}')
+        if tum.poses is None:
+            raise ValueError(f'evaluate["depth"] needs poses: {tum.gt_file} is missing')
+        depth_camera = evaluate.pop("camera", None) or camera_for(sequence or str(tum.sequence_dir))
+        with Image.open(tum.depth_dir / tum.depth_files[0]) as im0:
+            evaluation.check_depth_size(*im0.size, depth_camera)
     if pipe is None:
         pipe = SequencePipeline(cfg or ExtractorConfig(), selector_state, refiner_state, device=device, vit=vit)
     if tokens_fn is None and pipe.vit_hip is None:
@@ -476,6 +492,10 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     res["files"] = list(tum.rgb_files)
     res["timestamps"] = list(tum.timestamps)
     if evaluate is not None:
+        if with_depth:                                       # the keypoint depths depend on the frames alone: one gather for all spacings
+            need = min(n, max(len(evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))) + s for s in seq.spacings))
+            evaluate["camera"] = depth_camera
+            evaluate["kp_depth"] = evaluation.gather_keypoint_depth(pipe, tum.load_depth_raw(range(need)), res["frames"]["keypoints_pixel"], need)
         res["evaluation"] = {s: evaluation.evaluate_result(pipe, res, tum.poses, spacing=s, sequence=sequence, **evaluate)
                              for s in seq.spacings if s in res}
     return res

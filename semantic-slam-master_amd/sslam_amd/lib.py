@@ -87,6 +87,7 @@ EXPORTS = [
     "sslam_sim_argmax_d", "sslam_sim_argmax_ws_d", "sslam_sim_argmax_pairs_d", "sslam_sim_argmax_rows_d",
     "sslam_sim_argmax_rows_pairs_d", "sslam_row_lse_d", "sslam_row_lse_pairs_d", "sslam_val_frame_stats_d",
     "sslam_match_rank", "sslam_pose_nn_pairs", "sslam_match_score_pairs",
+    "sslam_keypoint_depth", "sslam_pose_depth_nn_pairs", "sslam_match_score_known_pairs",
 ]
 
 
@@ -131,6 +132,9 @@ def lib():
         L.sslam_match_rank.argtypes = [p, p, p, i, i, i, i, p, p, p, p, p]
         L.sslam_pose_nn_pairs.argtypes = [p, i, i, i, i, p, p, i, p, d, p, p, p, p, p, p]
         L.sslam_match_score_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p]
+        L.sslam_keypoint_depth.argtypes = [p, i, i, i, p, i, d, d, p, p]
+        L.sslam_pose_depth_nn_pairs.argtypes = [p, p, i, i, i, i, p, p, i, p] + [d] * 10 + [p, p, p, p, p, p, p]
+        L.sslam_match_score_known_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p, p]
         L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
         L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
         L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
@@ -899,6 +903,135 @@ def match_score_pairs(matches, value, count, gt_of_row, gt_count, out=None):
     dev = common_device(matches, value, count, gt_of_row, gt_count)
     o = _score_out(None, MATCH_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
     _run("match_score_pairs", lib().sslam_match_score_pairs, (matches, value, count, gt_of_row, gt_count, *o),
+         _dp(matches), _dp(value), _dp(count), _dp(gt_of_row), _dp(gt_count), n1, n_pairs, *(_dp(x) for x in o))
+    return tuple(o)
+
+
+# ------------------------------------------------------------------------------- pose-based scoring with depth (evaluate_depth.hip)
+POSE_DEPTH_SCORE_KEYS = ("gt_matches", "gt_count", "gt_of_row", "valid_count", "dist_sum", "dist_median")
+MATCH_KNOWN_SCORE_KEYS = ("tp", "fp", "fn", "unknown", "value_sum")
+CAMERA_FIELDS = ("fx", "fy", "cx", "cy", "depth_scale", "width", "height")
+
+
+def pose_depth_score_shapes(n_pairs: int, n1: int) -> dict:
+    """pose_score_shapes plus the two outputs the depth entries add: valid_count and unknown, (n_pairs,) int32."""
+    return dict(pose_score_shapes(n_pairs, n1), valid_count=((n_pairs,), torch.int32), unknown=((n_pairs,), torch.int32))
+
+
+def check_positive(name: str, v) -> float:
+    """v as a float: a finite number > 0, else ValueError - before any device work."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not (np.isfinite(float(v)) and float(v) > 0.0):
+        raise ValueError(f"{name} must be a finite number > 0, got {v!r}")
+    return float(v)
+
+
+def check_camera(camera) -> tuple:
+    """(fx, fy, cx, cy, depth_scale, width, height) as floats from an object with those attributes (evaluation.Camera): cx and cy
+    finite, the others finite and positive, else ValueError."""
+    if any(not hasattr(camera, f) for f in CAMERA_FIELDS):
+        raise ValueError(f"camera must have the attributes {', '.join(CAMERA_FIELDS)} (evaluation.Camera), got {camera!r}")
+    out = []
+    for f in CAMERA_FIELDS:
+        v = getattr(camera, f)
+        if f in ("cx", "cy"):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(float(v)):
+                raise ValueError(f"camera {f} must be a finite number, got {v!r}")
+            out.append(float(v))
+        else:
+            out.append(check_positive(f"camera {f}", v))
+    return tuple(out)
+
+
+def _depth_score_out(out, keys, n_pairs, n1, dev=None):
+    shapes = pose_depth_score_shapes(n_pairs, n1)
+    if out is None:
+        return [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in keys]
+    if len(out) != len(keys):
+        raise ValueError(f"out must hold {len(keys)} tensors: {', '.join(keys)}")
+    for key, t in zip(keys, out):
+        if t is None:
+            raise ValueError(f"out `{key}` is required")
+        _check_arrays(shapes[key][0], (f"out `{key}`", t, shapes[key][1]))
+    return list(out)
+
+
+def keypoint_depth(depth, kp_pixel, scale_x=1.0, scale_y=1.0, out=None):
+    """sslam_keypoint_depth: depth (n, h, w) uint16 raw depth images, kp_pixel (n, K, 2) fp32; scale_x / scale_y take keypoint
+    units to depth pixels.  Returns kp_depth (n, K) int32: the raw value under each keypoint (nearest pixel), -1 outside the image
+    or for a NaN coordinate; a raw 0 (no measurement) stays 0.  out: an optional tensor of that shape.  One launch, no host read."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.uint16 or depth.dim() != 3 or not depth.is_contiguous() or \
+            min(depth.shape) < 1:
+        raise ValueError("depth must be a contiguous uint16 tensor of shape (n, h, w)")
+    n, h, w = (int(v) for v in depth.shape)
+    if not isinstance(kp_pixel, torch.Tensor) or kp_pixel.dim() != 3 or int(kp_pixel.shape[1]) < 1:
+        raise ValueError(f"kp_pixel must be a contiguous fp32 tensor of shape ({n}, K, 2)")
+    k = int(kp_pixel.shape[1])
+    _check_arrays((n, k, 2), ("kp_pixel", kp_pixel, torch.float32))
+    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
+    _check_arrays((n, k), ("out `kp_depth`", out, torch.int32))
+    dev = common_device(depth, kp_pixel, out)
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.int32, device=dev)
+    _run("keypoint_depth", lib().sslam_keypoint_depth, (depth, kp_pixel, out), _dp(depth), n, h, w, _dp(kp_pixel), k, C.c_double(sx),
+         C.c_double(sy), _dp(out))
+    return out
+
+
+def pose_depth_nn_pairs(kp_bank, kp_depth_bank, first, second, T, camera, scale_x=1.0, scale_y=1.0, threshold=3.0, n1=None, n2=None,
+                        out=None):
+    """sslam_pose_depth_nn_pairs: kp_bank (n_bank, K, 2) fp32 and kp_depth_bank (n_bank, K) int32 (keypoint_depth's output for the
+    same bank); first / second as pose_nn_pairs takes them; T (n_pairs, 12) or (n_pairs, 3, 4) float64 device tensor, [R | t] from
+    camera first to camera second in metres; camera: an evaluation.Camera (fx, fy, cx, cy, depth_scale and the view width x height
+    in depth pixels); scale_x / scale_y: keypoint units to depth pixels.
+    Returns (gt_matches, gt_count, gt_of_row, valid_count, dist_sum, dist_median) - POSE_DEPTH_SCORE_KEYS; gt_of_row is -2 in a row
+    without ground truth (include/sslam_hip.h).  out: optional tensors of those shapes.  One launch, no host read."""
+    _check_bank("kp_bank", kp_bank, ("K", 2))
+    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
+    if kp_depth_bank is None:
+        raise ValueError("kp_depth_bank is required")
+    _check_arrays((n_bank, k), ("kp_depth_bank", kp_depth_bank, torch.int32))
+    n_pairs = check_pair_lists(first, second, kp_bank.device)
+    n1, n2 = (k if v is None else v for v in (n1, n2))
+    for name, v in (("n1", n1), ("n2", n2)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= k:
+            raise ValueError(f"{name} must be an int in [1, {k}], got {v!r}")
+    n1, n2 = int(n1), int(n2)
+    t = check_threshold(threshold)
+    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
+    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
+    if not isinstance(T, torch.Tensor) or T.dtype != torch.float64 or not T.is_contiguous() or \
+            tuple(T.shape) not in ((n_pairs, 12), (n_pairs, 3, 4)):
+        raise ValueError(f"T must be a contiguous float64 tensor of shape ({n_pairs}, 12) or ({n_pairs}, 3, 4)")
+    if k > EVAL_MAX_K:
+        raise SslamHipError(f"pose_depth_nn_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are searched on the device")
+    o = None if out is None else _depth_score_out(out, POSE_DEPTH_SCORE_KEYS, n_pairs, n1)
+    dev = common_device(kp_bank, kp_depth_bank, first, second, T)
+    o = _depth_score_out(None, POSE_DEPTH_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
+    _run("pose_depth_nn_pairs", lib().sslam_pose_depth_nn_pairs, (kp_bank, kp_depth_bank, first, second, T, *o),
+         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, n1, n2, _dp(first), _dp(second), n_pairs, _dp(T),
+         *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), *(_dp(x) for x in o))
+    return tuple(o)
+
+
+def match_score_known_pairs(matches, value, count, gt_of_row, gt_count, out=None):
+    """sslam_match_score_known_pairs: match_score_pairs against a gt_of_row that may hold -2 (pose_depth_nn_pairs).
+    Returns (tp, fp, fn, unknown (P,) int32, value_sum (P,) float64) - MATCH_KNOWN_SCORE_KEYS: unknown counts the listed rows whose
+    query has no ground truth, fp = count - tp - unknown.  out: optional tensors of those shapes.  One launch, no host read."""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or matches.shape[0] < 1 or matches.shape[1] < 1:
+        raise ValueError("matches must be a tensor of shape (n_pairs >= 1, n1 >= 1, 2)")
+    n_pairs, n1 = int(matches.shape[0]), int(matches.shape[1])
+    for name, t in (("value", value), ("count", count), ("gt_of_row", gt_of_row), ("gt_count", gt_count)):
+        if t is None:
+            raise ValueError(f"{name} is required")
+    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+    _check_arrays((n_pairs, n1), ("value", value, torch.float32), ("gt_of_row", gt_of_row, torch.int32))
+    _check_arrays((n_pairs,), ("count", count, torch.int32), ("gt_count", gt_count, torch.int32))
+    if n1 > EVAL_MAX_K:
+        raise SslamHipError(f"match_score_known_pairs: lists of {n1} rows; at most {EVAL_MAX_K} are scored on the device")
+    o = None if out is None else _depth_score_out(out, MATCH_KNOWN_SCORE_KEYS, n_pairs, n1)
+    dev = common_device(matches, value, count, gt_of_row, gt_count)
+    o = _depth_score_out(None, MATCH_KNOWN_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
+    _run("match_score_known_pairs", lib().sslam_match_score_known_pairs, (matches, value, count, gt_of_row, gt_count, *o),
          _dp(matches), _dp(value), _dp(count), _dp(gt_of_row), _dp(gt_count), n1, n_pairs, *(_dp(x) for x in o))
     return tuple(o)
 

@@ -693,6 +693,81 @@ class SequencePipeline:
                                       res["gt_of_row"][a:b], res["gt_count"][a:b], out=tuple(res[key][a:b] for key in lib.MATCH_SCORE_KEYS))
         return res
 
+    def depth_scales(self, camera) -> tuple:
+        """(scale_x, scale_y): from this pipeline's keypoint units (input_size wide and high) to the depth pixels of `camera`."""
+        _, _, _, _, _, w, h = lib.check_camera(camera)
+        return w / self.cfg.input_size, h / self.cfg.input_size
+
+    def keypoint_depth(self, depth_u16, keypoints_pixel, out=None):
+        """The raw depth under every keypoint (csrc/evaluate_depth.hip): depth_u16 (n, h, w) uint16 device tensor - TUM's raw
+        values, metres times 5000 - for the n frames whose keypoints_pixel (n, K, 2) extract() returned; the keypoint is taken to
+        the depth image by w / input_size and h / input_size and rounded to the nearest pixel.  Returns (n, K) int32: the raw
+        value, 0 where the sensor measured nothing, -1 outside the image.  out: an (n, K) int32 tensor (a slice of a sequence-sized
+        bank: depth images need not stay on the device).  One launch, nothing read on the host."""
+        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dim() != 3:
+            raise ValueError("depth_u16 (n, h, w) uint16 expected")
+        return lib.keypoint_depth(depth_u16, keypoints_pixel, int(depth_u16.shape[2]) / self.cfg.input_size,
+                                  int(depth_u16.shape[1]) / self.cfg.input_size, out=out)
+
+    def alloc_pose_depth_scores(self, n_pairs: int, k: int | None = None, with_matches: bool = True) -> dict:
+        """Output buffers of pose_depth_scores() for n_pairs pairs of k keypoints (num_keypoints by default)."""
+        k = self.cfg.num_keypoints if k is None else k
+        keys = lib.POSE_DEPTH_SCORE_KEYS + (lib.MATCH_KNOWN_SCORE_KEYS if with_matches else ())
+        shapes = lib.pose_depth_score_shapes(n_pairs, k)
+        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in keys}
+
+    def pose_depth_scores(self, keypoints_pixel, kp_depth, first, second, T, camera, threshold: float = 3.0,
+                          matches: dict | None = None, out: dict | None = None) -> dict:
+        """pose_scores() against the translation-aware ground truth (csrc/evaluate_depth.hip): every keypoint of frame first[p] is
+        back-projected with its depth kp_depth (N, K) int32 - keypoint_depth()'s output for the same bank - moved by T[p] and
+        projected into frame second[p]; from there the nearest-keypoint search and the list scoring of pose_scores().
+        T: (P, 3, 4), (P, 12) or (P, 4, 4) float64 (device tensor or host array; of a 4 x 4 the top three rows count), camera a
+        coordinates -> camera b coordinates in metres: evaluation.pair_transforms.  camera: an evaluation.Camera; its width x height
+        is the depth image, which the keypoints are scaled to by width / input_size and height / input_size.
+        Returns device tensors per listed pair: gt_matches, gt_count, gt_of_row (-2: the row has no ground truth), valid_count,
+        dist_sum, dist_median, and with matches tp, fp, fn, unknown, value_sum (include/sslam_hip.h).  out:
+        alloc_pose_depth_scores buffers.  Two launches per 65 535 pairs, nothing read on the host."""
+        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
+            raise ValueError("keypoints_pixel (N, K, 2) expected")
+        if not isinstance(kp_depth, torch.Tensor) or tuple(kp_depth.shape) != tuple(keypoints_pixel.shape[:2]):
+            raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
+        if first is None or second is None:
+            raise ValueError("pose_depth_scores needs both pair lists, first= and second=")
+        t = lib.check_threshold(threshold)
+        sx, sy = self.depth_scales(camera)
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)
+        dev, k = keypoints_pixel.device, int(keypoints_pixel.shape[1])
+        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
+        lib.check_pair_lists(first, second, dev)
+        if T is None:
+            raise ValueError("T (P, 3, 4) float64 is required: evaluation.pair_transforms(poses, pairs)")
+        if not isinstance(T, torch.Tensor):
+            T = torch.from_numpy(np.ascontiguousarray(np.asarray(T, dtype=np.float64)))
+        if T.dtype != torch.float64 or tuple(T.shape) not in ((n_pairs, 12), (n_pairs, 3, 4), (n_pairs, 4, 4)):
+            raise ValueError(f"T must be float64 of shape ({n_pairs}, 3, 4), ({n_pairs}, 12) or ({n_pairs}, 4, 4), got {T.dtype} {tuple(T.shape)}")
+        if T.dim() == 3 and T.shape[1] == 4:
+            T = T[:, :3]
+        T = T.to(dev).contiguous().reshape(n_pairs, 12)
+        if matches is not None:
+            if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "value", "match_count")):
+                raise ValueError("matches must be the dictionary match_pairs(rule=...) returned: matches, value, match_count")
+            if tuple(matches["matches"].shape) != (n_pairs, k, 2):
+                raise ValueError(f"matches holds {tuple(matches['matches'].shape)}, the pair lists ask for {(n_pairs, k, 2)}")
+        keys = lib.POSE_DEPTH_SCORE_KEYS + (lib.MATCH_KNOWN_SCORE_KEYS if matches is not None else ())
+        res = dict(out) if out is not None else self.alloc_pose_depth_scores(n_pairs, k, matches is not None)
+        if any(key not in res for key in keys):
+            raise ValueError(f"out must hold {', '.join(keys)} (alloc_pose_depth_scores)")
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
+            b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
+            lib.pose_depth_nn_pairs(keypoints_pixel, kp_depth, first[a:b], second[a:b], T[a:b], camera, sx, sy, t,
+                                    out=tuple(res[key][a:b] for key in lib.POSE_DEPTH_SCORE_KEYS))
+            if matches is not None:
+                lib.match_score_known_pairs(matches["matches"][a:b], matches["value"][a:b], matches["match_count"][a:b],
+                                            res["gt_of_row"][a:b], res["gt_count"][a:b],
+                                            out=tuple(res[key][a:b] for key in lib.MATCH_KNOWN_SCORE_KEYS))
+        return res
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts

@@ -3,7 +3,8 @@ semantic-slam/data/tum_dataset.py:210-273, without the training-pair / augmentat
 
   <sequence>/rgb/*.png          sorted by file name           (tum_dataset.py:212)
   <sequence>/depth/*.png        uint16, metres = value / 5000 (tum_dataset.py:139); paired with rgb BY SORTED INDEX,
-                                truncated to the shorter list (:219-223) - not by associate.py
+                                truncated to the shorter list (:219-223) - not by associate.py; load_depth_raw hands the
+                                raw values to the depth ground truth of sslam_amd.evaluation
   <sequence>/groundtruth.txt    "ts tx ty tz qx qy qz qw"; each frame takes the pose with the nearest timestamp (:248-252)
 
 Quirk kept on purpose: the frame timestamp is float(name.split('.')[0]), i.e. the file name's WHOLE-second part
@@ -82,6 +83,43 @@ class TUMSequence:
         return np.stack([np.asarray(Image.open(self.rgb_path(i)).convert("RGB")) for i in indices])
 
     def load_depth(self, i: int) -> np.ndarray:
-        """(H, W) float32 metres (loaded for completeness: no stage of the path consumes depth)."""
+        """(H, W) float32 metres, the reference's form.  The depth ground truth of sslam_amd.evaluation consumes the raw values:
+        load_depth_raw."""
         from PIL import Image
         return np.asarray(Image.open(self.depth_dir / self.depth_files[i])).astype(np.float32) / 5000.0
+
+    def load_depth_raw(self, indices) -> np.ndarray:
+        """(n, h, w) uint16: the depth PNGs' raw values (metres times 5000, 0 = no measurement), frame i being the i-th depth
+        file - the pairing by sorted index of the class above.  What evaluation.evaluate(depth=) consumes."""
+        from PIL import Image
+        indices = list(indices)
+        if not self.depth_files:
+            raise ValueError(f"no depth images under {self.depth_dir}")
+        if any(not 0 <= i < len(self.depth_files) for i in indices):
+            raise ValueError(f"{len(self.depth_files)} depth frames do not cover the indices")
+        frames = []
+        for i in indices:
+            with Image.open(self.depth_dir / self.depth_files[i]) as im:
+                a = np.asarray(im)
+            if a.ndim != 2 or a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 65535:
+                raise ValueError(f"{self.depth_files[i]}: a single-channel 16-bit depth image expected, got {a.dtype} {a.shape}")
+            frames.append(a.astype(np.uint16))
+        if len({f.shape for f in frames}) > 1:
+            raise ValueError("depth images of unequal size")
+        return np.stack(frames) if frames else np.zeros((0, 0, 0), np.uint16)
+
+
+# Calibrated intrinsics of the three TUM RGB-D sensors (fx, fy, cx, cy); depth images are 640 x 480, 5000 units per metre.
+# freiburg1 and freiburg3 are the values the reference's dataset settings hold; freiburg2 is TUM's published calibration.
+_TUM_INTRINSICS = {"freiburg1": (517.3, 516.5, 318.6, 255.3), "freiburg2": (520.9, 521.0, 325.1, 249.7),
+                   "freiburg3": (535.4, 539.2, 320.1, 247.6)}
+
+
+def camera_for(sequence_name: str):
+    """The evaluation.Camera of a TUM sequence by its name ('rgbd_dataset_freiburg1_xyz', a path ending in it, 'fr1/xyz' is NOT
+    recognised): the calibrated intrinsics of freiburg1 / 2 / 3, else the default Camera() (525 / 319.5 / 239.5)."""
+    from .evaluation import Camera
+    for key, (fx, fy, cx, cy) in _TUM_INTRINSICS.items():
+        if key in str(sequence_name):
+            return Camera(fx=fx, fy=fy, cx=cx, cy=cy)
+    return Camera()

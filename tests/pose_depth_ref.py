@@ -1,0 +1,175 @@
+"""A float64 numpy restatement of the depth ground truth of the scoring stage (csrc/evaluate_depth.hip; include/sslam_hip.h states
+the contract), spelling out the operation order the header gives: every product, quotient and sum below is one numpy float64
+operation, rounded once, in the header's order.  The distances, the nearest-keypoint search, the threshold and the compaction
+are tests/pose_eval_ref.py's own functions, called on the warped points.
+
+Tolerances (none comes from what the code under test gives):
+  integers        equal.  tests/pose_depth_cases.py holds every case >= 1e-6 px (1e-6 m for Z') away from each decision - a tie, the
+                  threshold, a rounding boundary of the depth gather, Z' = 0, a view edge - a million times the rounding of a float64
+                  coordinate below 4096 (4.5e-13), so no integer can turn on a rounding.
+  distances       dist_sum / valid_count and dist_median within ABS = 1e-10 px, the bound tests/pose_eval_ref.py already holds float64
+                  distances to.  Each distance is the same sequence of correctly rounded operations on both sides; only the order
+                  of the sum differs.  Both orders are trees: the device adds a thread's 4 rows, 6 butterfly steps and up to 16 waves
+                  (26 additions deep), numpy sums pairwise over blocks of 128 in 8 lanes (about as deep).  A sum of non-negative
+                  terms d additions deep is off by at most d * 2^-53 relative; a valid row's distance is below the diagonal of
+                  the view plus the keypoint range, < 2000 px, so the two means differ by < 2 * 26 * 1.1e-16 * 2000 = 1.2e-11 px.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+import pose_eval_ref as pr
+
+ABS = pr.ABS_POSED
+
+
+@dataclass(frozen=True)
+class Cam:
+    """The attributes sslam_amd.evaluation.Camera has (the tests of the restatement need no package)."""
+    fx: float = 525.0
+    fy: float = 525.0
+    cx: float = 319.5
+    cy: float = 239.5
+    depth_scale: float = 5000.0
+    width: int = 640
+    height: int = 480
+
+
+def keypoint_depth(depth, kp, scale_x=1.0, scale_y=1.0):
+    """(n, K) int32: depth (n, h, w) uint16 under the keypoints kp (n, K, 2) fp32; -1 outside the image or for a NaN."""
+    n, h, w = depth.shape
+    with np.errstate(invalid="ignore"):
+        u = kp[..., 0].astype(np.float64) * np.float64(scale_x)
+        v = kp[..., 1].astype(np.float64) * np.float64(scale_y)
+        c, r = np.floor(u + 0.5), np.floor(v + 0.5)
+        inside = (c >= 0) & (c < w) & (r >= 0) & (r < h)                 # on the doubles; a NaN fails each
+    ci, ri = np.where(inside, c, 0).astype(np.int64), np.where(inside, r, 0).astype(np.int64)
+    val = depth[np.arange(n)[:, None], ri, ci].astype(np.int32)
+    return np.where(inside, val, -1).astype(np.int32)
+
+
+def project(kp1, d1, T, cam, scale_x=1.0, scale_y=1.0):
+    """kp1 (n, 2) fp32 with raw depths d1 (n,) int32 through T (12 float64, [R | t] row-major).  Returns a dict of float64 arrays:
+    u2, v2 (the projection in depth pixels), Z2, z, warped (n, 2) in keypoint units, valid (n,) bool."""
+    m = np.asarray(T, dtype=np.float64).reshape(12)
+    fx, fy, cx, cy, ds = (np.float64(v) for v in (cam.fx, cam.fy, cam.cx, cam.cy, cam.depth_scale))
+    sx, sy, vw, vh = np.float64(scale_x), np.float64(scale_y), np.float64(cam.width), np.float64(cam.height)
+    x, y = kp1[:, 0].astype(np.float64), kp1[:, 1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        u, v, z = x * sx, y * sy, d1.astype(np.float64) / ds
+        X, Y = ((u - cx) * z) / fx, ((v - cy) * z) / fy
+        X2 = ((m[0] * X + m[1] * Y) + m[2] * z) + m[3]
+        Y2 = ((m[4] * X + m[5] * Y) + m[6] * z) + m[7]
+        Z2 = ((m[8] * X + m[9] * Y) + m[10] * z) + m[11]
+        u2, v2 = (fx * X2) / Z2 + cx, (fy * Y2) / Z2 + cy
+        valid = (d1 > 0) & (Z2 > 0) & (-0.5 <= u2) & (u2 < vw - 0.5) & (-0.5 <= v2) & (v2 < vh - 0.5)
+        warped = np.stack([u2 / sx, v2 / sy], axis=1)
+    return dict(u2=u2, v2=v2, Z2=Z2, z=z, warped=warped, valid=valid)
+
+
+def pose_depth_nn(kp1, kp2, d1, T, cam, threshold, scale_x=1.0, scale_y=1.0):
+    """One pair: dict of gt_matches (n, 2) int64 zero-padded, gt_count, gt_of_row (n,) int32 (-2: no ground truth), valid_count,
+    dist_sum, dist_median, min_dists (inf in the rows without ground truth), valid."""
+    pj = project(kp1, d1, T, cam, scale_x, scale_y)
+    valid = pj["valid"]
+    n = len(kp1)
+    w = np.where(valid[:, None], pj["warped"], 0.0)                       # a row without ground truth searches from (0, 0), dropped below
+    r = pr.pose_nn(w, kp2, None, threshold)                               # pose_eval_ref's distances, argmin, threshold and compaction
+    md = r["min_dists"]
+    kept = r["gt_matches"][:r["gt_count"]]
+    kept = kept[valid[kept[:, 0]]]                                        # its kept rows, those without ground truth taken out
+    gt = np.zeros((n, 2), np.int64)
+    gt[:len(kept)] = kept
+    keep = valid & (r["gt_of_row"] >= 0)
+    row = np.where(valid, r["gt_of_row"], -2).astype(np.int32)
+    v = int(valid.sum())
+    srt = np.sort(np.where(valid, md, np.inf))
+    med = float((srt[(v - 1) >> 1] + srt[v >> 1]) / 2) if v else 0.0
+    return dict(gt_matches=gt, gt_count=int(keep.sum()), gt_of_row=row, valid_count=v, dist_sum=float(md[valid].sum()), dist_median=med,
+                min_dists=np.where(valid, md, np.inf), valid=valid)
+
+
+def absent(n):
+    return dict(pr.absent(n), valid_count=0, valid=np.zeros(n, bool))
+
+
+def pose_depth_nn_pairs(bank, depth_bank, first, second, T, cam, threshold, scale_x=1.0, scale_y=1.0, n1=None, n2=None):
+    """The listed pairs of a bank (n_bank, K, 2) with depths (n_bank, K): a list of pose_depth_nn dicts."""
+    k = bank.shape[1]
+    n1, n2 = k if n1 is None else n1, k if n2 is None else n2
+    out = []
+    for p, (a, b) in enumerate(zip(first, second)):
+        if not (0 <= a < len(bank) and 0 <= b < len(bank)):
+            out.append(absent(n1))
+        else:
+            out.append(pose_depth_nn(bank[a, :n1], bank[b, :n2], depth_bank[a, :n1], T[p], cam, threshold, scale_x, scale_y))
+    return out
+
+
+def match_score_known(pred, values, gt_of_row, gt_count):
+    """tp, fp, fn, unknown, value_sum of one pair's list pred (c, 2) / values (c,) against gt_of_row (-2: no ground truth)."""
+    pred = np.asarray(pred).reshape(-1, 2)
+    n = len(gt_of_row)
+    unknown = int(sum(0 <= i < n and gt_of_row[i] == -2 for i, _ in pred))
+    tp = int(sum(0 <= i < n and gt_of_row[i] != -2 and gt_of_row[i] == j for i, j in pred))
+    return tp, len(pred) - tp - unknown, int(gt_count) - tp, unknown, float(np.asarray(values, dtype=np.float64).sum())
+
+
+def margins(kp1, kp2, d1, T, cam, threshold, scale_x=1.0, scale_y=1.0):
+    """What the case lists hold every pair to, from the restatement's own float64 values: dict of
+    edge  min |nearest distance - threshold| over the valid rows,
+    gap   the least gap from a kept row's nearest point to the nearest point at ANOTHER location,
+    z     min |Z'| over the rows with a depth measurement,
+    view  min distance of a projection to a view edge over the rows with a measurement and Z' > 0
+    (inf where no row qualifies)."""
+    pj = project(kp1, d1, T, cam, scale_x, scale_y)
+    r = pose_depth_nn(kp1, kp2, d1, T, cam, threshold, scale_x, scale_y)
+    valid, md = r["valid"], r["min_dists"]
+    out = dict(edge=np.inf, gap=np.inf, z=np.inf, view=np.inf)
+    if valid.any():
+        out["edge"] = float(np.min(np.abs(md[valid] - threshold)))
+    for i in np.where(valid & (md < threshold))[0]:
+        d = pr.distances(pj["warped"][i:i + 1], kp2, None)[0]
+        other = np.any(kp2 != kp2[d.argmin()], axis=1)
+        if other.any():
+            out["gap"] = min(out["gap"], float(d[other].min() - md[i]))
+    has = d1 > 0
+    if has.any():
+        out["z"] = float(np.min(np.abs(pj["Z2"][has])))
+    front = has & (pj["Z2"] > 0)
+    if front.any():
+        u2, v2 = pj["u2"][front], pj["v2"][front]
+        edges = np.stack([np.abs(u2 + 0.5), np.abs(u2 - (cam.width - 0.5)), np.abs(v2 + 0.5), np.abs(v2 - (cam.height - 0.5))])
+        out["view"] = float(edges.min())
+    return out
+
+
+def gather_margin(kp, scale_x=1.0, scale_y=1.0):
+    """min distance of u + 0.5 and v + 0.5 from an integer over the finite coordinates of kp (.., 2) (inf without one)."""
+    u = kp[..., 0].astype(np.float64) * np.float64(scale_x) + 0.5
+    v = kp[..., 1].astype(np.float64) * np.float64(scale_y) + 0.5
+    t = np.concatenate([u.ravel(), v.ravel()])
+    t = t[np.isfinite(t)]
+    return float(np.min(np.abs(t - np.rint(t)))) if t.size else np.inf
+
+
+def homography_for(R, cam, scale_x=1.0, scale_y=1.0):
+    """H = S^-1 K R K^-1 S (9 float64): what the depth warp reduces to when t = 0, in keypoint units."""
+    K = np.array([[cam.fx, 0, cam.cx], [0, cam.fy, cam.cy], [0, 0, 1.0]])
+    S = np.diag([scale_x, scale_y, 1.0])
+    return (np.linalg.inv(S) @ K @ np.asarray(R, dtype=np.float64) @ np.linalg.inv(K) @ S).reshape(9)
+
+
+def rotation(axis, angle):
+    """Rodrigues: the (3, 3) float64 rotation by `angle` radians about `axis`."""
+    k = np.asarray(axis, dtype=np.float64)
+    k = k / np.linalg.norm(k)
+    kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(angle) * kx + (1 - np.cos(angle)) * (kx @ kx)
+
+
+def rigid(R, t):
+    """(12,) float64 row-major [R | t]."""
+    return np.concatenate([np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64).reshape(3, 1)], axis=1).reshape(12)
