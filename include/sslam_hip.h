@@ -670,6 +670,75 @@ int sslam_match_score_known_pairs(const int64_t *matches, const float *value, co
                                   const int32_t *gt_count, int n1, int n_pairs, int32_t *tp, int32_t *fp, int32_t *fn, int32_t *unknown,
                                   double *value_sum, void *stream);
 
+/* ---- Geometric verification: the relative pose of every listed pair from its match list and the depths under the keypoints
+ * (csrc/pose_estimate.hip).  The scoring entries above take the pose as an input; this one produces it: RANSAC over 3-point
+ * samples, Horn's closed-form absolute orientation, a refit over the inliers.  All arithmetic is float64; every product, quotient,
+ * sum and square root is rounded once, in the order written (no contraction); the sampler is 64-bit integer arithmetic.  One launch
+ * for all pairs, one workgroup per pair, one thread per hypothesis; no atomics, no scratch, no allocation, no host read: capturable.
+ *   kp_bank (n_bank, K, 2) fp32, kp_depth_bank (n_bank, K) int32, pair_first / pair_second (n_pairs) int32: as
+ *   sslam_pose_depth_nn_pairs takes them (an index outside [0, n_bank) makes the pair ABSENT).  matches (n_pairs, n1, 2) int64 and
+ *   count (n_pairs) int32: the lists a finalize entry or sslam_match_rank wrote, rows (idx1 in frame a, idx2 in frame b); only the
+ *   first count[p] SLOTS of a pair are listed, count[p] clamped to [0, n1].  fx .. view_h as in sslam_pose_depth_nn_pairs (view_w
+ *   and view_h are checked and otherwise take no part: the keypoint of frame b exists, so no view test is made); threshold in
+ *   keypoint units; n_hyp hypotheses, 1 .. SSLAM_POSE_MAX_HYP; seed: any 64-bit value.
+ * USABLE ROWS.  A listed slot is usable when 0 <= idx1 < K, 0 <= idx2 < K and both raw depths are > 0.  Its points are the
+ *   back-projections of sslam_pose_depth_nn_pairs: for keypoint (x, y) with raw depth d,
+ *     u = x*scale_x, v = y*scale_y, z = d / depth_scale;  X = ((u - cx) * z) / fx, Y = ((v - cy) * z) / fy, Z = z;
+ *   X_a from frame a's keypoint idx1, X_b from frame b's keypoint idx2.  n_usable counts the usable slots; "usable row u" is the
+ *   u-th of them in slot order, u = 0 .. n_usable - 1.
+ * SAMPLER.  mix(x): x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31 (splitmix64's
+ *   finalizer, modulo 2^64).  draw(h, k, n) = ((mix(seed + 0x9e3779b97f4a7c15 * (3*h + k + 1)) >> 32) * n) >> 32, a function of
+ *   (seed, h, k) and the range alone - not of the pair's position or frames.  Hypothesis h samples the usable rows
+ *     i0 = draw(h, 0, n_usable);   i1 = draw(h, 1, n_usable - 1), plus 1 if >= i0;
+ *     i2 = draw(h, 2, n_usable - 2), plus 1 if >= min(i0, i1), then plus 1 if >= max(i0, i1):   three distinct rows, no rejection.
+ * SOLVER, the same for a hypothesis and for the refit, over a set of rows with a stated order of sums; every sum starts from +0.0:
+ *     c_a = (sum X_a) / n, c_b = (sum X_b) / n, component by component (n the number of rows, as a double);
+ *     M[i][j] = sum (X_a[i] - c_a[i]) * (X_b[j] - c_b[j])                                   (i, j over x, y, z: Sxx = M[0][0], ...)
+ *     N (symmetric 4 x 4):  N00 = (Sxx + Syy) + Szz   N01 = Syz - Szy           N02 = Szx - Sxz           N03 = Sxy - Syx
+ *                                                     N11 = (Sxx - Syy) - Szz   N12 = Sxy + Syx           N13 = Szx + Sxz
+ *                                                                               N22 = (Syy - Sxx) - Szz   N23 = Syz + Szy
+ *                                                                                                         N33 = (Szz - Sxx) - Syy
+ *   Cyclic Jacobi on A = N with V = I: exactly 8 sweeps over (p, q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a rotation is skipped
+ *   when a_pq == 0.0; otherwise
+ *     theta = (a_qq - a_pp) / (2 * a_pq);   t = sgn / (|theta| + sqrt(theta*theta + 1)), sgn = -1 for theta < 0, else +1;
+ *     c = 1 / sqrt(t*t + 1);   s = t * c;   h = t * a_pq;   a_pp = a_pp - h;   a_qq = a_qq + h;   a_pq = 0;
+ *     for the two r outside {p, q}, with g = a_rp, k = a_rq (symmetric entries):  a_rp = c*g - s*k;   a_rq = s*g + c*k;
+ *     for every row r of V, with g = v_rp, k = v_rq:                              v_rp = c*g - s*k;   v_rq = s*g + c*k.
+ *   (w, x, y, z) = the column of V under the largest diagonal entry of A, the lowest index on equality; each divided by
+ *   sqrt(((w*w + x*x) + y*y) + z*z); all four negated when w < 0.  With ww = w*w, ...:
+ *     r00 = ((ww + xx) - yy) - zz   r01 = 2 * (x*y - w*z)         r02 = 2 * (x*z + w*y)
+ *     r10 = 2 * (x*y + w*z)         r11 = ((ww - xx) + yy) - zz   r12 = 2 * (y*z - w*x)
+ *     r20 = 2 * (x*z - w*y)         r21 = 2 * (y*z + w*x)         r22 = ((ww - xx) - yy) + zz
+ *     t_i = c_b[i] - ((r_i0 * c_a[0] + r_i1 * c_a[1]) + r_i2 * c_a[2]).
+ *   A hypothesis sums its three rows in the order i0, i1, i2: ((0 + r0) + r1) + r2.  No transcendental function anywhere.
+ * SCORE of a pose [R | t] on a usable row: X', Y', Z', u', v' from X_a by the formulas of sslam_pose_depth_nn_pairs;
+ *   dx = u' / scale_x - x_b, dy = v' / scale_y - y_b against frame b's keypoint; s = dx*dx + dy*dy; the row is an INLIER iff
+ *   Z' > 0 and sqrt(s) < threshold (a NaN fails both).  A pose with a non-finite entry has no inliers.
+ *   The best hypothesis has the most inliers, the lowest h on equality.
+ * REFIT, when the best hypothesis has 3 inliers at least: the solver over its inliers, n = their number.  THE ORDER of each sum:
+ *   thread t of 256 adds, from +0.0, the terms of the usable rows t, t + 256, t + 512, ... ascending, a row that is no inlier
+ *   adding +0.0; then lanes by xor 32 .. 1 within each wave of 64; then the four waves, ((w0 + w1) + w2) + w3: one order per
+ *   n_usable, whatever n_hyp.  The refit is scored; it is KEPT iff its inlier count is >= the hypothesis'; else the hypothesis stays.
+ * Outputs, per pair:
+ *     T (n_pairs, 12) float64         [R | t] row-major, camera a -> camera b, as sslam_pose_depth_nn_pairs takes it;
+ *     inlier_count, usable_count, best_hypothesis, refit_kept (n_pairs) int32 each: the inliers of T, n_usable, h, 0 or 1;
+ *     inlier_of_slot (n_pairs, n1) int32    per slot: 1 an inlier of T, 0 not, -1 listed but not usable; 0 past the count;
+ *     rms (n_pairs) float64           sqrt((sum s) / inlier_count) over the inliers of T, the sum in the refit's order; 0 without.
+ *   NO POSE - an absent pair (no slot is usable: the whole mask is 0) or n_usable < 3: T = [I | 0], inlier_count 0,
+ *   usable_count = n_usable, best_hypothesis -1, refit_kept 0, rms 0; the mask is 0 in the usable slots, -1 in the other listed ones.
+ *   A pair's outputs are a function of that pair's rows, the camera, the threshold, n_hyp and the seed alone.  NaN keypoints under
+ *   a positive depth are outside the contract, as for the entries above: the outputs stay inside their arrays.
+ * SSLAM_E_INVALID: a NULL or misaligned pointer; a non-positive size; n1 above K; n_hyp outside 1 .. SSLAM_POSE_MAX_HYP; a threshold
+ * that is negative, NaN or infinite; fx, fy, depth_scale, scale_x, scale_y, view_w or view_h not finite and positive; cx or cy not
+ * finite.  SSLAM_E_UNSUPPORTED: K above SSLAM_EVAL_MAX_K.  Every refusal comes before anything is launched. */
+#define SSLAM_POSE_MAX_HYP 1024
+int sslam_pose_ransac_pairs(const float *kp_bank, const int32_t *kp_depth_bank, int n_bank, int K, const int32_t *pair_first,
+                            const int32_t *pair_second, int n_pairs, const int64_t *matches, const int32_t *count, int n1, double fx,
+                            double fy, double cx, double cy, double depth_scale, double scale_x, double scale_y, double view_w,
+                            double view_h, double threshold, int n_hyp, uint64_t seed, double *T, int32_t *inlier_count,
+                            int32_t *usable_count, int32_t *best_hypothesis, int32_t *refit_kept, int32_t *inlier_of_slot, double *rms,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

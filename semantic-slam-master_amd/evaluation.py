@@ -6,7 +6,8 @@ keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (
     evaluate_matches               DescriptorQualityTester.evaluate_matches               test/test_descriptor_quality.py:187-231
 
 Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate_depth.hip):
-compute_repeatability_depth and compute_ground_truth_matches_depth.
+compute_repeatability_depth and compute_ground_truth_matches_depth - and, beside matching.py's matchers, the step that follows
+them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
 result.  There is no CPU implementation here: without the GPU library these functions raise.
@@ -109,6 +110,49 @@ def compute_ground_truth_matches_depth(kpts1, kpts2, depth1, T_rel, camera, thre
     _, (gt, cnt, _, _, _, _) = _pose_depth_nn(kpts1, kpts2, depth1, T_rel, camera, threshold)
     out = gt[0, :int(cnt.item())]
     return out if isinstance(kpts1, torch.Tensor) else out.cpu().numpy()
+
+
+def estimate_relative_pose(kp1, kp2, depth1, depth2, matches, camera=None, threshold: float = 3.0, hypotheses: int = 256, seed: int = 0):
+    """The rigid motion from camera 1 to camera 2 that the matches agree on: kp1 (N, 2) and kp2 (M, 2) in the pixels of the raw
+    depth images depth1, depth2 (h, w) uint16 of their frames (scale 1), matches (P, 2) [idx1, idx2] as a matcher returns them,
+    camera an sslam_amd.evaluation.Camera (the default one if None).  RANSAC over 3-point samples of the matches with a depth on
+    both sides, Horn's closed form, a refit over the inliers (sslam_pose_ransac_pairs, include/sslam_hip.h); threshold is the
+    reprojection distance in pixels.  numpy in, numpy out; one pair.
+    Returns (T (4, 4) float64 with X_2 = T X_1 - the identity when fewer than 3 matches have both depths -, inlier mask (P,) bool)."""
+    from sslam_amd.evaluation import Camera
+    camera = Camera() if camera is None else camera
+    lib.check_camera(camera)
+    t, n_hyp, seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+    depths = []
+    for name, d in (("depth1", depth1), ("depth2", depth2)):
+        d = torch.from_numpy(np.ascontiguousarray(d)) if isinstance(d, np.ndarray) else d
+        if not isinstance(d, torch.Tensor) or d.dtype != torch.uint16 or d.dim() != 2:
+            raise ValueError(f"{name} (h, w) uint16 expected: the frame's raw depth image")
+        check_depth_size(d.shape[1], d.shape[0], camera)
+        depths.append(d)
+    k1, k2 = np.asarray(kp1, dtype=np.float32), np.asarray(kp2, dtype=np.float32)
+    if k1.ndim != 2 or k2.ndim != 2 or k1.shape[1] != 2 or k2.shape[1] != 2 or k1.shape[0] < 1 or k2.shape[0] < 1:
+        raise ValueError(f"keypoints (N >= 1, 2) and (M >= 1, 2) expected, got {k1.shape} and {k2.shape}")
+    mt = np.asarray(matches)
+    if mt.size == 0:
+        return np.eye(4), np.zeros(0, bool)
+    if mt.ndim != 2 or mt.shape[1] != 2 or mt.dtype.kind not in "iu":
+        raise ValueError(f"matches (P, 2) of integer indices expected, got {mt.shape} {mt.dtype}")
+    k, p = max(len(k1), len(k2), len(mt)), len(mt)
+    if k > lib.EVAL_MAX_K:
+        raise lib.SslamHipError(f"estimate_relative_pose: {k} keypoints or matches; at most {lib.EVAL_MAX_K} are handled on the device")
+    bank = torch.zeros((2, k, 2), dtype=torch.float32, device="cuda")
+    bank[0, :len(k1)], bank[1, :len(k2)] = _dev(k1, torch.float32), _dev(k2, torch.float32)
+    kp_depth = torch.full((2, k), -1, dtype=torch.int32, device="cuda")         # the padding rows: no depth, never usable
+    for f, (d, n) in enumerate(zip(depths, (len(k1), len(k2)))):
+        kp_depth[f, :n] = lib.keypoint_depth(d.to("cuda").contiguous()[None], bank[f:f + 1, :n].contiguous())[0]      # pixel units: scale 1
+    first = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    count = torch.full((1,), p, dtype=torch.int32, device="cuda")
+    out = lib.pose_ransac_pairs(bank, kp_depth, first, first + 1, _dev(mt.astype(np.int64)[None], torch.int64), count, camera, 1.0, 1.0,
+                                t, n_hyp, seed)
+    T = np.eye(4)
+    T[:3] = out[0].cpu().numpy().reshape(3, 4)
+    return T, out[5][0].cpu().numpy() == 1
 
 
 def evaluate_matches(pred_matches, gt_matches, num_kpts1: int, num_kpts2: int) -> dict:

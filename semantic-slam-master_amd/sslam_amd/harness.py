@@ -418,7 +418,9 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     beside it must be one) and scored against the poses of groundtruth.txt: the result gains 'evaluation', {spacing:
     {'repeatability': ..., 'descriptor_quality': ...}} for every spacing that has a pair.  A key "depth": True reads the
     sequence's depth PNGs as well (TUMSequence.load_depth_raw) and scores against the translation-aware ground truth
-    (evaluate_result's depth=) with tum.camera_for(sequence), or with the Camera given under "camera".
+    (evaluate_result's depth=) with tum.camera_for(sequence), or with the Camera given under "camera".  A key "odometry": True
+    (it needs the depth PNGs and the poses too) adds 'odometry', {spacing: odometry.odometry_result's dictionary} over the same
+    pairs at the same threshold: the pose every pair's match list agrees on, its inlier ratio, RPE and - at spacing 1 - ATE.
     Returns StreamingSequence.result() plus 'files' and 'timestamps'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -436,7 +438,10 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
         with_depth = evaluate.pop("depth", False)
         if not isinstance(with_depth, bool):
             raise ValueError('evaluate["depth"] is a flag, True or False: the images are read from the sequence directory')
-        if not with_depth and "camera" in evaluate:
+        with_odometry = evaluate.pop("odometry", False)
+        if not isinstance(with_odometry, bool):
+            raise ValueError('evaluate["odometry"] is a flag, True or False')
+        if not (with_depth or with_odometry) and "camera" in evaluate:
             raise ValueError('evaluate["camera"] describes the depth images: it needs "depth": True')
         if rule is None:
             rule = MatchRule.mnn_ratio(0.9 if ratio is None else ratio)
@@ -446,7 +451,7 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     n = len(tum)
     if n == 0:
         raise ValueError(f"no rgb frames under {tum.rgb_dir}")
-    if evaluate is not None and with_depth:                  # what the depth scoring needs is judged before the sequence is run
+    if evaluate is not None and (with_depth or with_odometry):      # what the depth scoring needs is judged before the sequence is run
         from .tum import camera_for
         if not tum.depth_files:
             raise ValueError(f'evaluate["depth"]: no depth images under {tum.depth_dir}')
@@ -492,10 +497,18 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     res["files"] = list(tum.rgb_files)
     res["timestamps"] = list(tum.timestamps)
     if evaluate is not None:
-        if with_depth:                                       # the keypoint depths depend on the frames alone: one gather for all spacings
+        if with_depth or with_odometry:                      # the keypoint depths depend on the frames alone: one gather for all spacings
             need = min(n, max(len(evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))) + s for s in seq.spacings))
+            kp_depth = evaluation.gather_keypoint_depth(pipe, tum.load_depth_raw(range(need)), res["frames"]["keypoints_pixel"], need)
+        if with_depth:
             evaluate["camera"] = depth_camera
-            evaluate["kp_depth"] = evaluation.gather_keypoint_depth(pipe, tum.load_depth_raw(range(need)), res["frames"]["keypoints_pixel"], need)
+            evaluate["kp_depth"] = kp_depth
         res["evaluation"] = {s: evaluation.evaluate_result(pipe, res, tum.poses, spacing=s, sequence=sequence, **evaluate)
                              for s in seq.spacings if s in res}
+        if with_odometry:                                    # the same pairs, the same threshold: the pose each list agrees on
+            from . import odometry
+            res["odometry"] = {s: odometry.odometry_result(pipe, res, camera=depth_camera, poses=tum.poses, spacing=s,
+                                                           num_pairs=int(evaluate.get("num_pairs", 50)),
+                                                           threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth)
+                               for s in seq.spacings if s in res and evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))}
     return res

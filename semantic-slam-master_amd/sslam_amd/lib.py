@@ -88,6 +88,7 @@ EXPORTS = [
     "sslam_sim_argmax_rows_pairs_d", "sslam_row_lse_d", "sslam_row_lse_pairs_d", "sslam_val_frame_stats_d",
     "sslam_match_rank", "sslam_pose_nn_pairs", "sslam_match_score_pairs",
     "sslam_keypoint_depth", "sslam_pose_depth_nn_pairs", "sslam_match_score_known_pairs",
+    "sslam_pose_ransac_pairs",
 ]
 
 
@@ -135,6 +136,7 @@ def lib():
         L.sslam_keypoint_depth.argtypes = [p, i, i, i, p, i, d, d, p, p]
         L.sslam_pose_depth_nn_pairs.argtypes = [p, p, i, i, i, i, p, p, i, p] + [d] * 10 + [p, p, p, p, p, p, p]
         L.sslam_match_score_known_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p, p]
+        L.sslam_pose_ransac_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [i, C.c_uint64] + [p] * 7 + [p]
         L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
         L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
         L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
@@ -1033,6 +1035,77 @@ def match_score_known_pairs(matches, value, count, gt_of_row, gt_count, out=None
     o = _depth_score_out(None, MATCH_KNOWN_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
     _run("match_score_known_pairs", lib().sslam_match_score_known_pairs, (matches, value, count, gt_of_row, gt_count, *o),
          _dp(matches), _dp(value), _dp(count), _dp(gt_of_row), _dp(gt_count), n1, n_pairs, *(_dp(x) for x in o))
+    return tuple(o)
+
+
+# ------------------------------------------------------------------------------- relative pose from matches and depth (pose_estimate.hip)
+POSE_MAX_HYP = 1024     # SSLAM_POSE_MAX_HYP
+POSE_RANSAC_KEYS = ("T", "inlier_count", "usable_count", "best_hypothesis", "refit_kept", "inlier_of_slot", "rms")
+
+
+def pose_ransac_shapes(n_pairs: int, n1: int) -> dict:
+    """name -> (shape, dtype) of the outputs of pose_ransac_pairs for n_pairs pairs with lists of n1 slots."""
+    one = ((n_pairs,), torch.int32)
+    return {"T": ((n_pairs, 12), torch.float64), "inlier_count": one, "usable_count": one, "best_hypothesis": one, "refit_kept": one,
+            "inlier_of_slot": ((n_pairs, n1), torch.int32), "rms": ((n_pairs,), torch.float64)}
+
+
+def check_hypotheses(hypotheses) -> int:
+    """The number of RANSAC hypotheses: an int in 1 .. POSE_MAX_HYP, else ValueError - before any device work."""
+    if isinstance(hypotheses, bool) or not isinstance(hypotheses, (int, np.integer)) or not 1 <= int(hypotheses) <= POSE_MAX_HYP:
+        raise ValueError(f"hypotheses must be an int in [1, {POSE_MAX_HYP}], got {hypotheses!r}")
+    return int(hypotheses)
+
+
+def check_seed(seed) -> int:
+    """The sampler's seed: an int in [0, 2^64), else ValueError."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
+    return int(seed)
+
+
+def pose_ransac_pairs(kp_bank, kp_depth_bank, first, second, matches, count, camera, scale_x=1.0, scale_y=1.0, threshold=3.0,
+                      hypotheses=256, seed=0, out=None):
+    """sslam_pose_ransac_pairs: kp_bank (n_bank, K, 2) fp32 and kp_depth_bank (n_bank, K) int32 (keypoint_depth's output for the same
+    bank); first / second as pose_nn_pairs takes them; matches (P, n1, 2) int64 and count (P,) int32: the lists a matcher or
+    match_rank wrote for the same pairs; camera: an evaluation.Camera; scale_x / scale_y: keypoint units to depth pixels;
+    threshold in keypoint units; hypotheses in 1 .. POSE_MAX_HYP; seed: the sampler's 64-bit seed.
+    Returns (T (P, 12) float64 [R | t] camera first -> camera second, inlier_count, usable_count, best_hypothesis, refit_kept (P,)
+    int32, inlier_of_slot (P, n1) int32, rms (P,) float64) - POSE_RANSAC_KEYS, include/sslam_hip.h states them.  out: optional
+    tensors of those shapes.  One launch, no host read."""
+    _check_bank("kp_bank", kp_bank, ("K", 2))
+    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
+    if kp_depth_bank is None:
+        raise ValueError("kp_depth_bank is required")
+    _check_arrays((n_bank, k), ("kp_depth_bank", kp_depth_bank, torch.int32))
+    n_pairs = check_pair_lists(first, second, kp_bank.device)
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_pairs or \
+            not 1 <= int(matches.shape[1]) <= k:
+        raise ValueError(f"matches must be a tensor of shape ({n_pairs}, n1 in [1, {k}], 2)")
+    n1 = int(matches.shape[1])
+    if count is None:
+        raise ValueError("count is required")
+    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+    _check_arrays((n_pairs,), ("count", count, torch.int32))
+    t = check_threshold(threshold)
+    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
+    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
+    n_hyp, seed = check_hypotheses(hypotheses), check_seed(seed)
+    if k > EVAL_MAX_K:
+        raise SslamHipError(f"pose_ransac_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are handled on the device")
+    shapes = pose_ransac_shapes(n_pairs, n1)
+    if out is not None:
+        if len(out) != len(POSE_RANSAC_KEYS):
+            raise ValueError(f"out must hold {len(POSE_RANSAC_KEYS)} tensors: {', '.join(POSE_RANSAC_KEYS)}")
+        for key, x in zip(POSE_RANSAC_KEYS, out):
+            if x is None:
+                raise ValueError(f"out `{key}` is required")
+            _check_arrays(shapes[key][0], (f"out `{key}`", x, shapes[key][1]))
+    dev = common_device(kp_bank, kp_depth_bank, first, second, matches, count)
+    o = list(out) if out is not None else [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in POSE_RANSAC_KEYS]
+    _run("pose_ransac_pairs", lib().sslam_pose_ransac_pairs, (kp_bank, kp_depth_bank, first, second, matches, count, *o),
+         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1,
+         *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), n_hyp, C.c_uint64(seed), *(_dp(x) for x in o))
     return tuple(o)
 
 

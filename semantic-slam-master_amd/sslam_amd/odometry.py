@@ -1,0 +1,225 @@
+"""Frame-to-frame odometry from the device's own features: the relative pose of every pair from its match list and the depth under
+the keypoints (SequencePipeline.estimate_poses; csrc/pose_estimate.hip), the chained trajectory, and the two figures the
+reference judges itself against ORB-SLAM3 by - RPE and ATE (scripts/evaluate_baseline.py:57-129, which computes them with evo
+for a baseline's trajectory file and has no way to produce either for its own features).
+
+Everything here is host-side float64 numpy on the per-pair numbers read back ONCE: extraction, the depth gather, matching and the
+RANSAC launch all stay on the device.
+
+  per pair          E = inv(T_gt) @ T_est with T_gt = evaluation.relative_transform(pose_a, pose_b); the translation error is
+                    |E[:3, 3]| in metres, the rotation error the angle of E[:3, :3] in degrees (evo's RPE of one pair);
+                    inlier_ratio = inlier_count / match_count - a quality figure that needs no ground truth
+  rpe_summary       rmse / mean / median / std (np.std, evo's) of both, the keys of the reference's compute_rpe
+  ate_summary       the estimated positions aligned to the true ones by a rigid motion WITHOUT scale (Kabsch), then the same
+                    statistics and min / max of the position errors: the keys of compute_ate
+  chain             pose_{i+1} = pose_i @ inv(T_i): camera-to-world poses, as TUM's groundtruth.txt has them, from the
+                    camera-i -> camera-(i+1) transforms of consecutive pairs
+
+The keypoints are patch centres on a 16-pixel grid.  Nobody has measured which reprojection threshold suits them on real data:
+no real RGB-D sequence was at hand when this was written.  3.0 keypoint units is only the scoring stage's default, taken over here.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import lib
+from .evaluation import Camera, check_depth_size, gather_keypoint_depth, relative_transform
+from .pipeline import MatchRule
+
+_INT_KEYS = ("inlier_count", "usable_count", "best_hypothesis", "refit_kept")
+
+
+def _as44(T) -> np.ndarray:
+    """(P, 4, 4) float64 from (P, 12), (P, 3, 4) or (P, 4, 4)."""
+    T = np.asarray(T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T, dtype=np.float64)
+    if T.ndim == 2 and T.shape[1] == 12:
+        T = T.reshape(-1, 3, 4)
+    if T.ndim != 3 or tuple(T.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"transforms (P, 12), (P, 3, 4) or (P, 4, 4) expected, got {T.shape}")
+    if T.shape[1] == 3:
+        T = np.concatenate([T, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (len(T), 1, 4))], axis=1)
+    return T
+
+
+def _check_poses(poses) -> np.ndarray:
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+        raise ValueError(f"poses (N, 4, 4) expected, got {poses.shape}")
+    return poses
+
+
+def rotation_angle_deg(R) -> float:
+    """The angle of a 3 x 3 rotation in degrees: arccos((trace - 1) / 2), the argument clipped to [-1, 1]."""
+    return float(np.degrees(np.arccos(np.clip((np.trace(np.asarray(R, dtype=np.float64)) - 1.0) / 2.0, -1.0, 1.0))))
+
+
+def relative_pose_errors(T_est, poses, pairs) -> dict:
+    """Per pair (a, b) of `pairs`: E = inv(T_gt) @ T_est with T_gt = relative_transform(poses[a], poses[b]).
+    T_est: (P, 12), (P, 3, 4) or (P, 4, 4), camera a -> camera b.  Returns {'translation': (P,) metres, 'rotation': (P,) degrees}."""
+    T_est, poses = _as44(T_est), _check_poses(poses)
+    if len(T_est) != len(pairs):
+        raise ValueError(f"{len(T_est)} transforms for {len(pairs)} pairs")
+    if any(not (0 <= a < len(poses) and 0 <= b < len(poses)) for a, b in pairs):
+        raise ValueError(f"{len(poses)} poses do not cover the pairs")
+    E = [np.linalg.inv(relative_transform(poses[a], poses[b])) @ T for (a, b), T in zip(pairs, T_est)]
+    return {"translation": np.array([np.linalg.norm(e[:3, 3]) for e in E], dtype=np.float64),
+            "rotation": np.array([rotation_angle_deg(e[:3, :3]) for e in E], dtype=np.float64)}
+
+
+def _statistics(v, extremes: bool = False) -> dict:
+    v = np.asarray(v, dtype=np.float64)
+    if v.ndim != 1 or v.size == 0:
+        raise ValueError("one error per pair (or pose) expected, for at least one")
+    out = {"rmse": float(np.sqrt(np.mean(v * v))), "mean": float(np.mean(v)), "median": float(np.median(v)), "std": float(np.std(v))}
+    if extremes:
+        out.update(min=float(np.min(v)), max=float(np.max(v)))
+    return out
+
+
+def rpe_summary(errors: dict) -> dict:
+    """relative_pose_errors' dictionary -> the reference's compute_rpe dictionary: {'translation': rmse / mean / median / std in
+    metres, 'rotation': the same in degrees}."""
+    if not isinstance(errors, dict) or any(key not in errors for key in ("translation", "rotation")):
+        raise ValueError("the dictionary relative_pose_errors returned expected")
+    return {"translation": _statistics(errors["translation"]), "rotation": _statistics(errors["rotation"])}
+
+
+def align_rigid(src, dst) -> tuple:
+    """(R, t) of the rigid motion WITHOUT scale that takes the points src (N, 3) closest to dst (N, 3) in the least-squares sense
+    (Kabsch, with the reflection guard): dst ~ R src + t."""
+    src, dst = np.asarray(src, dtype=np.float64), np.asarray(dst, dtype=np.float64)
+    if src.shape != dst.shape or src.ndim != 2 or src.shape[1] != 3 or len(src) == 0:
+        raise ValueError(f"two (N, 3) point sets expected, got {src.shape} and {dst.shape}")
+    cs, cd = src.mean(axis=0), dst.mean(axis=0)
+    U, _, Vt = np.linalg.svd((dst - cd).T @ (src - cs))
+    S = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0 else -1.0])
+    R = U @ S @ Vt
+    return R, cd - R @ cs
+
+
+def ate_summary(trajectory, poses) -> dict:
+    """The reference's compute_ate dictionary (rmse / mean / median / std / min / max, metres) for an estimated trajectory (N, 4, 4)
+    against the true poses (N, 4, 4), both camera-to-world: the positions are aligned rigidly without scale, then compared."""
+    est, gt = _as44(trajectory), _check_poses(poses)
+    if len(est) != len(gt):
+        raise ValueError(f"{len(est)} estimated poses against {len(gt)} true ones")
+    R, t = align_rigid(est[:, :3, 3], gt[:, :3, 3])
+    return _statistics(np.linalg.norm(est[:, :3, 3] @ R.T + t - gt[:, :3, 3], axis=1), extremes=True)
+
+
+def chain(T, start=None) -> np.ndarray:
+    """(P + 1, 4, 4) camera-to-world poses from the P transforms camera i -> camera i + 1 of consecutive pairs:
+    pose_0 = start (the identity if None), pose_{i+1} = pose_i @ inv(T_i)."""
+    T = _as44(T)
+    pose = np.eye(4) if start is None else np.asarray(start, dtype=np.float64)
+    if pose.shape != (4, 4):
+        raise ValueError(f"start must be a 4 x 4 pose, got {pose.shape}")
+    out = [pose]
+    for Ti in T:
+        out.append(out[-1] @ np.linalg.inv(Ti))
+    return np.stack(out)
+
+
+def consecutive_pairs(n_frames: int, spacing: int = 1, num_pairs=None) -> list:
+    """The pairs (i, i + spacing), i = 0 .. n_frames - spacing - 1, the first num_pairs of them if given."""
+    for name, v, lo in (("n_frames", n_frames, 0), ("spacing", spacing, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    if num_pairs is not None and (isinstance(num_pairs, bool) or not isinstance(num_pairs, (int, np.integer)) or num_pairs < 1):
+        raise ValueError(f"num_pairs must be None or an integer >= 1, got {num_pairs!r}")
+    p = max(0, int(n_frames) - int(spacing))
+    return [(i, i + int(spacing)) for i in range(p if num_pairs is None else min(p, int(num_pairs)))]
+
+
+def _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n_frames, keypoints_shape=None):
+    """Everything odometry / odometry_result can refuse before any device work -> the Camera to use."""
+    lib.check_threshold(threshold)
+    lib.check_hypotheses(hypotheses)
+    lib.check_seed(seed)
+    camera = Camera() if camera is None else camera
+    lib.check_camera(camera)
+    if poses is not None and len(_check_poses(poses)) < n_frames:
+        raise ValueError(f"{len(poses)} poses, the pairs name {n_frames} frames")
+    if kp_depth is not None:
+        if depth is not None:
+            raise ValueError("depth= and kp_depth= are two forms of one argument: pass one")
+        if not isinstance(kp_depth, torch.Tensor) or kp_depth.dtype != torch.int32 or \
+                (keypoints_shape is not None and tuple(kp_depth.shape) != tuple(keypoints_shape[:2])):
+            raise ValueError("kp_depth must be the int32 tensor gather_keypoint_depth returned for these keypoints")
+        return camera
+    ok = (isinstance(depth, np.ndarray) and depth.dtype == np.uint16) or (isinstance(depth, torch.Tensor) and depth.dtype == torch.uint16)
+    if not ok or depth.ndim != 3:
+        raise ValueError("odometry needs depth: (N, h, w) uint16 raw depth images, numpy or tensor")
+    if int(depth.shape[0]) < n_frames:
+        raise ValueError(f"depth holds {int(depth.shape[0])} frames, the pairs name {n_frames}")
+    check_depth_size(depth.shape[2], depth.shape[1], camera)
+    return camera
+
+
+def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed) -> dict:
+    """The RANSAC launch on the listed pairs, ONE host read-back of (P, 18) float64, the host-side figures."""
+    first, second = [a for a, _ in pairs], [b for _, b in pairs]
+    est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
+    cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
+           [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
+    host = torch.cat(cols, dim=1).cpu().numpy()             # integers up to 4096: exact in float64
+    T = _as44(host[:, :12])
+    out = {"pairs": list(pairs), "T": T}
+    out.update({key: host[:, 12 + i].astype(np.int64) for i, key in enumerate(_INT_KEYS)})
+    out["match_count"] = host[:, 16].astype(np.int64)
+    out["rms"] = host[:, 17].copy()
+    out["inlier_ratio"] = np.where(out["match_count"] > 0, out["inlier_count"] / np.maximum(out["match_count"], 1), 0.0)
+    if spacing == 1:
+        out["trajectory"] = chain(T, None if poses is None else np.asarray(poses, dtype=np.float64)[pairs[0][0]])
+    if poses is not None:
+        out["rpe"] = rpe_summary(relative_pose_errors(T, poses, pairs))
+        out["ate"] = ate_summary(out["trajectory"], np.asarray(poses, dtype=np.float64)[:len(pairs) + 1]) if spacing == 1 else None
+    return out
+
+
+def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None, rule=None,
+             threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None) -> dict:
+    """The relative pose of every pair (i, i + spacing) of a sequence, from its own features: the frames images_u8 (N, H, W, 3)
+    uint8 (a pipeline built with vit=) or their ViT tokens (tokens=), their raw depth images depth (N, h, w) uint16 (numpy or
+    tensor) and camera (an evaluation.Camera; the default one if None).  The frames are extracted once, the depth under every
+    keypoint gathered (evaluation.gather_keypoint_depth), the pairs matched under `rule` (MatchRule.mnn_ratio(0.9) if None) and
+    the poses estimated (SequencePipeline.estimate_poses: threshold in keypoint units, hypotheses, seed); ONE read-back.
+    Returns, per pair: 'pairs', 'T' (P, 4, 4) camera i -> camera i + spacing, 'inlier_count', 'usable_count', 'best_hypothesis',
+    'refit_kept', 'match_count', 'rms', 'inlier_ratio' = inlier_count / match_count; for spacing 1 'trajectory' (P + 1, 4, 4), the
+    chained camera-to-world poses starting at the identity (at poses[0] with poses); with poses (N, 4, 4) also 'rpe'
+    (rpe_summary) and 'ate' (ate_summary of the trajectory; None for another spacing)."""
+    src = tokens if tokens is not None else images_u8
+    if src is None:
+        raise ValueError("images_u8 or tokens= required")
+    pairs = consecutive_pairs(int(src.shape[0]), spacing, num_pairs)
+    if not pairs:
+        raise ValueError(f"{int(src.shape[0])} frames hold no pair at spacing {spacing}")
+    n = pairs[-1][1] + 1
+    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
+    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
+    ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
+    kp_depth = gather_keypoint_depth(pipe, depth, ex["keypoints_pixel"], n)
+    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
+    return _estimate(pipe, ex["keypoints_pixel"], kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed)
+
+
+def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None,
+                    threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, *, kp_depth=None) -> dict:
+    """odometry() for a StreamingSequence.result() / run_frames / run_directory result: the keypoints and the match lists of every
+    pair (i, i + spacing) are already in device memory, under whichever rule the sequence was run with, so nothing is extracted
+    or matched again.  depth=: the raw depth images of the result's frames; kp_depth=: instead, the (N, K) int32 bank
+    gather_keypoint_depth returned for result["frames"]["keypoints_pixel"], as evaluation.evaluate_result takes it."""
+    if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
+        raise ValueError("a StreamingSequence / run_directory result expected")
+    kp = result["frames"]["keypoints_pixel"]
+    pairs = consecutive_pairs(int(kp.shape[0]), spacing, num_pairs)
+    if not pairs or spacing not in result:
+        raise ValueError(f"the result holds no pair at spacing {spacing}")
+    n = pairs[-1][1] + 1
+    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
+    mm = result[spacing]
+    matches = {key: mm[key][:len(pairs)] for key in ("matches", "match_count")}
+    if kp_depth is None:
+        kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
+    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed)

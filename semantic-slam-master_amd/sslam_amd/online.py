@@ -291,3 +291,56 @@ class RankedFrameStepper(RuleFrameStepper):
         else:
             out["best"] = None if first else {k: v[0] for k, v in self.ranked.items()}
         return out
+
+
+class PoseFrameStepper(RuleFrameStepper):
+    """RuleFrameStepper whose step also estimates the camera's motion since the previous frame: the online form of
+    sslam_amd.odometry, previous-frame form only (no spacings=).  step() takes the frame's raw depth image beside it; behind the
+    finalize launch, on the same one stream - as ordinary launches or inside the captured graph - the depth under this frame's
+    keypoints is gathered (sslam_keypoint_depth) into slot 1 of a two-slot bank, sslam_pose_ransac_pairs runs on pair (0, 1) with
+    the step's own match list, and slot 1 is handed over to slot 0 as the frame's features are.  The sampler depends on the
+    seed alone, not on the pair's place, so a step's pose is bit for bit the row the batched odometry() gives for the same two
+    frames.  step() returns what the parent returns plus "pose": T (12,) float64 [R | t] previous camera -> this camera,
+    inlier_count, usable_count, best_hypothesis, refit_kept, inlier_of_slot (K,), rms - views of static buffers, None before the
+    second frame.  rule: MatchRule.mnn_ratio(0.9) if None, as odometry() has it."""
+
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, depth_height: int, depth_width: int, camera=None,
+                 use_graph: bool = True, tokens_in: bool = False, rule=None, threshold: float = 3.0, hypotheses: int = 256,
+                 seed: int = 0):
+        from .evaluation import Camera, check_depth_size
+        from .pipeline import MatchRule
+        self.threshold, self.hypotheses, self.seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+        self.camera = Camera() if camera is None else camera
+        check_depth_size(depth_width, depth_height, self.camera)      # before anything is allocated
+        super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=None,
+                         rule=MatchRule.mnn_ratio(0.9) if rule is None else rule)
+        dev, K = self.device, self.cfg.num_keypoints
+        self.depth = torch.zeros((1, depth_height, depth_width), dtype=torch.uint16, device=dev)
+        self.kp_depth = torch.full((2, K), -1, dtype=torch.int32, device=dev)       # slot 0: the previous frame's, slot 1: this frame's
+        self._first = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._second = torch.ones((1,), dtype=torch.int32, device=dev)
+        self.pose = pipe.alloc_pose(1, K)
+
+    def _after_match(self) -> None:
+        p = self.pipe
+        p.keypoint_depth(self.depth, self.cur["keypoints_pixel"], out=self.kp_depth[1:2])
+        p.estimate_poses(self.pair["keypoints_pixel"], self.kp_depth, self._first, self._second, self.m, self.camera, self.threshold,
+                         self.hypotheses, self.seed, out=self.pose)
+        self.kp_depth[0].copy_(self.kp_depth[1])
+
+    @torch.no_grad()
+    def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
+        """image_u8, tokens: as FrameStepper.step takes them; depth_u16: (h, w) or (1, h, w) uint16, the frame's raw depth image."""
+        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dtype != torch.uint16 or depth_u16.numel() != self.depth.numel():
+            raise ValueError(f"depth_u16 must be a uint16 tensor of shape {tuple(self.depth.shape[1:])}")
+        if self.use_graph and self._graph is None:
+            self._capture()                      # before the frame's depth goes into its static buffer, as the image does in the parent
+        self.depth.copy_(depth_u16.reshape(self.depth.shape), non_blocking=True)
+        first = self.n_frames == 0
+        out = super().step(image_u8, tokens)
+        out["pose"] = None if first else {k: v[0] for k, v in self.pose.items()}
+        return out
+
+    def reset(self) -> None:
+        super().reset()
+        self.kp_depth.fill_(-1)

@@ -768,6 +768,54 @@ class SequencePipeline:
                                             out=tuple(res[key][a:b] for key in lib.MATCH_KNOWN_SCORE_KEYS))
         return res
 
+    def alloc_pose(self, n_pairs: int, k: int | None = None) -> dict:
+        """Output buffers of estimate_poses() for n_pairs pairs whose match lists hold k slots (num_keypoints by default)."""
+        k = self.cfg.num_keypoints if k is None else k
+        shapes = lib.pose_ransac_shapes(n_pairs, k)
+        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in lib.POSE_RANSAC_KEYS}
+
+    def estimate_poses(self, keypoints_pixel, kp_depth, first, second, matches: dict, camera, threshold: float = 3.0,
+                       hypotheses: int = 256, seed: int = 0, out: dict | None = None) -> dict:
+        """Geometric verification (csrc/pose_estimate.hip): for every listed pair of the bank keypoints_pixel (N, K, 2), the rigid
+        motion its match list agrees on.  The matches whose two keypoints both have a depth measurement - kp_depth (N, K) int32,
+        keypoint_depth()'s output for the same bank - are back-projected; `hypotheses` 3-point samples are solved in closed form
+        (Horn), scored by reprojection into the second frame against `threshold` (in this pipeline's keypoint units), and the best
+        is refitted over its inliers.
+        first / second: as match_pairs takes them.  matches: the dictionary match() / match_pairs() returned for the same pairs
+        under any rule, or rank_matches()' output (matches (P, n1, 2), match_count (P,)).  camera: an evaluation.Camera.  seed:
+        the sampler's 64-bit seed; a pair's result depends on its own rows and the seed alone, not on its place in the list.
+        Returns device tensors per listed pair: T (P, 12) float64 [R | t] camera first -> camera second in metres,
+        inlier_count, usable_count, best_hypothesis, refit_kept (P,) int32, inlier_of_slot (P, n1) int32 (1 inlier, 0 not, -1 no
+        depth; 0 past the count), rms (P,) float64 (include/sslam_hip.h).  A pair with fewer than 3 usable matches gets the
+        identity and best_hypothesis -1.  out: alloc_pose buffers (or row slices).  One launch per 65 535 pairs, no host read."""
+        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
+            raise ValueError("keypoints_pixel (N, K, 2) expected")
+        if not isinstance(kp_depth, torch.Tensor) or tuple(kp_depth.shape) != tuple(keypoints_pixel.shape[:2]):
+            raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
+        if first is None or second is None:
+            raise ValueError("estimate_poses needs both pair lists, first= and second=")
+        t = lib.check_threshold(threshold)
+        n_hyp, seed = lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+        sx, sy = self.depth_scales(camera)
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)
+        if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "match_count")):
+            raise ValueError("matches must be the dictionary match() / match_pairs() / rank_matches() returned: matches, match_count")
+        mt = matches["matches"]
+        if not isinstance(mt, torch.Tensor) or mt.dim() != 3 or int(mt.shape[0]) != n_pairs or mt.shape[2] != 2:
+            raise ValueError(f"matches holds {tuple(getattr(mt, 'shape', ()))}, the pair lists ask for ({n_pairs}, n1, 2)")
+        dev, n1 = keypoints_pixel.device, int(mt.shape[1])
+        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
+        lib.check_pair_lists(first, second, dev)
+        res = dict(out) if out is not None else self.alloc_pose(n_pairs, n1)
+        if any(key not in res for key in lib.POSE_RANSAC_KEYS):
+            raise ValueError(f"out must hold {', '.join(lib.POSE_RANSAC_KEYS)} (alloc_pose)")
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
+            b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
+            lib.pose_ransac_pairs(keypoints_pixel, kp_depth, first[a:b], second[a:b], mt[a:b], matches["match_count"][a:b], camera, sx, sy,
+                                  t, n_hyp, seed, out=tuple(res[key][a:b] for key in lib.POSE_RANSAC_KEYS))
+        return res
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
