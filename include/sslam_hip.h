@@ -739,6 +739,74 @@ int sslam_pose_ransac_pairs(const float *kp_bank, const int32_t *kp_depth_bank, 
                             int32_t *usable_count, int32_t *best_hypothesis, int32_t *refit_kept, int32_t *inlier_of_slot, double *rms,
                             void *stream);
 
+/* ---- Pose refinement: robust Gauss-Newton on the reprojection error (csrc/pose_refine.hip).  The entry above ends in one Horn
+ * solve, a 3-D point-to-point fit in which every inlier pulls equally; this one takes ANY initial pose of a pair - the entry's own,
+ * a motion model's prediction, a pose from elsewhere - and minimises the Huber cost of the reprojection into frame b over the rows
+ * that pose agrees with.  All arithmetic is float64: + - * / sqrt only, every operation rounded once in the order written (no
+ * contraction), no transcendental function.  One launch for all pairs, one 256-thread workgroup per pair; no atomics, no scratch,
+ * no allocation, no host read: capturable.  Results are written with ordinary stores.
+ *   kp_bank .. threshold: the arguments of sslam_pose_ransac_pairs without n_hyp and seed, with the same meaning.
+ *   T_in (n_pairs, 12) float64, 8-byte aligned: the initial [R | t] of every pair, row-major, camera a -> camera b.
+ *   huber: finite and > 0, in keypoint units.   n_iter: the most Gauss-Newton steps, 0 .. SSLAM_REFINE_MAX_ITER.
+ * USABLE ROWS: those of sslam_pose_ransac_pairs, in slot order; X_a, and frame b's keypoint (x_b, y_b), of usable row u.
+ * SELECTED ROWS: the usable rows that are inliers of T_in by that entry's SCORE (Z' > 0 and sqrt(s) < threshold; a T_in with a
+ *   non-finite entry has none).  They are fixed for the whole call.
+ * ONE ROW under a pose [R | t], with kx = fx / scale_x and ky = fy / scale_y:
+ *     X', Y', Z', u', v' from X_a by the formulas of sslam_pose_depth_nn_pairs;
+ *     rx = u' / scale_x - x_b;   ry = v' / scale_y - y_b;   s = rx*rx + ry*ry;   d = sqrt(s);
+ *     if d <= huber:  w = 1, rho = s;   otherwise (a NaN included):  w = huber / d,  rho = (2 * huber) * d - huber * huber;
+ *     iz = 1 / Z';   a = kx * iz;   b = ky * iz;   c = -(a * (X' * iz));   e = -(b * (Y' * iz));
+ *     Ju = (a, 0, c, c*Y', a*Z' - c*X', -(a*Y'));      Jv = (0, b, e, e*Y' - b*Z', -(e*X'), b*X');
+ *   the rows of the 2 x 6 Jacobian of (rx, ry) in the LEFT perturbation X'' = X' + v + w x X' (camera b), parameters
+ *   (vx, vy, vz, wx, wy, wz): the projection's 2 x 3 Jacobian at X' times [I | -[X']x].  The two zeros are +0.0 and are
+ *   multiplied like any other entry.  The row's 28 terms:
+ *     rho;    H_ij = w * (Ju[i]*Ju[j] + Jv[i]*Jv[j]) for i <= j, row-major (21);    g_i = w * (Ju[i]*rx + Jv[i]*ry) (6).
+ * ONE PASS at a pose: cost = sum rho, H = sum H_ij, g = sum g_i over the selected rows, each of the 28 sums in THE ORDER of the
+ *   entry above's refit - thread t of 256 adds, from +0.0, the terms of the usable rows t, t + 256, ... ascending, a usable row that
+ *   is not selected adding +0.0; lanes by xor 32 .. 1; the four waves ((w0 + w1) + w2) + w3 - and `behind`, the number of selected
+ *   rows whose Z' > 0 is false.
+ * STEP from the totals of the pass at the current pose, H read as symmetric: an unpivoted LDL^T,
+ *     for j = 0 .. 5:   D_j = H_jj, then for k = 0 .. j-1 ascending  D_j = D_j - (L_jk * L_jk) * D_k;
+ *                       for i = j+1 .. 5:  L_ij = H_ij, then for k = 0 .. j-1 ascending  L_ij = L_ij - (L_ik * L_jk) * D_k;  L_ij = L_ij / D_j;
+ *     y_i = -g_i, then for k = 0 .. i-1 ascending  y_i = y_i - L_ik * y_k                                       (i = 0 .. 5);
+ *     delta_i = y_i / D_i, then for k = i+1 .. 5 ascending  delta_i = delta_i - L_ki * delta_k                  (i = 5 .. 0).
+ *   A pivot D_j that is not finite and > 0 ENDS the iteration.  delta = (vx, vy, vz, wx, wy, wz).  The update:
+ *     w = 1, x = 0.5 * wx, y = 0.5 * wy, z = 0.5 * wz;  each divided by sqrt(((w*w + x*x) + y*y) + z*z);  dR = r00 .. r22 of the
+ *     entry above's quaternion formulas;
+ *     R_ij <- (dR_i0 * R_0j + dR_i1 * R_1j) + dR_i2 * R_2j;       t_i <- ((dR_i0 * t_0 + dR_i1 * t_1) + dR_i2 * t_2) + v_i.
+ * ITERATION.  Pass 0 at T_in gives cost_in.  Up to n_iter times: a step from the current pose gives a trial pose; the pass at the
+ *   trial; the trial is ACCEPTED - becomes the current pose, its totals the current totals - iff its cost is finite, its `behind`
+ *   is 0 and its cost < the current cost.  The first trial that is not accepted ends the iteration: n_iter + 1 passes at most.
+ * KEEP RULE.  With a step accepted, the current pose is scored over ALL usable rows at `threshold` (a pose with a non-finite entry
+ *   has no inliers); it is returned iff its inlier count >= T_in's (the number of selected rows).  Otherwise T = T_in.
+ * Outputs, per pair:
+ *     T (n_pairs, 12) float64             the returned pose;
+ *     status (n_pairs) int32              0 refined and returned;  1 no step accepted (n_iter 0, a minimum already, a pivot that
+ *                                         is not positive, the first trial rejected);  2 steps accepted but the result has fewer
+ *                                         inliers than T_in and is not kept;  3 not attempted: an absent pair, a non-finite entry
+ *                                         in T_in, or fewer than 3 selected rows;
+ *     iterations (n_pairs) int32          the accepted steps (also under status 2);
+ *     selected_count, usable_count, inlier_count_in, inlier_count (n_pairs) int32: the selected rows, n_usable, the inliers of
+ *                                         T_in (= selected_count) and of T over the usable rows;
+ *     inlier_of_slot (n_pairs, n1) int32  the entry above's encoding, for T;
+ *     cost_in, cost (n_pairs) float64     the pass' cost at T_in and at T (cost = cost_in under status 1 and 2);
+ *     rms (n_pairs) float64               the entry above's, for T;
+ *     info (n_pairs, 21) float64          the upper triangle of the pass' H at T, row-major: the information matrix of the
+ *                                         pose in the perturbation's parameters, in keypoint units^-2 (unit residual weight).
+ *   Under status 1, 2 and 3 T = T_in bit for bit.  Under status 3 all six counts, cost_in, cost, rms and info are 0 and the mask is
+ *   the entry above's NO POSE mask.  A pair's outputs are a function of that pair's rows, its T_in row, the camera, threshold, huber
+ *   and n_iter alone.  T and T_in are different arrays.  NaN keypoints under a positive depth are outside the contract, as above.
+ * SSLAM_E_INVALID: the entry above's list (n_hyp apart), plus: huber not finite and > 0; n_iter outside 0 .. SSLAM_REFINE_MAX_ITER; a
+ * NULL or misaligned T_in.  SSLAM_E_UNSUPPORTED: K above SSLAM_EVAL_MAX_K.  Every refusal comes before anything is launched. */
+#define SSLAM_REFINE_MAX_ITER 16
+int sslam_pose_refine_pairs(const float *kp_bank, const int32_t *kp_depth_bank, int n_bank, int K, const int32_t *pair_first,
+                            const int32_t *pair_second, int n_pairs, const int64_t *matches, const int32_t *count, int n1, double fx,
+                            double fy, double cx, double cy, double depth_scale, double scale_x, double scale_y, double view_w,
+                            double view_h, double threshold, const double *T_in, double huber, int n_iter, double *T, int32_t *status,
+                            int32_t *iterations, int32_t *selected_count, int32_t *usable_count, int32_t *inlier_count_in,
+                            int32_t *inlier_count, int32_t *inlier_of_slot, double *cost_in, double *cost, double *rms, double *info,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ struct KnobInit {
 } g_knob_init;
 }  // namespace
 
-extern "C" int sslam_version(void) { return 640; }
+extern "C" int sslam_version(void) { return 650; }
 extern "C" const char *sslam_arch(void) { return "gfx950"; }
 extern "C" long long sslam_launch_count(void) { return __atomic_load_n(&g_sslam_launches, __ATOMIC_RELAXED); }
 

@@ -7,7 +7,8 @@ keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (
 
 Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate_depth.hip):
 compute_repeatability_depth and compute_ground_truth_matches_depth - and, beside matching.py's matchers, the step that follows
-them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip).
+them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip), and refine_relative_pose, that
+motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
 result.  There is no CPU implementation here: without the GPU library these functions raise.
@@ -112,17 +113,9 @@ def compute_ground_truth_matches_depth(kpts1, kpts2, depth1, T_rel, camera, thre
     return out if isinstance(kpts1, torch.Tensor) else out.cpu().numpy()
 
 
-def estimate_relative_pose(kp1, kp2, depth1, depth2, matches, camera=None, threshold: float = 3.0, hypotheses: int = 256, seed: int = 0):
-    """The rigid motion from camera 1 to camera 2 that the matches agree on: kp1 (N, 2) and kp2 (M, 2) in the pixels of the raw
-    depth images depth1, depth2 (h, w) uint16 of their frames (scale 1), matches (P, 2) [idx1, idx2] as a matcher returns them,
-    camera an sslam_amd.evaluation.Camera (the default one if None).  RANSAC over 3-point samples of the matches with a depth on
-    both sides, Horn's closed form, a refit over the inliers (sslam_pose_ransac_pairs, include/sslam_hip.h); threshold is the
-    reprojection distance in pixels.  numpy in, numpy out; one pair.
-    Returns (T (4, 4) float64 with X_2 = T X_1 - the identity when fewer than 3 matches have both depths -, inlier mask (P,) bool)."""
-    from sslam_amd.evaluation import Camera
-    camera = Camera() if camera is None else camera
-    lib.check_camera(camera)
-    t, n_hyp, seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+def _pair_on_device(who, kp1, kp2, depth1, depth2, matches, camera):
+    """One pair as the pose entries take it: (bank (2, k, 2), kp_depth (2, k), first, count, matches (1, P, 2)) on the device, or
+    None for an empty match list.  Everything is judged before any device work."""
     depths = []
     for name, d in (("depth1", depth1), ("depth2", depth2)):
         d = torch.from_numpy(np.ascontiguousarray(d)) if isinstance(d, np.ndarray) else d
@@ -135,12 +128,12 @@ def estimate_relative_pose(kp1, kp2, depth1, depth2, matches, camera=None, thres
         raise ValueError(f"keypoints (N >= 1, 2) and (M >= 1, 2) expected, got {k1.shape} and {k2.shape}")
     mt = np.asarray(matches)
     if mt.size == 0:
-        return np.eye(4), np.zeros(0, bool)
+        return None
     if mt.ndim != 2 or mt.shape[1] != 2 or mt.dtype.kind not in "iu":
         raise ValueError(f"matches (P, 2) of integer indices expected, got {mt.shape} {mt.dtype}")
     k, p = max(len(k1), len(k2), len(mt)), len(mt)
     if k > lib.EVAL_MAX_K:
-        raise lib.SslamHipError(f"estimate_relative_pose: {k} keypoints or matches; at most {lib.EVAL_MAX_K} are handled on the device")
+        raise lib.SslamHipError(f"{who}: {k} keypoints or matches; at most {lib.EVAL_MAX_K} are handled on the device")
     bank = torch.zeros((2, k, 2), dtype=torch.float32, device="cuda")
     bank[0, :len(k1)], bank[1, :len(k2)] = _dev(k1, torch.float32), _dev(k2, torch.float32)
     kp_depth = torch.full((2, k), -1, dtype=torch.int32, device="cuda")         # the padding rows: no depth, never usable
@@ -148,11 +141,60 @@ def estimate_relative_pose(kp1, kp2, depth1, depth2, matches, camera=None, thres
         kp_depth[f, :n] = lib.keypoint_depth(d.to("cuda").contiguous()[None], bank[f:f + 1, :n].contiguous())[0]      # pixel units: scale 1
     first = torch.zeros((1,), dtype=torch.int32, device="cuda")
     count = torch.full((1,), p, dtype=torch.int32, device="cuda")
-    out = lib.pose_ransac_pairs(bank, kp_depth, first, first + 1, _dev(mt.astype(np.int64)[None], torch.int64), count, camera, 1.0, 1.0,
-                                t, n_hyp, seed)
+    return bank, kp_depth, first, count, _dev(mt.astype(np.int64)[None], torch.int64)
+
+
+def estimate_relative_pose(kp1, kp2, depth1, depth2, matches, camera=None, threshold: float = 3.0, hypotheses: int = 256, seed: int = 0):
+    """The rigid motion from camera 1 to camera 2 that the matches agree on: kp1 (N, 2) and kp2 (M, 2) in the pixels of the raw
+    depth images depth1, depth2 (h, w) uint16 of their frames (scale 1), matches (P, 2) [idx1, idx2] as a matcher returns them,
+    camera an sslam_amd.evaluation.Camera (the default one if None).  RANSAC over 3-point samples of the matches with a depth on
+    both sides, Horn's closed form, a refit over the inliers (sslam_pose_ransac_pairs, include/sslam_hip.h); threshold is the
+    reprojection distance in pixels.  numpy in, numpy out; one pair.
+    Returns (T (4, 4) float64 with X_2 = T X_1 - the identity when fewer than 3 matches have both depths -, inlier mask (P,) bool)."""
+    from sslam_amd.evaluation import Camera
+    camera = Camera() if camera is None else camera
+    lib.check_camera(camera)
+    t, n_hyp, seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+    pair = _pair_on_device("estimate_relative_pose", kp1, kp2, depth1, depth2, matches, camera)
+    if pair is None:
+        return np.eye(4), np.zeros(0, bool)
+    bank, kp_depth, first, count, mt = pair
+    out = lib.pose_ransac_pairs(bank, kp_depth, first, first + 1, mt, count, camera, 1.0, 1.0, t, n_hyp, seed)
     T = np.eye(4)
     T[:3] = out[0].cpu().numpy().reshape(3, 4)
     return T, out[5][0].cpu().numpy() == 1
+
+
+def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, threshold: float = 3.0, huber=None, iterations: int = 5):
+    """The step behind estimate_relative_pose: the pose T (4, 4) or (3, 4) from camera 1 to camera 2 - that function's, or any other
+    initial pose - refined by Gauss-Newton on the Huber cost of the reprojection error over the matches T agrees with at
+    `threshold` (sslam_pose_refine_pairs, include/sslam_hip.h).  kp1 .. camera as estimate_relative_pose takes them; huber: the
+    Huber delta in pixels, threshold / 3 if None; iterations: the most steps.  numpy in, numpy out; one pair.
+    Returns (T (4, 4) float64 - the T given when no step lowers the cost or the result would lose inliers -, inlier mask (P,) bool,
+    info (6, 6) float64: the information matrix of the returned pose in the parameters (vx, vy, vz, wx, wy, wz) of a left
+    perturbation in camera 2; zero when the refinement was not attempted)."""
+    from sslam_amd.evaluation import Camera
+    camera = Camera() if camera is None else camera
+    lib.check_camera(camera)
+    t, n_iter = lib.check_threshold(threshold), lib.check_iterations(iterations)
+    hub = lib.check_huber(t / 3.0 if huber is None else huber)
+    T0 = np.asarray(T, dtype=np.float64)
+    if T0.shape not in ((4, 4), (3, 4)):
+        raise ValueError(f"T (4, 4) or (3, 4) expected, got {T0.shape}")
+    pair = _pair_on_device("refine_relative_pose", kp1, kp2, depth1, depth2, matches, camera)
+    T4 = np.eye(4)
+    T4[:3] = T0[:3]
+    if pair is None:
+        return T4, np.zeros(0, bool), np.zeros((6, 6))
+    bank, kp_depth, first, count, mt = pair
+    out = lib.pose_refine_pairs(bank, kp_depth, first, first + 1, mt, count, camera, _dev(np.ascontiguousarray(T0[:3]).reshape(1, 12), torch.float64),
+                                1.0, 1.0, t, hub, n_iter)
+    T4[:3] = out[0].cpu().numpy().reshape(3, 4)
+    tri = out[11][0].cpu().numpy()
+    iu = np.triu_indices(6)
+    info = np.zeros((6, 6))
+    info[iu], info[iu[1], iu[0]] = tri, tri
+    return T4, out[7][0].cpu().numpy() == 1, info
 
 
 def evaluate_matches(pred_matches, gt_matches, num_kpts1: int, num_kpts2: int) -> dict:

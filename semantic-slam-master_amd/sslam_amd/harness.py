@@ -421,6 +421,8 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     (evaluate_result's depth=) with tum.camera_for(sequence), or with the Camera given under "camera".  A key "odometry": True
     (it needs the depth PNGs and the poses too) adds 'odometry', {spacing: odometry.odometry_result's dictionary} over the same
     pairs at the same threshold: the pose every pair's match list agrees on, its inlier ratio, RPE and - at spacing 1 - ATE.
+    A key "refine": True beside it (it needs "odometry": True) refines every pose on the reprojection error
+    (odometry_result's refine=True: the summaries are the refined poses', RANSAC's own stay under 'ransac').
     Returns StreamingSequence.result() plus 'files' and 'timestamps'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -441,6 +443,11 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
         with_odometry = evaluate.pop("odometry", False)
         if not isinstance(with_odometry, bool):
             raise ValueError('evaluate["odometry"] is a flag, True or False')
+        with_refine = evaluate.pop("refine", False)
+        if not isinstance(with_refine, bool):
+            raise ValueError('evaluate["refine"] is a flag, True or False')
+        if with_refine and not with_odometry:
+            raise ValueError('evaluate["refine"] refines the odometry\'s poses: it needs "odometry": True')
         if not (with_depth or with_odometry) and "camera" in evaluate:
             raise ValueError('evaluate["camera"] describes the depth images: it needs "depth": True')
         if rule is None:
@@ -509,6 +516,6 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
             from . import odometry
             res["odometry"] = {s: odometry.odometry_result(pipe, res, camera=depth_camera, poses=tum.poses, spacing=s,
                                                            num_pairs=int(evaluate.get("num_pairs", 50)),
-                                                           threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth)
+                                                           threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth, refine=with_refine)
                                for s in seq.spacings if s in res and evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))}
     return res

@@ -88,7 +88,7 @@ EXPORTS = [
     "sslam_sim_argmax_rows_pairs_d", "sslam_row_lse_d", "sslam_row_lse_pairs_d", "sslam_val_frame_stats_d",
     "sslam_match_rank", "sslam_pose_nn_pairs", "sslam_match_score_pairs",
     "sslam_keypoint_depth", "sslam_pose_depth_nn_pairs", "sslam_match_score_known_pairs",
-    "sslam_pose_ransac_pairs",
+    "sslam_pose_ransac_pairs", "sslam_pose_refine_pairs",
 ]
 
 
@@ -137,6 +137,7 @@ def lib():
         L.sslam_pose_depth_nn_pairs.argtypes = [p, p, i, i, i, i, p, p, i, p] + [d] * 10 + [p, p, p, p, p, p, p]
         L.sslam_match_score_known_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p, p]
         L.sslam_pose_ransac_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [i, C.c_uint64] + [p] * 7 + [p]
+        L.sslam_pose_refine_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [p, d, i] + [p] * 12 + [p]
         L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
         L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
         L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
@@ -1106,6 +1107,84 @@ def pose_ransac_pairs(kp_bank, kp_depth_bank, first, second, matches, count, cam
     _run("pose_ransac_pairs", lib().sslam_pose_ransac_pairs, (kp_bank, kp_depth_bank, first, second, matches, count, *o),
          _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1,
          *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), n_hyp, C.c_uint64(seed), *(_dp(x) for x in o))
+    return tuple(o)
+
+
+# ------------------------------------------------------------------------------- pose refinement on the reprojection error (pose_refine.hip)
+REFINE_MAX_ITER = 16    # SSLAM_REFINE_MAX_ITER
+POSE_REFINE_KEYS = ("T", "status", "iterations", "selected_count", "usable_count", "inlier_count_in", "inlier_count", "inlier_of_slot",
+                    "cost_in", "cost", "rms", "info")
+# status: refined and returned / no step accepted / steps accepted but fewer inliers, not kept / not attempted
+REFINE_OK, REFINE_NO_STEP, REFINE_NOT_KEPT, REFINE_NOT_ATTEMPTED = 0, 1, 2, 3
+
+
+def pose_refine_shapes(n_pairs: int, n1: int) -> dict:
+    """name -> (shape, dtype) of the outputs of pose_refine_pairs for n_pairs pairs with lists of n1 slots."""
+    one, real = ((n_pairs,), torch.int32), ((n_pairs,), torch.float64)
+    return {"T": ((n_pairs, 12), torch.float64), "status": one, "iterations": one, "selected_count": one, "usable_count": one,
+            "inlier_count_in": one, "inlier_count": one, "inlier_of_slot": ((n_pairs, n1), torch.int32), "cost_in": real, "cost": real,
+            "rms": real, "info": ((n_pairs, 21), torch.float64)}
+
+
+def check_huber(huber) -> float:
+    """The Huber delta of the refinement, in keypoint units: a finite number > 0, else ValueError - before any device work."""
+    return check_positive("huber", huber)
+
+
+def check_iterations(iterations) -> int:
+    """The most Gauss-Newton steps: an int in 0 .. REFINE_MAX_ITER, else ValueError - before any device work."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= REFINE_MAX_ITER:
+        raise ValueError(f"iterations must be an int in [0, {REFINE_MAX_ITER}], got {iterations!r}")
+    return int(iterations)
+
+
+def pose_refine_pairs(kp_bank, kp_depth_bank, first, second, matches, count, camera, T_in, scale_x=1.0, scale_y=1.0, threshold=3.0,
+                      huber=1.0, iterations=5, out=None):
+    """sslam_pose_refine_pairs: kp_bank .. camera, scale_x / scale_y and threshold as pose_ransac_pairs takes them; T_in (P, 12) or
+    (P, 3, 4) float64 device tensor, the initial [R | t] of every pair (camera first -> camera second); huber: the Huber delta in
+    keypoint units; iterations: the most Gauss-Newton steps, 0 .. REFINE_MAX_ITER.
+    Returns (T (P, 12) float64, status, iterations, selected_count, usable_count, inlier_count_in, inlier_count (P,) int32,
+    inlier_of_slot (P, n1) int32, cost_in, cost, rms (P,) float64, info (P, 21) float64: the upper triangle of the 6 x 6
+    information matrix, row-major) - POSE_REFINE_KEYS, include/sslam_hip.h states them.  out: optional tensors of those shapes
+    (T must not be T_in).  One launch, no host read."""
+    _check_bank("kp_bank", kp_bank, ("K", 2))
+    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
+    if kp_depth_bank is None:
+        raise ValueError("kp_depth_bank is required")
+    _check_arrays((n_bank, k), ("kp_depth_bank", kp_depth_bank, torch.int32))
+    n_pairs = check_pair_lists(first, second, kp_bank.device)
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_pairs or \
+            not 1 <= int(matches.shape[1]) <= k:
+        raise ValueError(f"matches must be a tensor of shape ({n_pairs}, n1 in [1, {k}], 2)")
+    n1 = int(matches.shape[1])
+    if count is None:
+        raise ValueError("count is required")
+    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+    _check_arrays((n_pairs,), ("count", count, torch.int32))
+    t = check_threshold(threshold)
+    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
+    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
+    hub, n_iter = check_huber(huber), check_iterations(iterations)
+    if not isinstance(T_in, torch.Tensor) or T_in.dtype != torch.float64 or not T_in.is_contiguous() or \
+            tuple(T_in.shape) not in ((n_pairs, 12), (n_pairs, 3, 4)):
+        raise ValueError(f"T_in must be a contiguous float64 tensor of shape ({n_pairs}, 12) or ({n_pairs}, 3, 4)")
+    if k > EVAL_MAX_K:
+        raise SslamHipError(f"pose_refine_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are handled on the device")
+    shapes = pose_refine_shapes(n_pairs, n1)
+    if out is not None:
+        if len(out) != len(POSE_REFINE_KEYS):
+            raise ValueError(f"out must hold {len(POSE_REFINE_KEYS)} tensors: {', '.join(POSE_REFINE_KEYS)}")
+        for key, x in zip(POSE_REFINE_KEYS, out):
+            if x is None:
+                raise ValueError(f"out `{key}` is required")
+            _check_arrays(shapes[key][0], (f"out `{key}`", x, shapes[key][1]))
+        if out[0].data_ptr() == T_in.data_ptr():
+            raise ValueError("out `T` must not be T_in")
+    dev = common_device(kp_bank, kp_depth_bank, first, second, matches, count, T_in)
+    o = list(out) if out is not None else [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in POSE_REFINE_KEYS]
+    _run("pose_refine_pairs", lib().sslam_pose_refine_pairs, (kp_bank, kp_depth_bank, first, second, matches, count, T_in, *o),
+         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1,
+         *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), _dp(T_in), C.c_double(hub), n_iter, *(_dp(x) for x in o))
     return tuple(o)
 
 

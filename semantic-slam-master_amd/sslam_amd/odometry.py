@@ -3,8 +3,9 @@ the keypoints (SequencePipeline.estimate_poses; csrc/pose_estimate.hip), the cha
 reference judges itself against ORB-SLAM3 by - RPE and ATE (scripts/evaluate_baseline.py:57-129, which computes them with evo
 for a baseline's trajectory file and has no way to produce either for its own features).
 
-Everything here is host-side float64 numpy on the per-pair numbers read back ONCE: extraction, the depth gather, matching and the
-RANSAC launch all stay on the device.
+Everything here is host-side float64 numpy on the per-pair numbers read back ONCE: extraction, the depth gather, matching, the
+RANSAC launch and - with refine=True - the refinement launch behind it (SequencePipeline.refine_poses; csrc/pose_refine.hip:
+Gauss-Newton on the Huber reprojection cost over RANSAC's inliers) all stay on the device.
 
   per pair          E = inv(T_gt) @ T_est with T_gt = evaluation.relative_transform(pose_a, pose_b); the translation error is
                     |E[:3, 3]| in metres, the rotation error the angle of E[:3, :3] in degrees (evo's RPE of one pair);
@@ -157,29 +158,80 @@ def _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed
     return camera
 
 
-def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed) -> dict:
-    """The RANSAC launch on the listed pairs, ONE host read-back of (P, 18) float64, the host-side figures."""
-    first, second = [a for a, _ in pairs], [b for _, b in pairs]
-    est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
-    cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
-           [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
-    host = torch.cat(cols, dim=1).cpu().numpy()             # integers up to 4096: exact in float64
-    T = _as44(host[:, :12])
-    out = {"pairs": list(pairs), "T": T}
-    out.update({key: host[:, 12 + i].astype(np.int64) for i, key in enumerate(_INT_KEYS)})
-    out["match_count"] = host[:, 16].astype(np.int64)
-    out["rms"] = host[:, 17].copy()
+def info_matrix(info) -> np.ndarray:
+    """(P, 6, 6) symmetric information matrices from refine_poses' info (P, 21), the upper triangles row-major."""
+    info = np.asarray(info.detach().cpu().numpy() if isinstance(info, torch.Tensor) else info, dtype=np.float64)
+    if info.ndim != 2 or info.shape[1] != 21:
+        raise ValueError(f"info (P, 21) expected, got {info.shape}")
+    iu = np.triu_indices(6)
+    H = np.zeros((len(info), 6, 6))
+    H[:, iu[0], iu[1]] = info
+    H[:, iu[1], iu[0]] = info
+    return H
+
+
+def _summaries(out: dict, T, poses, pairs, spacing) -> None:
+    """The figures built from the transforms T: inlier_ratio, the chained trajectory, RPE and ATE, written into out."""
     out["inlier_ratio"] = np.where(out["match_count"] > 0, out["inlier_count"] / np.maximum(out["match_count"], 1), 0.0)
     if spacing == 1:
         out["trajectory"] = chain(T, None if poses is None else np.asarray(poses, dtype=np.float64)[pairs[0][0]])
     if poses is not None:
         out["rpe"] = rpe_summary(relative_pose_errors(T, poses, pairs))
         out["ate"] = ate_summary(out["trajectory"], np.asarray(poses, dtype=np.float64)[:len(pairs) + 1]) if spacing == 1 else None
+
+
+_REFINE_INT = ("status", "iterations", "selected_count", "inlier_count")
+_REFINE_REAL = ("cost_in", "cost", "rms")
+
+
+def _check_refine(refine, threshold, huber, iterations) -> None:
+    """What the refinement's arguments can be refused for, before any device work."""
+    if not isinstance(refine, bool):
+        raise ValueError(f"refine must be a bool, got {refine!r}")
+    if refine:
+        lib.check_huber(float(threshold) / 3.0 if huber is None else huber)
+        lib.check_iterations(iterations)
+
+
+def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine=False,
+              huber=None, iterations=5) -> dict:
+    """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it), ONE host read-back of (P, 18)
+    float64 ((P, 58) with refine), the host-side figures."""
+    first, second = [a for a, _ in pairs], [b for _, b in pairs]
+    est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
+    cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
+           [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
+    if refine:
+        ref = pipe.refine_poses(keypoints_pixel, kp_depth, first, second, matches, camera, est, threshold, huber, iterations)
+        cols += [ref["T"]] + [ref[key].to(torch.float64)[:, None] for key in _REFINE_INT] + [ref[key][:, None] for key in _REFINE_REAL] + \
+                [ref["info"]]
+    host = torch.cat(cols, dim=1).cpu().numpy()             # integers up to 4096: exact in float64
+    T = _as44(host[:, :12])
+    out = {"pairs": list(pairs), "T": T}
+    out.update({key: host[:, 12 + i].astype(np.int64) for i, key in enumerate(_INT_KEYS)})
+    out["match_count"] = host[:, 16].astype(np.int64)
+    out["rms"] = host[:, 17].copy()
+    if not refine:
+        _summaries(out, T, poses, pairs, spacing)
+        return out
+    ransac = {key: out[key] for key in ("T", "inlier_count", "rms", "match_count")}
+    _summaries(ransac, T, poses, pairs, spacing)
+    del ransac["match_count"]
+    r = host[:, 18:]
+    out["T"] = _as44(r[:, :12])
+    got = {key: r[:, 12 + i].astype(np.int64) for i, key in enumerate(_REFINE_INT)}
+    out["inlier_count"] = got["inlier_count"]
+    out["rms"] = r[:, 18].copy()
+    _summaries(out, out["T"], poses, pairs, spacing)
+    out["ransac"] = ransac
+    out["refine"] = {"status": got["status"], "iterations": got["iterations"], "selected_count": got["selected_count"],
+                     "cost_in": r[:, 16].copy(), "cost": r[:, 17].copy(), "info": info_matrix(r[:, 19:40])}
     return out
 
 
 def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None, rule=None,
-             threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None) -> dict:
+             threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, refine: bool = False, huber=None,
+             iterations: int = 5) -> dict:
     """The relative pose of every pair (i, i + spacing) of a sequence, from its own features: the frames images_u8 (N, H, W, 3)
     uint8 (a pipeline built with vit=) or their ViT tokens (tokens=), their raw depth images depth (N, h, w) uint16 (numpy or
     tensor) and camera (an evaluation.Camera; the default one if None).  The frames are extracted once, the depth under every
@@ -188,7 +240,12 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     Returns, per pair: 'pairs', 'T' (P, 4, 4) camera i -> camera i + spacing, 'inlier_count', 'usable_count', 'best_hypothesis',
     'refit_kept', 'match_count', 'rms', 'inlier_ratio' = inlier_count / match_count; for spacing 1 'trajectory' (P + 1, 4, 4), the
     chained camera-to-world poses starting at the identity (at poses[0] with poses); with poses (N, 4, 4) also 'rpe'
-    (rpe_summary) and 'ate' (ate_summary of the trajectory; None for another spacing)."""
+    (rpe_summary) and 'ate' (ate_summary of the trajectory; None for another spacing).
+    refine=True puts SequencePipeline.refine_poses behind the RANSAC launch (huber: threshold / 3 if None; iterations Gauss-Newton
+    steps at most), still with ONE read-back: 'T', 'inlier_count', 'rms', 'inlier_ratio', 'trajectory', 'rpe' and 'ate' are then the
+    refined poses' (a pair whose refinement is not kept or not attempted keeps RANSAC's pose), 'ransac' holds the unrefined 'T',
+    'inlier_count', 'rms' and the summaries built from them, and 'refine' holds 'status', 'iterations', 'selected_count', 'cost_in',
+    'cost' and 'info' (P, 6, 6), the information matrix of every refined pose.  With refine=False nothing changes."""
     src = tokens if tokens is not None else images_u8
     if src is None:
         raise ValueError("images_u8 or tokens= required")
@@ -197,19 +254,23 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
         raise ValueError(f"{int(src.shape[0])} frames hold no pair at spacing {spacing}")
     n = pairs[-1][1] + 1
     camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
+    _check_refine(refine, threshold, huber, iterations)
     rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
     ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
     kp_depth = gather_keypoint_depth(pipe, depth, ex["keypoints_pixel"], n)
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
-    return _estimate(pipe, ex["keypoints_pixel"], kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed)
+    return _estimate(pipe, ex["keypoints_pixel"], kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine,
+                     huber, iterations)
 
 
 def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None,
-                    threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, *, kp_depth=None) -> dict:
+                    threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, *, kp_depth=None, refine: bool = False, huber=None,
+                    iterations: int = 5) -> dict:
     """odometry() for a StreamingSequence.result() / run_frames / run_directory result: the keypoints and the match lists of every
     pair (i, i + spacing) are already in device memory, under whichever rule the sequence was run with, so nothing is extracted
     or matched again.  depth=: the raw depth images of the result's frames; kp_depth=: instead, the (N, K) int32 bank
-    gather_keypoint_depth returned for result["frames"]["keypoints_pixel"], as evaluation.evaluate_result takes it."""
+    gather_keypoint_depth returned for result["frames"]["keypoints_pixel"], as evaluation.evaluate_result takes it.
+    refine, huber, iterations: as odometry() takes them."""
     if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
         raise ValueError("a StreamingSequence / run_directory result expected")
     kp = result["frames"]["keypoints_pixel"]
@@ -218,8 +279,9 @@ def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spa
         raise ValueError(f"the result holds no pair at spacing {spacing}")
     n = pairs[-1][1] + 1
     camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
+    _check_refine(refine, threshold, huber, iterations)
     mm = result[spacing]
     matches = {key: mm[key][:len(pairs)] for key in ("matches", "match_count")}
     if kp_depth is None:
         kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
-    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed)
+    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine, huber, iterations)

@@ -302,14 +302,23 @@ class PoseFrameStepper(RuleFrameStepper):
     seed alone, not on the pair's place, so a step's pose is bit for bit the row the batched odometry() gives for the same two
     frames.  step() returns what the parent returns plus "pose": T (12,) float64 [R | t] previous camera -> this camera,
     inlier_count, usable_count, best_hypothesis, refit_kept, inlier_of_slot (K,), rms - views of static buffers, None before the
-    second frame.  rule: MatchRule.mnn_ratio(0.9) if None, as odometry() has it."""
+    second frame.  rule: MatchRule.mnn_ratio(0.9) if None, as odometry() has it.
+    refine=True puts sslam_pose_refine_pairs behind the RANSAC launch, on the same stream and inside the same graph
+    (SequencePipeline.refine_poses from RANSAC's pose: huber, threshold / 3 if None, and iterations as odometry() takes them):
+    "pose" keeps RANSAC's keys untouched and gains "refined", the refinement's outputs (T, status, iterations, ..., info (21,)) as
+    views of static buffers.  With refine=False no further buffer is allocated and no further launch is made."""
 
     def __init__(self, pipe: SequencePipeline, height: int, width: int, depth_height: int, depth_width: int, camera=None,
                  use_graph: bool = True, tokens_in: bool = False, rule=None, threshold: float = 3.0, hypotheses: int = 256,
-                 seed: int = 0):
+                 seed: int = 0, refine: bool = False, huber=None, iterations: int = 5):
         from .evaluation import Camera, check_depth_size
         from .pipeline import MatchRule
         self.threshold, self.hypotheses, self.seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+        if not isinstance(refine, bool):
+            raise ValueError(f"refine must be a bool, got {refine!r}")
+        self.refine = refine
+        if refine:
+            self.huber, self.iterations = lib.check_huber(self.threshold / 3.0 if huber is None else huber), lib.check_iterations(iterations)
         self.camera = Camera() if camera is None else camera
         check_depth_size(depth_width, depth_height, self.camera)      # before anything is allocated
         super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=None,
@@ -320,12 +329,16 @@ class PoseFrameStepper(RuleFrameStepper):
         self._first = torch.zeros((1,), dtype=torch.int32, device=dev)
         self._second = torch.ones((1,), dtype=torch.int32, device=dev)
         self.pose = pipe.alloc_pose(1, K)
+        self.refined = pipe.alloc_pose_refine(1, K) if refine else None
 
     def _after_match(self) -> None:
         p = self.pipe
         p.keypoint_depth(self.depth, self.cur["keypoints_pixel"], out=self.kp_depth[1:2])
         p.estimate_poses(self.pair["keypoints_pixel"], self.kp_depth, self._first, self._second, self.m, self.camera, self.threshold,
                          self.hypotheses, self.seed, out=self.pose)
+        if self.refine:
+            p.refine_poses(self.pair["keypoints_pixel"], self.kp_depth, self._first, self._second, self.m, self.camera, self.pose, self.threshold,
+                           self.huber, self.iterations, out=self.refined)
         self.kp_depth[0].copy_(self.kp_depth[1])
 
     @torch.no_grad()
@@ -339,6 +352,8 @@ class PoseFrameStepper(RuleFrameStepper):
         first = self.n_frames == 0
         out = super().step(image_u8, tokens)
         out["pose"] = None if first else {k: v[0] for k, v in self.pose.items()}
+        if self.refine and not first:
+            out["pose"]["refined"] = {k: v[0] for k, v in self.refined.items()}
         return out
 
     def reset(self) -> None:

@@ -816,6 +816,58 @@ class SequencePipeline:
                                   t, n_hyp, seed, out=tuple(res[key][a:b] for key in lib.POSE_RANSAC_KEYS))
         return res
 
+    def alloc_pose_refine(self, n_pairs: int, k: int | None = None) -> dict:
+        """Output buffers of refine_poses() for n_pairs pairs whose match lists hold k slots (num_keypoints by default)."""
+        k = self.cfg.num_keypoints if k is None else k
+        shapes = lib.pose_refine_shapes(n_pairs, k)
+        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in lib.POSE_REFINE_KEYS}
+
+    def refine_poses(self, keypoints_pixel, kp_depth, first, second, matches: dict, camera, pose, threshold: float = 3.0,
+                     huber: float | None = None, iterations: int = 5, out: dict | None = None) -> dict:
+        """Pose refinement (csrc/pose_refine.hip): for every listed pair, up to `iterations` Gauss-Newton steps on the Huber cost of
+        the reprojection error into the second frame, from the initial pose `pose` - the dictionary estimate_poses() returned for
+        the same pairs, or any (P, 12) float64 device tensor of [R | t] rows (a motion model's prediction, the previous step's
+        output).  The rows refined over are the usable matches that are inliers of `pose` at `threshold` (keypoint units), fixed
+        for the call; huber: the Huber delta in keypoint units, threshold / 3 if None.  keypoints_pixel, kp_depth, first, second,
+        matches, camera: as estimate_poses takes them.
+        Returns device tensors per listed pair: T (P, 12) float64, status (0 refined, 1 no step accepted, 2 refined but fewer
+        inliers: not kept, 3 not attempted), iterations, selected_count, usable_count, inlier_count_in, inlier_count (P,) int32,
+        inlier_of_slot (P, n1) int32, cost_in, cost, rms (P,) float64 and info (P, 21) float64, the upper triangle of the 6 x 6
+        information matrix in the parameters (vx, vy, vz, wx, wy, wz) of a left perturbation in the second camera
+        (include/sslam_hip.h).  Under status 1, 2 and 3 T is `pose` bit for bit.  out: alloc_pose_refine buffers (or row slices).
+        One launch per 65 535 pairs, no host read."""
+        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
+            raise ValueError("keypoints_pixel (N, K, 2) expected")
+        if not isinstance(kp_depth, torch.Tensor) or tuple(kp_depth.shape) != tuple(keypoints_pixel.shape[:2]):
+            raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
+        if first is None or second is None:
+            raise ValueError("refine_poses needs both pair lists, first= and second=")
+        t = lib.check_threshold(threshold)
+        n_iter = lib.check_iterations(iterations)
+        hub = lib.check_huber(t / 3.0 if huber is None else huber)
+        sx, sy = self.depth_scales(camera)
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)
+        if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "match_count")):
+            raise ValueError("matches must be the dictionary match() / match_pairs() / rank_matches() returned: matches, match_count")
+        mt = matches["matches"]
+        if not isinstance(mt, torch.Tensor) or mt.dim() != 3 or int(mt.shape[0]) != n_pairs or mt.shape[2] != 2:
+            raise ValueError(f"matches holds {tuple(getattr(mt, 'shape', ()))}, the pair lists ask for ({n_pairs}, n1, 2)")
+        t_in = pose["T"] if isinstance(pose, dict) and "T" in pose else pose
+        if not isinstance(t_in, torch.Tensor) or t_in.dtype != torch.float64 or tuple(t_in.shape) != (n_pairs, 12) or not t_in.is_contiguous():
+            raise ValueError(f"pose must be estimate_poses()' dictionary or a contiguous float64 tensor of shape ({n_pairs}, 12)")
+        dev, n1 = keypoints_pixel.device, int(mt.shape[1])
+        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
+        lib.check_pair_lists(first, second, dev)
+        res = dict(out) if out is not None else self.alloc_pose_refine(n_pairs, n1)
+        if any(key not in res for key in lib.POSE_REFINE_KEYS):
+            raise ValueError(f"out must hold {', '.join(lib.POSE_REFINE_KEYS)} (alloc_pose_refine)")
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
+            b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
+            lib.pose_refine_pairs(keypoints_pixel, kp_depth, first[a:b], second[a:b], mt[a:b], matches["match_count"][a:b], camera, t_in[a:b],
+                                  sx, sy, t, hub, n_iter, out=tuple(res[key][a:b] for key in lib.POSE_REFINE_KEYS))
+        return res
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
