@@ -32,9 +32,97 @@ extern "C" {
 #endif
 
 #define SSLAM_OK 0
-#define SSLAM_E_INVALID (-1)     /* null pointer / non-positive size / misaligned pointer */
+#define SSLAM_E_INVALID (-1)     /* null pointer / non-positive size / misaligned pointer (ALIGNMENT AND STRIDES below) */
 #define SSLAM_E_UNSUPPORTED (-2) /* shape outside what the kernels are built for */
 #define SSLAM_E_LAUNCH (-3)      /* hipGetLastError() != hipSuccess after the launch */
+
+/* ---- ALIGNMENT AND STRIDES, every entry that takes device pointers.  An entry's result is a function of its operands' VALUES, not
+ * of their addresses: it is the same bits wherever the operands lie, down to the alignments below and at every stride named here
+ * (tests/test_gpu_loose_operands.py runs each entry with every operand at its least alignment, just past and just before a
+ * 256-byte boundary, and with padded, zero and negative strides).
+ * Below, per entry, the LEAST alignment in bytes of each pointer argument: the widest access the entry's kernels make to it - 1 a
+ * byte, 2 a bf16 or uint16, 4 an fp32 or int32 word, 8 an int64, a float64 or an (x, y) pair loaded as one, 16 a four-word vector -
+ * or the stricter demand the entry has always made (sslam_bn_tokens wants 16 throughout).  A pointer that misses its alignment:
+ * SSLAM_E_INVALID before anything is launched, nothing written.  An optional pointer that is NULL is aligned.  Arguments that are
+ * frame slices of a larger array need no more than this: a caller may hand `scores + f * K` or `sal + f * G * G` for any f, K, G.
+ * A workspace is aligned like any other argument and a misaligned one is refused, not ignored.  The img of sslam_preprocess_u8 and
+ * sslam_keypoint_intensity may lie anywhere; sslam_preprocess_u8_patches serves a dword-aligned one only and answers any other with
+ * SSLAM_E_UNSUPPORTED, not SSLAM_E_INVALID, as for a resampling ratio it does not cover: the caller takes sslam_preprocess_u8 then.
+ * The pointers INSIDE sslam_vit_weights_t / sslam_vit_weights_f32_t are not checked: 16-byte aligned, every one.
+ * STRIDES are signed 64-bit counts of floats, named after the semicolon.  Pair p (or frame f of a bank) starts at
+ * base + p * stride in plain pointer arithmetic, so: stride 0 broadcasts one frame to every pair; a stride above rows * width
+ * leaves a gap the kernels never read; a stride below it makes frames overlap (rows are only read); a NEGATIVE stride is
+ * accepted and walks backwards from the base - the caller hands the address of pair 0 and owns every frame the call reaches.
+ * stride1, stride2 and frame_stride must be multiples of 4 floats (every frame then keeps the base's 16-byte alignment), else
+ * SSLAM_E_INVALID; they need not be multiples of the row width.  sstride1, sstride2 and score_stride may be any value.
+ *   sslam_preprocess_u8: img 1, bounds_h 4, coefs_h 4, bounds_v 4, coefs_v 4, out_chw 4
+ *   sslam_preprocess_u8_patches: img 4, bounds_h 4, coefs_h 4, bounds_v 4, coefs_v 4, out_patches_bf16 2
+ *   sslam_keypoint_intensity: img 1, bounds_h 4, coefs_h 4, bounds_v 4, coefs_v 4, kp_pixel 4, out 4
+ *   sslam_bn_tokens: tokens 16, gamma 16, beta 16, run_mean 16, run_var 16, out_feat 16, out_mean 16, out_var 16
+ *   sslam_bn_tokens_bf16copy: tokens 16, gamma 16, beta 16, run_mean 16, run_var 16, out_feat 16, out_mean 16, out_var 16,
+ *         out_feat_bf16 16
+ *   sslam_selector_saliency: feat 16, w1_packed 16, b1 4, w2 4, b2 4, sal 4
+ *   sslam_selector_saliency_ws: feat 16, w1_packed 16, b1 4, w2 4, b2 4, sal 4, workspace 16
+ *   sslam_f32_to_bf16: in 16, out_bf16 16
+ *   sslam_selector_saliency_bf16: feat_bf16 16, w1_packed_bf16 16, b1 4, w2 4, b2 4, sal 4
+ *   sslam_select_keypoints: sal 4, kp_xy 4, scores 4, idx 4, kp_pixel 4, status 4
+ *   sslam_gather: feat 16, kp_xy 4, out 16
+ *   sslam_refine: x 16, packed 16, desc 16
+ *   sslam_refine_d: x 16, packed 16, desc 16
+ *   sslam_gather_refine: feat 16, kp_xy 4, packed 16, desc 16
+ *   sslam_gather_refine_d: feat 16, kp_xy 4, packed 16, desc 16
+ *   sslam_gather_refine_ws: feat 16, kp_xy 4, packed 16, desc 16, workspace 4
+ *   sslam_gather_refine_ws_d: feat 16, kp_xy 4, packed 16, desc 16, workspace 4
+ *   sslam_refine_bf16: x 16, packed_bf16 16, desc 4
+ *   sslam_gather_refine_bf16: feat 16, kp_xy 4, packed_bf16 16, desc 4
+ *   sslam_sim_argmax: desc1 16, desc2 16, nn12 4, s12 4, nn21 4, s21 4, second12 4; strides: stride1, stride2
+ *   sslam_sim_argmax_d: desc1 16, desc2 16, nn12 4, s12 4, nn21 4, s21 4, second12 4; strides: stride1, stride2
+ *   sslam_sim_argmax_ws: desc1 16, desc2 16, nn12 4, s12 4, nn21 4, s21 4, second12 4, workspace 8; strides: stride1, stride2
+ *   sslam_sim_argmax_ws_d: desc1 16, desc2 16, nn12 4, s12 4, nn21 4, s21 4, second12 4, workspace 8; strides: stride1, stride2
+ *   sslam_sim_argmax_pairs: bank 16, pair_first 4, pair_second 4, nn12 4, s12 4, nn21 4, s21 4, second12 4, workspace 8;
+ *         strides: frame_stride
+ *   sslam_sim_argmax_pairs_d: bank 16, pair_first 4, pair_second 4, nn12 4, s12 4, nn21 4, s21 4, second12 4, workspace 8;
+ *         strides: frame_stride
+ *   sslam_sim_argmax_rows: desc1 16, desc2 16, nn12 4, s12 4, second12 4; strides: stride1, stride2
+ *   sslam_sim_argmax_rows_d: desc1 16, desc2 16, nn12 4, s12 4, second12 4; strides: stride1, stride2
+ *   sslam_sim_argmax_rows_pairs: bank 16, pair_first 4, pair_second 4, nn12 4, s12 4, second12 4; strides: frame_stride
+ *   sslam_sim_argmax_rows_pairs_d: bank 16, pair_first 4, pair_second 4, nn12 4, s12 4, second12 4; strides: frame_stride
+ *   sslam_match_finalize: nn12 4, s12 4, nn21 4, scores1 4, scores2 4, intensity1 4, intensity2 4, matches 8, quality 4, count
+ *         4; strides: sstride1, sstride2
+ *   sslam_match_finalize_pairs: nn12 4, s12 4, nn21 4, pair_first 4, pair_second 4, scores_bank 4, intensity_bank 4, matches 8,
+ *         quality 4, count 4; strides: score_stride
+ *   sslam_match_finalize_rule: nn12 4, s12 4, second12 4, nn21 4, matches 8, value 4, count 4
+ *   sslam_match_finalize_rule_pairs: nn12 4, s12 4, second12 4, nn21 4, matches 8, value 4, count 4, pair_first 4, pair_second 4
+ *   sslam_match_rank: matches 8, value 4, count 4, out_matches 8, out_value 4, out_count 4, out_slot 4
+ *   sslam_row_lse: desc1 16, desc2 16, s12 4, lse 4, ce 4, s00 4; strides: stride1, stride2
+ *   sslam_row_lse_d: desc1 16, desc2 16, s12 4, lse 4, ce 4, s00 4; strides: stride1, stride2
+ *   sslam_row_lse_pairs: bank 16, pair_first 4, pair_second 4, s12 4, lse 4, ce 4, s00 4; strides: frame_stride
+ *   sslam_row_lse_pairs_d: bank 16, pair_first 4, pair_second 4, s12 4, lse 4, ce 4, s00 4; strides: frame_stride
+ *   sslam_edge_pool: images_chw 16, pooled 4, edge_max 4
+ *   sslam_val_frame_stats: saliency 4, pooled 4, edge_max 4, descriptors 4, stats 4, desc_mean 4, desc_m2 4
+ *   sslam_val_frame_stats_d: saliency 4, pooled 4, edge_max 4, descriptors 4, stats 4, desc_mean 4, desc_m2 4
+ *   sslam_val_pair_stats: saliency1 4, saliency2 4, nn12 4, nn21 4, s12 4, ce 4, s00 4, stats 4, n_matches 4
+ *   sslam_val_pair_stats_pairs: saliency_bank 4, pair_first 4, pair_second 4, nn12 4, nn21 4, s12 4, ce 4, s00 4, stats 4,
+ *         n_matches 4
+ *   sslam_vit_forward: images_chw 16, workspace 16, tokens_out 16
+ *   sslam_vit_forward_form: images_chw 16, workspace 16, tokens_out 16
+ *   sslam_vit_forward_patches: patches_bf16 16, workspace 16, tokens_out 16
+ *   sslam_vit_forward_patches_form: patches_bf16 16, workspace 16, tokens_out 16
+ *   sslam_vit_forward_f32: images_chw 16, workspace 16, tokens_out 16
+ *   sslam_vit_forward_f32_form: images_chw 16, workspace 16, tokens_out 16
+ *   sslam_pose_nn_pairs: kp_bank 8, pair_first 4, pair_second 4, H 8, gt_matches 8, gt_count 4, gt_of_row 4, dist_sum 8,
+ *         dist_median 8
+ *   sslam_match_score_pairs: matches 8, value 4, count 4, gt_of_row 4, gt_count 4, tp 4, fp 4, fn 4, value_sum 8
+ *   sslam_keypoint_depth: depth 2, kp_pixel 8, kp_depth 4
+ *   sslam_pose_depth_nn_pairs: kp_bank 8, kp_depth_bank 4, pair_first 4, pair_second 4, T 8, valid_count 4, gt_matches 8,
+ *         gt_count 4, gt_of_row 4, dist_sum 8, dist_median 8
+ *   sslam_match_score_known_pairs: matches 8, value 4, count 4, gt_of_row 4, gt_count 4, tp 4, fp 4, fn 4, value_sum 8, unknown
+ *         4
+ *   sslam_pose_ransac_pairs: kp_bank 8, kp_depth_bank 4, pair_first 4, pair_second 4, matches 8, count 4, T 8, inlier_count 4,
+ *         usable_count 4, best_hypothesis 4, refit_kept 4, inlier_of_slot 4, rms 8
+ *   sslam_pose_refine_pairs: kp_bank 8, kp_depth_bank 4, pair_first 4, pair_second 4, matches 8, count 4, T_in 8, T 8, status 4,
+ *         iterations 4, selected_count 4, usable_count 4, inlier_count_in 4, inlier_count 4, inlier_of_slot 4, cost_in 8, cost
+ *         8, rms 8, info 8 */
 
 #define SSLAM_C 384   /* backbone embed dim (ViT-S/16), dino_backbone.py:50 */
 #define SSLAM_HID 384 /* refiner hidden dim, configs/train_config.yaml:13 */
@@ -129,7 +217,7 @@ int sslam_selector_saliency_ws(const float *feat, int n_frames, int G, const flo
 /* ---- A3, bf16 THROUGHPUT mode (BASELINE.json configs[1] "bf16 conv stack").  Same layer as
  * sslam_selector_saliency with bf16 operands (round-to-nearest-even), fp32 accumulation on v_mfma_f32_32x32x16_bf16 and
  * the fp32 epilogue.  NOT index-exact against the fp32 reference: callers report the agreement rate next to it.
- * sslam_f32_to_bf16: the bf16 copy of the feature map (n % 8 == 0, 16-byte aligned pointers).
+ * sslam_f32_to_bf16: the bf16 copy of the feature map (n % 8 == 0).
  * sslam_pack_conv3x3_bf16_host: w (hs,384,3,3) fp32 -> 9*384*hs bf16 in MFMA-fragment order. */
 int sslam_f32_to_bf16(const float *in, void *out_bf16, long long n, void *stream);
 /* sslam_bn_tokens that also writes the bf16 copy of out_feat (same shape) in the same pass */
@@ -520,7 +608,7 @@ int sslam_val_pair_stats_pairs(const float *saliency_bank, int G, int n_bank, co
  * then the same row tree), descriptors / banks with rows of 256 floats, and every similarity ONE fma chain over k = 0 .. 255
  * ascending - bit-identical to the oracle at that width (ora_refine(d_out = 256), ora_sim_argmax(d = 256)).
  * Any other d: SSLAM_E_UNSUPPORTED before anything is launched; NULL / misaligned / non-positive arguments: SSLAM_E_INVALID as in
- * the unsuffixed entry (the refiner's _d entries also want `desc` 16-byte aligned).  Strides stay explicit, in floats.  Outputs,
+ * the unsuffixed entry.  Strides stay explicit, in floats.  Outputs,
  * workspace sizes (sslam_sim_argmax_workspace_bytes, sslam_gather_refine_workspace_bytes: neither depends on d), absent pairs and
  * launch forms are those of the unsuffixed entries.  The packed refiner buffer of width d holds sslam_refiner_layout_d(...).total
  * floats: the layout of sslam_refiner_layout with out_w (d x 384, packed) and out_b (d) at the end.

@@ -43,6 +43,16 @@ extern long long g_sslam_knob[KNOB_COUNT];
 static inline long long sslam_knob(int id, long long dflt) { const long long v = g_sslam_knob[id]; return v == SSLAM_KNOB_UNSET ? dflt : v; }
 static inline bool sslam_knob_set(int id) { return g_sslam_knob[id] != SSLAM_KNOB_UNSET; }
 
+// true when one of the pointers misses the alignment `a` (a power of two: the widest access a kernel makes to the argument,
+// include/sslam_hip.h states it per entry); a NULL pointer - an optional argument that is absent - never does
+template <class... P>
+static inline bool sslam_misaligned(unsigned a, P... p) {
+    uintptr_t bits = 0;
+    const uintptr_t each[] = {(uintptr_t)p...};
+    for (const uintptr_t v : each) bits |= v;
+    return (bits & (uintptr_t)(a - 1)) != 0;
+}
+
 #define SSLAM_CHECK_LAUNCH()                                   \
     do {                                                       \
         sslam_count_launches(1);                               \

@@ -294,6 +294,7 @@ extern "C" int sslam_pose_depth_nn_pairs(const float *kp_bank, const int32_t *kp
     if ((uintptr_t)kp_bank & 7 || (uintptr_t)kp_depth_bank & 3 || (uintptr_t)pair_first & 3 || (uintptr_t)pair_second & 3 ||
         (uintptr_t)T & 7)
         return SSLAM_E_INVALID;
+    if (sslam_misaligned(8, gt_matches, dist_sum, dist_median) || sslam_misaligned(4, gt_count, gt_of_row, valid_count)) return SSLAM_E_INVALID;
     if (K > EVAL_MAX_K) return SSLAM_E_UNSUPPORTED;
     const int P = eval_pow2(n1);
     const int main_bytes = (P > n2 ? P : n2) * 8;
@@ -311,6 +312,8 @@ extern "C" int sslam_match_score_known_pairs(const int64_t *matches, const float
                                              int32_t *unknown, double *value_sum, void *stream) {
     if (!matches || !value || !count || !gt_of_row || !gt_count || !tp || !fp || !fn || !unknown || !value_sum) return SSLAM_E_INVALID;
     if (n1 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
+    if (sslam_misaligned(8, matches, value_sum) || sslam_misaligned(4, value, count, gt_of_row, gt_count, tp, fp, fn, unknown))
+        return SSLAM_E_INVALID;
     if (n1 > EVAL_MAX_K) return SSLAM_E_UNSUPPORTED;
     hipLaunchKernelGGL(match_score_known_kernel, dim3((unsigned)n_pairs), dim3(256), 0, (hipStream_t)stream, (const long long *)matches,
                        value, count, gt_of_row, gt_count, n1, tp, fp, fn, unknown, value_sum);

@@ -589,6 +589,7 @@ extern "C" int sslam_sim_argmax_ws_d(const float *desc1, long long stride1, int 
                                      void *workspace, long long workspace_bytes, int d, void *stream) {
     if (!desc1 || !desc2 || !nn12 || !nn21 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3) || ((uintptr_t)workspace & 7)) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, nn12, s12, nn21, s21, second12)) return SSLAM_E_INVALID;      // written word by word
     return SSLAM_BY_WIDTH(d,
                           launch_sim_argmax<128>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, nn21, s21, second12, workspace,
                                                  workspace_bytes, stream, StridedPairs{}),
@@ -609,6 +610,7 @@ extern "C" int sslam_sim_argmax_pairs_d(const float *bank, long long frame_strid
     if (!bank || !pair_first || !pair_second || !nn12 || !nn21 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)bank & 15) || (frame_stride & 3) || ((uintptr_t)workspace & 7) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3))
         return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, nn12, s12, nn21, s21, second12)) return SSLAM_E_INVALID;
     const ListedPairs lp{pair_first, pair_second, n_bank};
     return SSLAM_BY_WIDTH(d,
                           launch_sim_argmax<128>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, nn21, s21, second12,
@@ -644,6 +646,9 @@ extern "C" int sslam_match_finalize(const int32_t *nn12, const float *s12, const
     if (!nn12 || !s12 || !nn21 || !scores1 || !scores2 || !matches || !quality || !count || n1 <= 0 || n2 <= 0 ||
         n_pairs <= 0)
         return SSLAM_E_INVALID;
+    // every array is read and written element by element: int32 / fp32 words, the match rows int64
+    if (sslam_misaligned(4, nn12, s12, nn21, scores1, scores2, intensity1, intensity2, quality, count) || sslam_misaligned(8, matches))
+        return SSLAM_E_INVALID;
     hipLaunchKernelGGL(match_finalize_kernel<StridedPairs>, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, nn21, n1, n2,
                        scores1, sstride1, scores2, sstride2, intensity1, intensity2, w_desc, w_sal, min_saliency, min_sim,
                        min_intensity, (long long *)matches, quality, count, StridedPairs{});
@@ -660,6 +665,7 @@ extern "C" int sslam_match_finalize_pairs(const int32_t *nn12, const float *s12,
         n_bank <= 0 || n_pairs <= 0)
         return SSLAM_E_INVALID;
     if (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, nn12, s12, nn21, scores_bank, intensity_bank, quality, count) || sslam_misaligned(8, matches)) return SSLAM_E_INVALID;
     hipLaunchKernelGGL(match_finalize_kernel<ListedPairs>, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, nn12, s12, nn21, K, K,
                        scores_bank, score_stride, scores_bank, score_stride, intensity_bank, intensity_bank, w_desc, w_sal,
                        min_saliency, min_sim, min_intensity, (long long *)matches, quality, count,
@@ -691,6 +697,7 @@ extern "C" int sslam_sim_argmax_rows_d(const float *desc1, long long stride1, in
                                        int n_pairs, int32_t *nn12, float *s12, float *second12, int d, void *stream) {
     if (!desc1 || !desc2 || !nn12 || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3)) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, nn12, s12, second12)) return SSLAM_E_INVALID;
     return SSLAM_BY_WIDTH(d,
                           launch_sim_argmax_rows<128>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, stream, StridedPairs{}),
                           launch_sim_argmax_rows<256>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, nn12, s12, second12, stream, StridedPairs{}));
@@ -705,6 +712,7 @@ extern "C" int sslam_sim_argmax_rows_pairs_d(const float *bank, long long frame_
                                              int d, void *stream) {
     if (!bank || !pair_first || !pair_second || !nn12 || n_bank <= 0 || K <= 0 || n_pairs <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)bank & 15) || (frame_stride & 3) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3)) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, nn12, s12, second12)) return SSLAM_E_INVALID;
     const ListedPairs lp{pair_first, pair_second, n_bank};
     return SSLAM_BY_WIDTH(d,
                           launch_sim_argmax_rows<128>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, nn12, s12, second12, stream, lp),
@@ -724,6 +732,7 @@ static bool rule_args_ok(const int32_t *nn12, const float *s12, const float *sec
     if (!nn12 || !s12 || !matches || !value || !count || n1 <= 0 || n2 <= 0 || n_pairs <= 0) return false;
     if (rule != SSLAM_RULE_RATIO_BEST && rule != SSLAM_RULE_RATIO_SECOND && rule != SSLAM_RULE_TRACKED) return false;
     if (rule != SSLAM_RULE_TRACKED && (!second12 || !nn21)) return false;
+    if (sslam_misaligned(4, nn12, s12, second12, nn21, value, count) || sslam_misaligned(8, matches)) return false;
     return rule != SSLAM_RULE_RATIO_SECOND || n2 >= 2;
 }
 

@@ -112,6 +112,8 @@ extern "C" int sslam_match_rank(const int64_t *matches, const float *value, cons
     if (!matches || !value || !count || !out_matches || !out_value || !out_count || n1 <= 0 || n_pairs <= 0 || best <= 0 || best > n1)
         return SSLAM_E_INVALID;
     if (ascending != 0 && ascending != 1) return SSLAM_E_INVALID;
+    // read and written element by element: the match rows int64, everything else 4-byte words
+    if (sslam_misaligned(8, matches, out_matches) || sslam_misaligned(4, value, count, out_value, out_count, out_slot)) return SSLAM_E_INVALID;
     const void *ins[3] = {matches, value, count}, *outs[4] = {out_matches, out_value, out_count, out_slot};
     for (const void *o : outs)
         for (const void *in : ins)

@@ -633,7 +633,7 @@ extern "C" int sslam_refine_d(const float *x, long long rows, const float *packe
 }
 extern "C" int sslam_refine(const float *x, long long rows, const float *packed, int n_blocks, float *desc, void *stream) {
     if (!x || !packed || !desc || rows <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)x | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
+    if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;      // desc: stored as 16-byte vectors
     return launch_refine(nullptr, 0, nullptr, 1, x, rows, packed, n_blocks, SSLAM_D, desc, stream);
 }
 
@@ -641,13 +641,15 @@ extern "C" int sslam_gather_refine_d(const float *feat, int n_frames, int G, con
                                      int n_blocks, float *desc, int d, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, kp_xy)) return SSLAM_E_INVALID;
     if (!width_ok(d)) return SSLAM_E_UNSUPPORTED;
     return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, d, desc, stream);
 }
 extern "C" int sslam_gather_refine(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
                                    int n_blocks, float *desc, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)feat | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;   // desc: stored as 16-byte vectors
+    if (sslam_misaligned(4, kp_xy)) return SSLAM_E_INVALID;
     return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, SSLAM_D, desc, stream);
 }
 
@@ -658,7 +660,8 @@ extern "C" long long sslam_gather_refine_workspace_bytes(int n_frames, int K) {
 
 static int gather_refine_ws(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed, int n_blocks,
                             int d, float *desc, void *workspace, long long workspace_bytes, void *stream) {
-    if (distinct_form(n_frames, K) && workspace && !((uintptr_t)workspace & 3) &&
+    if (sslam_misaligned(4, workspace)) return SSLAM_E_INVALID;      // int32 words; NULL is allowed: the direct launch
+    if (distinct_form(n_frames, K) && workspace &&
         workspace_bytes >= distinct_ws(n_frames, (long long)n_frames * K).bytes)
         return launch_refine_distinct(feat, n_frames, G, kp_xy, K, packed, n_blocks, d, desc, workspace, stream);
     return launch_refine(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed, n_blocks, d, desc, stream);
@@ -668,19 +671,21 @@ extern "C" int sslam_gather_refine_ws_d(const float *feat, int n_frames, int G, 
                                         int n_blocks, float *desc, void *workspace, long long workspace_bytes, int d, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, kp_xy)) return SSLAM_E_INVALID;
     if (!width_ok(d)) return SSLAM_E_UNSUPPORTED;
     return gather_refine_ws(feat, n_frames, G, kp_xy, K, packed, n_blocks, d, desc, workspace, workspace_bytes, stream);
 }
 extern "C" int sslam_gather_refine_ws(const float *feat, int n_frames, int G, const float *kp_xy, int K, const float *packed,
                                       int n_blocks, float *desc, void *workspace, long long workspace_bytes, void *stream) {
     if (!feat || !kp_xy || !packed || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)feat | (uintptr_t)packed) & 15) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)packed | (uintptr_t)desc) & 15) return SSLAM_E_INVALID;   // desc: stored as 16-byte vectors
+    if (sslam_misaligned(4, kp_xy)) return SSLAM_E_INVALID;
     return gather_refine_ws(feat, n_frames, G, kp_xy, K, packed, n_blocks, SSLAM_D, desc, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sslam_gather(const float *feat, int n_frames, int G, const float *kp_xy, int K, float *out, void *stream) {
     if (!feat || !kp_xy || !out || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)feat | (uintptr_t)out) & 15) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)out) & 15 || sslam_misaligned(4, kp_xy)) return SSLAM_E_INVALID;
     const long long rows = (long long)n_frames * K, items = rows * (SSLAM_C / 4);
     hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, feat, G, kp_xy,
                        K, rows, out);

@@ -343,13 +343,13 @@ static int launch_bf16(const float *feat, int G, const float *kp_xy, int K, cons
 
 extern "C" int sslam_refine_bf16(const float *x, long long rows, const void *packed_bf16, int n_blocks, float *desc, void *stream) {
     if (!x || !packed_bf16 || !desc || rows <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)x | (uintptr_t)packed_bf16) & 15) return SSLAM_E_INVALID;
+    if (((uintptr_t)x | (uintptr_t)packed_bf16) & 15 || sslam_misaligned(4, desc)) return SSLAM_E_INVALID;
     return launch_bf16(nullptr, 0, nullptr, 1, x, rows, packed_bf16, n_blocks, desc, stream);
 }
 
 extern "C" int sslam_gather_refine_bf16(const float *feat, int n_frames, int G, const float *kp_xy, int K, const void *packed_bf16,
                                         int n_blocks, float *desc, void *stream) {
     if (!feat || !kp_xy || !packed_bf16 || !desc || n_frames <= 0 || G <= 1 || K <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)feat | (uintptr_t)packed_bf16) & 15) return SSLAM_E_INVALID;
+    if (((uintptr_t)feat | (uintptr_t)packed_bf16) & 15 || sslam_misaligned(4, kp_xy, desc)) return SSLAM_E_INVALID;
     return launch_bf16(feat, G, kp_xy, K, nullptr, (long long)n_frames * K, packed_bf16, n_blocks, desc, stream);
 }

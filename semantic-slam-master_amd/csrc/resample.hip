@@ -305,7 +305,10 @@ static int preprocess_launch(const uint8_t *img, int n, int h, int w, int size, 
     if (!img || !bounds_h || !coefs_h || !bounds_v || !coefs_v || !out_v || n <= 0 || h <= 0 || w <= 0 || size <= 0)
         return SSLAM_E_INVALID;
     if (ksize_h <= 0 || ksize_v <= 0 || ksize_h > SSLAM_MAX_TAPS || ksize_v > SSLAM_MAX_TAPS) return SSLAM_E_INVALID;
-    if (PATCH && (size % 16 || ((uintptr_t)out_v & 1))) return SSLAM_E_INVALID;
+    if (PATCH && size % 16) return SSLAM_E_INVALID;
+    // the image is read byte by byte (the fast kernel realigns a dword-aligned base itself): any address; the tables are int32 words,
+    // the output fp32 words or bf16 halves
+    if (sslam_misaligned(4, bounds_h, coefs_h, bounds_v, coefs_v) || sslam_misaligned(PATCH ? 2 : 4, out_v)) return SSLAM_E_INVALID;
     // input rows one output tile can need: TY output rows span TY*scale input rows plus the filter support
     if ((long long)(TY * (long long)h + size - 1) / size + ksize_v + 2 > MAXR) return SSLAM_E_UNSUPPORTED;
     // the fast kernel prefers 32-row tiles (less vertical-halo re-filtering) when their input rows fit its LDS buffer
@@ -373,6 +376,7 @@ extern "C" int sslam_keypoint_intensity(const uint8_t *img, int n, int h, int w,
     if (!img || !bounds_h || !coefs_h || !bounds_v || !coefs_v || !kp_pixel || !out || n <= 0 || h <= 0 || w <= 0 ||
         size <= 0 || K <= 0)
         return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, bounds_h, coefs_h, bounds_v, coefs_v, kp_pixel, out)) return SSLAM_E_INVALID;
     const long long total = (long long)n * K;
     hipLaunchKernelGGL(intensity_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, h, w,
                        size, bounds_h, coefs_h, ksize_h, bounds_v, coefs_v, ksize_v, kp_pixel, K, total, out);

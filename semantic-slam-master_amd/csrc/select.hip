@@ -228,6 +228,7 @@ extern "C" int sslam_select_keypoints(const float *sal, int n_frames, int G, int
                                       double min_score_percentile, float *kp_xy, float *scores, int32_t *idx,
                                       float *kp_pixel, int32_t *status, void *stream) {
     if (!sal || !kp_xy || !scores || !status || n_frames <= 0 || G <= 0 || K <= 0) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, sal, kp_xy, scores, idx, kp_pixel, status)) return SSLAM_E_INVALID;      // every access is one word
     const int n = G * G;
     if (n > MAXN || K > MAXN || nms_radius < 0 || nms_radius > 8) return SSLAM_E_UNSUPPORTED;
     int P = 1;

@@ -731,6 +731,7 @@ extern "C" int sslam_selector_saliency_ws(const float *feat, int n_frames, int G
                                           long long workspace_bytes, void *stream) {
     if (!feat || !w1_packed || !b1 || !w2 || !b2 || !sal || n_frames <= 0 || G <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat | (uintptr_t)w1_packed | (uintptr_t)workspace) & 15) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, b1, w2, b2, sal)) return SSLAM_E_INVALID;      // read and written word by word
     const long long rows = (long long)n_frames * G * G;
     if (rows * (long long)(SSLAM_C * 4) > 0xffffffffLL) return SSLAM_E_UNSUPPORTED;   // one buffer descriptor spans the feature map
     hipStream_t st = (hipStream_t)stream;

@@ -409,6 +409,7 @@ extern "C" int sslam_selector_saliency_bf16(const void *feat_bf16, int n_frames,
                                             const float *b1, const float *w2, const float *b2, int hs, float *sal, void *stream) {
     if (!feat_bf16 || !w1_packed_bf16 || !b1 || !w2 || !b2 || !sal || n_frames <= 0 || G <= 0) return SSLAM_E_INVALID;
     if (((uintptr_t)feat_bf16 | (uintptr_t)w1_packed_bf16) & 15) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, b1, w2, b2, sal)) return SSLAM_E_INVALID;      // read and written word by word
     const long long rows = (long long)n_frames * G * G;
     if (rows * (long long)(SSLAM_C * 2) > 0xffffffffLL) return SSLAM_E_UNSUPPORTED;   // one buffer descriptor spans the bf16 feature map
     hipStream_t st = (hipStream_t)stream;

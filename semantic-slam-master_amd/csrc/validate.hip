@@ -434,6 +434,7 @@ extern "C" int sslam_row_lse_d(const float *desc1, long long stride1, int n1, co
     if (!desc1 || !desc2 || !s12 || (!lse && !ce) || n1 <= 0 || n2 <= 0 || n_pairs <= 0 || !temperature_ok(temperature))
         return SSLAM_E_INVALID;
     if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15 || (stride1 & 3) || (stride2 & 3)) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, s12, lse, ce, s00)) return SSLAM_E_INVALID;
     return SSLAM_BY_WIDTH(d,
                           launch_row_lse<128>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, s12, temperature, lse, ce, s00, stream, StridedPairs{}),
                           launch_row_lse<256>(desc1, stride1, n1, desc2, stride2, n2, n_pairs, s12, temperature, lse, ce, s00, stream, StridedPairs{}));
@@ -450,6 +451,7 @@ extern "C" int sslam_row_lse_pairs_d(const float *bank, long long frame_stride, 
         !temperature_ok(temperature))
         return SSLAM_E_INVALID;
     if (((uintptr_t)bank & 15) || (frame_stride & 3) || (((uintptr_t)pair_first | (uintptr_t)pair_second) & 3)) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, s12, lse, ce, s00)) return SSLAM_E_INVALID;
     const ListedPairs lp{pair_first, pair_second, n_bank};
     return SSLAM_BY_WIDTH(d,
                           launch_row_lse<128>(bank, frame_stride, K, bank, frame_stride, K, n_pairs, s12, temperature, lse, ce, s00, stream, lp),
@@ -464,7 +466,7 @@ extern "C" int sslam_row_lse_pairs(const float *bank, long long frame_stride, in
 
 extern "C" int sslam_edge_pool(const float *images_chw, int n_frames, int size, float *pooled, float *edge_max, void *stream) {
     if (!images_chw || !pooled || !edge_max || n_frames <= 0 || size <= 0) return SSLAM_E_INVALID;
-    if (((uintptr_t)images_chw & 15) || ((uintptr_t)edge_max & 3)) return SSLAM_E_INVALID;
+    if (((uintptr_t)images_chw & 15) || sslam_misaligned(4, pooled, edge_max)) return SSLAM_E_INVALID;
     if (size % 16 || size / 16 > 65535 || n_frames > 65535) return SSLAM_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     // 0 is below the bits of every magnitude: the maximum is a 32-bit unsigned atomic max, which no order can change
@@ -481,6 +483,7 @@ extern "C" int sslam_val_frame_stats_d(const float *saliency, const float *poole
     if (!saliency || !stats || n_frames <= 0 || G <= 0 || G > 4096) return SSLAM_E_INVALID;
     if ((pooled != nullptr) != (edge_max != nullptr)) return SSLAM_E_INVALID;
     if (descriptors && (!desc_mean || !desc_m2 || K <= 0)) return SSLAM_E_INVALID;
+    if (sslam_misaligned(4, saliency, pooled, edge_max, descriptors, stats, desc_mean, desc_m2)) return SSLAM_E_INVALID;      // word by word
     if (d != 128 && d != 256) return SSLAM_E_UNSUPPORTED;
     if (d == 128)
         hipLaunchKernelGGL(val_frame_stats_kernel<128>, dim3((unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, saliency, pooled,
@@ -500,13 +503,13 @@ static bool pair_stats_args_ok(const float *saliency, int G, const int32_t *nn12
                                const float *s00, int n1, int n2, int n_pairs, float temperature, const float *stats,
                                const int32_t *n_matches) {
     return saliency && nn12 && nn21 && s12 && ce && s00 && stats && n_matches && G > 0 && G <= 4096 && n1 > 0 && n2 > 0 &&
-           n_pairs > 0 && temperature_ok(temperature);
+           n_pairs > 0 && temperature_ok(temperature) && !sslam_misaligned(4, saliency, nn12, nn21, s12, ce, s00, stats, n_matches);
 }
 
 extern "C" int sslam_val_pair_stats(const float *saliency1, const float *saliency2, int G, const int32_t *nn12, const int32_t *nn21,
                                     const float *s12, const float *ce, const float *s00, int n1, int n2, int n_pairs,
                                     float temperature, float *stats, int32_t *n_matches, void *stream) {
-    if (!pair_stats_args_ok(saliency1, G, nn12, nn21, s12, ce, s00, n1, n2, n_pairs, temperature, stats, n_matches) || !saliency2)
+    if (!pair_stats_args_ok(saliency1, G, nn12, nn21, s12, ce, s00, n1, n2, n_pairs, temperature, stats, n_matches) || !saliency2 || sslam_misaligned(4, saliency2))
         return SSLAM_E_INVALID;
     hipLaunchKernelGGL(val_pair_stats_kernel<StridedPairs>, dim3((unsigned)n_pairs), dim3(256), 0, (hipStream_t)stream, saliency1, saliency2,
                        G * G, nn12, nn21, s12, ce, s00, n1, n2, temperature, stats, n_matches, StridedPairs{});

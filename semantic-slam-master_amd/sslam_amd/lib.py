@@ -1370,8 +1370,12 @@ def vit_workspace_bytes(n_frames: int, size: int, form: int | None = None) -> in
 
 
 def _with_form(fn, form):
-    """The *_form entries take `form` before the trailing stream argument."""
-    return lambda *a: fn(*a[:-1], int(form), a[-1])
+    """The *_form entries take `form` before the trailing stream argument.  The call keeps the entry's name (what a test that
+    watches _run sees)."""
+    def call(*a):
+        return fn(*a[:-1], int(form), a[-1])
+    call.__name__ = fn.__name__
+    return call
 
 
 def vit_forward_patches(patches, size: int, weights: VitWeights, workspace, out=None, form: int | None = None):
@@ -1430,6 +1434,6 @@ def vit_forward_f32(images_chw, weights: VitWeightsF32, workspace, out=None, att
         _run("vit_forward_f32", lib().sslam_vit_forward_f32, (images_chw, workspace, out,),
              _dp(images_chw), n, size, C.byref(weights), _dp(workspace), workspace.numel() * workspace.element_size(), _dp(out))
     else:
-        _run("vit_forward_f32_form", lambda *a: lib().sslam_vit_forward_f32_form(*a[:-1], int(attention_form), a[-1]), (images_chw, workspace, out,),
+        _run("vit_forward_f32_form", _with_form(lib().sslam_vit_forward_f32_form, attention_form), (images_chw, workspace, out,),
              _dp(images_chw), n, size, C.byref(weights), _dp(workspace), workspace.numel() * workspace.element_size(), _dp(out))
     return out

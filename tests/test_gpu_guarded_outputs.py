@@ -79,20 +79,32 @@ def _bf16_bits(a):
 
 
 class Bufs:
-    """The guarded inputs and outputs of ONE call."""
+    """The guarded inputs and outputs of ONE call.  An operand's name is its argument's name in include/sslam_hip.h: under a
+    gd.Placement (tests/test_gpu_loose_operands.py) the name decides where the operand lies."""
 
     def __init__(self, T):
         self.T, self.ins, self.outs = T, [], []
 
     def i(self, name, array, fill=None, guard=gd.GUARD):
         """An input between bands of NaN bits (`fill`: a byte, for uint8 images) -> the device tensor."""
-        whole, mid = gd.guarded_input(self.T, array, fill=fill, guard_bytes=guard)
+        whole, mid = gd.guarded_input(self.T, array, fill=fill, guard_bytes=guard, name=name)
         self.ins.append((name, whole, mid, mid.clone(), fill))
         return mid
 
+    def frames(self, name, array, stride, fill=None, guard=gd.GUARD):
+        """A strided input: the frames (or rows) array[0], array[1], .. lie |stride| elements apart in ONE guarded input, the gaps
+        holding NaN bits (`fill`: a byte, for uint8 images) - gd.spread.  stride 0: frame 0 alone, which every pair reads.  A
+        negative stride: the same layout, read backwards from its last frame.  -> (the device tensor, the address to hand to
+        the entry: where the frame of pair 0 starts)."""
+        if stride == 0:
+            t = self.i(name, array[:1], fill=fill, guard=guard)
+            return t, t.data_ptr()
+        t = self.i(name, gd.spread(array, abs(stride), fill=fill), fill=fill, guard=guard)
+        return t, t.data_ptr() + (t.element_size() * abs(stride) * (array.shape[0] - 1) if stride < 0 else 0)
+
     def o(self, name, shape, dtype=None, guard=gd.GUARD):
         """A sentinel-filled output between sentinel bands -> the device tensor."""
-        whole, mid = gd.guarded(self.T, shape, dtype or self.T.float32, guard_bytes=guard)
+        whole, mid = gd.guarded(self.T, shape, dtype or self.T.float32, guard_bytes=guard, name=name)
         self.outs.append((name, whole, mid))
         return mid
 
@@ -169,10 +181,11 @@ def _tables(b, hip, h, w, size, bicubic):
 
 
 def _image(b, imgs, base, fill):
-    """The frames between bands of `fill`, their base `base` bytes past a 16-byte boundary."""
+    """The frames between bands of `fill`, their base `base` bytes past a 16-byte boundary (under a gd.Placement: past where
+    that puts the operand)."""
     flat = np.concatenate([np.full(base, fill, np.uint8), imgs.reshape(-1)])
-    view = b.i("images", flat, fill=fill)[base:].view(imgs.shape)
-    assert view.data_ptr() % 4 == base
+    view = b.i("img", flat, fill=fill)[base:].view(imgs.shape)
+    assert gd.placement is not None or view.data_ptr() % 4 == base
     return view
 
 
@@ -199,11 +212,13 @@ def test_preprocess_u8_patches(T, hip, h, w, size, base):
     for fill in FILLS:
         b = Bufs(T)
         th, tv = _tables(b, hip, h, w, size, False)
-        out = b.o("out_patches", (A0_FRAMES, (size // 16) ** 2, 768), T.bfloat16)
-        got = hip.preprocess_u8_patches(_image(b, case["imgs"], base, fill), size, th, tv, out=out)
-        fast = th[2] <= 7 and base == 0
+        out = b.o("out_patches_bf16", (A0_FRAMES, (size // 16) ** 2, 768), T.bfloat16)
+        img = _image(b, case["imgs"], base, fill)
+        got = hip.preprocess_u8_patches(img, size, th, tv, out=out)
+        fast = th[2] <= 7 and img.data_ptr() % 4 == 0
+        assert gd.placement is not None or (img.data_ptr() % 4 == 0) == (base == 0)
         assert (got is not None) == fast, (th[2], base)
-        b.check(f"preprocess_u8_patches {h}x{w}->{size} base {base} bands {fill:#04x}", unwritten=() if fast else ("out_patches",))
+        b.check(f"preprocess_u8_patches {h}x{w}->{size} base {base} bands {fill:#04x}", unwritten=() if fast else ("out_patches_bf16",))
         if fast:
             assert_bits(T, out, case["patches"], "preprocess_u8_patches")
         runs.append((out,))
@@ -217,7 +232,7 @@ def test_keypoint_intensity(T, hip, h, w, size, base):
     for fill in FILLS:
         b = Bufs(T)
         th, tv = _tables(b, hip, h, w, size, True)
-        out = b.o("intensity", (A0_FRAMES, A0_K))
+        out = b.o("out", (A0_FRAMES, A0_K))
         hip.keypoint_intensity(_image(b, case["imgs"], base, fill), size, th, tv, b.i("kp_pixel", case["kp"]), out=out)
         b.check(f"keypoint_intensity {h}x{w}->{size} base {base} bands {fill:#04x}")
         assert_bits(T, out, case["inten"], "keypoint_intensity")
@@ -738,8 +753,8 @@ def _stack(per):
     return np.stack([p[0] for p in per]), np.stack([p[1] for p in per]), np.array([p[2] for p in per], np.int32)
 
 
-def _finalize_out(b, T, n_pairs, n1):
-    return b.o("matches", (n_pairs, n1, 2), T.int64), b.o("quality", (n_pairs, n1)), b.o("count", (n_pairs,), T.int32)
+def _finalize_out(b, T, n_pairs, n1, value="quality"):
+    return b.o("matches", (n_pairs, n1, 2), T.int64), b.o(value, (n_pairs, n1)), b.o("count", (n_pairs,), T.int32)
 
 
 def _check_finalize(T, out, want, what):
@@ -785,8 +800,8 @@ def test_match_finalize_pairs(T, hip, K, n_pairs, run):
     b = Bufs(T)
     out = _finalize_out(b, T, n_pairs, K)
     hip.match_finalize_pairs(b.i("nn12", c["nn12"]), b.i("s12", c["s12"]), b.i("nn21", c["nn21"]), b.i("pair_first", c["first"]),
-                             b.i("pair_second", c["second"]), b.i("scores", c["scores"]),
-                             b.i("intensity", c["intensity"]) if "intensity1" in kw else None, *thr, out=out)
+                             b.i("pair_second", c["second"]), b.i("scores_bank", c["scores"]),
+                             b.i("intensity_bank", c["intensity"]) if "intensity1" in kw else None, *thr, out=out)
     b.check(f"match_finalize_pairs K {K} x {n_pairs} {run}")
     _check_finalize(T, out, _stack(per), f"match_finalize_pairs {run}")
 
@@ -806,12 +821,12 @@ def test_match_finalize_rule(T, hip, n1, n2, n_pairs, rule):
     c = sim_case(n1, n2, 128, n_pairs)
     param = float(np.float32(mc.MIDDLE[rule]))
     b = Bufs(T)
-    out = _finalize_out(b, T, n_pairs, n1)
+    out = _finalize_out(b, T, n_pairs, n1, "value")
     args = (*_rule_inputs(b, c, rule), n1, n2, n_pairs, RULES[rule], param)
     if rule == mc.MNN_RATIO and n2 < 2:
         with pytest.raises(ValueError):
             hip.match_finalize_rule(*args, out=out)
-        b.check(f"match_finalize_rule ({n1}, {n2}) {rule}, refused", unwritten=("matches", "quality", "count"))
+        b.check(f"match_finalize_rule ({n1}, {n2}) {rule}, refused", unwritten=("matches", "value", "count"))
         return
     hip.match_finalize_rule(*args, out=out)
     b.check(f"match_finalize_rule ({n1}, {n2}) x {n_pairs} {rule}")
@@ -826,12 +841,12 @@ def test_match_finalize_rule_pairs(T, hip, K, n_pairs, rule):
     c = bank_case(K, 128, n_pairs)
     param = float(np.float32(mc.MIDDLE[rule]))
     b = Bufs(T)
-    out = _finalize_out(b, T, n_pairs, K)
+    out = _finalize_out(b, T, n_pairs, K, "value")
     args = (*_rule_inputs(b, c, rule), b.i("pair_first", c["first"]), b.i("pair_second", c["second"]), 4, RULES[rule], param)
     if rule == mc.MNN_RATIO and K < 2:
         with pytest.raises(ValueError):
             hip.match_finalize_rule_pairs(*args, out=out)
-        b.check(f"match_finalize_rule_pairs K {K} {rule}, refused", unwritten=("matches", "quality", "count"))
+        b.check(f"match_finalize_rule_pairs K {K} {rule}, refused", unwritten=("matches", "value", "count"))
         return
     hip.match_finalize_rule_pairs(*args, out=out)
     b.check(f"match_finalize_rule_pairs K {K} x {n_pairs} {rule}")
@@ -918,8 +933,8 @@ def test_vit_forward_bf16(T, hip, size, frames, form, entry):
     runs = []
     for fill in FILLS:
         b = Bufs(T)
-        d_x = b.i(entry, x, guard=gd.GUARD_WIDE)
-        out = b.o("tokens", (frames, 5 + g * g, 384), guard=gd.GUARD_WIDE)
+        d_x = b.i({"images": "images_chw", "patches": "patches_bf16"}[entry], x, guard=gd.GUARD_WIDE)
+        out = b.o("tokens_out", (frames, 5 + g * g, 384), guard=gd.GUARD_WIDE)
         ws = gd.dirty(T, need, fill)
         if entry == "patches":
             hip.vit_forward_patches(d_x, size, hv.w, ws, out=out, form=named)
@@ -942,8 +957,8 @@ def test_vit_forward_f32(T, hip, size, frames, attention):
     runs = []
     for fill in FILLS:
         b = Bufs(T)
-        out = b.o("tokens", (frames, 5 + g * g, 384), guard=gd.GUARD_WIDE)
-        hip.vit_forward_f32(b.i("images", c["x"].cpu().numpy(), guard=gd.GUARD_WIDE), hv.w, gd.dirty(T, need, fill), out=out,
+        out = b.o("tokens_out", (frames, 5 + g * g, 384), guard=gd.GUARD_WIDE)
+        hip.vit_forward_f32(b.i("images_chw", c["x"].cpu().numpy(), guard=gd.GUARD_WIDE), hv.w, gd.dirty(T, need, fill), out=out,
                             attention_form={"one_pass": hip.ATTN_ONE_PASS, "key_split": hip.ATTN_KEY_SPLIT}[attention])
         b.check(f"vit_forward_f32 {size} x {frames} {attention} workspace {fill:#04x}")
         runs.append((out,))

@@ -26,8 +26,9 @@ def T():
     return torch
 
 
-def _dev(T, a):
-    return None if a is None else T.from_numpy(np.ascontiguousarray(a)).cuda()
+def _dev(T, a, name=None):
+    """The device copy of an input; `name`, its argument in include/sslam_hip.h, places it under a guarded.Placement."""
+    return guarded.device_input(T, a, name)
 
 
 def _outputs(T, keys, n_pairs, n1):
@@ -36,7 +37,7 @@ def _outputs(T, keys, n_pairs, n1):
     shapes, out = lib.pose_depth_score_shapes(n_pairs, n1), {}
     for key in keys:
         shape, dt = shapes[key]
-        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt)
+        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt, name=key)
         out[key] = (whole, mid, mid.view(T.float64) if dt == T.float64 else mid)
     return out
 
@@ -55,8 +56,8 @@ def _untouched(T, what, *pairs):
 
 def gather(T, c):
     from sslam_amd import lib
-    dd, dk = _dev(T, c["depth"]), _dev(T, c["kp"])
-    whole, mid = guarded.guarded(T, c["kp"].shape[:2], T.int32)
+    dd, dk = _dev(T, c["depth"], "depth"), _dev(T, c["kp"], "kp_pixel")
+    whole, mid = guarded.guarded(T, c["kp"].shape[:2], T.int32, name="kp_depth")
     n0 = lib.launch_count()
     lib.keypoint_depth(dd, dk, c["scale_x"], c["scale_y"], out=mid)
     assert lib.launch_count() - n0 == 1, "one launch"
@@ -69,7 +70,8 @@ def gather(T, c):
 def depth_nn(T, c, threshold=None):
     """sslam_pose_depth_nn_pairs on a case of pose_depth_cases, one launch into poisoned, guarded outputs -> dict of numpy arrays."""
     from sslam_amd import lib
-    db, dd, df, ds, dt = (_dev(T, c[key]) for key in ("bank", "depth_bank", "first", "second", "T"))
+    db, dd, df, ds, dt = (_dev(T, c[key], name) for key, name in (("bank", "kp_bank"), ("depth_bank", "kp_depth_bank"), ("first", "pair_first"),
+                                                                  ("second", "pair_second"), ("T", "T")))
     out = _outputs(T, lib.POSE_DEPTH_SCORE_KEYS, len(c["first"]), c["n1"])
     n0 = lib.launch_count()
     lib.pose_depth_nn_pairs(db, dd, df, ds, dt, c["cam"], c["scale_x"], c["scale_y"], c["threshold"] if threshold is None else threshold,
@@ -163,7 +165,7 @@ def test_translation_is_seen_by_the_depth_entry_and_not_by_the_homography(T):
 def score(T, c, gt_of_row, count, known=True):
     from sslam_amd import lib
     host = [(c["matches"], np.int64), (c["value"], np.float32), (count, np.int32), (gt_of_row, np.int32), (c["gt_count"], np.int32)]
-    ins = [_dev(T, np.asarray(a, dt)) for a, dt in host]
+    ins = [_dev(T, np.asarray(a, dt), name) for (a, dt), name in zip(host, ("matches", "value", "count", "gt_of_row", "gt_count"))]
     keys = lib.MATCH_KNOWN_SCORE_KEYS if known else lib.MATCH_SCORE_KEYS
     out = _outputs(T, keys, len(count), c["n1"])
     n0 = lib.launch_count()

@@ -24,8 +24,9 @@ def T():
     return torch
 
 
-def _dev(T, a):
-    return None if a is None else T.from_numpy(np.ascontiguousarray(a)).cuda()
+def _dev(T, a, name=None):
+    """The device copy of an input; `name`, its argument in include/sslam_hip.h, places it under a guarded.Placement."""
+    return guarded.device_input(T, a, name)
 
 
 def _outputs(T, keys, n_pairs, n1):
@@ -34,7 +35,7 @@ def _outputs(T, keys, n_pairs, n1):
     shapes, out = lib.pose_score_shapes(n_pairs, n1), {}
     for key in keys:
         shape, dt = shapes[key]
-        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt)
+        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt, name=key)
         out[key] = (whole, mid, mid.view(T.float64) if dt == T.float64 else mid)
     return out
 
@@ -49,7 +50,8 @@ def _collect(out, what):
 def pose_nn(T, bank, first, second, H, thr, n1=None, n2=None):
     """One launch into poisoned, guarded outputs; the inputs come back untouched.  -> dict of numpy arrays."""
     from sslam_amd import lib
-    db, df, ds, dh = _dev(T, bank), _dev(T, np.asarray(first, np.int32)), _dev(T, np.asarray(second, np.int32)), _dev(T, H)
+    db, df, ds, dh = (_dev(T, bank, "kp_bank"), _dev(T, np.asarray(first, np.int32), "pair_first"),
+                      _dev(T, np.asarray(second, np.int32), "pair_second"), _dev(T, H, "H"))
     out = _outputs(T, lib.POSE_SCORE_KEYS, len(first), bank.shape[1] if n1 is None else n1)
     n0 = lib.launch_count()
     lib.pose_nn_pairs(db, df, ds, dh, thr, n1=n1, n2=n2, out=tuple(out[key][2] for key in lib.POSE_SCORE_KEYS))
@@ -60,8 +62,9 @@ def pose_nn(T, bank, first, second, H, thr, n1=None, n2=None):
 
 def match_score(T, pred, value, count, gt_of_row, gt_count):
     from sslam_amd import lib
-    ins = [_dev(T, np.asarray(a, dt)) for a, dt in ((pred, np.int64), (value, np.float32), (count, np.int32), (gt_of_row, np.int32),
-                                                     (gt_count, np.int32))]
+    ins = [_dev(T, np.asarray(a, dt), name) for a, dt, name in ((pred, np.int64, "matches"), (value, np.float32, "value"),
+                                                                  (count, np.int32, "count"), (gt_of_row, np.int32, "gt_of_row"),
+                                                                  (gt_count, np.int32, "gt_count"))]
     out = _outputs(T, lib.MATCH_SCORE_KEYS, pred.shape[0], pred.shape[1])
     n0 = lib.launch_count()
     lib.match_score_pairs(*ins, out=tuple(out[key][2] for key in lib.MATCH_SCORE_KEYS))

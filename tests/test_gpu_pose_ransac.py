@@ -38,17 +38,18 @@ def _outputs(T, n_pairs, n1):
     shapes, out = lib.pose_ransac_shapes(n_pairs, n1), {}
     for key in lib.POSE_RANSAC_KEYS:
         shape, dt = shapes[key]
-        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt)
+        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt, name=key)
         out[key] = (whole, mid, mid.view(T.float64) if dt == T.float64 else mid)
     return out
 
 
 INPUTS = ("bank", "depth_bank", "first", "second", "matches", "count")
+ARG = dict(bank="kp_bank", depth_bank="kp_depth_bank", first="pair_first", second="pair_second", matches="matches", count="count")      # include/sslam_hip.h
 
 
 def _inputs(T, c):
     """The case's inputs between NaN-bit bands: {key: (whole, middle)}."""
-    return {key: guarded.guarded_input(T, c[key]) for key in INPUTS}
+    return {key: guarded.guarded_input(T, c[key], name=ARG[key]) for key in INPUTS}
 
 
 def run_case(T, c, seed, n_hyp=None, threshold=None):

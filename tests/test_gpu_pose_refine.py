@@ -37,12 +37,13 @@ def _outputs(T, n_pairs, n1):
     shapes, out = lib.pose_refine_shapes(n_pairs, n1), {}
     for key in lib.POSE_REFINE_KEYS:
         shape, dt = shapes[key]
-        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt)
+        whole, mid = guarded.guarded(T, shape, T.int64 if dt == T.float64 else dt, name=key)
         out[key] = (whole, mid, mid.view(T.float64) if dt == T.float64 else mid)
     return out
 
 
 INPUTS = ("bank", "depth_bank", "first", "second", "matches", "count")
+ARG = dict(bank="kp_bank", depth_bank="kp_depth_bank", first="pair_first", second="pair_second", matches="matches", count="count")      # include/sslam_hip.h
 
 
 def run_case(T, c, **override):
@@ -50,8 +51,8 @@ def run_case(T, c, **override):
     from sslam_amd import lib
     a = dict(threshold=c["threshold"], huber=c["huber"], n_iter=c["n_iter"], T_in=c["T_in"])
     a.update(override)
-    ins = {key: guarded.guarded_input(T, c[key]) for key in INPUTS}
-    ins["T_in"] = guarded.guarded_input(T, np.ascontiguousarray(a["T_in"]).view(np.int64))      # float64 bits, NaN among them
+    ins = {key: guarded.guarded_input(T, c[key], name=ARG[key]) for key in INPUTS}
+    ins["T_in"] = guarded.guarded_input(T, np.ascontiguousarray(a["T_in"]).view(np.int64), name="T_in")      # float64 bits, NaN among them
     out = _outputs(T, len(c["first"]), c["n1"])
     n0 = lib.launch_count()
     lib.pose_refine_pairs(*(ins[key][1] for key in INPUTS), c["cam"], ins["T_in"][1].view(T.float64), c["scale_x"], c["scale_y"], a["threshold"],
