@@ -90,6 +90,9 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t *__restri
 //    multiply hipcc picks for `int * int` is quarter rate and was half of this kernel's VALU time;
 //  - the uint8 intermediate row is kept packed (R | G<<8 | B<<16) so the vertical pass reads one dword per tap;
 //  - the vertical coefficients of an output row are wave-uniform (a wave owns whole rows): scalar loads.
+//  - the planar fp32 image is written once and not read by this launch: non-temporal dword stores (0.522 -> 0.514 ms at 613
+//    frames; on the 2-byte stores of the PATCH form they cost 0.11 ms, so those keep the default policy).  A lane still owns
+//    one column: 16-byte stores from four columns per lane were slower in both forms tried (DESIGN_HISTORY.md)
 //  - TAPS (3, 5 or 7) is the compile-time tap count: 640 -> 448 bilinear needs 5, so two of seven tap slots would be zeros.
 //  - PATCH = true: the output is not the planar fp32 image but the ViT's patch-embedding operand - bf16 rows of 768 per
 //    16 x 16 patch, k = c * 256 + ky * 16 + kx (what im2patch_kernel of vit.hip made from the fp32 image): the same
@@ -151,6 +154,13 @@ __global__ __launch_bounds__(256) void preprocess_fast_kernel(const uint8_t *__r
                     wds[i][4] = hi[0], wds[i][5] = hi[1];
                 }
             }
+            // hipcc sinks a row's loads into the conditional block that filters it - load, s_waitcnt vmcnt(0), filter, row after
+            // row: one memory round trip per source row and wave.  An empty asm that names every loaded dword keeps the loads of
+            // all RB rows in front of the first filter (0.514 -> 0.432 ms at 613 frames; RB = 2, 4, 5, 6 and 10 were slower)
+#pragma unroll
+            for (int i = 0; i < RB; i++)
+#pragma unroll
+                for (int j = 0; j < NW; j++) asm volatile("" : "+v"(wds[i][j]));
 #pragma unroll
             for (int i = 0; i < RB; i++) {
                 const int rr = rr0 + 4 * i;
@@ -201,9 +211,9 @@ __global__ __launch_bounds__(256) void preprocess_fast_kernel(const uint8_t *__r
                     o[512] = (__bf16)lut[2][clip8(s2)];
                 } else {
                     float *o = out + (long long)f * 3 * plane + (long long)oy * size + (x0 + xx);
-                    o[0] = lut[0][clip8(s0)];
-                    o[plane] = lut[1][clip8(s1)];
-                    o[2 * plane] = lut[2][clip8(s2)];
+                    __builtin_nontemporal_store(lut[0][clip8(s0)], o);
+                    __builtin_nontemporal_store(lut[1][clip8(s1)], o + plane);
+                    __builtin_nontemporal_store(lut[2][clip8(s2)], o + 2 * plane);
                 }
             }
         }
@@ -242,6 +252,77 @@ __global__ __launch_bounds__(256) void intensity_kernel(const uint8_t *__restric
     }
     const int R = clip8(a0), Gc = clip8(a1), B = clip8(a2);
     const int L = (R * 19595 + Gc * 38470 + B * 7471 + 0x8000) >> 16;   // Pillow "L" (ITU-R 601-2, 16-bit fixed)
+    out[i] = (float)L / 255.0f;
+}
+
+// A9 in the idiom of preprocess_fast_kernel (horizontal taps <= 7, vertical taps <= 7, a dword-aligned image base, all frames
+// inside one 32-bit descriptor): a keypoint's source rows come as range-checked dword loads at the dword below the first byte,
+// all issued before the first is used, and are re-aligned with v_alignbyte; 32-bit offsets into one descriptor; every product
+// is an 8-bit sample times a 22-bit coefficient (v_mad_i32_i24), and the "L" step multiplies 8-bit by 16-bit values: every sum
+// stays what the 32-bit arithmetic of intensity_kernel gives.  TAPS / VT are the compile-time tap bounds (3, 5 or 7); rows past
+// a keypoint's own count are not loaded and take a zero coefficient.
+template <int TAPS, int VT>
+__global__ __launch_bounds__(256) void intensity_fast_kernel(const uint8_t *__restrict__ img, unsigned total_bytes, int h, int w,
+                                                              int size, const int *__restrict__ bh, const int *__restrict__ ch,
+                                                              int ksh, const int *__restrict__ bv, const int *__restrict__ cv,
+                                                              int ksv, const float *__restrict__ kp_pixel, int K, int total,
+                                                              float *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const unsigned f = (unsigned)i / (unsigned)K;
+    const __amdgpu_buffer_rsrc_t irs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(img), 0, (int)((total_bytes + 3u) & ~3u), 0x00020000);
+    // numpy round() is half-to-even; clip to the resized image (visualize_matches_sequence.py:93-94)
+    int X = (int)__builtin_rintf(kp_pixel[2 * (size_t)i]), Y = (int)__builtin_rintf(kp_pixel[2 * (size_t)i + 1]);
+    X = min(max(X, 0), size - 1);
+    Y = min(max(Y, 0), size - 1);
+    const int xmin = bh[2 * X], xn = bh[2 * X + 1], ymin = bv[2 * Y], yn = bv[2 * Y + 1];
+    constexpr int NW = (3 * TAPS + 3 + 3) / 4;                               // dwords covering 3*TAPS bytes at any alignment
+    const unsigned col0 = f * (unsigned)(h * w * 3) + (unsigned)(ymin * w + xmin) * 3u;
+    const unsigned rstride = (unsigned)w * 3u;
+    unsigned wds[VT][8];
+#pragma unroll
+    for (int ry = 0; ry < VT; ry++) {
+#pragma unroll
+        for (int j = 0; j < NW; j++) wds[ry][j] = 0;
+        if (ry < yn) {
+            const int a0 = (int)((col0 + (unsigned)ry * rstride) & ~3u);
+            const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(irs, a0, 0, 0);
+            wds[ry][0] = lo[0], wds[ry][1] = lo[1], wds[ry][2] = lo[2], wds[ry][3] = lo[3];
+            if constexpr (NW == 5) wds[ry][4] = __builtin_amdgcn_raw_buffer_load_b32(irs, a0, 16, 0);
+            if constexpr (NW == 6) {
+                const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(irs, a0, 16, 0);
+                wds[ry][4] = hi[0], wds[ry][5] = hi[1];
+            }
+        }
+    }
+    int kh[TAPS], kv[VT];
+#pragma unroll
+    for (int t = 0; t < TAPS; t++) kh[t] = t < xn ? ch[X * ksh + min(t, ksh - 1)] : 0;
+#pragma unroll
+    for (int t = 0; t < VT; t++) kv[t] = t < yn ? cv[Y * ksv + min(t, ksv - 1)] : 0;
+    int a0 = 1 << (PREC - 1), a1 = a0, a2 = a0;
+#pragma unroll
+    for (int ry = 0; ry < VT; ry++) {
+        const int sh = (int)((col0 + (unsigned)ry * rstride) & 3u);
+        unsigned al[NW];                                                     // bytes of the row's first sample onwards, in order
+#pragma unroll
+        for (int j = 0; j < NW - 1; j++) al[j] = __builtin_amdgcn_alignbyte(wds[ry][j + 1], wds[ry][j], sh);
+        al[NW - 1] = wds[ry][NW - 1] >> (8 * sh);
+        int s0 = 1 << (PREC - 1), s1 = s0, s2 = s0;
+#pragma unroll
+        for (int t = 0; t < TAPS; t++) {
+            const int o = 3 * t;
+            s0 += __mul24((int)((al[o >> 2] >> (8 * (o & 3))) & 255), kh[t]);
+            s1 += __mul24((int)((al[(o + 1) >> 2] >> (8 * ((o + 1) & 3))) & 255), kh[t]);
+            s2 += __mul24((int)((al[(o + 2) >> 2] >> (8 * ((o + 2) & 3))) & 255), kh[t]);
+        }
+        a0 += __mul24(clip8(s0), kv[ry]);
+        a1 += __mul24(clip8(s1), kv[ry]);
+        a2 += __mul24(clip8(s2), kv[ry]);
+    }
+    const int R = clip8(a0), Gc = clip8(a1), B = clip8(a2);
+    const int L = (__mul24(R, 19595) + __mul24(Gc, 38470) + __mul24(B, 7471) + 0x8000) >> 16;   // Pillow "L": < 2^24
     out[i] = (float)L / 255.0f;
 }
 
@@ -377,9 +458,33 @@ extern "C" int sslam_keypoint_intensity(const uint8_t *img, int n, int h, int w,
         size <= 0 || K <= 0)
         return SSLAM_E_INVALID;
     if (sslam_misaligned(4, bounds_h, coefs_h, bounds_v, coefs_v, kp_pixel, out)) return SSLAM_E_INVALID;
-    const long long total = (long long)n * K;
-    hipLaunchKernelGGL(intensity_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, h, w,
-                       size, bounds_h, coefs_h, ksize_h, bounds_v, coefs_v, ksize_v, kp_pixel, K, total, out);
+    const long long total = (long long)n * K, bytes = (long long)n * h * w * 3;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    // the fast kernel: few taps both ways, a dword-aligned base, every byte offset and keypoint index in 32 bits
+    const bool fast = ksize_h <= 7 && ksize_v <= 7 && !((uintptr_t)img & 3) && bytes <= 0xfffffff0LL && total <= 0x7fffff00LL;
+#define FASTI(T, V)                                                                                                    \
+    hipLaunchKernelGGL((intensity_fast_kernel<T, V>), grid, dim3(256), 0, (hipStream_t)stream, img, (unsigned)bytes, h, w, size, \
+                       bounds_h, coefs_h, ksize_h, bounds_v, coefs_v, ksize_v, kp_pixel, K, (int)total, out)
+#define FASTV(T)                                                                                                       \
+    {                                                                                                                  \
+        if (ksize_v <= 3)                                                                                              \
+            FASTI(T, 3);                                                                                               \
+        else if (ksize_v <= 5)                                                                                         \
+            FASTI(T, 5);                                                                                               \
+        else                                                                                                           \
+            FASTI(T, 7);                                                                                               \
+    }
+    if (fast && ksize_h <= 3)
+        FASTV(3)
+    else if (fast && ksize_h <= 5)
+        FASTV(5)
+    else if (fast)
+        FASTV(7)
+    else
+        hipLaunchKernelGGL(intensity_kernel, grid, dim3(256), 0, (hipStream_t)stream, img, h, w, size, bounds_h, coefs_h,
+                           ksize_h, bounds_v, coefs_v, ksize_v, kp_pixel, K, total, out);
+#undef FASTV
+#undef FASTI
     SSLAM_CHECK_LAUNCH();
     return SSLAM_OK;
 }
