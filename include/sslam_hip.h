@@ -707,7 +707,7 @@ int sslam_match_score_pairs(const int64_t *matches, const float *value, const in
                             const int32_t *gt_count, int n1, int n_pairs, int32_t *tp, int32_t *fp, int32_t *fn,
                             double *value_sum, void *stream);
 
-/* ---- The same scores against a translation-aware ground truth: depth and the full relative pose (csrc/evaluate_depth.hip).
+/* ---- The same scores against a translation-aware ground truth: depth and the full relative pose (csrc/evaluate.hip).
  * The entries above keep the reference's ground truth, H = K R K^-1 with the translation dropped; these use the D of RGB-D:
  * back-project a keypoint with its depth, move it by [R | t], project it into the other frame.  All arithmetic is float64, every
  * product, quotient and sum rounded once in the order written (no contraction).  Each entry is one launch that only enqueues:

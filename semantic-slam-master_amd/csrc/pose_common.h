@@ -1,5 +1,6 @@
-// pose_common.h - what the pose kernels share (pose_estimate.hip, pose_refine.hip): a pair's rows, the back-projection, the score of
-// a pose on a row, and the workgroup's float64 sums in the order include/sslam_hip.h states.
+// pose_common.h - what the pose kernels share (evaluate.hip, pose_estimate.hip, pose_refine.hip): the camera and the argument checks
+// of the depth-taking entries, a pair's rows and the list of its usable ones, the back-projection, the projection under a pose, the
+// score of a pose on a row, and the workgroup's float64 sums in the order include/sslam_hip.h states.
 #pragma once
 #include "common.h"
 
@@ -11,10 +12,25 @@ constexpr int POSE_THREADS = 256;      // the workgroup, whatever n_hyp: ONE ord
 constexpr int POSE_WAVES = POSE_THREADS / 64;
 
 inline bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
+inline bool finite_nonnegative(double v) { return v >= 0.0 && v - v == 0.0; }      // a threshold: no NaN, negative or infinite one
 
 struct PoseCamera {
     double fx, fy, cx, cy, depth_scale, scale_x, scale_y;
 };
+
+// What the entries that take a depth bank check alike - every failure is an invalid argument: the camera, the scales and the view,
+// the threshold, and the bank and pair-list pointers.
+inline bool pose_args_ok(const float *kp_bank, const int32_t *kp_depth_bank, const int32_t *pair_first, const int32_t *pair_second,
+                         double fx, double fy, double cx, double cy, double depth_scale, double scale_x, double scale_y, double view_w,
+                         double view_h, double threshold) {
+    if (!kp_bank || !kp_depth_bank || !pair_first || !pair_second) return false;
+    if (!finite_nonnegative(threshold)) return false;
+    if (!finite_positive(fx) || !finite_positive(fy) || !finite_positive(depth_scale) || !finite_positive(scale_x) ||
+        !finite_positive(scale_y))
+        return false;
+    if (cx - cx != 0.0 || cy - cy != 0.0 || !finite_positive(view_w) || !finite_positive(view_h)) return false;
+    return !((uintptr_t)kp_bank & 7) && !sslam_misaligned(4, kp_depth_bank, pair_first, pair_second);
+}
 
 struct PoseRow {
     double ax, ay, az, bx, by, bz;      // X_a, X_b
@@ -25,10 +41,28 @@ struct PosePair {
     const float2 *f1, *f2;
     const int *d1, *d2;
     const long long *matches;
-    int K;
+    int K, count;                       // count: the list's, clamped to its n1 slots
+    bool present;                       // both frames lie in the bank (uniform over the workgroup)
 };
 
-// the back-projection of sslam_pose_depth_nn_pairs
+// workgroup p's pair; an absent pair reads frame 0 and has no usable row
+__device__ __forceinline__ PosePair pose_pair(const float *kp_bank, const int *kp_depth_bank, int n_bank, int K, const int *pair_first,
+                                              const int *pair_second, const long long *matches, const int *count, int n1, long long p) {
+    const int a = pair_first[p], b = pair_second[p];
+    PosePair pp;
+    pp.present = (unsigned)a < (unsigned)n_bank && (unsigned)b < (unsigned)n_bank;
+    const int cnt = count[p];
+    pp.count = cnt < 0 ? 0 : (cnt > n1 ? n1 : cnt);
+    pp.f1 = reinterpret_cast<const float2 *>(kp_bank) + (long long)(pp.present ? a : 0) * K;
+    pp.f2 = reinterpret_cast<const float2 *>(kp_bank) + (long long)(pp.present ? b : 0) * K;
+    pp.d1 = kp_depth_bank + (long long)(pp.present ? a : 0) * K;
+    pp.d2 = kp_depth_bank + (long long)(pp.present ? b : 0) * K;
+    pp.matches = matches + p * n1 * 2;
+    pp.K = K;
+    return pp;
+}
+
+// a keypoint and the raw depth under it, in the camera's metres
 __device__ __forceinline__ void pose_back_project(const float2 q, int d, const PoseCamera &cam, double &X, double &Y, double &Z) {
     const double u = (double)q.x * cam.scale_x, v = (double)q.y * cam.scale_y, z = (double)d / cam.depth_scale;
     X = ((u - cam.cx) * z) / cam.fx;
@@ -42,6 +76,33 @@ __device__ __forceinline__ bool pose_usable(const PosePair &pp, int slot) {
     return pp.d1[i1] > 0 && pp.d2[i2] > 0;
 }
 
+// The usable rows in list order: uslot[u] is the slot of the u-th one.  A slot that is not usable gets its mask entry here (-1 a
+// listed row without depth, 0 past the count or of an absent pair), a usable one is left to the caller.  Every thread of the
+// workgroup calls it (two barriers per POSE_THREADS slots) and gets the number of usable rows.
+__device__ __forceinline__ int pose_list_usable(const PosePair &pp, int n1, unsigned short *uslot, int *wcnt, int *inlier_of_slot,
+                                                int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    int n_usable = 0;
+    for (int base = 0; base < n1; base += POSE_THREADS) {
+        const int r = base + tid;
+        const bool use = pp.present && r < pp.count && pose_usable(pp, r);
+        if (r < n1 && !use) inlier_of_slot[r] = (pp.present && r < pp.count) ? -1 : 0;
+        const unsigned long long mk = __ballot(use);
+        if (lane == 0) wcnt[wave] = __popcll(mk);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < POSE_WAVES; w++) {
+            const int n = wcnt[w];
+            if (w < wave) before += n;
+            total += n;
+        }
+        if (use) uslot[n_usable + before + __popcll(mk & ((1ull << lane) - 1ull))] = (unsigned short)r;
+        n_usable += total;
+        __syncthreads();
+    }
+    return n_usable;
+}
+
 // a USABLE slot's row
 __device__ __forceinline__ PoseRow pose_row(const PosePair &pp, int slot, const PoseCamera &cam) {
     const long long i1 = pp.matches[2 * slot], i2 = pp.matches[2 * slot + 1];
@@ -52,13 +113,21 @@ __device__ __forceinline__ PoseRow pose_row(const PosePair &pp, int slot, const 
     return r;
 }
 
+// a point under [R | t], projected into the other camera: the depth pixel (u2, v2) and the depth Z2 there
+__device__ __forceinline__ void pose_project(const double *m, double X, double Y, double Z, const PoseCamera &cam, double &u2, double &v2,
+                                             double &Z2) {
+    const double X2 = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
+    const double Y2 = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
+    Z2 = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
+    u2 = (cam.fx * X2) / Z2 + cam.cx;
+    v2 = (cam.fy * Y2) / Z2 + cam.cy;
+}
+
 // X_a under [R | t], projected into frame b, in keypoint units: the inlier test and the squared distance
 __device__ __forceinline__ bool pose_inlier(const double *m, double X, double Y, double Z, const float2 kb, const PoseCamera &cam,
                                             double threshold, double &s) {
-    const double X2 = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-    const double Y2 = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-    const double Z2 = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    const double u2 = (cam.fx * X2) / Z2 + cam.cx, v2 = (cam.fy * Y2) / Z2 + cam.cy;
+    double u2, v2, Z2;
+    pose_project(m, X, Y, Z, cam, u2, v2, Z2);
     const double dx = u2 / cam.scale_x - (double)kb.x, dy = v2 / cam.scale_y - (double)kb.y;
     s = dx * dx + dy * dy;
     return Z2 > 0.0 && __builtin_sqrt(s) < threshold;      // a NaN fails both

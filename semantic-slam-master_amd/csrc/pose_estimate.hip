@@ -144,41 +144,14 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_ransac_kernel(const float *
     __shared__ unsigned long long wkey[POSE_WAVES];
     __shared__ int wcnt[POSE_WAVES];
 
-    const int tid = threadIdx.x, nt = POSE_THREADS, lane = tid & 63, wave = tid >> 6, n_waves = POSE_WAVES;
+    const int tid = threadIdx.x, nt = POSE_THREADS, lane = tid & 63, wave = tid >> 6;
     const long long p = blockIdx.x;
     inlier_of_slot += p * n1;
     T_out += p * 12;
-    const int a = pair_first[p], b = pair_second[p];
-    const bool present = (unsigned)a < (unsigned)n_bank && (unsigned)b < (unsigned)n_bank;      // uniform over the workgroup
-    int cnt = count[p];
-    cnt = cnt < 0 ? 0 : (cnt > n1 ? n1 : cnt);
-    PosePair pp;
-    pp.f1 = reinterpret_cast<const float2 *>(kp_bank) + (long long)(present ? a : 0) * K;
-    pp.f2 = reinterpret_cast<const float2 *>(kp_bank) + (long long)(present ? b : 0) * K;
-    pp.d1 = kp_depth_bank + (long long)(present ? a : 0) * K;
-    pp.d2 = kp_depth_bank + (long long)(present ? b : 0) * K;
-    pp.matches = matches + p * n1 * 2;
-    pp.K = K;
+    const PosePair pp = pose_pair(kp_bank, kp_depth_bank, n_bank, K, pair_first, pair_second, matches, count, n1, p);
 
-    // ---- the usable rows in list order; every slot that is not usable gets its mask entry here, a usable one at the end
-    int n_usable = 0;
-    for (int base = 0; base < n1; base += nt) {
-        const int r = base + tid;
-        const bool use = present && r < cnt && pose_usable(pp, r);
-        if (r < n1 && !use) inlier_of_slot[r] = (present && r < cnt) ? -1 : 0;
-        const unsigned long long mk = __ballot(use);
-        if (lane == 0) wcnt[wave] = __popcll(mk);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < n_waves; w++) {
-            const int n = wcnt[w];
-            if (w < wave) before += n;
-            total += n;
-        }
-        if (use) uslot[n_usable + before + __popcll(mk & ((1ull << lane) - 1ull))] = (unsigned short)r;
-        n_usable += total;
-        __syncthreads();
-    }
+    // ---- the usable rows in list order; every slot that is not usable gets its mask entry there, a usable one at the end
+    const int n_usable = pose_list_usable(pp, n1, uslot, wcnt, inlier_of_slot, tid);
 
     if (n_usable < 3) {                                  // no pose (an absent pair has no usable row)
         for (int u = tid; u < n_usable; u += nt) inlier_of_slot[uslot[u]] = 0;
@@ -358,19 +331,15 @@ extern "C" int sslam_pose_ransac_pairs(const float *kp_bank, const int32_t *kp_d
                                        double view_w, double view_h, double threshold, int n_hyp, uint64_t seed, double *T,
                                        int32_t *inlier_count, int32_t *usable_count, int32_t *best_hypothesis, int32_t *refit_kept,
                                        int32_t *inlier_of_slot, double *rms, void *stream) {
-    if (!kp_bank || !kp_depth_bank || !pair_first || !pair_second || !matches || !count || !T || !inlier_count || !usable_count ||
-        !best_hypothesis || !refit_kept || !inlier_of_slot || !rms)
+    if (!pose_args_ok(kp_bank, kp_depth_bank, pair_first, pair_second, fx, fy, cx, cy, depth_scale, scale_x, scale_y, view_w, view_h,
+                      threshold))
+        return SSLAM_E_INVALID;
+    if (!matches || !count || !T || !inlier_count || !usable_count || !best_hypothesis || !refit_kept || !inlier_of_slot || !rms)
         return SSLAM_E_INVALID;
     if (n_bank <= 0 || K <= 0 || n1 <= 0 || n_pairs <= 0 || n1 > K) return SSLAM_E_INVALID;
     if (n_hyp < 1 || n_hyp > POSE_MAX_HYP) return SSLAM_E_INVALID;
-    if (!(threshold >= 0.0) || threshold - threshold != 0.0) return SSLAM_E_INVALID;       // NaN, negative, infinite
-    if (!finite_positive(fx) || !finite_positive(fy) || !finite_positive(depth_scale) || !finite_positive(scale_x) ||
-        !finite_positive(scale_y))
-        return SSLAM_E_INVALID;
-    if (cx - cx != 0.0 || cy - cy != 0.0 || !finite_positive(view_w) || !finite_positive(view_h)) return SSLAM_E_INVALID;
-    if ((uintptr_t)kp_bank & 7 || (uintptr_t)kp_depth_bank & 3 || (uintptr_t)pair_first & 3 || (uintptr_t)pair_second & 3 ||
-        (uintptr_t)matches & 7 || (uintptr_t)count & 3 || (uintptr_t)T & 7 || (uintptr_t)rms & 7 || (uintptr_t)inlier_count & 3 ||
-        (uintptr_t)usable_count & 3 || (uintptr_t)best_hypothesis & 3 || (uintptr_t)refit_kept & 3 || (uintptr_t)inlier_of_slot & 3)
+    if (sslam_misaligned(8, matches, T, rms) ||
+        sslam_misaligned(4, count, inlier_count, usable_count, best_hypothesis, refit_kept, inlier_of_slot))
         return SSLAM_E_INVALID;
     if (K > POSE_MAX_N1) return SSLAM_E_UNSUPPORTED;
     const PoseCamera cam = {fx, fy, cx, cy, depth_scale, scale_x, scale_y};

@@ -5,7 +5,7 @@ keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (
     compute_ground_truth_matches   DescriptorQualityTester.compute_ground_truth_matches   test/test_descriptor_quality.py:144-185
     evaluate_matches               DescriptorQualityTester.evaluate_matches               test/test_descriptor_quality.py:187-231
 
-Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate_depth.hip):
+Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate.hip):
 compute_repeatability_depth and compute_ground_truth_matches_depth - and, beside matching.py's matchers, the step that follows
 them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip), and refine_relative_pose, that
 motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip).

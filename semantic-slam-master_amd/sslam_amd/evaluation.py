@@ -18,7 +18,7 @@ The warp is the reference's: H = K R K^-1 with the TUM intrinsics 525 / 319.5 / 
 rotation of the relative pose pose2 pose1^-1 ROUNDED TO FLOAT32 (data/tum_dataset.py:191-195 hands it over as a float tensor);
 the translation is ignored, as there.
 
-A second, opt-in ground truth uses the D of RGB-D (depth=, camera=; csrc/evaluate_depth.hip): every keypoint is back-projected
+A second, opt-in ground truth uses the D of RGB-D (depth=, camera=; csrc/evaluate.hip): every keypoint is back-projected
 with its depth, moved by the full relative pose relative_transform = inv(pose_b) @ pose_a (float64, not rounded) and projected
 into the other frame with the sequence's own intrinsics (Camera; tum.camera_for).  A keypoint without a depth measurement, behind
 the other camera or outside its view has no ground truth: it leaves the repeatability's denominator, and a match on it is counted

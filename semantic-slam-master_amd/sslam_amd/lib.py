@@ -844,9 +844,9 @@ def pose_score_shapes(n_pairs: int, n1: int) -> dict:
             "fn": ((n_pairs,), torch.int32), "value_sum": ((n_pairs,), torch.float64)}
 
 
-def _score_out(out, keys, n_pairs, n1, dev=None):
-    """The output tensors of a scoring call: `out` checked against the shapes (no device needed), or fresh ones on dev."""
-    shapes = pose_score_shapes(n_pairs, n1)
+def _outputs(shapes, keys, out, dev=None):
+    """The output tensors of a call, in the order of `keys`: `out` checked against `shapes` (name -> (shape, dtype); no device
+    needed), or fresh ones on dev."""
     if out is None:
         return [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in keys]
     if len(out) != len(keys):
@@ -858,39 +858,71 @@ def _score_out(out, keys, n_pairs, n1, dev=None):
     return list(out)
 
 
+def _pose_operands(what, kp_bank, first, second, threshold, depth=None, rows=None, listed=None):
+    """The operands the bank-and-pairs wrappers share, checked before any device work: the bank kp_bank (n_bank, K, 2), the pair
+    lists and the threshold; depth: (kp_depth_bank, camera, scale_x, scale_y) of a wrapper that takes them; rows: (n1, n2) of a
+    search, None standing for K - or listed: (matches, count), a match list of n1 slots per pair; K against EVAL_MAX_K.
+    Returns (n_bank, k, n_pairs, n1, n2 - None for a list -, the C doubles every such entry takes in this order: with depth fx, fy,
+    cx, cy, depth_scale, scale_x, scale_y, view_w, view_h, then the threshold)."""
+    _check_bank("kp_bank", kp_bank, ("K", 2))
+    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
+    if depth is not None:
+        if depth[0] is None:
+            raise ValueError("kp_depth_bank is required")
+        _check_arrays((n_bank, k), ("kp_depth_bank", depth[0], torch.int32))
+    n_pairs = check_pair_lists(first, second, kp_bank.device)
+    if listed is None:
+        n1, n2 = (k if v is None else v for v in rows)
+        for name, v in (("n1", n1), ("n2", n2)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= k:
+                raise ValueError(f"{name} must be an int in [1, {k}], got {v!r}")
+        n1, n2 = int(n1), int(n2)
+    else:
+        matches, count = listed
+        if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_pairs or \
+                not 1 <= int(matches.shape[1]) <= k:
+            raise ValueError(f"matches must be a tensor of shape ({n_pairs}, n1 in [1, {k}], 2)")
+        n1, n2 = int(matches.shape[1]), None
+        if count is None:
+            raise ValueError("count is required")
+        _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+        _check_arrays((n_pairs,), ("count", count, torch.int32))
+    doubles = (check_threshold(threshold),)
+    if depth is not None:
+        fx, fy, cx, cy, ds, vw, vh = check_camera(depth[1])
+        doubles = (fx, fy, cx, cy, ds, check_positive("scale_x", depth[2]), check_positive("scale_y", depth[3]), vw, vh) + doubles
+    if k > EVAL_MAX_K:
+        raise SslamHipError(f"{what}: {k} keypoints per frame; at most {EVAL_MAX_K} are handled on the device")
+    return n_bank, k, n_pairs, n1, n2, tuple(C.c_double(v) for v in doubles)
+
+
+def _check_pose_rows(name, t, n_pairs, cols):
+    """t: a pair's homography or [R | t] per row - a contiguous float64 tensor (n_pairs, cols) or (n_pairs, 3, cols / 3)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or \
+            tuple(t.shape) not in ((n_pairs, cols), (n_pairs, 3, cols // 3)):
+        raise ValueError(f"{name} must be a contiguous float64 tensor of shape ({n_pairs}, {cols}) or ({n_pairs}, 3, {cols // 3})")
+
+
 def pose_nn_pairs(kp_bank, first, second, H=None, threshold=3.0, n1=None, n2=None, out=None):
     """sslam_pose_nn_pairs: kp_bank (n_bank, K, 2) fp32 pixel keypoints; first / second: 1-D int32 DEVICE lists naming each pair's
     two frames (-1 = absent pair); H (n_pairs, 9) or (n_pairs, 3, 3) float64 device tensor of homographies first -> second, or None
     for the raw coordinates.  n1 / n2: the rows of the first / second frame that count (K by default).
     Returns (gt_matches (P, n1, 2) int64, gt_count (P,) int32, gt_of_row (P, n1) int32, dist_sum (P,) float64, dist_median (P,)
     float64) - include/sslam_hip.h states them; out: optional tensors of those shapes to write into.  One launch, no host read."""
-    _check_bank("kp_bank", kp_bank, ("K", 2))
-    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
-    n_pairs = check_pair_lists(first, second, kp_bank.device)
-    n1, n2 = (k if v is None else v for v in (n1, n2))
-    for name, v in (("n1", n1), ("n2", n2)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= k:
-            raise ValueError(f"{name} must be an int in [1, {k}], got {v!r}")
-    n1, n2 = int(n1), int(n2)
-    t = check_threshold(threshold)
+    n_bank, k, n_pairs, n1, n2, (t,) = _pose_operands("pose_nn_pairs", kp_bank, first, second, threshold, rows=(n1, n2))
     if H is not None:
-        if not isinstance(H, torch.Tensor) or H.dtype != torch.float64 or not H.is_contiguous() or \
-                tuple(H.shape) not in ((n_pairs, 9), (n_pairs, 3, 3)):
-            raise ValueError(f"H must be a contiguous float64 tensor of shape ({n_pairs}, 9) or ({n_pairs}, 3, 3)")
-    if k > EVAL_MAX_K:
-        raise SslamHipError(f"pose_nn_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are searched on the device")
-    o = None if out is None else _score_out(out, POSE_SCORE_KEYS, n_pairs, n1)
+        _check_pose_rows("H", H, n_pairs, 9)
+    shapes = pose_score_shapes(n_pairs, n1)
+    o = None if out is None else _outputs(shapes, POSE_SCORE_KEYS, out)
     dev = common_device(kp_bank, first, second, H)
-    o = _score_out(None, POSE_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
+    o = _outputs(shapes, POSE_SCORE_KEYS, None, dev) if o is None else o
     _run("pose_nn_pairs", lib().sslam_pose_nn_pairs, (kp_bank, first, second, H, *o),
-         _dp(kp_bank), n_bank, k, n1, n2, _dp(first), _dp(second), n_pairs, _dp(H), C.c_double(t), *(_dp(x) for x in o))
+         _dp(kp_bank), n_bank, k, n1, n2, _dp(first), _dp(second), n_pairs, _dp(H), t, *(_dp(x) for x in o))
     return tuple(o)
 
 
-def match_score_pairs(matches, value, count, gt_of_row, gt_count, out=None):
-    """sslam_match_score_pairs: a match list (matches (P, n1, 2) int64, value (P, n1) fp32, count (P,) int32, as a finalize entry
-    wrote it; idx1 unique within a pair) against gt_of_row (P, n1) / gt_count (P,) of pose_nn_pairs over the same pairs.
-    Returns (tp, fp, fn (P,) int32, value_sum (P,) float64); out: optional tensors of those shapes.  One launch, no host read."""
+def _match_score(what, entry, keys, matches, value, count, gt_of_row, gt_count, out):
+    """match_score_pairs and match_score_known_pairs: the entry and its output keys apart, one call."""
     if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or matches.shape[0] < 1 or matches.shape[1] < 1:
         raise ValueError("matches must be a tensor of shape (n_pairs >= 1, n1 >= 1, 2)")
     n_pairs, n1 = int(matches.shape[0]), int(matches.shape[1])
@@ -901,16 +933,24 @@ def match_score_pairs(matches, value, count, gt_of_row, gt_count, out=None):
     _check_arrays((n_pairs, n1), ("value", value, torch.float32), ("gt_of_row", gt_of_row, torch.int32))
     _check_arrays((n_pairs,), ("count", count, torch.int32), ("gt_count", gt_count, torch.int32))
     if n1 > EVAL_MAX_K:
-        raise SslamHipError(f"match_score_pairs: lists of {n1} rows; at most {EVAL_MAX_K} are scored on the device")
-    o = None if out is None else _score_out(out, MATCH_SCORE_KEYS, n_pairs, n1)
+        raise SslamHipError(f"{what}: lists of {n1} rows; at most {EVAL_MAX_K} are scored on the device")
+    shapes = pose_depth_score_shapes(n_pairs, n1)
+    o = None if out is None else _outputs(shapes, keys, out)
     dev = common_device(matches, value, count, gt_of_row, gt_count)
-    o = _score_out(None, MATCH_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
-    _run("match_score_pairs", lib().sslam_match_score_pairs, (matches, value, count, gt_of_row, gt_count, *o),
+    o = _outputs(shapes, keys, None, dev) if o is None else o
+    _run(what, getattr(lib(), entry), (matches, value, count, gt_of_row, gt_count, *o),
          _dp(matches), _dp(value), _dp(count), _dp(gt_of_row), _dp(gt_count), n1, n_pairs, *(_dp(x) for x in o))
     return tuple(o)
 
 
-# ------------------------------------------------------------------------------- pose-based scoring with depth (evaluate_depth.hip)
+def match_score_pairs(matches, value, count, gt_of_row, gt_count, out=None):
+    """sslam_match_score_pairs: a match list (matches (P, n1, 2) int64, value (P, n1) fp32, count (P,) int32, as a finalize entry
+    wrote it; idx1 unique within a pair) against gt_of_row (P, n1) / gt_count (P,) of pose_nn_pairs over the same pairs.
+    Returns (tp, fp, fn (P,) int32, value_sum (P,) float64); out: optional tensors of those shapes.  One launch, no host read."""
+    return _match_score("match_score_pairs", "sslam_match_score_pairs", MATCH_SCORE_KEYS, matches, value, count, gt_of_row, gt_count, out)
+
+
+# ------------------------------------------------------------------------------- pose-based scoring with depth (evaluate.hip)
 POSE_DEPTH_SCORE_KEYS = ("gt_matches", "gt_count", "gt_of_row", "valid_count", "dist_sum", "dist_median")
 MATCH_KNOWN_SCORE_KEYS = ("tp", "fp", "fn", "unknown", "value_sum")
 CAMERA_FIELDS = ("fx", "fy", "cx", "cy", "depth_scale", "width", "height")
@@ -945,19 +985,6 @@ def check_camera(camera) -> tuple:
     return tuple(out)
 
 
-def _depth_score_out(out, keys, n_pairs, n1, dev=None):
-    shapes = pose_depth_score_shapes(n_pairs, n1)
-    if out is None:
-        return [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in keys]
-    if len(out) != len(keys):
-        raise ValueError(f"out must hold {len(keys)} tensors: {', '.join(keys)}")
-    for key, t in zip(keys, out):
-        if t is None:
-            raise ValueError(f"out `{key}` is required")
-        _check_arrays(shapes[key][0], (f"out `{key}`", t, shapes[key][1]))
-    return list(out)
-
-
 def keypoint_depth(depth, kp_pixel, scale_x=1.0, scale_y=1.0, out=None):
     """sslam_keypoint_depth: depth (n, h, w) uint16 raw depth images, kp_pixel (n, K, 2) fp32; scale_x / scale_y take keypoint
     units to depth pixels.  Returns kp_depth (n, K) int32: the raw value under each keypoint (nearest pixel), -1 outside the image
@@ -988,31 +1015,15 @@ def pose_depth_nn_pairs(kp_bank, kp_depth_bank, first, second, T, camera, scale_
     in depth pixels); scale_x / scale_y: keypoint units to depth pixels.
     Returns (gt_matches, gt_count, gt_of_row, valid_count, dist_sum, dist_median) - POSE_DEPTH_SCORE_KEYS; gt_of_row is -2 in a row
     without ground truth (include/sslam_hip.h).  out: optional tensors of those shapes.  One launch, no host read."""
-    _check_bank("kp_bank", kp_bank, ("K", 2))
-    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
-    if kp_depth_bank is None:
-        raise ValueError("kp_depth_bank is required")
-    _check_arrays((n_bank, k), ("kp_depth_bank", kp_depth_bank, torch.int32))
-    n_pairs = check_pair_lists(first, second, kp_bank.device)
-    n1, n2 = (k if v is None else v for v in (n1, n2))
-    for name, v in (("n1", n1), ("n2", n2)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= k:
-            raise ValueError(f"{name} must be an int in [1, {k}], got {v!r}")
-    n1, n2 = int(n1), int(n2)
-    t = check_threshold(threshold)
-    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
-    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
-    if not isinstance(T, torch.Tensor) or T.dtype != torch.float64 or not T.is_contiguous() or \
-            tuple(T.shape) not in ((n_pairs, 12), (n_pairs, 3, 4)):
-        raise ValueError(f"T must be a contiguous float64 tensor of shape ({n_pairs}, 12) or ({n_pairs}, 3, 4)")
-    if k > EVAL_MAX_K:
-        raise SslamHipError(f"pose_depth_nn_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are searched on the device")
-    o = None if out is None else _depth_score_out(out, POSE_DEPTH_SCORE_KEYS, n_pairs, n1)
+    n_bank, k, n_pairs, n1, n2, doubles = _pose_operands("pose_depth_nn_pairs", kp_bank, first, second, threshold,
+                                                         depth=(kp_depth_bank, camera, scale_x, scale_y), rows=(n1, n2))
+    _check_pose_rows("T", T, n_pairs, 12)
+    shapes = pose_depth_score_shapes(n_pairs, n1)
+    o = None if out is None else _outputs(shapes, POSE_DEPTH_SCORE_KEYS, out)
     dev = common_device(kp_bank, kp_depth_bank, first, second, T)
-    o = _depth_score_out(None, POSE_DEPTH_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
+    o = _outputs(shapes, POSE_DEPTH_SCORE_KEYS, None, dev) if o is None else o
     _run("pose_depth_nn_pairs", lib().sslam_pose_depth_nn_pairs, (kp_bank, kp_depth_bank, first, second, T, *o),
-         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, n1, n2, _dp(first), _dp(second), n_pairs, _dp(T),
-         *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), *(_dp(x) for x in o))
+         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, n1, n2, _dp(first), _dp(second), n_pairs, _dp(T), *doubles, *(_dp(x) for x in o))
     return tuple(o)
 
 
@@ -1020,23 +1031,8 @@ def match_score_known_pairs(matches, value, count, gt_of_row, gt_count, out=None
     """sslam_match_score_known_pairs: match_score_pairs against a gt_of_row that may hold -2 (pose_depth_nn_pairs).
     Returns (tp, fp, fn, unknown (P,) int32, value_sum (P,) float64) - MATCH_KNOWN_SCORE_KEYS: unknown counts the listed rows whose
     query has no ground truth, fp = count - tp - unknown.  out: optional tensors of those shapes.  One launch, no host read."""
-    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or matches.shape[0] < 1 or matches.shape[1] < 1:
-        raise ValueError("matches must be a tensor of shape (n_pairs >= 1, n1 >= 1, 2)")
-    n_pairs, n1 = int(matches.shape[0]), int(matches.shape[1])
-    for name, t in (("value", value), ("count", count), ("gt_of_row", gt_of_row), ("gt_count", gt_count)):
-        if t is None:
-            raise ValueError(f"{name} is required")
-    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
-    _check_arrays((n_pairs, n1), ("value", value, torch.float32), ("gt_of_row", gt_of_row, torch.int32))
-    _check_arrays((n_pairs,), ("count", count, torch.int32), ("gt_count", gt_count, torch.int32))
-    if n1 > EVAL_MAX_K:
-        raise SslamHipError(f"match_score_known_pairs: lists of {n1} rows; at most {EVAL_MAX_K} are scored on the device")
-    o = None if out is None else _depth_score_out(out, MATCH_KNOWN_SCORE_KEYS, n_pairs, n1)
-    dev = common_device(matches, value, count, gt_of_row, gt_count)
-    o = _depth_score_out(None, MATCH_KNOWN_SCORE_KEYS, n_pairs, n1, dev) if o is None else o
-    _run("match_score_known_pairs", lib().sslam_match_score_known_pairs, (matches, value, count, gt_of_row, gt_count, *o),
-         _dp(matches), _dp(value), _dp(count), _dp(gt_of_row), _dp(gt_count), n1, n_pairs, *(_dp(x) for x in o))
-    return tuple(o)
+    return _match_score("match_score_known_pairs", "sslam_match_score_known_pairs", MATCH_KNOWN_SCORE_KEYS, matches, value, count,
+                        gt_of_row, gt_count, out)
 
 
 # ------------------------------------------------------------------------------- relative pose from matches and depth (pose_estimate.hip)
@@ -1074,39 +1070,16 @@ def pose_ransac_pairs(kp_bank, kp_depth_bank, first, second, matches, count, cam
     Returns (T (P, 12) float64 [R | t] camera first -> camera second, inlier_count, usable_count, best_hypothesis, refit_kept (P,)
     int32, inlier_of_slot (P, n1) int32, rms (P,) float64) - POSE_RANSAC_KEYS, include/sslam_hip.h states them.  out: optional
     tensors of those shapes.  One launch, no host read."""
-    _check_bank("kp_bank", kp_bank, ("K", 2))
-    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
-    if kp_depth_bank is None:
-        raise ValueError("kp_depth_bank is required")
-    _check_arrays((n_bank, k), ("kp_depth_bank", kp_depth_bank, torch.int32))
-    n_pairs = check_pair_lists(first, second, kp_bank.device)
-    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_pairs or \
-            not 1 <= int(matches.shape[1]) <= k:
-        raise ValueError(f"matches must be a tensor of shape ({n_pairs}, n1 in [1, {k}], 2)")
-    n1 = int(matches.shape[1])
-    if count is None:
-        raise ValueError("count is required")
-    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
-    _check_arrays((n_pairs,), ("count", count, torch.int32))
-    t = check_threshold(threshold)
-    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
-    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
+    n_bank, k, n_pairs, n1, _, doubles = _pose_operands("pose_ransac_pairs", kp_bank, first, second, threshold,
+                                                        depth=(kp_depth_bank, camera, scale_x, scale_y), listed=(matches, count))
     n_hyp, seed = check_hypotheses(hypotheses), check_seed(seed)
-    if k > EVAL_MAX_K:
-        raise SslamHipError(f"pose_ransac_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are handled on the device")
     shapes = pose_ransac_shapes(n_pairs, n1)
-    if out is not None:
-        if len(out) != len(POSE_RANSAC_KEYS):
-            raise ValueError(f"out must hold {len(POSE_RANSAC_KEYS)} tensors: {', '.join(POSE_RANSAC_KEYS)}")
-        for key, x in zip(POSE_RANSAC_KEYS, out):
-            if x is None:
-                raise ValueError(f"out `{key}` is required")
-            _check_arrays(shapes[key][0], (f"out `{key}`", x, shapes[key][1]))
+    o = None if out is None else _outputs(shapes, POSE_RANSAC_KEYS, out)
     dev = common_device(kp_bank, kp_depth_bank, first, second, matches, count)
-    o = list(out) if out is not None else [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in POSE_RANSAC_KEYS]
+    o = _outputs(shapes, POSE_RANSAC_KEYS, None, dev) if o is None else o
     _run("pose_ransac_pairs", lib().sslam_pose_ransac_pairs, (kp_bank, kp_depth_bank, first, second, matches, count, *o),
-         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1,
-         *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), n_hyp, C.c_uint64(seed), *(_dp(x) for x in o))
+         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1, *doubles, n_hyp,
+         C.c_uint64(seed), *(_dp(x) for x in o))
     return tuple(o)
 
 
@@ -1147,44 +1120,19 @@ def pose_refine_pairs(kp_bank, kp_depth_bank, first, second, matches, count, cam
     inlier_of_slot (P, n1) int32, cost_in, cost, rms (P,) float64, info (P, 21) float64: the upper triangle of the 6 x 6
     information matrix, row-major) - POSE_REFINE_KEYS, include/sslam_hip.h states them.  out: optional tensors of those shapes
     (T must not be T_in).  One launch, no host read."""
-    _check_bank("kp_bank", kp_bank, ("K", 2))
-    n_bank, k = int(kp_bank.shape[0]), int(kp_bank.shape[1])
-    if kp_depth_bank is None:
-        raise ValueError("kp_depth_bank is required")
-    _check_arrays((n_bank, k), ("kp_depth_bank", kp_depth_bank, torch.int32))
-    n_pairs = check_pair_lists(first, second, kp_bank.device)
-    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_pairs or \
-            not 1 <= int(matches.shape[1]) <= k:
-        raise ValueError(f"matches must be a tensor of shape ({n_pairs}, n1 in [1, {k}], 2)")
-    n1 = int(matches.shape[1])
-    if count is None:
-        raise ValueError("count is required")
-    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
-    _check_arrays((n_pairs,), ("count", count, torch.int32))
-    t = check_threshold(threshold)
-    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
-    sx, sy = check_positive("scale_x", scale_x), check_positive("scale_y", scale_y)
+    n_bank, k, n_pairs, n1, _, doubles = _pose_operands("pose_refine_pairs", kp_bank, first, second, threshold,
+                                                        depth=(kp_depth_bank, camera, scale_x, scale_y), listed=(matches, count))
     hub, n_iter = check_huber(huber), check_iterations(iterations)
-    if not isinstance(T_in, torch.Tensor) or T_in.dtype != torch.float64 or not T_in.is_contiguous() or \
-            tuple(T_in.shape) not in ((n_pairs, 12), (n_pairs, 3, 4)):
-        raise ValueError(f"T_in must be a contiguous float64 tensor of shape ({n_pairs}, 12) or ({n_pairs}, 3, 4)")
-    if k > EVAL_MAX_K:
-        raise SslamHipError(f"pose_refine_pairs: {k} keypoints per frame; at most {EVAL_MAX_K} are handled on the device")
+    _check_pose_rows("T_in", T_in, n_pairs, 12)
     shapes = pose_refine_shapes(n_pairs, n1)
-    if out is not None:
-        if len(out) != len(POSE_REFINE_KEYS):
-            raise ValueError(f"out must hold {len(POSE_REFINE_KEYS)} tensors: {', '.join(POSE_REFINE_KEYS)}")
-        for key, x in zip(POSE_REFINE_KEYS, out):
-            if x is None:
-                raise ValueError(f"out `{key}` is required")
-            _check_arrays(shapes[key][0], (f"out `{key}`", x, shapes[key][1]))
-        if out[0].data_ptr() == T_in.data_ptr():
-            raise ValueError("out `T` must not be T_in")
+    o = None if out is None else _outputs(shapes, POSE_REFINE_KEYS, out)
+    if o is not None and o[0].data_ptr() == T_in.data_ptr():
+        raise ValueError("out `T` must not be T_in")
     dev = common_device(kp_bank, kp_depth_bank, first, second, matches, count, T_in)
-    o = list(out) if out is not None else [torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in POSE_REFINE_KEYS]
+    o = _outputs(shapes, POSE_REFINE_KEYS, None, dev) if o is None else o
     _run("pose_refine_pairs", lib().sslam_pose_refine_pairs, (kp_bank, kp_depth_bank, first, second, matches, count, T_in, *o),
-         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1,
-         *(C.c_double(v) for v in (fx, fy, cx, cy, ds, sx, sy, vw, vh, t)), _dp(T_in), C.c_double(hub), n_iter, *(_dp(x) for x in o))
+         _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1, *doubles,
+         _dp(T_in), C.c_double(hub), n_iter, *(_dp(x) for x in o))
     return tuple(o)
 
 

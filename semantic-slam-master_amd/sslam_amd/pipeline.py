@@ -123,6 +123,20 @@ def _host_pair_list(name: str, t):
     return torch.from_numpy(a.astype(np.int32))
 
 
+def _checked_match_lists(matches, n_pairs: int, k: int | None = None):
+    """The `matches` dictionary of a pose method, judged against its pair lists; returns its (P, n1, 2) tensor.  k: the scoring
+    methods' lists - k slots and a `value`; None: any list of a matcher or of rank_matches()."""
+    keys = ("matches", "match_count") if k is None else ("matches", "value", "match_count")
+    source = "match() / match_pairs() / rank_matches()" if k is None else "match_pairs(rule=...)"
+    if not isinstance(matches, dict) or any(key not in matches for key in keys):
+        raise ValueError(f"matches must be the dictionary {source} returned: {', '.join(keys)}")
+    mt = matches["matches"]
+    if not isinstance(mt, torch.Tensor) or mt.dim() != 3 or int(mt.shape[0]) != n_pairs or mt.shape[2] != 2 or \
+            (k is not None and int(mt.shape[1]) != k):
+        raise ValueError(f"matches holds {tuple(getattr(mt, 'shape', ()))}, the pair lists ask for ({n_pairs}, {'n1' if k is None else k}, 2)")
+    return mt
+
+
 REFINER_ORDER_HEAD = ["input_proj.weight", "input_proj.bias"]
 REFINER_ORDER_BLOCK = ["norm1.weight", "norm1.bias", "fc1.weight", "fc1.bias", "norm2.weight", "norm2.bias",
                        "fc2.weight", "fc2.bias"]
@@ -638,13 +652,38 @@ class SequencePipeline:
                        out=(res["matches"], res[val], res["match_count"], res.get("slot")))
         return res
 
+    def _pose_buffers(self, shapes_of, keys, n_pairs: int, k: int | None, out: dict | None = None, alloc: str = "") -> dict:
+        """The buffers of a pose method: fresh ones for n_pairs pairs of k rows (num_keypoints by default) from a lib.*_shapes
+        function, or the caller's `out`, which must hold every key (`alloc` names the method that makes them)."""
+        if out is not None:
+            if any(key not in out for key in keys):
+                raise ValueError(f"out must hold {', '.join(keys)} ({alloc})")
+            return dict(out)
+        shapes = shapes_of(n_pairs, self.cfg.num_keypoints if k is None else k)
+        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in keys}
+
+    def _pose_operands(self, what: str, keypoints_pixel, first, second, *kp_depth):
+        """What the pose methods check alike, before any device work: the bank keypoints_pixel (N, K, 2), the kp_depth (N, K) of a
+        method that takes one, and the two pair lists (as match_pairs takes them; host sequences are uploaded once).
+        Returns (first, second - on the bank's device -, n_pairs, K, that device)."""
+        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
+            raise ValueError("keypoints_pixel (N, K, 2) expected")
+        for d in kp_depth:
+            if not isinstance(d, torch.Tensor) or tuple(d.shape) != tuple(keypoints_pixel.shape[:2]):
+                raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
+        if first is None or second is None:
+            raise ValueError(f"{what} needs both pair lists, first= and second=")
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)             # a malformed list is refused before anything is uploaded
+        dev = keypoints_pixel.device
+        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
+        lib.check_pair_lists(first, second, dev)
+        return first, second, n_pairs, int(keypoints_pixel.shape[1]), dev
+
     def alloc_pose_scores(self, n_pairs: int, k: int | None = None, with_matches: bool = True) -> dict:
         """Output buffers of pose_scores() for n_pairs pairs of k keypoints (num_keypoints by default); with_matches: also the
         tp / fp / fn / value_sum a match list is scored into."""
-        k = self.cfg.num_keypoints if k is None else k
-        keys = lib.POSE_SCORE_KEYS + (lib.MATCH_SCORE_KEYS if with_matches else ())
-        shapes = lib.pose_score_shapes(n_pairs, k)
-        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in keys}
+        return self._pose_buffers(lib.pose_score_shapes, lib.POSE_SCORE_KEYS + (lib.MATCH_SCORE_KEYS if with_matches else ()), n_pairs, k)
 
     def pose_scores(self, keypoints_pixel, first, second, H, threshold: float = 3.0, matches: dict | None = None,
                     out: dict | None = None) -> dict:
@@ -659,16 +698,8 @@ class SequencePipeline:
         Returns device tensors, one row per listed pair: gt_matches (P, K, 2) int64, gt_count (P,) int32 (= the repeatable count),
         gt_of_row (P, K) int32, dist_sum, dist_median (P,) float64, and with matches tp, fp, fn (P,) int32, value_sum (P,) float64.
         out: alloc_pose_scores buffers (or row slices of them).  Two launches per 65 535 pairs, nothing read on the host."""
-        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
-            raise ValueError("keypoints_pixel (N, K, 2) expected")
-        if first is None or second is None:
-            raise ValueError("pose_scores needs both pair lists, first= and second=")
+        first, second, n_pairs, k, dev = self._pose_operands("pose_scores", keypoints_pixel, first, second)
         t = lib.check_threshold(threshold)
-        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
-        n_pairs = lib.check_pair_lists(first, second)
-        dev, k = keypoints_pixel.device, int(keypoints_pixel.shape[1])
-        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
-        lib.check_pair_lists(first, second, dev)
         if H is not None:
             if not isinstance(H, torch.Tensor):
                 H = torch.from_numpy(np.ascontiguousarray(np.asarray(H, dtype=np.float64)))
@@ -676,14 +707,9 @@ class SequencePipeline:
                 raise ValueError(f"H must be float64 of shape ({n_pairs}, 3, 3) or ({n_pairs}, 9), got {H.dtype} {tuple(H.shape)}")
             H = H.to(dev).contiguous()
         if matches is not None:
-            if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "value", "match_count")):
-                raise ValueError("matches must be the dictionary match_pairs(rule=...) returned: matches, value, match_count")
-            if tuple(matches["matches"].shape) != (n_pairs, k, 2):
-                raise ValueError(f"matches holds {tuple(matches['matches'].shape)}, the pair lists ask for {(n_pairs, k, 2)}")
-        keys = lib.POSE_SCORE_KEYS + (lib.MATCH_SCORE_KEYS if matches is not None else ())
-        res = dict(out) if out is not None else self.alloc_pose_scores(n_pairs, k, matches is not None)
-        if any(key not in res for key in keys):
-            raise ValueError(f"out must hold {', '.join(keys)} (alloc_pose_scores)")
+            _checked_match_lists(matches, n_pairs, k)
+        res = self._pose_buffers(lib.pose_score_shapes, lib.POSE_SCORE_KEYS + (lib.MATCH_SCORE_KEYS if matches is not None else ()),
+                                 n_pairs, k, out, "alloc_pose_scores")
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
             b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
             lib.pose_nn_pairs(keypoints_pixel, first[a:b], second[a:b], None if H is None else H[a:b], t,
@@ -699,7 +725,7 @@ class SequencePipeline:
         return w / self.cfg.input_size, h / self.cfg.input_size
 
     def keypoint_depth(self, depth_u16, keypoints_pixel, out=None):
-        """The raw depth under every keypoint (csrc/evaluate_depth.hip): depth_u16 (n, h, w) uint16 device tensor - TUM's raw
+        """The raw depth under every keypoint (csrc/evaluate.hip): depth_u16 (n, h, w) uint16 device tensor - TUM's raw
         values, metres times 5000 - for the n frames whose keypoints_pixel (n, K, 2) extract() returned; the keypoint is taken to
         the depth image by w / input_size and h / input_size and rounded to the nearest pixel.  Returns (n, K) int32: the raw
         value, 0 where the sensor measured nothing, -1 outside the image.  out: an (n, K) int32 tensor (a slice of a sequence-sized
@@ -711,14 +737,12 @@ class SequencePipeline:
 
     def alloc_pose_depth_scores(self, n_pairs: int, k: int | None = None, with_matches: bool = True) -> dict:
         """Output buffers of pose_depth_scores() for n_pairs pairs of k keypoints (num_keypoints by default)."""
-        k = self.cfg.num_keypoints if k is None else k
-        keys = lib.POSE_DEPTH_SCORE_KEYS + (lib.MATCH_KNOWN_SCORE_KEYS if with_matches else ())
-        shapes = lib.pose_depth_score_shapes(n_pairs, k)
-        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in keys}
+        return self._pose_buffers(lib.pose_depth_score_shapes,
+                                  lib.POSE_DEPTH_SCORE_KEYS + (lib.MATCH_KNOWN_SCORE_KEYS if with_matches else ()), n_pairs, k)
 
     def pose_depth_scores(self, keypoints_pixel, kp_depth, first, second, T, camera, threshold: float = 3.0,
                           matches: dict | None = None, out: dict | None = None) -> dict:
-        """pose_scores() against the translation-aware ground truth (csrc/evaluate_depth.hip): every keypoint of frame first[p] is
+        """pose_scores() against the translation-aware ground truth (csrc/evaluate.hip): every keypoint of frame first[p] is
         back-projected with its depth kp_depth (N, K) int32 - keypoint_depth()'s output for the same bank - moved by T[p] and
         projected into frame second[p]; from there the nearest-keypoint search and the list scoring of pose_scores().
         T: (P, 3, 4), (P, 12) or (P, 4, 4) float64 (device tensor or host array; of a 4 x 4 the top three rows count), camera a
@@ -727,19 +751,9 @@ class SequencePipeline:
         Returns device tensors per listed pair: gt_matches, gt_count, gt_of_row (-2: the row has no ground truth), valid_count,
         dist_sum, dist_median, and with matches tp, fp, fn, unknown, value_sum (include/sslam_hip.h).  out:
         alloc_pose_depth_scores buffers.  Two launches per 65 535 pairs, nothing read on the host."""
-        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
-            raise ValueError("keypoints_pixel (N, K, 2) expected")
-        if not isinstance(kp_depth, torch.Tensor) or tuple(kp_depth.shape) != tuple(keypoints_pixel.shape[:2]):
-            raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
-        if first is None or second is None:
-            raise ValueError("pose_depth_scores needs both pair lists, first= and second=")
+        first, second, n_pairs, k, dev = self._pose_operands("pose_depth_scores", keypoints_pixel, first, second, kp_depth)
         t = lib.check_threshold(threshold)
         sx, sy = self.depth_scales(camera)
-        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
-        n_pairs = lib.check_pair_lists(first, second)
-        dev, k = keypoints_pixel.device, int(keypoints_pixel.shape[1])
-        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
-        lib.check_pair_lists(first, second, dev)
         if T is None:
             raise ValueError("T (P, 3, 4) float64 is required: evaluation.pair_transforms(poses, pairs)")
         if not isinstance(T, torch.Tensor):
@@ -750,14 +764,10 @@ class SequencePipeline:
             T = T[:, :3]
         T = T.to(dev).contiguous().reshape(n_pairs, 12)
         if matches is not None:
-            if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "value", "match_count")):
-                raise ValueError("matches must be the dictionary match_pairs(rule=...) returned: matches, value, match_count")
-            if tuple(matches["matches"].shape) != (n_pairs, k, 2):
-                raise ValueError(f"matches holds {tuple(matches['matches'].shape)}, the pair lists ask for {(n_pairs, k, 2)}")
-        keys = lib.POSE_DEPTH_SCORE_KEYS + (lib.MATCH_KNOWN_SCORE_KEYS if matches is not None else ())
-        res = dict(out) if out is not None else self.alloc_pose_depth_scores(n_pairs, k, matches is not None)
-        if any(key not in res for key in keys):
-            raise ValueError(f"out must hold {', '.join(keys)} (alloc_pose_depth_scores)")
+            _checked_match_lists(matches, n_pairs, k)
+        res = self._pose_buffers(lib.pose_depth_score_shapes,
+                                 lib.POSE_DEPTH_SCORE_KEYS + (lib.MATCH_KNOWN_SCORE_KEYS if matches is not None else ()), n_pairs, k,
+                                 out, "alloc_pose_depth_scores")
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
             b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
             lib.pose_depth_nn_pairs(keypoints_pixel, kp_depth, first[a:b], second[a:b], T[a:b], camera, sx, sy, t,
@@ -770,9 +780,7 @@ class SequencePipeline:
 
     def alloc_pose(self, n_pairs: int, k: int | None = None) -> dict:
         """Output buffers of estimate_poses() for n_pairs pairs whose match lists hold k slots (num_keypoints by default)."""
-        k = self.cfg.num_keypoints if k is None else k
-        shapes = lib.pose_ransac_shapes(n_pairs, k)
-        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in lib.POSE_RANSAC_KEYS}
+        return self._pose_buffers(lib.pose_ransac_shapes, lib.POSE_RANSAC_KEYS, n_pairs, k)
 
     def estimate_poses(self, keypoints_pixel, kp_depth, first, second, matches: dict, camera, threshold: float = 3.0,
                        hypotheses: int = 256, seed: int = 0, out: dict | None = None) -> dict:
@@ -788,28 +796,12 @@ class SequencePipeline:
         inlier_count, usable_count, best_hypothesis, refit_kept (P,) int32, inlier_of_slot (P, n1) int32 (1 inlier, 0 not, -1 no
         depth; 0 past the count), rms (P,) float64 (include/sslam_hip.h).  A pair with fewer than 3 usable matches gets the
         identity and best_hypothesis -1.  out: alloc_pose buffers (or row slices).  One launch per 65 535 pairs, no host read."""
-        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
-            raise ValueError("keypoints_pixel (N, K, 2) expected")
-        if not isinstance(kp_depth, torch.Tensor) or tuple(kp_depth.shape) != tuple(keypoints_pixel.shape[:2]):
-            raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
-        if first is None or second is None:
-            raise ValueError("estimate_poses needs both pair lists, first= and second=")
+        first, second, n_pairs, _, _ = self._pose_operands("estimate_poses", keypoints_pixel, first, second, kp_depth)
         t = lib.check_threshold(threshold)
         n_hyp, seed = lib.check_hypotheses(hypotheses), lib.check_seed(seed)
         sx, sy = self.depth_scales(camera)
-        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
-        n_pairs = lib.check_pair_lists(first, second)
-        if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "match_count")):
-            raise ValueError("matches must be the dictionary match() / match_pairs() / rank_matches() returned: matches, match_count")
-        mt = matches["matches"]
-        if not isinstance(mt, torch.Tensor) or mt.dim() != 3 or int(mt.shape[0]) != n_pairs or mt.shape[2] != 2:
-            raise ValueError(f"matches holds {tuple(getattr(mt, 'shape', ()))}, the pair lists ask for ({n_pairs}, n1, 2)")
-        dev, n1 = keypoints_pixel.device, int(mt.shape[1])
-        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
-        lib.check_pair_lists(first, second, dev)
-        res = dict(out) if out is not None else self.alloc_pose(n_pairs, n1)
-        if any(key not in res for key in lib.POSE_RANSAC_KEYS):
-            raise ValueError(f"out must hold {', '.join(lib.POSE_RANSAC_KEYS)} (alloc_pose)")
+        mt = _checked_match_lists(matches, n_pairs)
+        res = self._pose_buffers(lib.pose_ransac_shapes, lib.POSE_RANSAC_KEYS, n_pairs, int(mt.shape[1]), out, "alloc_pose")
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
             b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
             lib.pose_ransac_pairs(keypoints_pixel, kp_depth, first[a:b], second[a:b], mt[a:b], matches["match_count"][a:b], camera, sx, sy,
@@ -818,9 +810,7 @@ class SequencePipeline:
 
     def alloc_pose_refine(self, n_pairs: int, k: int | None = None) -> dict:
         """Output buffers of refine_poses() for n_pairs pairs whose match lists hold k slots (num_keypoints by default)."""
-        k = self.cfg.num_keypoints if k is None else k
-        shapes = lib.pose_refine_shapes(n_pairs, k)
-        return {key: torch.empty(shapes[key][0], dtype=shapes[key][1], device=self.device) for key in lib.POSE_REFINE_KEYS}
+        return self._pose_buffers(lib.pose_refine_shapes, lib.POSE_REFINE_KEYS, n_pairs, k)
 
     def refine_poses(self, keypoints_pixel, kp_depth, first, second, matches: dict, camera, pose, threshold: float = 3.0,
                      huber: float | None = None, iterations: int = 5, out: dict | None = None) -> dict:
@@ -836,32 +826,16 @@ class SequencePipeline:
         information matrix in the parameters (vx, vy, vz, wx, wy, wz) of a left perturbation in the second camera
         (include/sslam_hip.h).  Under status 1, 2 and 3 T is `pose` bit for bit.  out: alloc_pose_refine buffers (or row slices).
         One launch per 65 535 pairs, no host read."""
-        if not isinstance(keypoints_pixel, torch.Tensor) or keypoints_pixel.dim() != 3 or keypoints_pixel.shape[2] != 2:
-            raise ValueError("keypoints_pixel (N, K, 2) expected")
-        if not isinstance(kp_depth, torch.Tensor) or tuple(kp_depth.shape) != tuple(keypoints_pixel.shape[:2]):
-            raise ValueError(f"kp_depth {tuple(keypoints_pixel.shape[:2])} int32 expected: keypoint_depth() of the same bank")
-        if first is None or second is None:
-            raise ValueError("refine_poses needs both pair lists, first= and second=")
+        first, second, n_pairs, _, _ = self._pose_operands("refine_poses", keypoints_pixel, first, second, kp_depth)
         t = lib.check_threshold(threshold)
         n_iter = lib.check_iterations(iterations)
         hub = lib.check_huber(t / 3.0 if huber is None else huber)
         sx, sy = self.depth_scales(camera)
-        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
-        n_pairs = lib.check_pair_lists(first, second)
-        if not isinstance(matches, dict) or any(key not in matches for key in ("matches", "match_count")):
-            raise ValueError("matches must be the dictionary match() / match_pairs() / rank_matches() returned: matches, match_count")
-        mt = matches["matches"]
-        if not isinstance(mt, torch.Tensor) or mt.dim() != 3 or int(mt.shape[0]) != n_pairs or mt.shape[2] != 2:
-            raise ValueError(f"matches holds {tuple(getattr(mt, 'shape', ()))}, the pair lists ask for ({n_pairs}, n1, 2)")
+        mt = _checked_match_lists(matches, n_pairs)
         t_in = pose["T"] if isinstance(pose, dict) and "T" in pose else pose
         if not isinstance(t_in, torch.Tensor) or t_in.dtype != torch.float64 or tuple(t_in.shape) != (n_pairs, 12) or not t_in.is_contiguous():
             raise ValueError(f"pose must be estimate_poses()' dictionary or a contiguous float64 tensor of shape ({n_pairs}, 12)")
-        dev, n1 = keypoints_pixel.device, int(mt.shape[1])
-        first, second = (x if x.is_cuda else x.to(dev) for x in (first, second))
-        lib.check_pair_lists(first, second, dev)
-        res = dict(out) if out is not None else self.alloc_pose_refine(n_pairs, n1)
-        if any(key not in res for key in lib.POSE_REFINE_KEYS):
-            raise ValueError(f"out must hold {', '.join(lib.POSE_REFINE_KEYS)} (alloc_pose_refine)")
+        res = self._pose_buffers(lib.pose_refine_shapes, lib.POSE_REFINE_KEYS, n_pairs, int(mt.shape[1]), out, "alloc_pose_refine")
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
             b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
             lib.pose_refine_pairs(keypoints_pixel, kp_depth, first[a:b], second[a:b], mt[a:b], matches["match_count"][a:b], camera, t_in[a:b],

@@ -1,4 +1,4 @@
-"""A float64 numpy restatement of the depth ground truth of the scoring stage (csrc/evaluate_depth.hip; include/sslam_hip.h states
+"""A float64 numpy restatement of the depth ground truth of the scoring stage (csrc/evaluate.hip; include/sslam_hip.h states
 the contract), spelling out the operation order the header gives: every product, quotient and sum below is one numpy float64
 operation, rounded once, in the header's order.  The distances, the nearest-keypoint search, the threshold and the compaction
 are tests/pose_eval_ref.py's own functions, called on the warped points.

@@ -1,5 +1,5 @@
 """The depth ground truth of the scoring stage (sslam_keypoint_depth, sslam_pose_depth_nn_pairs, sslam_match_score_known_pairs;
-csrc/evaluate_depth.hip) as far as a machine without a GPU can see it: the margins every seeded case of tests/pose_depth_cases.py
+csrc/evaluate.hip) as far as a machine without a GPU can see it: the margins every seeded case of tests/pose_depth_cases.py
 keeps from each decision, the restatement of tests/pose_depth_ref.py against closed forms, and the Python layer - the header, the
 refusals of the three C entries (which come before any launch), the bindings' argument checks, relative_transform, camera_for,
 load_depth_raw, the summaries' arithmetic and evaluate(depth=)'s argument errors.
@@ -354,7 +354,7 @@ def test_entries_are_declared_exported_and_listed():
     for text in ("floor(u + 0.5)", "X = ((u - cx) * z) / fx", "u' = (fx * X') / Z' + cx", "HAS NO GROUND TRUTH", "-0.5 <= u' < view_w - 0.5",
                  "(dist[(v-1)>>1] + dist[v>>1]) / 2", "fp = count - tp - unknown", "no occlusion test"):
         assert text in hdr, text
-    assert os.path.exists(os.path.join(lib.CSRC, "evaluate_depth.hip"))
+    assert os.path.exists(os.path.join(lib.CSRC, "evaluate.hip"))
     assert lib.POSE_DEPTH_SCORE_KEYS == ("gt_matches", "gt_count", "gt_of_row", "valid_count", "dist_sum", "dist_median")
     assert lib.MATCH_KNOWN_SCORE_KEYS == ("tp", "fp", "fn", "unknown", "value_sum")
     import torch
