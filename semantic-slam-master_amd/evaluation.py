@@ -8,7 +8,8 @@ keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (
 Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate.hip):
 compute_repeatability_depth and compute_ground_truth_matches_depth - and, beside matching.py's matchers, the step that follows
 them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip), and refine_relative_pose, that
-motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip).
+motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip).  And, between the selector and all
+of them, refine_keypoints_subcell: the selected cells moved to their sub-cell saliency peaks (csrc_ext/subcell.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
 result.  There is no CPU implementation here: without the GPU library these functions raise.
@@ -195,6 +196,38 @@ def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, thre
     info = np.zeros((6, 6))
     info[iu], info[iu[1], iu[0]] = tri, tri
     return T4, out[7][0].cpu().numpy() == 1, info
+
+
+def refine_keypoints_subcell(saliency, keypoints):
+    """The step between the selector and everything geometric: saliency (G, G) fp32 - one frame's map - and keypoints (N, 2), the
+    whole cells (x, y) in patch units that KeypointSelector.select_keypoints returned for it -> (N, 2) fp32 patch coordinates, each
+    keypoint at the vertex of the per-axis parabola through its cell's saliency and the two neighbours' (sslx_subcell_keypoints,
+    include/sslam_ext.h; DinoBackbone.patch_to_pixel takes the result to pixels as it takes the cells).  A border axis, a cell
+    that is no maximum along an axis and a plateau keep the cell's coordinate.
+    numpy in, numpy out: shapes and values are judged on the host before any device work, and a keypoint that is no whole cell
+    of the grid is a ValueError.  Torch tensors in, a device tensor out: shapes are judged, nothing is read on the host and
+    nothing but the result leaves the device - a keypoint that is no whole cell of the grid (outside it, fractional, NaN) then
+    comes back as (0, 0), the entry's answer to an index out of range."""
+    tensors = isinstance(saliency, torch.Tensor) or isinstance(keypoints, torch.Tensor)
+    saliency = saliency if isinstance(saliency, torch.Tensor) else np.asarray(saliency)
+    keypoints = keypoints if isinstance(keypoints, torch.Tensor) else np.asarray(keypoints)
+    if tuple(saliency.shape) != (saliency.shape[0],) * 2 or saliency.shape[0] < 1:
+        raise ValueError(f"saliency (G, G) expected, got {tuple(saliency.shape)}")
+    if len(keypoints.shape) != 2 or keypoints.shape[1] != 2 or keypoints.shape[0] < 1:
+        raise ValueError(f"keypoints (N >= 1, 2) expected, got {tuple(keypoints.shape)}")
+    g = int(saliency.shape[0])
+    if not tensors:
+        kp = np.asarray(keypoints)
+        cells = np.floor(kp)
+        if not np.isfinite(kp).all() or (cells != kp).any() or (cells < 0).any() or (cells >= g).any():
+            raise ValueError(f"keypoints must be whole cells of the {g} x {g} grid, as select_keypoints returns them")
+    kp = _dev(keypoints, torch.float32)
+    x, y = kp[:, 0], kp[:, 1]
+    whole = (x >= 0) & (x < g) & (y >= 0) & (y < g) & (x == x.floor()) & (y == y.floor())       # false for a NaN
+    cell = torch.where(whole, y, torch.zeros_like(y)).long() * g + torch.where(whole, x, torch.zeros_like(x)).long()
+    idx = torch.where(whole, cell, torch.full_like(cell, -1)).to(torch.int32)
+    out = lib.subcell_keypoints(_dev(saliency, torch.float32)[None], idx[None].contiguous())[0][0]
+    return out if tensors else out.cpu().numpy()
 
 
 def evaluate_matches(pred_matches, gt_matches, num_kpts1: int, num_kpts2: int) -> dict:

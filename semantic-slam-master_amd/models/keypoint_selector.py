@@ -99,12 +99,62 @@ class KeypointSelector(nn.Module):
             return kp, sc
         return _select_keypoints_eager(sal, num_keypoints, nms_radius, min_score_percentile)
 
+    def refine_keypoints(self, saliency_map: torch.Tensor, keypoints: torch.Tensor) -> torch.Tensor:
+        """Sub-cell localisation, the step behind select_keypoints (not in the reference): saliency_map (B, H, W, 1) and the
+        keypoints (B, N, 2) it returned - whole cells (x, y) - -> (B, N, 2) fp32 patch coordinates, each keypoint moved to the
+        vertex of the per-axis parabola through its cell's saliency and the two neighbours' (include/sslam_ext.h states the
+        arithmetic).  A border axis, a cell that is no maximum along an axis and a plateau keep the cell's coordinate.
+        CUDA tensors under no_grad: the HIP kernel (libsslam_ext.so: sslx_subcell_keypoints; a missing library RAISES), nothing
+        read on the host - a keypoint that is no whole cell of the grid (outside it, fractional, NaN) comes back as (0, 0), the
+        entry's answer to an index out of range.  Otherwise the same formula in eager torch ops, attached to the autograd graph
+        of saliency_map; there such a keypoint is a ValueError."""
+        B, H, W, _ = saliency_map.shape
+        if H != W:
+            raise lib.SslamHipError("square patch grids only (DinoBackbone always produces grid_h == grid_w)")
+        if keypoints.dim() != 3 or keypoints.shape[0] != B or keypoints.shape[2] != 2:
+            raise ValueError(f"keypoints ({B}, N, 2) expected, got {tuple(keypoints.shape)}")
+        sal = saliency_map.squeeze(-1)
+        kp = keypoints.detach()
+        if sal.is_cuda and not (torch.is_grad_enabled() and saliency_map.requires_grad):
+            # a coordinate that is no whole cell of the grid must not alias a cell: it becomes the entry's out-of-range index
+            # (every comparison is false for a NaN, and only whole in-grid values are converted to integers)
+            x, y = kp[..., 0], kp[..., 1]
+            whole = (x >= 0) & (x < W) & (y >= 0) & (y < H) & (x == x.floor()) & (y == y.floor())
+            cell = torch.where(whole, y, torch.zeros_like(y)).long() * W + torch.where(whole, x, torch.zeros_like(x)).long()
+            idx = torch.where(whole, cell, torch.full_like(cell, -1)).to(torch.int32)
+            return lib.subcell_keypoints(sal.detach().contiguous().float(), idx.contiguous())[0]
+        return _refine_keypoints_eager(sal.float(), kp)
+
     def _apply_nms(self, saliency: torch.Tensor, radius: int) -> torch.Tensor:
         """(B, H, W) -> (B, H, W): keep exact local maxima of the (2r+1)^2 window (keypoint_selector.py:209-226)."""
         if radius == 0:
             return saliency
         pooled = F.max_pool2d(saliency.unsqueeze(1), kernel_size=2 * radius + 1, stride=1, padding=radius).squeeze(1)
         return saliency * (saliency == pooled).float()
+
+
+def _refine_keypoints_eager(sal: torch.Tensor, kp: torch.Tensor) -> torch.Tensor:
+    """sslx_subcell_keypoints in plain torch ops, operation by operation (include/sslam_ext.h): sal (B, G, G) fp32, kp (B, N, 2)
+    whole cells -> (B, N, 2)."""
+    B, G, _ = sal.shape
+    x, y = kp[..., 0].long(), kp[..., 1].long()
+    if bool(((x < 0) | (x >= G) | (y < 0) | (y >= G) | (kp[..., 0] != x) | (kp[..., 1] != y)).any()):
+        raise ValueError(f"keypoints must be whole cells inside the {G} x {G} grid")
+    flat = sal.reshape(B, G * G)
+    cell = y * G + x
+    bx, by = (x == 0) | (x == G - 1), (y == 0) | (y == G - 1)
+    c = flat.gather(1, cell)
+    zero = torch.zeros((), dtype=sal.dtype, device=sal.device)
+
+    def axis(lo, hi, border):
+        m, p = flat.gather(1, torch.where(border, cell, lo)), flat.gather(1, torch.where(border, cell, hi))
+        a, b = c - m, c - p
+        den = a + b
+        off = (a - b) / (den + den)
+        refined = ~border & (a >= 0) & (b >= 0) & (den > 0) & (off >= -0.5) & (off <= 0.5)
+        return torch.where(refined, off, zero)
+
+    return torch.stack([x.to(sal.dtype) + axis(cell - 1, cell + 1, bx), y.to(sal.dtype) + axis(cell - G, cell + G, by)], dim=-1)
 
 
 def _topk_canonical(values: torch.Tensor, flat_index: torch.Tensor, k: int):

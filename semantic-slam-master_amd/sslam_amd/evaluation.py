@@ -276,6 +276,25 @@ def _check_depth(depth, kp_depth, poses, use_pose, camera, keypoints_shape, n_fr
     return camera
 
 
+def check_subcell(subcell):
+    """subcell= of the scoring and odometry calls: None (follow the pipeline), True or False - judged before any device work."""
+    if subcell not in (None, False, True):
+        raise ValueError(f"subcell must be None, True or False, got {subcell!r}")
+    return subcell
+
+
+def geometry_bank(frames: dict, subcell=None):
+    """The keypoint bank (N, K, 2) geometry reads from an extract() dictionary or a result's "frames": subcell None - the refined
+    keypoints_subpixel where the pipeline wrote them (ExtractorConfig.subcell), else the cell centres keypoints_pixel
+    (SequencePipeline.geometry_keypoints); False - the cell centres whatever is there; True - the refined ones, or ValueError."""
+    check_subcell(subcell)
+    if subcell is False:
+        return frames["keypoints_pixel"]
+    if subcell and "keypoints_subpixel" not in frames:
+        raise ValueError("subcell=True needs the refined keypoints: build the pipeline with ExtractorConfig(subcell=True)")
+    return frames["keypoints_subpixel"] if "keypoints_subpixel" in frames else frames["keypoints_pixel"]
+
+
 def gather_keypoint_depth(pipe, depth, keypoints_pixel, n_frames: int):
     """(N, K) int32 device bank of the raw depth under every keypoint of the first n_frames frames (-1 in the frames behind them):
     the depth images go to the device DEPTH_CHUNK frames at a time and do not stay there."""
@@ -336,7 +355,7 @@ def _score(pipe, keypoints_pixel, pairs, poses, use_pose: bool, threshold: float
 
 def evaluate(pipe, images_u8=None, poses=None, spacing: int = 1, num_pairs: int = 50, use_pose: bool = True,
              ratio_threshold: float = 0.9, threshold: float = 3.0, tokens=None, sequence: str = "", *, depth=None,
-             camera=None) -> dict:
+             camera=None, subcell=None) -> dict:
     """Score a checkpoint the way the reference's two testers score it, on the device: the frames images_u8 (N, H, W, 3) uint8
     (a pipeline built with vit=) or their ViT tokens (tokens=, as SequencePipeline.run takes them), the camera poses (N, 4, 4)
     float64 as TUMSequence.poses holds them.  Only the first num_pairs + spacing frames are used, as the testers' max_frames cuts
@@ -349,8 +368,11 @@ def evaluate(pipe, images_u8=None, poses=None, spacing: int = 1, num_pairs: int 
     truth: the depth under every keypoint is gathered chunk by chunk for the frames used, and the two dictionaries come from
     depth_repeatability_summary / depth_descriptor_quality_summary (extra keys: valid_keypoints, num_unknown_matches,
     pairs_without_ground_truth).  depth= needs poses and use_pose=True.
+    subcell: on a pipeline with ExtractorConfig(subcell=True) the depth lookups and every score read the refined keypoints
+    (geometry_bank); subcell=False forces the cell centres.  The matcher is the same either way.
     Returns {'repeatability': RepeatabilityTester.test_sequence's dictionary, 'descriptor_quality':
     DescriptorQualityTester.test_sequence's} (repeatability_summary / descriptor_quality_summary state the keys)."""
+    check_subcell(subcell)
     if depth is None and camera is not None:
         raise ValueError("camera= describes the depth images: it needs depth=")
     if depth is not None and poses is None:
@@ -371,19 +393,22 @@ def evaluate(pipe, images_u8=None, poses=None, spacing: int = 1, num_pairs: int 
     matches = None
     if poses is not None:
         matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
+    kp = geometry_bank(ex, subcell)
     if depth is not None:
-        return _score_depth(pipe, ex["keypoints_pixel"], pairs, poses, depth, camera, threshold, matches, sequence)
-    return _score(pipe, ex["keypoints_pixel"], pairs, poses, use_pose, threshold, matches, sequence)
+        return _score_depth(pipe, kp, pairs, poses, depth, camera, threshold, matches, sequence)
+    return _score(pipe, kp, pairs, poses, use_pose, threshold, matches, sequence)
 
 
 def evaluate_result(pipe, result: dict, poses, spacing: int = 1, num_pairs: int = 50, use_pose: bool = True,
-                    threshold: float = 3.0, sequence: str = "", *, depth=None, camera=None, kp_depth=None) -> dict:
+                    threshold: float = 3.0, sequence: str = "", *, depth=None, camera=None, kp_depth=None, subcell=None) -> dict:
     """evaluate() for a StreamingSequence.result() / run_frames / run_directory result that was matched under
     MatchRule.mnn_ratio (rule=): the keypoints and the M4 lists of every pair (i, i + spacing) are already in device memory, so
     nothing is extracted or matched again - the first min(num_pairs, N - spacing) rows of result[spacing] are scored.
     depth=, camera=: as in evaluate() - the raw depth images of the result's frames.  kp_depth=: instead of depth=, the (N, K) int32
     bank gather_keypoint_depth(pipe, depth, result["frames"]["keypoints_pixel"], n) returned - it depends on the frames alone, so a
-    caller that scores several spacings gathers once, for the most frames any spacing names, and passes it to each call."""
+    caller that scores several spacings gathers once, for the most frames any spacing names, and passes it to each call.
+    subcell: as in evaluate() - a result of a pipeline with subcell=True is scored on its refined keypoints unless subcell=False;
+    a kp_depth= bank must have been gathered under the same bank (geometry_bank(result["frames"], subcell))."""
     depth_given = depth is not None or kp_depth is not None
     if not depth_given and camera is not None:
         raise ValueError("camera= describes the depth images: it needs depth=")
@@ -393,7 +418,7 @@ def evaluate_result(pipe, result: dict, poses, spacing: int = 1, num_pairs: int 
         raise ValueError("use_pose=True needs poses (N, 4, 4); pass use_pose=False for the raw repeatability")
     if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
         raise ValueError("a StreamingSequence / run_directory result expected")
-    kp = result["frames"]["keypoints_pixel"]
+    kp = geometry_bank(result["frames"], subcell)
     pairs = pair_list(int(kp.shape[0]), spacing, num_pairs)
     if not pairs or spacing not in result:
         raise ValueError(f"the result holds no pair at spacing {spacing}")

@@ -35,8 +35,10 @@ class SequenceMatcher:
         img = torch.from_numpy(np.ascontiguousarray(images_u8)).to(self.device)
         tokens = self.backbone.forward_tokens(self.pipe.preprocess(img)).float().contiguous()   # same ViT path as backbone.forward()
         out = self.pipe.extract(tokens, img)
-        return {"saliency": out["saliency"], "keypoints_pixel": out["keypoints_pixel"], "scores": out["scores"],
-                "intensity": out["intensity"], "descriptors": out["descriptors"]}
+        res = {"saliency": out["saliency"], "keypoints_pixel": out["keypoints_pixel"], "scores": out["scores"],
+               "intensity": out["intensity"], "descriptors": out["descriptors"]}
+        res.update({k: out[k] for k in lib.SUBCELL_KEYS if k in out})       # a config with subcell=True: the refined keypoints too
+        return res
 
     def extract(self, image_path: str) -> dict:
         """One image -> numpy dict with the reference's keys (visualize_matches_sequence.py:97-104)."""
@@ -423,6 +425,10 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     pairs at the same threshold: the pose every pair's match list agrees on, its inlier ratio, RPE and - at spacing 1 - ATE.
     A key "refine": True beside it (it needs "odometry": True) refines every pose on the reprojection error
     (odometry_result's refine=True: the summaries are the refined poses', RANSAC's own stay under 'ransac').
+    On a pipeline with ExtractorConfig(subcell=True) the depth under the keypoints, both scores and the odometry all read the
+    refined keypoints (evaluation.geometry_bank); a key "subcell": False puts all three on the cell centres instead - the one
+    depth gather, evaluate_result and odometry_result are handed the same choice - and "subcell": True on a pipeline that does
+    not localise its keypoints is a ValueError, raised before the sequence is run.
     Returns StreamingSequence.result() plus 'files' and 'timestamps'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -443,6 +449,7 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
         with_odometry = evaluate.pop("odometry", False)
         if not isinstance(with_odometry, bool):
             raise ValueError('evaluate["odometry"] is a flag, True or False')
+        subcell = evaluation.check_subcell(evaluate.pop("subcell", None))
         with_refine = evaluate.pop("refine", False)
         if not isinstance(with_refine, bool):
             raise ValueError('evaluate["refine"] is a flag, True or False')
@@ -471,6 +478,8 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
         pipe = SequencePipeline(cfg or ExtractorConfig(), selector_state, refiner_state, device=device, vit=vit)
     if tokens_fn is None and pipe.vit_hip is None:
         raise ValueError("vit= (HIP ViT) or tokens_fn required")
+    if evaluate is not None and subcell and not pipe.cfg.subcell:
+        raise ValueError('evaluate["subcell"]: True needs the refined keypoints: build the pipeline with ExtractorConfig(subcell=True)')
     with Image.open(tum.rgb_path(0)) as im0:
         w, h = im0.size
     workers = decode_workers or max(1, min(16, (os.cpu_count() or 2) - 1))
@@ -506,16 +515,17 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     if evaluate is not None:
         if with_depth or with_odometry:                      # the keypoint depths depend on the frames alone: one gather for all spacings
             need = min(n, max(len(evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))) + s for s in seq.spacings))
-            kp_depth = evaluation.gather_keypoint_depth(pipe, tum.load_depth_raw(range(need)), res["frames"]["keypoints_pixel"], need)
+            kp_depth = evaluation.gather_keypoint_depth(pipe, tum.load_depth_raw(range(need)), evaluation.geometry_bank(res["frames"], subcell), need)
         if with_depth:
             evaluate["camera"] = depth_camera
             evaluate["kp_depth"] = kp_depth
-        res["evaluation"] = {s: evaluation.evaluate_result(pipe, res, tum.poses, spacing=s, sequence=sequence, **evaluate)
+        res["evaluation"] = {s: evaluation.evaluate_result(pipe, res, tum.poses, spacing=s, sequence=sequence, subcell=subcell, **evaluate)
                              for s in seq.spacings if s in res}
         if with_odometry:                                    # the same pairs, the same threshold: the pose each list agrees on
             from . import odometry
             res["odometry"] = {s: odometry.odometry_result(pipe, res, camera=depth_camera, poses=tum.poses, spacing=s,
                                                            num_pairs=int(evaluate.get("num_pairs", 50)),
-                                                           threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth, refine=with_refine)
+                                                           threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth, refine=with_refine,
+                                                           subcell=subcell)
                                for s in seq.spacings if s in res and evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))}
     return res

@@ -1,4 +1,4 @@
-"""ctypes binding of libsslam_hip.so (include/sslam_hip.h) for torch tensors.
+"""ctypes binding of libsslam_hip.so (include/sslam_hip.h) and, at the end, of libsslam_ext.so (include/sslam_ext.h) for torch tensors.
 
 PyTorch is used for device memory and streams only: every wrapper passes raw device pointers and the current
 HIP stream to the C ABI.  There is NO fallback: if the library is missing or a call fails, an exception is raised.
@@ -1385,3 +1385,85 @@ def vit_forward_f32(images_chw, weights: VitWeightsF32, workspace, out=None, att
         _run("vit_forward_f32_form", _with_form(lib().sslam_vit_forward_f32_form, attention_form), (images_chw, workspace, out,),
              _dp(images_chw), n, size, C.byref(weights), _dp(workspace), workspace.numel() * workspace.element_size(), _dp(out))
     return out
+
+
+# ------------------------------------------------------------------------------------------ libsslam_ext.so (include/sslam_ext.h)
+# The second library: entries with the prefix sslx_, built from csrc_ext/ with csrc/'s flags, loaded and refused like the first.
+CSRC_EXT = os.path.join(_PKG, "csrc_ext")
+EXT_SO_PATH = os.path.join(CSRC_EXT, "libsslam_ext.so")
+EXT_EXPORTS = ["sslx_version", "sslx_arch", "sslx_launch_count", "sslx_subcell_keypoints"]
+SUBCELL_MAX_CELLS, SUBCELL_MAX_K = 4096, 4096
+FLAG_X, FLAG_Y, FLAG_RANGE = 1, 2, 4           # bits of subcell_keypoints' flags
+
+_ext = None
+
+
+def ext_build(force: bool = False) -> str:
+    """Compile libsslam_ext.so for gfx950 in-tree, as build() compiles the first library."""
+    inc = os.path.join(os.path.dirname(_PKG), "include")
+    srcs = [os.path.join(CSRC_EXT, f) for f in os.listdir(CSRC_EXT) if f.endswith((".hip", ".h"))]
+    srcs += [os.path.join(inc, "sslam_ext.h"), os.path.join(inc, "sslam_hip.h")]
+    stale = (not os.path.exists(EXT_SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(EXT_SO_PATH) for s in srcs)
+    if force or stale:
+        subprocess.check_call(["make", "-C", CSRC_EXT, "-s", "-j4"])
+    return EXT_SO_PATH
+
+
+def ext():
+    """Load libsslam_ext.so; raises if it has not been built (no silent fallback)."""
+    global _ext
+    if _ext is None:
+        if not os.path.exists(EXT_SO_PATH):
+            raise SslamHipError(f"{EXT_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                                f"(or `make -C {CSRC_EXT}`); this package has no non-HIP execution path")
+        L = C.CDLL(EXT_SO_PATH)
+        L.sslx_arch.restype = C.c_char_p
+        L.sslx_launch_count.restype = C.c_longlong
+        p, i = C.c_void_p, C.c_int
+        L.sslx_subcell_keypoints.argtypes = [p, i, i, p, i, p, p, p, p]
+        _ext = L
+    return _ext
+
+
+def ext_launch_count() -> int:
+    return int(ext().sslx_launch_count())
+
+
+def subcell_shapes(n: int, k: int) -> dict:
+    """The outputs of subcell_keypoints for n frames of k keypoints: key -> (shape, dtype), in the entry's order."""
+    return {"keypoints_subpatch": ((n, k, 2), torch.float32), "keypoints_subpixel": ((n, k, 2), torch.float32),
+            "subcell_flags": ((n, k), torch.int32)}
+
+
+SUBCELL_KEYS = ("keypoints_subpatch", "keypoints_subpixel", "subcell_flags")
+
+
+def subcell_keypoints(sal, idx, out=None):
+    """sslx_subcell_keypoints: sal (n, G, G) fp32 - the saliency the keypoints were selected from - and idx (n, K) int32, the flat
+    cells select_keypoints wrote.  Returns (kp_xy_sub (n, K, 2) fp32 in patch units, kp_pixel_sub (n, K, 2) fp32 = kp_xy_sub * 16 + 8,
+    flags (n, K) int32: FLAG_X | FLAG_Y where the axis was refined, FLAG_RANGE for an idx outside the grid) - each keypoint at the
+    vertex of the per-axis parabola through its cell and the two neighbours (include/sslam_ext.h states every operation).
+    out: optional tensors of those shapes to write into.  One launch, no host read; shapes and dtypes are judged first."""
+    if not isinstance(sal, torch.Tensor) or sal.dtype != torch.float32 or sal.dim() != 3 or sal.shape[1] != sal.shape[2] or \
+            min(sal.shape) < 1 or not sal.is_contiguous():
+        raise ValueError("sal must be a contiguous float32 tensor of shape (n, G, G)")
+    n, g = int(sal.shape[0]), int(sal.shape[1])
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.dim() != 2 or int(idx.shape[0]) != n or \
+            int(idx.shape[1]) < 1 or not idx.is_contiguous():
+        raise ValueError(f"idx must be a contiguous int32 tensor of shape ({n}, K)")
+    k = int(idx.shape[1])
+    if g * g > SUBCELL_MAX_CELLS or k > SUBCELL_MAX_K or n * k > 2 ** 31 - 1:
+        raise SslamHipError(f"subcell_keypoints: {_ERR[E_UNSUPPORTED]} (G * G <= {SUBCELL_MAX_CELLS}, K <= {SUBCELL_MAX_K}, "
+                            f"n * K < 2^31; got n = {n}, G = {g}, K = {k})")
+    shapes = subcell_shapes(n, k)
+    if out is not None:
+        if len(out) != 3:
+            raise ValueError("out must be (kp_xy_sub, kp_pixel_sub, flags)")
+        for key, t in zip(SUBCELL_KEYS, out):
+            if t is None:
+                raise ValueError(f"out `{key}` is required")
+            _check_arrays(shapes[key][0], (f"out `{key}`", t, shapes[key][1]))
+    dev = common_device(sal, idx, *(out or ()))
+    xy, px, fl = out if out is not None else (torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in SUBCELL_KEYS)
+    _run("subcell_keypoints", ext().sslx_subcell_keypoints, (sal, idx, xy, px, fl), _dp(sal), n, g, _dp(idx), k, _dp(xy), _dp(px), _dp(fl))
+    return xy, px, fl

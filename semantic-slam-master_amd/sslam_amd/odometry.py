@@ -16,7 +16,8 @@ Gauss-Newton on the Huber reprojection cost over RANSAC's inliers) all stay on t
   chain             pose_{i+1} = pose_i @ inv(T_i): camera-to-world poses, as TUM's groundtruth.txt has them, from the
                     camera-i -> camera-(i+1) transforms of consecutive pairs
 
-The keypoints are patch centres on a 16-pixel grid.  Nobody has measured which reprojection threshold suits them on real data:
+The keypoints are patch centres on a 16-pixel grid - or, on a pipeline with ExtractorConfig(subcell=True), the refined
+keypoints_subpixel, which everything here then reads (evaluation.geometry_bank).  Nobody has measured which reprojection threshold suits them on real data:
 no real RGB-D sequence was at hand when this was written.  3.0 keypoint units is only the scoring stage's default, taken over here.
 """
 from __future__ import annotations
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from . import lib
-from .evaluation import Camera, check_depth_size, gather_keypoint_depth, relative_transform
+from .evaluation import Camera, check_depth_size, check_subcell, gather_keypoint_depth, geometry_bank, relative_transform
 from .pipeline import MatchRule
 
 _INT_KEYS = ("inlier_count", "usable_count", "best_hypothesis", "refit_kept")
@@ -231,7 +232,7 @@ def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, sp
 
 def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None, rule=None,
              threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, refine: bool = False, huber=None,
-             iterations: int = 5) -> dict:
+             iterations: int = 5, *, subcell=None) -> dict:
     """The relative pose of every pair (i, i + spacing) of a sequence, from its own features: the frames images_u8 (N, H, W, 3)
     uint8 (a pipeline built with vit=) or their ViT tokens (tokens=), their raw depth images depth (N, h, w) uint16 (numpy or
     tensor) and camera (an evaluation.Camera; the default one if None).  The frames are extracted once, the depth under every
@@ -245,7 +246,10 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     steps at most), still with ONE read-back: 'T', 'inlier_count', 'rms', 'inlier_ratio', 'trajectory', 'rpe' and 'ate' are then the
     refined poses' (a pair whose refinement is not kept or not attempted keeps RANSAC's pose), 'ransac' holds the unrefined 'T',
     'inlier_count', 'rms' and the summaries built from them, and 'refine' holds 'status', 'iterations', 'selected_count', 'cost_in',
-    'cost' and 'info' (P, 6, 6), the information matrix of every refined pose.  With refine=False nothing changes."""
+    'cost' and 'info' (P, 6, 6), the information matrix of every refined pose.  With refine=False nothing changes.
+    subcell: on a pipeline with ExtractorConfig(subcell=True) the depth lookups, RANSAC and the refinement read the refined
+    keypoints (evaluation.geometry_bank); subcell=False forces the cell centres.  The match lists are the same either way."""
+    check_subcell(subcell)
     src = tokens if tokens is not None else images_u8
     if src is None:
         raise ValueError("images_u8 or tokens= required")
@@ -257,23 +261,25 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     _check_refine(refine, threshold, huber, iterations)
     rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
     ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
-    kp_depth = gather_keypoint_depth(pipe, depth, ex["keypoints_pixel"], n)
+    kp = geometry_bank(ex, subcell)
+    kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
-    return _estimate(pipe, ex["keypoints_pixel"], kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine,
+    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine,
                      huber, iterations)
 
 
 def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None,
                     threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, *, kp_depth=None, refine: bool = False, huber=None,
-                    iterations: int = 5) -> dict:
+                    iterations: int = 5, subcell=None) -> dict:
     """odometry() for a StreamingSequence.result() / run_frames / run_directory result: the keypoints and the match lists of every
     pair (i, i + spacing) are already in device memory, under whichever rule the sequence was run with, so nothing is extracted
     or matched again.  depth=: the raw depth images of the result's frames; kp_depth=: instead, the (N, K) int32 bank
     gather_keypoint_depth returned for result["frames"]["keypoints_pixel"], as evaluation.evaluate_result takes it.
-    refine, huber, iterations: as odometry() takes them."""
+    refine, huber, iterations, subcell: as odometry() takes them; a kp_depth= bank must have been gathered under the same bank
+    (evaluation.geometry_bank(result["frames"], subcell))."""
     if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
         raise ValueError("a StreamingSequence / run_directory result expected")
-    kp = result["frames"]["keypoints_pixel"]
+    kp = geometry_bank(result["frames"], subcell)
     pairs = consecutive_pairs(int(kp.shape[0]), spacing, num_pairs)
     if not pairs or spacing not in result:
         raise ValueError(f"the result holds no pair at spacing {spacing}")

@@ -47,6 +47,11 @@ from .pipeline import N_PREFIX, SequencePipeline, _checked_rule
 BANK_KEYS = ("descriptors", "scores", "intensity", "keypoints_pixel")      # what an earlier frame is kept for
 
 
+def bank_keys(pipe) -> tuple:
+    """BANK_KEYS, extended by the refined keypoints and their flags when the pipeline localises them (ExtractorConfig.subcell)."""
+    return BANK_KEYS + (lib.SUBCELL_KEYS if pipe.cfg.subcell else ())
+
+
 def _checked_spacings(spacings) -> tuple:
     if isinstance(spacings, (str, bytes)) or not hasattr(spacings, "__iter__"):
         raise ValueError(f"spacings must be a sequence of distinct positive ints, got {spacings!r}")
@@ -80,6 +85,7 @@ class FrameStepper:
             raise lib.SslamHipError("this pipeline was built without a ViT: pass tokens_in=True, or construct it with vit=")
         self.pipe, self.cfg, self.device = pipe, cfg, pipe.device
         self.tokens_in, self.use_graph = tokens_in, use_graph
+        self.bank_keys = bank_keys(pipe)
         dev, K = self.device, cfg.num_keypoints
         self.image = torch.zeros((1, height, width, 3), dtype=torch.uint8, device=dev)
         self.tokens = torch.zeros((1, N_PREFIX + cfg.grid ** 2, lib.C_FEAT), dtype=torch.float32, device=dev)
@@ -113,9 +119,9 @@ class FrameStepper:
         for v in one.values():
             v.zero_()
         # slots 0 .. ring - 1: frame j in slot j mod ring; slot `ring`: the static slot of the frame being extracted
-        self.bank = {k: torch.zeros((ring + 1,) + tuple(one[k].shape[1:]), dtype=one[k].dtype, device=dev) for k in BANK_KEYS}
+        self.bank = {k: torch.zeros((ring + 1,) + tuple(one[k].shape[1:]), dtype=one[k].dtype, device=dev) for k in self.bank_keys}
         self._ring = {k: v[:ring] for k, v in self.bank.items()}
-        self.cur = {k: (self.bank[k][ring:ring + 1] if k in BANK_KEYS else v) for k, v in one.items()}
+        self.cur = {k: (self.bank[k][ring:ring + 1] if k in self.bank_keys else v) for k, v in one.items()}
         self.m = pipe.alloc_match(len(spacings), self.cfg.num_keypoints, **self._rule_kw())
         i64 = dict(dtype=torch.int64, device=dev)
         self._t = torch.zeros((1,), **i64)                                   # the step counter: frames since reset()
@@ -138,7 +144,7 @@ class FrameStepper:
         self._aux = p.match(self.pair["descriptors"], self.pair["scores"], self.pair["intensity"], spacing=1, out=self.m,
                             **self._rule_kw())
         self._after_match()
-        for k in ("descriptors", "scores", "intensity", "keypoints_pixel"):      # this frame becomes the previous one
+        for k in self.bank_keys:      # this frame becomes the previous one
             self.pair[k][0].copy_(self.pair[k][1])
 
     def _body_spacings(self) -> None:
@@ -157,7 +163,7 @@ class FrameStepper:
         self._after_match()
         # this frame takes the ring slot of frame t - ring, which no spacing reaches any more
         torch.remainder(self._t, ring, out=self._slot)
-        for k in BANK_KEYS:
+        for k in self.bank_keys:
             self._ring[k].index_copy_(0, self._slot, self.cur[k])
         self._t.add_(1)
 
@@ -200,7 +206,9 @@ class FrameStepper:
     def step(self, image_u8: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
         """image_u8: (H, W, 3) or (1, H, W, 3) uint8, on the device or in host memory (pinned: the copy is asynchronous).
         tokens: (T, 384) / (1, T, 384) fp32 when the stepper was built with tokens_in.  Returns this frame's saliency /
-        keypoints_pixel / scores / idx / descriptors / intensity (views of static buffers, (K, ...) without the batch axis) and,
+        keypoints_pixel / scores / idx / descriptors / intensity - and, on a pipeline with subcell=True, keypoints_subpatch /
+        keypoints_subpixel / subcell_flags, whose launch is part of the captured graph - (views of static buffers, (K, ...) without
+        the batch axis) and,
         from the second frame on, matches (K, 2) int64 / quality (K,) / match_count against the previous frame (None before).
         With spacings: matches (S, K, 2) / quality (S, K) / match_count (S,), one row per spacing in the order given (views of
         static buffers; a spacing that reaches back before the first frame has count 0 and zero rows), and pair_first: a host
@@ -240,7 +248,8 @@ class FrameStepper:
             self._t.zero_()
 
     def frame(self, index: int) -> dict:
-        """With spacings: the bank rows (descriptors, scores, intensity, keypoints_pixel) of the frame with global index `index`,
+        """With spacings: the bank rows (descriptors, scores, intensity, keypoints_pixel; with subcell=True the refined keypoints
+        and their flags too) of the frame with global index `index`,
         one of the last max(spacings) stepped - what a pair_first entry names."""
         if self.spacings is None or not max(0, self.n_frames - self.ring) <= index < self.n_frames:
             raise ValueError(f"frame {index} is not in the bank")
@@ -333,11 +342,12 @@ class PoseFrameStepper(RuleFrameStepper):
 
     def _after_match(self) -> None:
         p = self.pipe
-        p.keypoint_depth(self.depth, self.cur["keypoints_pixel"], out=self.kp_depth[1:2])
-        p.estimate_poses(self.pair["keypoints_pixel"], self.kp_depth, self._first, self._second, self.m, self.camera, self.threshold,
+        kp = p.geometry_keypoints(self.pair)          # the refined bank on a pipeline with subcell=True, else the cell centres
+        p.keypoint_depth(self.depth, kp[1:2], out=self.kp_depth[1:2])
+        p.estimate_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.threshold,
                          self.hypotheses, self.seed, out=self.pose)
         if self.refine:
-            p.refine_poses(self.pair["keypoints_pixel"], self.kp_depth, self._first, self._second, self.m, self.camera, self.pose, self.threshold,
+            p.refine_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.pose, self.threshold,
                            self.huber, self.iterations, out=self.refined)
         self.kp_depth[0].copy_(self.kp_depth[1])
 

@@ -44,6 +44,14 @@ class ExtractorConfig:
     precision: str = "fp32"             # "fp32": bit-exact vs the CPU reference (the product default and the parity claim);
                                         # "bf16": BASELINE configs[1] throughput mode - saliency CNN + descriptor MLP on bf16
                                         # MFMA (fp32 accumulate), everything else unchanged; NOT index-exact
+    subcell: bool = False               # after A5, move each keypoint to the vertex of the per-axis parabola through its cell's
+                                        # saliency and its neighbours' (include/sslam_ext.h): extract() gains keypoints_subpatch,
+                                        # keypoints_subpixel and subcell_flags; every other output keeps its bits
+    subcell_descriptors: bool = False   # with subcell: A6 + A7 gather the descriptors at keypoints_subpatch, not at the cell
+
+    def __post_init__(self):
+        if self.subcell_descriptors and not self.subcell:
+            raise ValueError("subcell_descriptors=True gathers at the refined keypoints: it needs subcell=True")
 
     @property
     def grid(self) -> int:
@@ -264,6 +272,8 @@ class SequencePipeline:
         self.cfg = cfg
         self.device = torch.device(device)
         lib.lib()   # fail loudly if the HIP library is not built
+        if cfg.subcell:
+            lib.ext()   # nor the second one, where this pipeline launches from it
         if cfg.precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {cfg.precision!r}")
         if vit_precision not in ("bf16", "fp32"):          # checked whether or not a ViT is given: a typo must not pass silently
@@ -432,7 +442,17 @@ class SequencePipeline:
                    status=torch.empty((n,), dtype=torch.int32, device=dev))
         if with_intensity:
             out["intensity"] = torch.empty((n, K), **f32)
+        if cfg.subcell:
+            for key, (shape, dtype) in lib.subcell_shapes(n, K).items():
+                out[key] = torch.empty(shape, dtype=dtype, device=dev)
         return out
+
+    @staticmethod
+    def geometry_keypoints(out: dict) -> torch.Tensor:
+        """The keypoint bank (N, K, 2), in pixels of the input, that geometry should read from what extract() - or a stepper, or
+        result["frames"] of the harness - returned: the refined keypoints_subpixel where the pipeline ran with subcell=True, else
+        the cell centres keypoints_pixel."""
+        return out["keypoints_subpixel"] if "keypoints_subpixel" in out else out["keypoints_pixel"]
 
     def extract(self, tokens: torch.Tensor, images_u8: torch.Tensor | None = None, out: dict | None = None,
                 images_ready: "torch.cuda.Event | None" = None) -> dict:
@@ -446,6 +466,8 @@ class SequencePipeline:
         n, step = tokens.shape[0], self.launch_group()
         if out is None:
             out = self.alloc_extract(n, images_u8 is not None)
+        elif self.cfg.subcell and any(key not in out for key in lib.SUBCELL_KEYS):      # judged before anything is launched
+            raise ValueError(f"out must hold {', '.join(lib.SUBCELL_KEYS)} under subcell=True (alloc_extract)")
         for a in range(0, n, step):
             b = min(a + step, n)
             self._extract_group(tokens[a:b], None if images_u8 is None else images_u8[a:b], {k: v[a:b] for k, v in out.items()},
@@ -467,10 +489,14 @@ class SequencePipeline:
             lib.selector_saliency(feat, s.w1p, s.b1, s.w2, s.b2, s.hidden, out=out["saliency"], workspace=ws)
         lib.select_keypoints(out["saliency"], cfg.num_keypoints, cfg.nms_radius, cfg.min_score_percentile,
                              out=(out["keypoints_patch"], out["scores"], out["idx"], out["keypoints_pixel"], out["status"]))
+        if cfg.subcell:
+            lib.subcell_keypoints(out["saliency"], out["idx"], out=tuple(out[key] for key in lib.SUBCELL_KEYS))
+        # A6's bilinear gather takes fractional coordinates as it takes whole ones; A9 and the matcher keep the cell centres
+        kp = out["keypoints_subpatch"] if cfg.subcell_descriptors else out["keypoints_patch"]
         if self.bf16:
-            lib.gather_refine_bf16(feat, out["keypoints_patch"], self.refiner.packed_bf16, self.refiner.n_blocks, out=out["descriptors"])
+            lib.gather_refine_bf16(feat, kp, self.refiner.packed_bf16, self.refiner.n_blocks, out=out["descriptors"])
         else:
-            lib.gather_refine(feat, out["keypoints_patch"], self.refiner.packed, self.refiner.n_blocks, out=out["descriptors"], workspace=ws)
+            lib.gather_refine(feat, kp, self.refiner.packed, self.refiner.n_blocks, out=out["descriptors"], workspace=ws)
         if images_ready is not None:
             torch.cuda.current_stream(self.device).wait_event(images_ready)
         if images_u8 is not None and "intensity" in out:

@@ -189,6 +189,18 @@ def _takes_out(fn) -> bool:
         return False
 
 
+# A sharded form of the sub-cell keypoint localisation (ExtractorConfig.subcell) is not built and nothing here was run with it:
+# no gather carries the refined keypoints to rank 0 and no sharded stage reads them.  Such a pipeline is refused, not half served.
+_NO_SUBCELL = ("ShardedSequenceRunner has no sharded form of sub-cell keypoint localisation: build the pipeline with "
+               "ExtractorConfig(subcell=False), or run the sequence on one device")
+
+
+def _refuse_subcell(keys) -> None:
+    """ValueError if an extract dictionary or alloc_fn's buffers hold the refined keypoints: whatever callable made them."""
+    if "keypoints_subpixel" in keys:
+        raise ValueError(_NO_SUBCELL)
+
+
 class ShardedSequenceRunner:
     """extract_fn(tokens, images[, out]) -> dict with 'descriptors' (n, K, D), 'scores' (n, K), optional 'intensity' (n, K);
     if it takes `out` (a dict of row slices of preallocated buffers, as SequencePipeline.extract does) the block's outputs
@@ -213,6 +225,11 @@ class ShardedSequenceRunner:
         +0.26 ms per 613-frame block, 2.4 % of the step - more than the exchange it hides).  Without alloc_fn: "early"."""
         if halo not in ("late", "early"):
             raise ValueError(f"halo must be 'late' or 'early', got {halo!r}")
+        for fn in (extract_fn, match_fn, alloc_fn):
+            # a pipeline handed over as its bound methods is refused here already; any other callable - a wrapper, a lambda - in
+            # run(), by the keys of what it extracts or allocates (_refuse_subcell)
+            if getattr(getattr(getattr(fn, "__self__", None), "cfg", None), "subcell", False):
+                raise ValueError(_NO_SUBCELL)
         self.extract_fn, self.match_fn, self.spacing, self.group = extract_fn, match_fn, spacing, group
         self.alloc_fn, self.halo = alloc_fn, halo
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -249,11 +266,13 @@ class ShardedSequenceRunner:
         img = (lambda a, b: None if images_local is None else images_local[a:b])
         if self.world == 1:
             ex = self.extract_fn(tokens_local, images_local)
+            _refuse_subcell(ex)
             fields = {k: ex.get(k) for k in names}
         elif self.halo == "late" and self.alloc_fn is not None and _takes_out(self.extract_fn):
             # the whole block as ONE launch group, written into buffers with `sp` spare rows; then the exchange, then the matcher
             n_halo = sp if self.rank < self.world - 1 else 0
             full = self.alloc_fn(n + n_halo)
+            _refuse_subcell(full)
             if images_local is None:
                 # alloc_fn does not know whether pixels were passed: without them nothing writes 'intensity' - it must not be
                 # exchanged or handed to the matcher (whose intensity threshold would then read uninitialised memory)
@@ -269,6 +288,7 @@ class ShardedSequenceRunner:
             # boundary group, the rest of the block and the neighbour's halo all land in place.
             n_halo = sp if self.rank < self.world - 1 else 0
             ex_head = self.extract_fn(tokens_local[:sp], img(0, sp))
+            _refuse_subcell(ex_head)
             full = {k: torch.empty((n + (n_halo if k in names else 0),) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device)
                     for k, v in ex_head.items() if isinstance(v, torch.Tensor)}
             for k, v in full.items():
