@@ -58,7 +58,11 @@ long long sslx_launch_count(void);    /* kernels this library has launched in th
  * is used; each (x, y) pair is one 8-byte store.  No LDS, no atomics, no workspace: capturable in a graph.
  * SSLAM_E_INVALID: a NULL pointer; n_frames, G or K <= 0; a pointer that misses its alignment (above).
  * SSLAM_E_UNSUPPORTED: G * G above SSLX_SUBCELL_MAX_CELLS; K above SSLX_SUBCELL_MAX_K; n_frames * K above 2^31 - 1.
- * Every refusal comes before anything is launched and writes nothing. */
+ * Every refusal comes before anything is launched and writes nothing.
+ * SIZE LIMITS (as the block of that name in include/sslam_hip.h: the expressions the dispatch code tests, the code returned where
+ * one is false, and the widths in bits of the kernel's index expressions; tests/size_table.py, tests/test_size_limits_cpu.py):
+ *   sslx_subcell_keypoints: n_frames * K <= 0x7fffffff, else SSLAM_E_UNSUPPORTED; G <= 64 and K <= 4096, else SSLAM_E_UNSUPPORTED.
+ *         offsets: keypoint index n_frames * K 64, frame * G * G 64 */
 int sslx_subcell_keypoints(const float *sal, int n_frames, int G, const int32_t *idx, int K, float *kp_xy_sub, float *kp_pixel_sub,
                            int32_t *flags, void *stream);
 

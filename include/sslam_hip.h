@@ -124,6 +124,143 @@ extern "C" {
  *         iterations 4, selected_count 4, usable_count 4, inlier_count_in 4, inlier_count 4, inlier_of_slot 4, cost_in 8, cost
  *         8, rms 8, info 8 */
 
+/* ---- SIZE LIMITS, every entry that launches a kernel.  An entry is correct over the whole range it accepts and refuses one past it:
+ * below, per entry, the counts or byte sizes it accepts as the expression its dispatch code tests, and what it returns where the
+ * expression is false - before anything is launched, nothing written.  Where an entry cuts a call into launch groups by itself
+ * instead of refusing (sslam_preprocess_u8 and its patch form only), the line says how; every other entry leaves the cutting to
+ * its caller (sslam_amd.pipeline: ExtractorConfig.launch_group(), HipViT / HipViTF32.chunk_frames).  "offsets:" names the offset and
+ * index expressions of the entry's kernels with their width in bits - 31: a signed int that must stay non-negative, 32: an
+ * unsigned byte offset into one buffer descriptor, 64: long long, size_t or pointer arithmetic (profiles/size_limits.txt is the
+ * audit they are read from).  An entry with "no limit" indexes in 64 bits throughout and launches one workgroup or thread per
+ * frame, pair or row; what bounds it is the memory its operands take.  Shape limits stated with an entry (K, n1 <= 4096; G * G <=
+ * 4096; the descriptor widths 128 and 256; SSLAM_MAX_TAPS) are repeated here only where they are the entry's size limit.
+ * tests/size_table.py holds this block as data; tests/test_size_limits_cpu.py calls every entry one above each limit, and
+ * tests/test_gpu_size_limits.py runs the accepted side with operands past 2^31 bytes, bit for bit against the CPU oracle.
+ *   sslam_preprocess_u8: h * w * 3 <= 0x7fffffff, else SSLAM_E_UNSUPPORTED; (min(n, per_group) + 7) / 8 * 8 * tiles <= 0x7fffffff,
+ *         else SSLAM_E_UNSUPPORTED. n: any; cut into launch groups of per_group = min(65535, max(1, 0xfffffff0 / (h * w * 3)))
+ *         frames, rounded down to a multiple of 4 where h * w * 3 is none and per_group >= 4; a group whose base is not dword
+ *         aligned takes the general kernel. offsets: tiled kernel: frame * (h * w * 3) + (row * w + col) * 3 into the group's
+ *         descriptor 32, tiled kernel: output frame * 3 * size^2 64, general kernel: frame * h * w * 3 64, group base n0 * h * w *
+ *         3 64
+ *   sslam_preprocess_u8_patches: h * w * 3 <= 0x7fffffff, else SSLAM_E_UNSUPPORTED; (min(n, per_group) + 7) / 8 * 8 * tiles <=
+ *         0x7fffffff, else SSLAM_E_UNSUPPORTED. n: any; cut into launch groups of per_group = min(65535, max(1, 0xfffffff0 / (h *
+ *         w * 3))) frames, rounded down to a multiple of 4 where h * w * 3 is none and per_group >= 4; a group whose base is not
+ *         dword aligned is refused with SSLAM_E_UNSUPPORTED, as is a table of more than 7 horizontal taps (the caller takes
+ *         sslam_preprocess_u8 then). offsets: tiled kernel: frame * (h * w * 3) + (row * w + col) * 3 into the group's descriptor
+ *         32, tiled kernel: output frame * 3 * size^2 64, general kernel: frame * h * w * 3 64, group base n0 * h * w * 3 64
+ *   sslam_bn_tokens: group * (tokens_per_frame - n_prefix) <= 0x7fffffff - 112, else SSLAM_E_UNSUPPORTED. offsets: sweep kernel:
+ *         row of the group r + 16 * u, u < 7 31, sweep kernel: (frame * tokens_per_frame + token) * 384 64, register kernel: lane
+ *         offset loff = p * 384 + ch0 32, register kernel: frame * tokens_per_frame * 384 + step * 16 * 384 64
+ *   sslam_bn_tokens_bf16copy: group * (tokens_per_frame - n_prefix) <= 0x7fffffff - 112, else SSLAM_E_UNSUPPORTED. offsets: sweep
+ *         kernel: row of the group r + 16 * u, u < 7 31, sweep kernel: (frame * tokens_per_frame + token) * 384 64, register
+ *         kernel: lane offset loff = p * 384 + ch0 32, register kernel: frame * tokens_per_frame * 384 + step * 16 * 384 64
+ *   sslam_selector_saliency: n_frames * G * G * 1536 <= 0xffffffff, else SSLAM_E_UNSUPPORTED. offsets: cell * 1536 + 32 * k-group
+ *         into one descriptor over feat 32, (int)rows, cell and padded-cell indices 31, sal[cell] 64
+ *   sslam_selector_saliency_ws: n_frames * G * G * 1536 <= 0xffffffff, else SSLAM_E_UNSUPPORTED. offsets: cell * 1536 + 32 *
+ *         k-group into one descriptor over feat 32, (int)rows, cell and padded-cell indices 31, sal[cell] 64
+ *   sslam_selector_saliency_bf16: n_frames * G * G * 768 <= 0xffffffff, else SSLAM_E_UNSUPPORTED. offsets: cell * 768 + 16 *
+ *         k-group into one descriptor over feat_bf16 32, (int)rows, cell and padded-cell indices (the halo form runs below 2^30
+ *         cells only) 31, sal[cell] 64
+ *   sslam_sim_argmax: n_pairs * ceil(max(n1, n2) / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 *
+ *         (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64, keys[pair * n2 +
+ *         column] 64
+ *   sslam_sim_argmax_d: n_pairs * ceil(max(n1, n2) / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 *
+ *         (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64, keys[pair * n2 +
+ *         column] 64
+ *   sslam_sim_argmax_ws: n_pairs * ceil(max(n1, n2) / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 *
+ *         (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64, keys[pair * n2 +
+ *         column] 64
+ *   sslam_sim_argmax_ws_d: n_pairs * ceil(max(n1, n2) / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 *
+ *         (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64, keys[pair * n2 +
+ *         column] 64
+ *   sslam_sim_argmax_pairs: n_pairs * ceil(max(n1, n2) / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8
+ *         * (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64, keys[pair * n2 +
+ *         column] 64
+ *   sslam_sim_argmax_pairs_d: n_pairs * ceil(max(n1, n2) / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup =
+ *         8 * (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64, keys[pair * n2 +
+ *         column] 64
+ *   sslam_sim_argmax_rows: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 * (slot /
+ *         qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_sim_argmax_rows_d: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 * (slot
+ *         / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_sim_argmax_rows_pairs: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 *
+ *         (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_sim_argmax_rows_pairs_d: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 *
+ *         (slot / qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_row_lse: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 * (slot / qblocks)
+ *         + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_row_lse_d: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 * (slot /
+ *         qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_row_lse_pairs: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 * (slot /
+ *         qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_row_lse_pairs_d: n_pairs * ceil(n1 / 128) <= 0x7ffffff0 / 8, else SSLAM_E_UNSUPPORTED. offsets: workgroup = 8 * (slot /
+ *         qblocks) + xcd in one grid dimension 31, pair * stride, frame * frame_stride, row * D 64
+ *   sslam_edge_pool: n_frames <= 65535, else SSLAM_E_UNSUPPORTED; size / 16 <= 65535, else SSLAM_E_UNSUPPORTED. offsets: grid.z =
+ *         n_frames, grid.y = size / 16 31, frame * 3 * size^2 64
+ *   sslam_vit_forward: n_frames * T * 1536 <= 0x7fffffff * 64, T = (size / 16)^2 + 5, else SSLAM_E_UNSUPPORTED. offsets: rows *
+ *         VMLP in the GEMM tile index (rows * 1536 / 64 stays below 2^31) 31, workspace carving, token rows 64. untested - crosses
+ *         2^31 only from 89 478 486 token rows: a bf16 hidden activation of 275 GB, far above 24 GiB of one operand
+ *   sslam_vit_forward_form: n_frames * T * 1536 <= 0x7fffffff * 64, T = (size / 16)^2 + 5, else SSLAM_E_UNSUPPORTED. offsets: rows
+ *         * VMLP in the GEMM tile index (rows * 1536 / 64 stays below 2^31) 31, workspace carving, token rows 64. untested -
+ *         crosses 2^31 only from 89 478 486 token rows: a bf16 hidden activation of 275 GB, far above 24 GiB of one operand
+ *   sslam_vit_forward_patches: n_frames * T * 1536 <= 0x7fffffff * 64, T = (size / 16)^2 + 5, else SSLAM_E_UNSUPPORTED. offsets:
+ *         rows * VMLP in the GEMM tile index (rows * 1536 / 64 stays below 2^31) 31, workspace carving, token rows 64. untested -
+ *         crosses 2^31 only from 89 478 486 token rows: a bf16 hidden activation of 275 GB, far above 24 GiB of one operand
+ *   sslam_vit_forward_patches_form: n_frames * T * 1536 <= 0x7fffffff * 64, T = (size / 16)^2 + 5, else SSLAM_E_UNSUPPORTED.
+ *         offsets: rows * VMLP in the GEMM tile index (rows * 1536 / 64 stays below 2^31) 31, workspace carving, token rows 64.
+ *         untested - crosses 2^31 only from 89 478 486 token rows: a bf16 hidden activation of 275 GB, far above 24 GiB of one
+ *         operand
+ *   sslam_vit_forward_f32: n_frames * T * 1536 * 4 <= 0xfffffff0, T = (size / 16)^2 + 5, else SSLAM_E_UNSUPPORTED. offsets: GEMM A
+ *         operand: row * lda * 4 into one descriptor (widest: the MLP hidden activation) 32, workspace carving, token rows 64
+ *   sslam_vit_forward_f32_form: n_frames * T * 1536 * 4 <= 0xfffffff0, T = (size / 16)^2 + 5, else SSLAM_E_UNSUPPORTED. offsets:
+ *         GEMM A operand: row * lda * 4 into one descriptor (widest: the MLP hidden activation) 32, workspace carving, token rows
+ *         64
+ *   sslam_keypoint_depth: n * K <= 0x7fffffff, else SSLAM_E_UNSUPPORTED. offsets: keypoint index n * K 64, frame * h * w 64
+ *   sslam_select_keypoints: G * G <= 4096 and K <= 4096, else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per frame.
+ *         offsets: frame * G * G, frame * K 64
+ *   sslam_match_rank: n1 <= 4096, else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair. offsets: pair * n1 64
+ *   sslam_pose_nn_pairs: K <= 4096 (n1 <= 4096), else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair. offsets:
+ *         frame * K, pair * n1 64
+ *   sslam_pose_depth_nn_pairs: K <= 4096 (n1 <= 4096), else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair.
+ *         offsets: frame * K, pair * n1 64
+ *   sslam_pose_ransac_pairs: K <= 4096 (n1 <= 4096), else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair.
+ *         offsets: frame * K, pair * n1 64
+ *   sslam_pose_refine_pairs: K <= 4096 (n1 <= 4096), else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair.
+ *         offsets: frame * K, pair * n1 64
+ *   sslam_match_score_pairs: n1 <= 4096, else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair. offsets: pair * n1
+ *         64
+ *   sslam_match_score_known_pairs: n1 <= 4096, else SSLAM_E_UNSUPPORTED. indexes in 64 bits; one workgroup per pair. offsets: pair
+ *         * n1 64
+ *   sslam_keypoint_intensity: no limit - never refuses by size: above 0xfffffff0 bytes of frames or 0x7fffff00 keypoints (or with
+ *         more than 7 taps either way, or an img that is not dword aligned) it falls back from intensity_fast_kernel (32-bit
+ *         offsets into one descriptor) to intensity_kernel (64 bits); one thread per keypoint
+ *   sslam_f32_to_bf16: no limit - indexes in 64 bits; one thread per 8 elements
+ *   sslam_gather: no limit - indexes in 64 bits; one thread per four floats of a row
+ *   sslam_refine: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are int32: it
+ *         runs below 2^31 rows only, the direct form above)
+ *   sslam_refine_d: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are int32: it
+ *         runs below 2^31 rows only, the direct form above)
+ *   sslam_gather_refine: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are int32:
+ *         it runs below 2^31 rows only, the direct form above)
+ *   sslam_gather_refine_d: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are
+ *         int32: it runs below 2^31 rows only, the direct form above)
+ *   sslam_gather_refine_ws: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are
+ *         int32: it runs below 2^31 rows only, the direct form above)
+ *   sslam_gather_refine_ws_d: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are
+ *         int32: it runs below 2^31 rows only, the direct form above)
+ *   sslam_refine_bf16: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are int32:
+ *         it runs below 2^31 rows only, the direct form above)
+ *   sslam_gather_refine_bf16: no limit - indexes in 64 bits; one workgroup per 32 rows (row indices of the distinct-row form are
+ *         int32: it runs below 2^31 rows only, the direct form above)
+ *   sslam_match_finalize: no limit - indexes in 64 bits; one workgroup per pair
+ *   sslam_match_finalize_pairs: no limit - indexes in 64 bits; one workgroup per pair
+ *   sslam_match_finalize_rule: no limit - indexes in 64 bits; one workgroup per pair
+ *   sslam_match_finalize_rule_pairs: no limit - indexes in 64 bits; one workgroup per pair
+ *   sslam_val_pair_stats: no limit - indexes in 64 bits; one workgroup per pair
+ *   sslam_val_pair_stats_pairs: no limit - indexes in 64 bits; one workgroup per pair
+ *   sslam_val_frame_stats: no limit - indexes in 64 bits; one workgroup per frame
+ *   sslam_val_frame_stats_d: no limit - indexes in 64 bits; one workgroup per frame */
+
 #define SSLAM_C 384   /* backbone embed dim (ViT-S/16), dino_backbone.py:50 */
 #define SSLAM_HID 384 /* refiner hidden dim, configs/train_config.yaml:13 */
 #define SSLAM_D 128   /* descriptor dim, configs/train_config.yaml:12: the default width; the _d entries also take 256 */

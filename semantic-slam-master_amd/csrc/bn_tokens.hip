@@ -307,7 +307,8 @@ static int bn_launch(const float *tokens, int n_frames, int tokens_per_frame, in
     if (((uintptr_t)tokens | (uintptr_t)out_feat | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)run_mean |
          (uintptr_t)run_var | (uintptr_t)out_mean | (uintptr_t)out_var | (uintptr_t)out_bf16) & 15)
         return SSLAM_E_INVALID;
-    if ((long long)group * (tokens_per_frame - n_prefix) > 0x7fffffffLL) return SSLAM_E_UNSUPPORTED;
+    // the sweep kernel steps an int row index 16 * U past the group's last row before it clamps it
+    if ((long long)group * (tokens_per_frame - n_prefix) > 0x7fffffffLL - 16 * U) return SSLAM_E_UNSUPPORTED;
     const int cells = tokens_per_frame - n_prefix;
     if (train && group == 1 && cells <= 16 * 225 && sslam_knob(KNOB_BN_FORM, 0) != 1) {
         // one HBM read instead of three: every lane keeps its rows on the chip between the sweeps (bn_tokens_reg_kernel)
