@@ -1,0 +1,618 @@
+// pose_graph.hip - libsslam_graph.so: the pose graph over relative poses and their information matrices (include/sslam_graph.h
+// states the arithmetic operation by operation; tests/pose_graph_ref.py restates it in numpy float64).
+//   sslg_chain_poses   world -> camera poses from consecutive transforms, one thread per chain: the initial guess.
+//   sslg_pose_graph    one 256-thread workgroup per graph: Gauss-Newton with a Huber weight per edge, node 0 the anchor.
+// A step of sslg_pose_graph:
+//   assembly       256 edges at a time are STAGED, one thread per edge (the residual, w, and the 90 products w H, -(w H Ad),
+//                  w Ad^T H Ad, w H r, -(w Ad^T H r)), then WALKED in slot order by four groups of 63 threads: a thread owns one entry
+//                  position (21 of a diagonal block's lower triangle, 36 of an off-diagonal block, 6 of g) of the nodes n with
+//                  n % 4 == its group, so every word of A and g has one writer and takes its terms in ascending slot order.
+//   factorisation  right-looking on a sliding window in LDS: the lower triangle of the trailing (bw + 1) x (bw + 1) block, 64 KB at
+//                  band 20, 158 KB at band 32.  Column j: one thread per row divides by the pivot, a barrier, the 256 threads
+//                  subtract (L_ij L_kj) D_j from the triangle behind it (about (bw / 16)^2 / 2 entries each), a barrier, row
+//                  j + bw + 1 of A enters where column j was.  An element takes its updates in ascending k, as in the left-looking
+//                  statement of the header, so the bits are those.  The forward substitution rides along (y_i takes L_ij y_j as y_j
+//                  becomes final).  L leaves the window column by column, into the workspace where row j of A was.
+//   backward       by rows, in one wave: the deltas and the row's column of L (contiguous) in registers, the products in parallel, then
+//                  subtracted in ascending k by every lane; the next row's column is fetched meanwhile.
+// The window's slots: entry (i, k) of the trailing block lies at the unordered pair (i mod M, k mod M), M = bw + 1, of a packed
+// triangle - the M rows in flight have distinct residues, so the map is one to one, and the row that enters takes exactly the slots
+// of the column that left.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/sslam_graph.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int WAVES = NT / 64;
+constexpr int STAGE = 90;           // words staged per edge: BB 21, BA 36, AA 21, GB 6, GA 6
+constexpr int S_BB = 0, S_BA = 21, S_AA = 57, S_GB = 78, S_GA = 84;
+constexpr int WALK = 63;            // entry positions a walking group owns: 21 diagonal, 36 off-diagonal, 6 of g
+constexpr int GROUPS = 4;
+constexpr int TQ = (6 * SSLG_MAX_BAND + 5 + 15) / 16;      // columns of the trailing block a thread of the 16 x 16 tiling takes: 13
+
+long long g_launches = 0;   // diagnostic launch counter (sslg_launch_count): relaxed atomic adds, the library's only mutable state
+
+__device__ __forceinline__ bool fin(double v) { return v - v == 0.0; }
+inline bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
+inline bool finite_nonnegative(double v) { return v >= 0.0 && v - v == 0.0; }
+inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+__device__ __forceinline__ constexpr int tri_upper(int i, int j) {      // H(i, j) in the 21 words of info, either triangle
+    return i <= j ? 6 * i - (i * (i - 1)) / 2 + (j - i) : 6 * j - (j * (j - 1)) / 2 + (i - j);
+}
+__device__ __forceinline__ constexpr int tri_lower(int i, int j) { return (i * (i + 1)) / 2 + j; }      // i >= j
+
+// out = A o B
+__device__ __forceinline__ void compose(const double *A, const double *B, double *out) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[4 * i + j] = (A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j];
+        out[4 * i + 3] = ((A[4 * i] * B[3] + A[4 * i + 1] * B[7]) + A[4 * i + 2] * B[11]) + A[4 * i + 3];
+    }
+}
+
+__device__ __forceinline__ void inverse(const double *A, double *out) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[4 * i + j] = A[4 * j + i];
+        out[4 * i + 3] = -((A[i] * A[3] + A[4 + i] * A[7]) + A[8 + i] * A[11]);
+    }
+}
+
+// lane t's x, for a t the compiler knows (two v_readlane_b32)
+__device__ __forceinline__ double lane_value(double x, int t) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), t), hi = __builtin_amdgcn_readlane(__double2hiint(x), t);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double sum6(const double (&x)[6]) { return ((((x[0] + x[1]) + x[2]) + x[3]) + x[4]) + x[5]; }
+
+struct Edge {
+    double Tp[12], H[21], Hr[6], s, w, rho;
+};
+
+// the edge (Ca, Cb, Tm, info) at the poses: T_p, r, H r, s, w, rho
+__device__ __forceinline__ void edge_eval(const double *Ca, const double *Cb, const double *Tm, const double *info, double chi, Edge &e) {
+    double ca[12], cb[12], tm[12], ai[12], mi[12], D[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) ca[k] = Ca[k], cb[k] = Cb[k], tm[k] = Tm[k];
+#pragma unroll
+    for (int k = 0; k < 21; k++) e.H[k] = info[k];
+    inverse(ca, ai);
+    compose(cb, ai, e.Tp);
+    inverse(tm, mi);
+    compose(e.Tp, mi, D);
+    const double r[6] = {D[3], D[7], D[11], 0.5 * (D[9] - D[6]), 0.5 * (D[2] - D[8]), 0.5 * (D[4] - D[1])};
+    double x[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) x[k] = e.H[tri_upper(i, k)] * r[k];
+        e.Hr[i] = sum6(x);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) x[k] = r[k] * e.Hr[k];
+    e.s = sum6(x);
+    const bool quad = e.s <= chi * chi;                  // a NaN takes the linear branch and stays a NaN
+    const double q = __builtin_sqrt(e.s);
+    e.w = quad ? 1.0 : chi / q;
+    e.rho = quad ? e.s : (2.0 * chi) * q - chi * chi;
+}
+
+// the 90 staged words of an edge from its evaluation
+__device__ __forceinline__ void edge_stage(const Edge &e, double *st) {
+    double Ad[6][6];
+    const double *m = e.Tp;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            Ad[i][j] = m[4 * i + j];
+            Ad[3 + i][3 + j] = m[4 * i + j];
+            Ad[3 + i][j] = 0.0;
+        }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        Ad[0][3 + j] = m[7] * m[8 + j] - m[11] * m[4 + j];
+        Ad[1][3 + j] = m[11] * m[j] - m[3] * m[8 + j];
+        Ad[2][3 + j] = m[3] * m[4 + j] - m[7] * m[j];
+    }
+    double P[6][6], x[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) x[k] = e.H[tri_upper(i, k)] * Ad[k][j];
+            P[i][j] = sum6(x);
+            st[S_BA + 6 * i + j] = -(e.w * P[i][j]);
+        }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) x[k] = Ad[k][i] * P[k][j];
+            st[S_AA + tri_lower(i, j)] = e.w * sum6(x);
+            st[S_BB + tri_lower(i, j)] = e.w * e.H[tri_upper(i, j)];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) x[k] = Ad[k][i] * e.Hr[k];
+        st[S_GA + i] = -(e.w * sum6(x));
+        st[S_GB + i] = e.w * e.Hr[i];
+    }
+}
+
+// [R | t] <- [dR R | dR t + v] with dR from the unit quaternion of (1, wx / 2, wy / 2, wz / 2): sslam_pose_refine_pairs' update
+__device__ __forceinline__ void pose_update(const double *m, const double *delta, double *out) {
+    double w = 1.0, x = 0.5 * delta[3], y = 0.5 * delta[4], z = 0.5 * delta[5];
+    const double nrm = __builtin_sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / nrm;
+    x = x / nrm;
+    y = y / nrm;
+    z = z / nrm;
+    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    double R[9];
+    R[0] = ((ww + xx) - yy) - zz;
+    R[1] = 2.0 * (x * y - w * z);
+    R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z);
+    R[4] = ((ww - xx) + yy) - zz;
+    R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y);
+    R[7] = 2.0 * (y * z + w * x);
+    R[8] = ((ww - xx) - yy) + zz;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[4 * i + j] = (R[3 * i] * m[j] + R[3 * i + 1] * m[4 + j]) + R[3 * i + 2] * m[8 + j];
+        out[4 * i + 3] = ((R[3 * i] * m[3] + R[3 * i + 1] * m[7]) + R[3 * i + 2] * m[11]) + delta[i];
+    }
+}
+
+__device__ __forceinline__ double block_sum(double p, double *wsum, int tid) {
+    p = p + __shfl_xor(p, 32);
+    p = p + __shfl_xor(p, 16);
+    p = p + __shfl_xor(p, 8);
+    p = p + __shfl_xor(p, 4);
+    p = p + __shfl_xor(p, 2);
+    p = p + __shfl_xor(p, 1);
+    if ((tid & 63) == 0) wsum[tid >> 6] = p;
+    __syncthreads();
+    p = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    __syncthreads();                                     // wsum may be written again
+    return p;
+}
+
+__device__ __forceinline__ int block_count(int n, int *wcnt, int tid) {
+    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+    if ((tid & 63) == 0) wcnt[tid >> 6] = n;
+    __syncthreads();
+    n = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+    return n;
+}
+
+struct Graph {
+    const int *first, *second;
+    const double *T, *info;
+    int n_nodes, n_edges, band;
+};
+
+__device__ __forceinline__ bool edge_used(const Graph &g, int e, int &a, int &b) {
+    a = g.first[e];
+    b = g.second[e];
+    if (!(0 <= a && a < b && b < g.n_nodes && b - a <= g.band)) return false;
+    bool ok = true;
+    const double *t = g.T + (long long)e * 12, *h = g.info + (long long)e * 21;
+    for (int k = 0; k < 12; k++) ok = ok && fin(t[k]);
+    for (int k = 0; k < 21; k++) ok = ok && fin(h[k]);
+    return ok;
+}
+
+// the cost at the poses X, in the pass' order; with chi2, s of every used edge (+0.0 elsewhere) is written there
+__device__ __forceinline__ double graph_cost(const Graph &g, const double *X, double chi, double *chi2, double *wsum, int tid) {
+    double part = 0.0;
+    for (int e = tid; e < g.n_edges; e += NT) {
+        int a, b;
+        double rho = 0.0, s = 0.0;
+        if (edge_used(g, e, a, b)) {
+            Edge ed;
+            edge_eval(X + (long long)a * 12, X + (long long)b * 12, g.T + (long long)e * 12, g.info + (long long)e * 21, chi, ed);
+            rho = ed.rho;
+            s = ed.s;
+        }
+        part = part + rho;
+        if (chi2) chi2[e] = s;
+    }
+    return block_sum(part, wsum, tid);
+}
+
+__global__ __launch_bounds__(NT) void pose_graph_kernel(const int *__restrict__ edge_first, const int *__restrict__ edge_second,
+                                                        const double *__restrict__ edge_T, const double *__restrict__ edge_info,
+                                                        int n_nodes, int n_edges, const double *__restrict__ C_in, int band, double chi,
+                                                        double damping, int n_iter, double *workspace, long long ws_words, double *C,
+                                                        int *__restrict__ status, int *__restrict__ iterations,
+                                                        int *__restrict__ used_edges, int *__restrict__ skipped_edges,
+                                                        int *__restrict__ failed_row, double *__restrict__ cost_in,
+                                                        double *__restrict__ cost_out, double *__restrict__ edge_chi2) {
+    extern __shared__ double dyn[];                      // win: M (M + 1) / 2 words, then ring: M words (y, later delta)
+    __shared__ double wsum[WAVES];
+    __shared__ int wcnt[WAVES];
+    __shared__ int sa[NT], sb[NT];                       // the staged edges' nodes; sb < 0: not used
+
+    const int tid = threadIdx.x;
+    const long long gi = blockIdx.x;
+    Graph g;
+    g.first = edge_first + gi * n_edges;
+    g.second = edge_second + gi * n_edges;
+    g.T = edge_T + gi * n_edges * 12;
+    g.info = edge_info + gi * n_edges * 21;
+    g.n_nodes = n_nodes;
+    g.n_edges = n_edges;
+    g.band = band;
+    C_in += gi * n_nodes * 12;
+    C += gi * n_nodes * 12;
+    edge_chi2 += gi * n_edges;
+
+    const int n = 6 * (n_nodes - 1), bw = 6 * band + 5, W = bw + 1, M = W;
+    double *win = dyn, *ring = dyn + (M * (M + 1)) / 2;
+    double *Ab = workspace + gi * ws_words;
+    double *gv = Ab + (long long)n * W, *yv = gv + n, *dv = yv + n;
+    double *trial = dv + n;
+    double *stage = trial + (long long)n_nodes * 12;
+
+    // ---- C <- C_in; the edge counts; whether anything is attempted
+    int bad = 0, used = 0, skipped = 0;
+    for (int k = tid; k < n_nodes * 12; k += NT) {
+        const double v = C_in[k];
+        C[k] = v;
+        bad += !fin(v);
+    }
+    for (int e = tid; e < n_edges; e += NT) {
+        int a, b;
+        const bool u = edge_used(g, e, a, b);
+        used += u;
+        skipped += !u && a != -1;
+    }
+    bad = block_count(bad, wcnt, tid);
+    used = block_count(used, wcnt, tid);
+    skipped = block_count(skipped, wcnt, tid);
+    if (tid == 0) {
+        used_edges[gi] = used;
+        skipped_edges[gi] = skipped;
+    }
+    if (bad != 0 || used == 0) {                         // not attempted (uniform)
+        for (int e = tid; e < n_edges; e += NT) edge_chi2[e] = 0.0;
+        if (tid == 0) {
+            status[gi] = 3;
+            iterations[gi] = 0;
+            failed_row[gi] = -1;
+            cost_in[gi] = 0.0;
+            cost_out[gi] = 0.0;
+        }
+        return;
+    }
+    __syncthreads();                                     // C is read below by other threads than wrote it
+
+    const double c_in = graph_cost(g, C, chi, nullptr, wsum, tid);
+    double cur_cost = c_in;
+    int accepted = 0, failed = -1;
+    bool first_failed = false;
+
+#pragma unroll 1
+    for (int it = 0; it < n_iter; it++) {
+        // ---- assembly at the current poses
+        for (long long k = tid; k < (long long)n * W + n; k += NT) Ab[k] = 0.0;      // A and g
+        __syncthreads();
+#pragma unroll 1
+        for (int base = 0; base < n_edges; base += NT) {
+            const int e = base + tid;
+            int a = -1, b = -1;
+            if (e < n_edges && edge_used(g, e, a, b)) {
+                Edge ed;
+                edge_eval(C + (long long)a * 12, C + (long long)b * 12, g.T + (long long)e * 12, g.info + (long long)e * 21, chi, ed);
+                edge_stage(ed, stage + tid * STAGE);
+            } else {
+                b = -1;
+            }
+            sa[tid] = a;
+            sb[tid] = b;
+            __syncthreads();
+            const int grp = tid / WALK, pos = tid - grp * WALK;
+            if (grp < GROUPS) {
+                const int cnt = n_edges - base < NT ? n_edges - base : NT;
+#pragma unroll 1
+                for (int c = 0; c < cnt; c++) {
+                    const int eb = sb[c], ea = sa[c];
+                    if (eb < 0) continue;
+                    const double *st = stage + c * STAGE;
+                    const int rb = 6 * (eb - 1), ra = 6 * (ea - 1);
+                    const bool own_b = (eb & (GROUPS - 1)) == grp, own_a = ea >= 1 && (ea & (GROUPS - 1)) == grp;
+                    if (pos < 21) {                      // lower triangle of the diagonal blocks
+                        int i = 0;
+                        while (tri_lower(i + 1, 0) <= pos) i++;
+                        const int j = pos - tri_lower(i, 0);
+                        if (own_b) {
+                            double *p = Ab + (long long)(rb + i) * W + (j - i + bw);
+                            *p = *p + st[S_BB + pos];
+                        }
+                        if (own_a) {
+                            double *p = Ab + (long long)(ra + i) * W + (j - i + bw);
+                            *p = *p + st[S_AA + pos];
+                        }
+                    } else if (pos < 57) {               // the off-diagonal block (b, a)
+                        const int q = pos - 21, i = q / 6, j = q - 6 * i;
+                        if (own_b && ea >= 1) {
+                            double *p = Ab + (long long)(rb + i) * W + ((ra + j) - (rb + i) + bw);
+                            *p = *p + st[S_BA + q];
+                        }
+                    } else {                             // g
+                        const int i = pos - 57;
+                        if (own_b) gv[rb + i] = gv[rb + i] + st[S_GB + i];
+                        if (own_a) gv[ra + i] = gv[ra + i] + st[S_GA + i];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < n; i += NT) {
+            double *p = Ab + (long long)i * W + bw;
+            *p = *p + damping;
+        }
+        __syncthreads();
+
+        // ---- the factorisation and the forward substitution, column by column on the window
+        const int rows0 = n < M ? n : M;
+        for (int i = tid >> 4; i < rows0; i += 16)
+            for (int k = tid & 15; k <= i; k += 16) win[tri_lower(i, k)] = Ab[(long long)i * W + (k - i + bw)];
+        for (int i = tid; i < rows0; i += NT) ring[i] = -gv[i];
+        int fail = -1, jm = 0;                           // jm = j mod M
+#pragma unroll 1
+        for (int j = 0; j < n; j++) {
+            __syncthreads();                             // the window holds rows j .. j + bw of the trailing block
+            const double d = win[tri_lower(jm, jm)], yj = ring[jm];
+            if (!(d > 0.0 && fin(d))) {                  // uniform
+                fail = j;
+                break;
+            }
+            const int m = n - 1 - j < bw ? n - 1 - j : bw, inew = j + bw + 1;
+            double vnew = 0.0, gnew = 0.0;               // row inew of A, fetched now, stored when column j is dead
+            if (inew < n && tid <= bw) vnew = Ab[(long long)inew * W + tid];
+            if (inew < n && tid == 0) gnew = gv[inew];
+            if (tid >= 1 && tid <= m) {
+                int a = jm + tid;
+                a = a >= M ? a - M : a;
+                const int at = a >= jm ? tri_lower(a, jm) : tri_lower(jm, a);
+                const double l = win[at] / d;
+                win[at] = l;
+                Ab[(long long)j * W + tid] = l;          // column j of L, where row j of A was
+                ring[a] = ring[a] - l * yj;
+            }
+            if (tid == 0) {
+                Ab[(long long)j * W] = d;
+                yv[j] = yj;
+            }
+            __syncthreads();
+            // thread (ty, tx) of 16 x 16 takes the entries (j + ri, j + rk), ri = 1 + ty + 16 p, rk = 1 + tx + 16 q <= ri; its L_kj
+            // stay in registers for the column, and a row's reads are issued before its writes
+            // (a slot's row base a (a + 1) / 2 is computed once per column or row: the entry's index is then an add and a select)
+            const int tx = tid & 15, ty = tid >> 4, qn = (m + 15) >> 4, jmb = tri_lower(jm, 0);
+            double lkq[TQ];
+            int akq[TQ], kbq[TQ];
+#pragma unroll
+            for (int q = 0; q < TQ; q++) {
+                if (q < qn) {                            // uniform
+                    const int rk = 1 + tx + 16 * q;
+                    int ak = jm + rk;
+                    ak = ak >= M ? ak - M : ak;
+                    akq[q] = ak;
+                    kbq[q] = tri_lower(ak, 0);
+                    lkq[q] = rk <= m ? win[ak >= jm ? kbq[q] + jm : jmb + ak] : 0.0;
+                }
+            }
+            for (int p = 0, ri = 1 + ty; ri <= m; p++, ri += 16) {      // row ri takes the column groups q <= p, the last one up to tx <= ty
+                int ai = jm + ri;
+                ai = ai >= M ? ai - M : ai;
+                const int ib = tri_lower(ai, 0);
+                const double li = win[ai >= jm ? ib + jm : jmb + ai];
+                double cur[TQ];
+                int at[TQ];
+#pragma unroll
+                for (int q = 0; q < TQ; q++) {
+                    if (q <= p && (q < p || tx <= ty)) {
+                        at[q] = ai >= akq[q] ? ib + akq[q] : kbq[q] + ai;
+                        cur[q] = win[at[q]];
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < TQ; q++)
+                    if (q <= p && (q < p || tx <= ty)) win[at[q]] = cur[q] - (li * lkq[q]) * d;
+            }
+            __syncthreads();
+            if (inew < n && tid <= bw) {                 // entry (inew, j + 1 + tid): inew's residue is jm
+                int ak = jm + 1 + tid;
+                ak = ak >= M ? ak - M : ak;
+                win[ak >= jm ? tri_lower(ak, jm) : tri_lower(jm, ak)] = vnew;
+                if (tid == 0) ring[jm] = -gnew;
+            }
+            jm = jm + 1 == M ? 0 : jm + 1;
+        }
+        if (fail >= 0) {
+            failed = fail;
+            first_failed = it == 0;
+            break;
+        }
+
+        // ---- backward, by rows, in the first wave alone: lane t holds delta_{i+1+t+64q} and L_{i+1+t+64q, i} (q < 4: bw < 256) in
+        // registers, the products are formed in parallel, every lane subtracts them in ascending k (a lane's product read by
+        // v_readlane; a slot past the row's end holds +0.0, and x - (+0.0) is x), the deltas move up one lane, delta_i enters at
+        // lane 0.  No barrier, no LDS; the next row's column of L is fetched while this one is summed.
+        if (tid < 64) {
+            double dl[4] = {0.0, 0.0, 0.0, 0.0}, lc[4] = {0.0, 0.0, 0.0, 0.0};
+            double ycur = yv[n - 1], dcur = Ab[(long long)(n - 1) * W];
+#pragma unroll 1
+            for (int i = n - 1; i >= 0; i--) {
+                const int cnt = n - 1 - i < bw ? n - 1 - i : bw;
+                double pr[4], ln[4] = {0.0, 0.0, 0.0, 0.0}, ynext = 0.0, dnext = 1.0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) pr[q] = tid + 64 * q < cnt ? lc[q] * dl[q] : 0.0;
+                if (i > 0) {
+                    const int cn = n - i < bw ? n - i : bw;
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+                        if (tid + 64 * q < cn) ln[q] = Ab[(long long)(i - 1) * W + 1 + tid + 64 * q];
+                    ynext = yv[i - 1];
+                    dnext = Ab[(long long)(i - 1) * W];
+                }
+                double v = ycur / dcur;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (64 * q < cnt) {                  // uniform
+#pragma unroll
+                        for (int t = 0; t < 64; t++) v = v - lane_value(pr[q], t);
+                    }
+                }
+                if (tid == 0) dv[i] = v;
+#pragma unroll
+                for (int q = 3; q >= 0; q--) {
+                    const double carry = q > 0 ? lane_value(dl[q - 1], 63) : v;
+                    const double up = __shfl_up(dl[q], 1);
+                    dl[q] = tid == 0 ? carry : up;
+                    lc[q] = ln[q];
+                }
+                ycur = ynext;
+                dcur = dnext;
+            }
+        }
+        __syncthreads();
+
+        // ---- the trial poses and their cost
+        for (int m = tid; m < n_nodes; m += NT) {
+            double cm[12], out[12];
+#pragma unroll
+            for (int k = 0; k < 12; k++) cm[k] = C[(long long)m * 12 + k];
+            if (m == 0) {
+#pragma unroll
+                for (int k = 0; k < 12; k++) out[k] = cm[k];
+            } else {
+                double delta[6];
+#pragma unroll
+                for (int k = 0; k < 6; k++) delta[k] = dv[6 * (m - 1) + k];
+                pose_update(cm, delta, out);
+            }
+#pragma unroll
+            for (int k = 0; k < 12; k++) trial[(long long)m * 12 + k] = out[k];
+        }
+        __syncthreads();
+        const double c_trial = graph_cost(g, trial, chi, nullptr, wsum, tid);
+        if (!(fin(c_trial) && c_trial < cur_cost)) break;      // uniform: every thread holds the same total
+        cur_cost = c_trial;
+        accepted++;
+        for (int k = tid; k < n_nodes * 12; k += NT) C[k] = trial[k];
+        __syncthreads();
+    }
+
+    graph_cost(g, C, chi, edge_chi2, wsum, tid);
+    if (tid == 0) {
+        status[gi] = accepted > 0 ? 0 : (first_failed ? 2 : 1);
+        iterations[gi] = accepted;
+        failed_row[gi] = failed;
+        cost_in[gi] = c_in;
+        cost_out[gi] = cur_cost;
+    }
+}
+
+__global__ __launch_bounds__(NT) void chain_kernel(const double *__restrict__ T, const double *__restrict__ C_start, int n_graphs,
+                                                   int n_nodes, double *__restrict__ C) {
+    const long long gi = (long long)blockIdx.x * NT + threadIdx.x;
+    if (gi >= n_graphs) return;
+    double cur[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (C_start) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) cur[k] = C_start[gi * 12 + k];
+    }
+    double *out = C + gi * n_nodes * 12;
+    const double *t = T + gi * (n_nodes - 1) * 12;
+#pragma unroll
+    for (int k = 0; k < 12; k++) out[k] = cur[k];
+#pragma unroll 1
+    for (int i = 0; i + 1 < n_nodes; i++) {
+        double ti[12], nxt[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) ti[k] = t[(long long)i * 12 + k];
+        compose(ti, cur, nxt);
+#pragma unroll
+        for (int k = 0; k < 12; k++) out[(long long)(i + 1) * 12 + k] = cur[k] = nxt[k];
+    }
+}
+
+inline long long workspace_words(int n_nodes, int band) {      // per graph
+    const long long n = 6LL * (n_nodes - 1), W = 6LL * band + 6;
+    return n * W + 3 * n + 12LL * n_nodes + (long long)NT * STAGE;
+}
+
+inline int graph_shape(int n_graphs, int n_nodes, int band) {
+    if (n_graphs <= 0 || n_nodes <= 0 || band <= 0) return SSLAM_E_INVALID;
+    if (band > SSLG_MAX_BAND || n_nodes > SSLG_MAX_NODES || n_graphs > SSLG_MAX_GRAPHS) return SSLAM_E_UNSUPPORTED;
+    return SSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" int sslg_version(void) { return 100; }
+extern "C" const char *sslg_arch(void) { return "gfx950"; }
+extern "C" long long sslg_launch_count(void) { return __atomic_load_n(&g_launches, __ATOMIC_RELAXED); }
+
+extern "C" int sslg_chain_poses(const double *T, const double *C_start, int n_graphs, int n_nodes, double *C, void *stream) {
+    if (!C || n_graphs <= 0 || n_nodes <= 0 || (!T && n_nodes > 1) || C == C_start) return SSLAM_E_INVALID;
+    if (misaligned(T, 8) || misaligned(C_start, 8) || misaligned(C, 8)) return SSLAM_E_INVALID;
+    if (n_graphs > 0x7fffffff / NT || n_nodes > SSLG_MAX_NODES) return SSLAM_E_UNSUPPORTED;
+    hipLaunchKernelGGL(chain_kernel, dim3((unsigned)((n_graphs + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, T, C_start, n_graphs,
+                       n_nodes, C);
+    if (hipGetLastError() != hipSuccess) return SSLAM_E_LAUNCH;
+    __atomic_fetch_add(&g_launches, 1, __ATOMIC_RELAXED);      // a launch that failed is not counted
+    return SSLAM_OK;
+}
+
+extern "C" size_t sslg_pose_graph_workspace_bytes(int n_graphs, int n_nodes, int band) {
+    if (graph_shape(n_graphs, n_nodes, band) != SSLAM_OK) return 0;
+    return (size_t)n_graphs * (size_t)workspace_words(n_nodes, band) * sizeof(double);
+}
+
+extern "C" int sslg_pose_graph(const int32_t *edge_first, const int32_t *edge_second, const double *edge_T, const double *edge_info,
+                               int n_graphs, int n_nodes, int n_edges, const double *C_in, int band, double huber_chi, double damping,
+                               int n_iter, void *workspace, double *C, int32_t *status, int32_t *iterations, int32_t *used_edges,
+                               int32_t *skipped_edges, int32_t *failed_row, double *cost_in, double *cost, double *edge_chi2,
+                               void *stream) {
+    if (!edge_first || !edge_second || !edge_T || !edge_info || !C_in || !workspace || !C || !status || !iterations || !used_edges ||
+        !skipped_edges || !failed_row || !cost_in || !cost || !edge_chi2)
+        return SSLAM_E_INVALID;
+    if (n_edges <= 0 || graph_shape(n_graphs, n_nodes, band) == SSLAM_E_INVALID) return SSLAM_E_INVALID;
+    if (!finite_positive(huber_chi) || !finite_nonnegative(damping) || n_iter < 0 || n_iter > SSLG_GRAPH_MAX_ITER || C == C_in)
+        return SSLAM_E_INVALID;
+    for (const void *p : {(const void *)edge_T, (const void *)edge_info, (const void *)C_in, (const void *)workspace, (const void *)C,
+                          (const void *)cost_in, (const void *)cost, (const void *)edge_chi2})
+        if (misaligned(p, 8)) return SSLAM_E_INVALID;
+    for (const void *p : {(const void *)edge_first, (const void *)edge_second, (const void *)status, (const void *)iterations,
+                          (const void *)used_edges, (const void *)skipped_edges, (const void *)failed_row})
+        if (misaligned(p, 4)) return SSLAM_E_INVALID;
+    if (graph_shape(n_graphs, n_nodes, band) != SSLAM_OK || n_edges > SSLG_MAX_EDGES) return SSLAM_E_UNSUPPORTED;
+    const int M = 6 * band + 6;
+    const size_t lds = ((size_t)M * (M + 1) / 2 + M) * sizeof(double);      // the window and the ring: 159 192 bytes at band 32
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(pose_graph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return SSLAM_E_LAUNCH;
+    hipLaunchKernelGGL(pose_graph_kernel, dim3((unsigned)n_graphs), dim3(NT), lds, (hipStream_t)stream, (const int *)edge_first,
+                       (const int *)edge_second, edge_T, edge_info, n_nodes, n_edges, C_in, band, huber_chi, damping, n_iter,
+                       (double *)workspace, workspace_words(n_nodes, band), C, (int *)status, (int *)iterations, (int *)used_edges,
+                       (int *)skipped_edges, (int *)failed_row, cost_in, cost, edge_chi2);
+    if (hipGetLastError() != hipSuccess) return SSLAM_E_LAUNCH;
+    __atomic_fetch_add(&g_launches, 1, __ATOMIC_RELAXED);      // a launch that failed is not counted
+    return SSLAM_OK;
+}

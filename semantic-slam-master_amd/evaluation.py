@@ -8,7 +8,8 @@ keys, running on the HIP kernels sslam_pose_nn_pairs / sslam_match_score_pairs (
 Beside them, with the same return conventions, the two functions of the depth ground truth (csrc/evaluate.hip):
 compute_repeatability_depth and compute_ground_truth_matches_depth - and, beside matching.py's matchers, the step that follows
 them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip), and refine_relative_pose, that
-motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip).  And, between the selector and all
+motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip), and optimize_pose_graph, the
+poses of a whole sequence from those motions and their information matrices (csrc_graph/pose_graph.hip).  And, between the selector and all
 of them, refine_keypoints_subcell: the selected cells moved to their sub-cell saliency peaks (csrc_ext/subcell.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
@@ -196,6 +197,37 @@ def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, thre
     info = np.zeros((6, 6))
     info[iu], info[iu[1], iu[0]] = tri, tri
     return T4, out[7][0].cpu().numpy() == 1, info
+
+
+def optimize_pose_graph(first, second, T, info, n_nodes: int, C_init=None, band=None, huber_chi: float = 4.0, damping: float = 0.0,
+                        iterations: int = 8):
+    """The step behind refine_relative_pose: the poses of a sequence from the relative poses of its pairs and their information
+    matrices (sslg_pose_graph, include/sslam_graph.h).  first, second: the frames a < b of every pair (integer sequences; -1 in
+    first: a pair to leave out); T (E, 4, 4) or (E, 3, 4): camera a -> camera b, as refine_relative_pose returns it; info
+    (E, 6, 6): that function's information matrices; C_init (n_nodes, 4, 4) or (n_nodes, 3, 4) world -> camera, or None: the chain
+    of the pairs (i, i + 1), each of which must then be listed; band: the most b - a of a pair that is used, the largest listed
+    if None.  numpy in, numpy out; one graph.
+    Returns (C (n_nodes, 4, 4) float64 world -> camera - C_init when no step lowers the cost -, status (0 optimised, 1 no step
+    accepted, 2 a node no pair determines, 3 not attempted), chi2 (E,) float64: every used pair's squared residual at C)."""
+    first, second = [int(v) for v in np.asarray(first).reshape(-1)], [int(v) for v in np.asarray(second).reshape(-1)]
+    T, info = np.asarray(T, dtype=np.float64), np.asarray(info, dtype=np.float64)
+    if T.ndim != 3 or tuple(T.shape[1:]) not in ((4, 4), (3, 4)) or len(T) != len(first) or len(first) != len(second) or not first:
+        raise ValueError(f"T (E, 4, 4) or (E, 3, 4) for E = {len(first)} >= 1 pairs expected, got {T.shape}")
+    if info.shape != (len(first), 6, 6):
+        raise ValueError(f"info ({len(first)}, 6, 6) expected, got {info.shape}")
+    if C_init is not None:
+        C_init = np.asarray(C_init, dtype=np.float64)
+        if C_init.ndim != 3 or tuple(C_init.shape[1:]) not in ((4, 4), (3, 4)) or len(C_init) != n_nodes:
+            raise ValueError(f"C_init ({n_nodes}, 4, 4) or ({n_nodes}, 3, 4) expected, got {C_init.shape}")
+        C_init = _dev(np.ascontiguousarray(C_init[:, :3]).reshape(n_nodes, 12), torch.float64)
+    from sslam_amd.pipeline import SequencePipeline
+    iu = np.triu_indices(6)
+    out = SequencePipeline.optimize_pose_graph(first, second, _dev(np.ascontiguousarray(T[:, :3]).reshape(-1, 12), torch.float64),
+                                               _dev(np.ascontiguousarray(info[:, iu[0], iu[1]]), torch.float64), n_nodes, C_init, band,
+                                               huber_chi, damping, iterations)
+    C = np.tile(np.eye(4), (n_nodes, 1, 1))
+    C[:, :3] = out["C"].cpu().numpy().reshape(n_nodes, 3, 4)
+    return C, int(out["status"].cpu()), out["edge_chi2"].cpu().numpy()
 
 
 def refine_keypoints_subcell(saliency, keypoints):

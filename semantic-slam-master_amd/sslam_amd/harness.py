@@ -455,6 +455,11 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
             raise ValueError('evaluate["refine"] is a flag, True or False')
         if with_refine and not with_odometry:
             raise ValueError('evaluate["refine"] refines the odometry\'s poses: it needs "odometry": True')
+        with_graph = evaluate.pop("graph", False)
+        if not isinstance(with_graph, bool):
+            raise ValueError('evaluate["graph"] is a flag, True or False')
+        if with_graph and not with_refine:
+            raise ValueError('evaluate["graph"] optimises over the refined poses\' information matrices: it needs "refine": True')
         if not (with_depth or with_odometry) and "camera" in evaluate:
             raise ValueError('evaluate["camera"] describes the depth images: it needs "depth": True')
         if rule is None:
@@ -528,4 +533,9 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
                                                            threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth, refine=with_refine,
                                                            subcell=subcell)
                                for s in seq.spacings if s in res and evaluation.pair_list(n, s, int(evaluate.get("num_pairs", 50)))}
+            if with_graph:                                   # every spacing's refined poses as edges of one graph (odometry_result_graph)
+                res["odometry"]["graph"] = odometry.odometry_result_graph(
+                    pipe, res, camera=depth_camera, poses=tum.poses, spacings=tuple(s for s in seq.spacings if s in res),
+                    num_pairs=int(evaluate.get("num_pairs", 50)), threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth,
+                    subcell=subcell)["graph"]
     return res

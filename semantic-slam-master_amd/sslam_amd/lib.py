@@ -1467,3 +1467,167 @@ def subcell_keypoints(sal, idx, out=None):
     xy, px, fl = out if out is not None else (torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in SUBCELL_KEYS)
     _run("subcell_keypoints", ext().sslx_subcell_keypoints, (sal, idx, xy, px, fl), _dp(sal), n, g, _dp(idx), k, _dp(xy), _dp(px), _dp(fl))
     return xy, px, fl
+
+
+# ---------------------------------------------------------------------------------------- libsslam_graph.so (include/sslam_graph.h)
+# The third library: entries with the prefix sslg_, built from csrc_graph/ with csrc_ext/'s flags, loaded and refused like the others.
+CSRC_GRAPH = os.path.join(_PKG, "csrc_graph")
+GRAPH_SO_PATH = os.path.join(CSRC_GRAPH, "libsslam_graph.so")
+GRAPH_EXPORTS = ["sslg_version", "sslg_arch", "sslg_launch_count", "sslg_chain_poses", "sslg_pose_graph_workspace_bytes", "sslg_pose_graph"]
+GRAPH_MAX_BAND, GRAPH_MAX_NODES, GRAPH_MAX_EDGES, GRAPH_MAX_GRAPHS, GRAPH_MAX_ITER = 32, 4096, 1048576, 65535, 16
+POSE_GRAPH_KEYS = ("C", "status", "iterations", "used_edges", "skipped_edges", "failed_row", "cost_in", "cost", "edge_chi2")
+# status: a step was accepted / no step accepted / a failed pivot at the first step / not attempted
+GRAPH_OK, GRAPH_NO_STEP, GRAPH_SINGULAR, GRAPH_NOT_ATTEMPTED = 0, 1, 2, 3
+
+_graph = None
+
+
+def graph_build(force: bool = False) -> str:
+    """Compile libsslam_graph.so for gfx950 in-tree, as build() compiles the first library."""
+    inc = os.path.join(os.path.dirname(_PKG), "include")
+    srcs = [os.path.join(CSRC_GRAPH, f) for f in os.listdir(CSRC_GRAPH) if f.endswith((".hip", ".h"))]
+    srcs += [os.path.join(inc, "sslam_graph.h"), os.path.join(inc, "sslam_hip.h")]
+    stale = (not os.path.exists(GRAPH_SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(GRAPH_SO_PATH) for s in srcs)
+    if force or stale:
+        subprocess.check_call(["make", "-C", CSRC_GRAPH, "-s", "-j4"])
+    return GRAPH_SO_PATH
+
+
+def graph():
+    """Load libsslam_graph.so; raises if it has not been built (no silent fallback)."""
+    global _graph
+    if _graph is None:
+        if not os.path.exists(GRAPH_SO_PATH):
+            raise SslamHipError(f"{GRAPH_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                                f"(or `make -C {CSRC_GRAPH}`); this package has no non-HIP execution path")
+        L = C.CDLL(GRAPH_SO_PATH)
+        L.sslg_arch.restype = C.c_char_p
+        L.sslg_launch_count.restype = C.c_longlong
+        L.sslg_pose_graph_workspace_bytes.restype = C.c_size_t
+        p, i, d = C.c_void_p, C.c_int, C.c_double
+        L.sslg_pose_graph_workspace_bytes.argtypes = [i, i, i]
+        L.sslg_chain_poses.argtypes = [p, p, i, i, p, p]
+        L.sslg_pose_graph.argtypes = [p, p, p, p, i, i, i, p, i, d, d, i] + [p] * 11
+        _graph = L
+    return _graph
+
+
+def graph_launch_count() -> int:
+    return int(graph().sslg_launch_count())
+
+
+def check_band(band) -> int:
+    """The most b - a of a used edge: an int >= 1, else ValueError; above GRAPH_MAX_BAND: SslamHipError - before any device work."""
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or int(band) < 1:
+        raise ValueError(f"band must be an int >= 1, got {band!r}")
+    if int(band) > GRAPH_MAX_BAND:
+        raise SslamHipError(f"pose_graph: {_ERR[E_UNSUPPORTED]} (band <= {GRAPH_MAX_BAND}, got {band})")
+    return int(band)
+
+
+def check_damping(damping) -> float:
+    """What is added to the diagonal of the normal equations: a finite number >= 0, else ValueError - before any device work."""
+    if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) or not (float(damping) >= 0.0) or \
+            not np.isfinite(float(damping)):
+        raise ValueError(f"damping must be a finite number >= 0, got {damping!r}")
+    return float(damping)
+
+
+def check_graph_iterations(iterations) -> int:
+    """The most Gauss-Newton steps of the pose graph: an int in 0 .. GRAPH_MAX_ITER, else ValueError - before any device work."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= GRAPH_MAX_ITER:
+        raise ValueError(f"iterations must be an int in [0, {GRAPH_MAX_ITER}], got {iterations!r}")
+    return int(iterations)
+
+
+def _graph_rows(name, t, lead, tail, dtype):
+    """t: a contiguous tensor of `dtype` shaped lead + tail (a single graph may leave the graph axis out) -> it with the graph axis."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{name} must be a {dtype} tensor")
+    if lead is not None and t.dim() == len(lead) + len(tail) - 1 and lead[0] == 1:
+        t = t[None]
+    want = None if lead is None else tuple(lead) + tuple(tail)
+    if (want is not None and tuple(t.shape) != want) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape {want}, got {tuple(t.shape)}")
+    return t
+
+
+def pose_graph_shapes(n_graphs: int, n_nodes: int, n_edges: int) -> dict:
+    """name -> (shape, dtype) of the outputs of pose_graph."""
+    one, real = ((n_graphs,), torch.int32), ((n_graphs,), torch.float64)
+    return {"C": ((n_graphs, n_nodes, 12), torch.float64), "status": one, "iterations": one, "used_edges": one, "skipped_edges": one,
+            "failed_row": one, "cost_in": real, "cost": real, "edge_chi2": ((n_graphs, n_edges), torch.float64)}
+
+
+def pose_graph_workspace_bytes(n_graphs: int, n_nodes: int, band: int) -> int:
+    """sslg_pose_graph_workspace_bytes, restated: per graph n * (6 band + 6) + 3 n + 12 n_nodes + 256 * 90 float64 words with
+    n = 6 (n_nodes - 1).  Needs no library."""
+    n = 6 * (n_nodes - 1)
+    return 8 * n_graphs * (n * (6 * band + 6) + 3 * n + 12 * n_nodes + 256 * 90)
+
+
+def _check_graph_sizes(what, n_graphs, n_nodes, n_edges=1):
+    if n_graphs < 1 or n_nodes < 1 or n_edges < 1:
+        raise ValueError(f"{what}: at least one graph, node and edge slot expected, got {n_graphs}, {n_nodes}, {n_edges}")
+    if n_graphs > GRAPH_MAX_GRAPHS or n_nodes > GRAPH_MAX_NODES or n_edges > GRAPH_MAX_EDGES:
+        raise SslamHipError(f"{what}: {_ERR[E_UNSUPPORTED]} (n_graphs <= {GRAPH_MAX_GRAPHS}, n_nodes <= {GRAPH_MAX_NODES}, n_edges <= "
+                            f"{GRAPH_MAX_EDGES}; got {n_graphs}, {n_nodes}, {n_edges})")
+
+
+def chain_poses(T, n_nodes=None, start=None, out=None):
+    """sslg_chain_poses: T (n_graphs, n_nodes - 1, 12) float64 (or (n_nodes - 1, 12) for one chain), the transforms camera i ->
+    camera i + 1; start (n_graphs, 12) or None ([I | 0]).  Returns C (n_graphs, n_nodes, 12): C_0 = start, C_{i+1} = T_i o C_i,
+    world -> camera.  n_nodes: given to chain only the first n_nodes - 1 rows' worth (T must then be exactly that long).  One launch."""
+    if not isinstance(T, torch.Tensor) or T.dtype != torch.float64 or T.dim() not in (2, 3) or int(T.shape[-1]) != 12 or not T.is_contiguous():
+        raise ValueError("T must be a contiguous float64 tensor of shape (n_graphs, n_nodes - 1, 12) or (n_nodes - 1, 12)")
+    T3 = T[None] if T.dim() == 2 else T
+    n_graphs, nn = int(T3.shape[0]), int(T3.shape[1]) + 1
+    if n_nodes is not None and int(n_nodes) != nn:
+        raise ValueError(f"T holds {nn - 1} transforms, n_nodes = {n_nodes} needs {int(n_nodes) - 1}")
+    _check_graph_sizes("chain_poses", n_graphs, nn)
+    if start is not None:
+        start = _graph_rows("start", start, (n_graphs,), (12,), torch.float64)
+    if out is not None:
+        out = _graph_rows("out", out, (n_graphs,), (nn, 12), torch.float64)
+    dev = common_device(T3, start, out)
+    Cc = torch.empty((n_graphs, nn, 12), dtype=torch.float64, device=dev) if out is None else out
+    _run("chain_poses", graph().sslg_chain_poses, (T3, start, Cc), _dp(T3) if nn > 1 else None, _dp(start), n_graphs, nn, _dp(Cc))
+    return Cc
+
+
+def pose_graph(first, second, T, info, C_in, band, huber_chi=4.0, damping=0.0, iterations=8, out=None, workspace=None):
+    """sslg_pose_graph: first, second (n_graphs, n_edges) int32 (-1 in first: an absent slot), T (n_graphs, n_edges, 12) and info
+    (n_graphs, n_edges, 21) float64 as pose_refine_pairs writes them, C_in (n_graphs, n_nodes, 12) float64 world -> camera (one
+    graph may leave the graph axis out of all five).  band: the most b - a of a used edge; huber_chi: finite > 0; damping: finite
+    >= 0; iterations 0 .. GRAPH_MAX_ITER.  Returns POSE_GRAPH_KEYS' tensors (include/sslam_graph.h states them), always with the
+    graph axis.  out: optional tensors of pose_graph_shapes (C must not be C_in); workspace: optional uint8 tensor of at least
+    pose_graph_workspace_bytes.  One launch, no host read; everything is judged before the library is loaded."""
+    b, chi, damp, n_iter = check_band(band), check_positive("huber_chi", huber_chi), check_damping(damping), check_graph_iterations(iterations)
+    if not isinstance(C_in, torch.Tensor) or C_in.dtype != torch.float64 or C_in.dim() not in (2, 3) or int(C_in.shape[-1]) != 12 or \
+            not C_in.is_contiguous():
+        raise ValueError("C_in must be a contiguous float64 tensor of shape (n_graphs, n_nodes, 12) or (n_nodes, 12)")
+    C3 = C_in[None] if C_in.dim() == 2 else C_in
+    n_graphs, n_nodes = int(C3.shape[0]), int(C3.shape[1])
+    if not isinstance(first, torch.Tensor) or first.dim() not in (1, 2):
+        raise ValueError("first must be an int32 tensor of shape (n_graphs, n_edges) or (n_edges,)")
+    n_edges = int(first.shape[-1])
+    _check_graph_sizes("pose_graph", n_graphs, n_nodes, n_edges)
+    lead = (n_graphs, n_edges)
+    first = _graph_rows("first", first, lead, (), torch.int32)
+    second = _graph_rows("second", second, lead, (), torch.int32)
+    T = _graph_rows("T", T, lead, (12,), torch.float64)
+    info = _graph_rows("info", info, lead, (21,), torch.float64)
+    shapes = pose_graph_shapes(n_graphs, n_nodes, n_edges)
+    o = None if out is None else _outputs(shapes, POSE_GRAPH_KEYS, out)
+    if o is not None and o[0].data_ptr() == C3.data_ptr():
+        raise ValueError("out `C` must not be C_in")
+    need = pose_graph_workspace_bytes(n_graphs, n_nodes, b)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
+                                  workspace.numel() < need or not workspace.is_contiguous()):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    dev = common_device(first, second, T, info, C3, workspace, *(o or ()))
+    o = _outputs(shapes, POSE_GRAPH_KEYS, None, dev) if o is None else o
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _run("pose_graph", graph().sslg_pose_graph, (first, second, T, info, C3, ws, *o), _dp(first), _dp(second), _dp(T), _dp(info),
+         n_graphs, n_nodes, n_edges, _dp(C3), b, C.c_double(chi), C.c_double(damp), n_iter, _dp(ws), *(_dp(x) for x in o))
+    return tuple(o)

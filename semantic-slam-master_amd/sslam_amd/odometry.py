@@ -194,19 +194,23 @@ def _check_refine(refine, threshold, huber, iterations) -> None:
         lib.check_iterations(iterations)
 
 
-def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine=False,
-              huber=None, iterations=5) -> dict:
-    """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it), ONE host read-back of (P, 18)
-    float64 ((P, 58) with refine), the host-side figures."""
+def _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations):
+    """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it) -> ((P, 18) float64 device tensor -
+    (P, 58) with refine -, refine_poses' dictionary or None).  No host read."""
     first, second = [a for a, _ in pairs], [b for _, b in pairs]
     est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
     cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
            [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
+    ref = None
     if refine:
         ref = pipe.refine_poses(keypoints_pixel, kp_depth, first, second, matches, camera, est, threshold, huber, iterations)
         cols += [ref["T"]] + [ref[key].to(torch.float64)[:, None] for key in _REFINE_INT] + [ref[key][:, None] for key in _REFINE_REAL] + \
                 [ref["info"]]
-    host = torch.cat(cols, dim=1).cpu().numpy()             # integers up to 4096: exact in float64
+    return torch.cat(cols, dim=1), ref                      # integers up to 4096: exact in float64
+
+
+def _unpack(host, pairs, poses, spacing, refine) -> dict:
+    """The host-side figures from the rows _launch packed, read back."""
     T = _as44(host[:, :12])
     out = {"pairs": list(pairs), "T": T}
     out.update({key: host[:, 12 + i].astype(np.int64) for i, key in enumerate(_INT_KEYS)})
@@ -228,6 +232,14 @@ def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, sp
     out["refine"] = {"status": got["status"], "iterations": got["iterations"], "selected_count": got["selected_count"],
                      "cost_in": r[:, 16].copy(), "cost": r[:, 17].copy(), "info": info_matrix(r[:, 19:40])}
     return out
+
+
+def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine=False,
+              huber=None, iterations=5) -> dict:
+    """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it), ONE host read-back of (P, 18)
+    float64 ((P, 58) with refine), the host-side figures."""
+    packed, _ = _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations)
+    return _unpack(packed.cpu().numpy(), pairs, poses, spacing, refine)
 
 
 def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None, rule=None,
@@ -291,3 +303,117 @@ def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spa
     if kp_depth is None:
         kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
     return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine, huber, iterations)
+
+
+# ------------------------------------------------------------------------------------------------ the pose graph over all spacings
+GRAPH_SPACINGS = (1, 5, 10, 15, 20)          # the reference's own set
+_GRAPH_INT = ("status", "iterations", "used_edges", "skipped_edges", "failed_row")
+
+
+def _check_graph(spacings, n_frames, num_pairs, band, huber_chi, damping, graph_iterations) -> tuple:
+    """What the graph's arguments can be refused for, before any device work -> (the spacings that hold a pair, their pair lists,
+    the number of frames they name, the band)."""
+    spacings = tuple(spacings)
+    if not spacings or len(set(spacings)) != len(spacings) or 1 not in spacings:
+        raise ValueError(f"spacings must be distinct and hold 1 (the chain is the initial guess), got {spacings!r}")
+    lists = {s: consecutive_pairs(n_frames, s, num_pairs) for s in spacings}
+    lists = {s: p for s, p in lists.items() if p}
+    if 1 not in lists:
+        raise ValueError(f"{n_frames} frames hold no pair at spacing 1")
+    n = lists[1][-1][1] + 1                                  # the frames the chain reaches: the graph's nodes
+    lists = {s: [(a, b) for a, b in p if b < n] for s, p in lists.items()}
+    lists = {s: p for s, p in lists.items() if p}
+    band = lib.check_band(max(lists) if band is None else band)
+    lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(graph_iterations)
+    if n > lib.GRAPH_MAX_NODES:
+        raise lib.SslamHipError(f"odometry_graph: {n} frames, the pose graph takes {lib.GRAPH_MAX_NODES}")
+    return tuple(lists), lists, n, band
+
+
+def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
+           graph_iterations) -> dict:
+    """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back."""
+    pairs = [pr for s in lists for pr in lists[s]]
+    packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
+    start = None
+    if poses is not None:                                    # the chain of odometry() starts at poses[0]: so does this one
+        c0 = np.linalg.inv(np.asarray(poses, dtype=np.float64)[0])[:3].reshape(1, 12)
+        start = torch.from_numpy(np.ascontiguousarray(c0)).to(packed.device)
+    n1 = len(lists[1])
+    C_init = lib.chain_poses(ref["T"][:n1].contiguous(), n, start=start)[0]
+    g = pipe.optimize_pose_graph([a for a, _ in pairs], [b for _, b in pairs], ref, ref, n, C_init=C_init, band=band, huber_chi=huber_chi,
+                                 damping=damping, iterations=graph_iterations)
+    flat = torch.cat([packed.reshape(-1), g["C"].reshape(-1)] + [g[key].to(torch.float64).reshape(1) for key in _GRAPH_INT] +
+                     [g["cost_in"].reshape(1), g["cost"].reshape(1), g["edge_chi2"]]).cpu().numpy()          # the ONE read-back
+    P, w = len(pairs), int(packed.shape[1])
+    host, rest = flat[:P * w].reshape(P, w), flat[P * w:]
+    out, at = {}, 0
+    for s in lists:
+        out[s] = _unpack(host[at:at + len(lists[s])], lists[s], poses, s, True)
+        at += len(lists[s])
+    C = rest[:12 * n].reshape(n, 3, 4)
+    C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
+    graph = {"trajectory": np.stack([np.linalg.inv(c) for c in C44]), "pairs": pairs}
+    graph.update({key: int(rest[12 * n + i]) for i, key in enumerate(_GRAPH_INT)})
+    graph["cost_in"], graph["cost"] = float(rest[12 * n + 5]), float(rest[12 * n + 6])
+    graph["edge_chi2"] = rest[12 * n + 7:].copy()
+    if poses is not None:
+        graph["ate"] = ate_summary(graph["trajectory"], np.asarray(poses, dtype=np.float64)[:n])
+        graph["ate_chain"] = out[1]["ate"]
+    out["graph"] = graph
+    return out
+
+
+def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, spacings=GRAPH_SPACINGS, num_pairs=None, rule=None,
+                   threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, huber=None, iterations: int = 5, *,
+                   subcell=None, band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8) -> dict:
+    """odometry(refine=True) at every spacing of `spacings` at once, and the pose graph over all of their edges
+    (SequencePipeline.optimize_pose_graph; csrc_graph/pose_graph.hip): the frames are extracted once, the pairs of all spacings
+    matched in one match_pairs call, ONE RANSAC and ONE refinement launch run over the concatenated pair list, the refined
+    spacing-1 poses are chained on the device (the initial guess), the graph optimised - every refined pose an edge weighted by its
+    own information matrix, a pair whose refinement was not attempted left out - and everything read back ONCE.
+    images_u8 .. iterations, subcell: as odometry() takes them (num_pairs: per spacing; the graph's nodes are the frames the
+    spacing-1 pairs reach, and pairs that leave them are dropped).  band: the most b - a of a used edge, the largest spacing if
+    None; huber_chi, damping, graph_iterations: include/sslam_graph.h.
+    Returns {spacing: what odometry(spacing=spacing, refine=True) returns, ..., 'graph': {'trajectory' (N, 4, 4) camera-to-world,
+    'pairs', 'status', 'iterations', 'used_edges', 'skipped_edges', 'failed_row', 'cost_in', 'cost', 'edge_chi2' (one per listed
+    pair); with poses also 'ate' (ate_summary of the graph's trajectory) and 'ate_chain' (that of the spacing-1 chain)}}.
+    Nobody has measured this on real RGB-D data: no real sequence was at hand when this was written."""
+    check_subcell(subcell)
+    src = tokens if tokens is not None else images_u8
+    if src is None:
+        raise ValueError("images_u8 or tokens= required")
+    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
+    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
+    _check_refine(True, threshold, huber, iterations)
+    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
+    ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
+    kp = geometry_bank(ex, subcell)
+    kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
+    pairs = [pr for s in lists for pr in lists[s]]
+    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
+    return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
+                  damping, graph_iterations)
+
+
+def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=None, spacings=None, num_pairs=None, threshold: float = 3.0,
+                          hypotheses: int = 256, seed: int = 0, *, kp_depth=None, huber=None, iterations: int = 5, subcell=None, band=None,
+                          huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8) -> dict:
+    """odometry_graph() for a StreamingSequence.result() / run_frames / run_directory result: nothing is extracted or matched again.
+    spacings: those of the result if None.  depth= / kp_depth=, and everything else: as odometry_result() and odometry_graph()
+    take them."""
+    if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
+        raise ValueError("a StreamingSequence / run_directory result expected")
+    kp = geometry_bank(result["frames"], subcell)
+    if spacings is None:
+        spacings = tuple(sorted(k for k in result if isinstance(k, (int, np.integer)) and not isinstance(k, bool)))
+    if any(s not in result for s in spacings):
+        raise ValueError(f"the result holds no pairs at every spacing of {tuple(spacings)!r}")
+    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
+    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
+    _check_refine(True, threshold, huber, iterations)
+    matches = {key: torch.cat([result[s][key][:len(lists[s])] for s in lists]) for key in ("matches", "match_count")}
+    if kp_depth is None:
+        kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
+    return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
+                  damping, graph_iterations)

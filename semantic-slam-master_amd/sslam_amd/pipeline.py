@@ -868,6 +868,73 @@ class SequencePipeline:
                                   sx, sy, t, hub, n_iter, out=tuple(res[key][a:b] for key in lib.POSE_REFINE_KEYS))
         return res
 
+    @staticmethod
+    def optimize_pose_graph(first, second, T, info, n_nodes: int, C_init=None, band: int | None = None, huber_chi: float = 4.0,
+                            damping: float = 0.0, iterations: int = 8) -> dict:
+        """The pose graph over the relative poses of one sequence (csrc_graph/pose_graph.hip): world -> camera poses of n_nodes
+        frames, frame 0 the anchor, minimising the Huber cost of the edges' residuals under their information matrices.
+        first / second: the frames a < b of every edge, 1-D int32 device tensors or host sequences (-1 in first: an absent slot).
+        T: (E, 12) float64 device tensor, camera a -> camera b, or the dictionary estimate_poses() / refine_poses() returned for
+        these pairs; info: (E, 21) float64 device tensor, or refine_poses()' dictionary - the edges whose refinement status is 3
+        (not attempted: their info is zero) then become absent, on the device, without a read-back.
+        C_init: (n_nodes, 12) float64 world -> camera, or None: the chain of the edges (i, i + 1) (sslg_chain_poses) - with host
+        lists they are looked up (each must be listed), with device lists they must be the first n_nodes - 1 slots, in order.
+        band: the most b - a of a used edge; None: the largest b - a of the host lists (device lists need it given).
+        huber_chi, damping, iterations: include/sslam_graph.h.  Returns device tensors: C (n_nodes, 12) float64, status,
+        iterations, used_edges, skipped_edges, failed_row () int32, cost_in, cost () float64, edge_chi2 (E,) float64.  Two
+        launches at most, no host read.  It reads nothing of the pipeline (a static method: the drop-in calls it without one)."""
+        if isinstance(n_nodes, bool) or not isinstance(n_nodes, (int, np.integer)) or n_nodes < 1:
+            raise ValueError(f"n_nodes must be an integer >= 1, got {n_nodes!r}")
+        n_nodes = int(n_nodes)
+        status = info.get("status") if isinstance(info, dict) else None
+        t_rows = T["T"] if isinstance(T, dict) and "T" in T else T
+        info_rows = info["info"] if isinstance(info, dict) and "info" in info else info
+        host = not isinstance(first, torch.Tensor) and not isinstance(second, torch.Tensor)
+        if isinstance(first, torch.Tensor) != isinstance(second, torch.Tensor):
+            raise ValueError("first and second must both be device tensors or both host sequences")
+        if host:
+            fa, fb = [int(v) for v in first], [int(v) for v in second]
+            if len(fa) != len(fb) or not fa:
+                raise ValueError("first and second must name the same number of edges, at least one")
+            if band is None:
+                band = max([b - a for a, b in zip(fa, fb) if 0 <= a < b] or [1])
+        elif band is None:
+            raise ValueError("band= is required with device edge lists: the largest b - a is not read back")
+        band = lib.check_band(band)
+        lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
+        for name, t, cols in (("T", t_rows, 12), ("info", info_rows, 21)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or int(t.shape[1]) != cols or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float64 device tensor of shape (E, {cols}) or a dictionary holding one")
+        n_edges = int(t_rows.shape[0])
+        if int(info_rows.shape[0]) != n_edges or (host and len(fa) != n_edges):
+            raise ValueError(f"{n_edges} transforms for {int(info_rows.shape[0])} information matrices and {len(fa) if host else '?'} edges")
+        chain_rows = None
+        if C_init is None and n_nodes > 1:
+            if host:
+                where = {(a, b): e for e, (a, b) in reversed(list(enumerate(zip(fa, fb))))}
+                missing = [i for i in range(n_nodes - 1) if (i, i + 1) not in where]
+                if missing:
+                    raise ValueError(f"C_init=None chains the edges (i, i + 1): ({missing[0]}, {missing[0] + 1}) is not listed")
+                chain_rows = [where[(i, i + 1)] for i in range(n_nodes - 1)]
+            elif n_edges < n_nodes - 1:
+                raise ValueError(f"C_init=None chains the first {n_nodes - 1} slots: only {n_edges} are listed")
+        dev = t_rows.device
+        if host:
+            first = torch.tensor(fa, dtype=torch.int32, device=dev)
+            second = torch.tensor(fb, dtype=torch.int32, device=dev)
+        if status is not None:
+            first = torch.where(status == lib.REFINE_NOT_ATTEMPTED, torch.full_like(first, -1), first)
+        if C_init is None:
+            if n_nodes == 1:
+                rows = t_rows[:0]
+            elif chain_rows is None or chain_rows == list(range(n_nodes - 1)):
+                rows = t_rows[:n_nodes - 1]
+            else:
+                rows = t_rows.index_select(0, torch.tensor(chain_rows, dtype=torch.int64, device=dev))
+            C_init = lib.chain_poses(rows.contiguous(), n_nodes)[0]
+        res = lib.pose_graph(first.contiguous(), second, t_rows, info_rows, C_init, band, huber_chi, damping, iterations)
+        return {key: t[0] for key, t in zip(lib.POSE_GRAPH_KEYS, res)}
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
