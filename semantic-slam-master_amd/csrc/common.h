@@ -36,6 +36,7 @@ enum sslam_knob_id {
     KNOB_VIT_F32_NO_KEY_SPLIT,// SSLAM_VIT_F32_NO_KEY_SPLIT the one-pass attention also for launches of a few frames
     KNOB_RT_STOP,             // SSLAM_RT_STOP             probe builds only
     KNOB_REFINE_DISTINCT,     // SSLAM_REFINE_DISTINCT     sslam_gather_refine_ws: 0 the direct launch, 1 the distinct-row work list, at any size
+    KNOB_CONV_BORDER,         // SSLAM_CONV_BORDER         0: the frame-crossing halo tiling instead of the border-class tiling (unset: the latter where it applies)
     KNOB_COUNT
 };
 #define SSLAM_KNOB_UNSET (-0x7fffffffffffffffLL - 1)

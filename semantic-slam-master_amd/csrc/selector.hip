@@ -7,7 +7,7 @@
 // hits instead of nine sweeps over the feature map (which measured 8.8x the algorithmic HBM bytes).
 // Workgroup = 8 waves; every wave owns a 64 x (32*NI) sub-tile (2 x NI MFMA 32x32 tiles).  A rows are gathered from
 // the NHWC feature map with the tap's spatial shift (zero rows outside the grid are multiplied through, exactly as
-// the oracle does) and staged through LDS in the KP8 order (common.h) with a +4 float row pad: one conflict-free
+// the oracle does - but for the border-class tiling of the halo form below, which leaves those steps out) and staged through LDS in the KP8 order (common.h) with a +4 float row pad: one conflict-free
 // ds_read_b128 feeds four consecutive v_mfma_f32_32x32x2_f32 steps.  B (the pre-packed weights, MFMA-fragment order
 // [stage][k-group][n][8]) is either staged through LDS too or, BDIRECT, loaded straight from L2 into registers
 // (1 KB coalesced per wave-instruction).  Global->LDS staging is register double-buffered.
@@ -274,40 +274,21 @@ __global__ __launch_bounds__(512, (BDIRECT && WM == 2) ? 4 : 1) void selector_sa
 constexpr int HIMG_ROWS = 256;                  // 512 threads x 2 items of 8 floats / 4 items per row
 constexpr int HIMG_FLOATS = HIMG_ROWS * LDT;    // 36 864 B per buffer; two buffers -> two workgroups per CU (147 KB)
 
-// One tile of the halo form.  SMALL = false: 128 cells, waves 2 (rows) x 4 (columns), 64 x 64 per wave.  SMALL = true: 32 cells,
-// 8 column waves of 32 x 32 - a quarter of the work, used for the rows BEYOND the last whole round of big tiles (below).
-template <bool SMALL>
-__device__ __forceinline__ void halo_tile(float *hsmem, const float *__restrict__ feat, int n_rows, int G, const float *__restrict__ w1p,
+// The k loop and the epilogue of one tile of the halo form, whatever its image holds (SMALL: see halo_tile).
+template <bool SMALL, bool SKIPS, class SalIndex>
+__device__ __forceinline__ void halo_core(float *hsmem, const float *__restrict__ feat, int n_rows, const float *__restrict__ w1p,
                                           const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
-                                          float *__restrict__ sal, const int m0, const int m_end) {
-    // m_end: one past the last cell this tile computes (n_rows, or the end of the tile's frame in the per-frame tiling)
+                                          float *__restrict__ sal, const int (&a_voff)[2], const int (&a_base)[SMALL ? 1 : 2], const int tap_stride,
+                                          const int skip, SalIndex sal_index) {
+    // a_voff: byte offset into feat of this thread's two loader items (image rows (tid >> 2) + 128 i; beyond the descriptor: a zero
+    // row).  a_base: LDS float offset of this lane's cells.  tap_stride: image rows per dy.  skip (SKIPS only): bit t set = tap t
+    // multiplies nothing but padding for EVERY cell of the tile and is left out.  sal_index(t): where cell t of the tile goes, or -1.
     constexpr int WN = SMALL ? 8 : 4, NI = SMALL ? 1 : 2, MI = SMALL ? 1 : 2, BM = 32 * MI * (8 / WN), HS = 256, NSLAB = 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
-    const int cells = G * G, G1 = G + 1, P = (G + 2) * G1;
-    auto padded = [&](int m) {
-        const int f = m / cells, c = m - f * cells, y = c / G, x = c - y * G;
-        return f * P + (y + 1) * G1 + x;
-    };
-    const int p_lo = padded(m0) - (G + 2);
-
-    // loader: item i of this thread = 8 floats (k-group `kq` of the chunk) of image row (tid >> 2) + 128 i.  Rows outside the
-    // grid get an offset beyond the descriptor (the range check ignores the scalar chunk offset): the loads return zeros.
     const __amdgpu_buffer_rsrc_t frs =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(feat), 0, (int)((unsigned)n_rows * (SSLAM_C * 4u)), 0x00020000);
     const int kq = tid & 3;
-    int a_voff[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const int pr = p_lo + (tid >> 2) + 128 * i;
-        int off = -32;
-        if (pr >= 0) {
-            const int f = pr / P, q = pr - f * P, yy = q / G1, xx = q - yy * G1;
-            const long long m = (long long)f * cells + (yy - 1) * G + xx;
-            if (yy >= 1 && yy <= G && xx < G && m < n_rows) off = (int)((unsigned)m * (SSLAM_C * 4u) + kq * 32u);
-        }
-        a_voff[i] = off;
-    }
     float4 ra_lo, ra_hi;
 #define HL(I, C)                                                                                                   \
     {                                                                                                              \
@@ -321,14 +302,6 @@ __device__ __forceinline__ void halo_tile(float *hsmem, const float *__restrict_
         float *d = hsmem + (BUF) * HIMG_FLOATS + ((tid >> 2) + 128 * (I)) * LDT + kq * 8;                          \
         *reinterpret_cast<float4 *>(d) = ev;                                                                       \
         *reinterpret_cast<float4 *>(d + 4) = od;                                                                   \
-    }
-
-    // A fragment rows of this lane: image row of its cell (floats), + 4 h
-    int a_base[MI];
-#pragma unroll
-    for (int mi = 0; mi < MI; mi++) {
-        const int m = min(m0 + wm * 32 * MI + mi * 32 + r, m_end - 1);
-        a_base[mi] = (padded(m) - p_lo) * LDT + 4 * h;
     }
 
     f32x16 acc[MI][NI];
@@ -345,10 +318,14 @@ __device__ __forceinline__ void halo_tile(float *hsmem, const float *__restrict_
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(w1p), 0, 9 * SSLAM_C * HS * 4, 0x00020000);
     const int b_voff = ((wn * 32 * NI + r) * 2 + h) * 16;
     f32x4 bq[BK / 8][NI];
+    // the first stage that runs: tap 0 is skipped by the top (-> 3) and left (-> 1) classes; no class skips every tap
+    int s_first = 0;
+    if (SKIPS)
+        while ((skip >> s_first) & 1) s_first++;
 #pragma unroll
     for (int g = 0; g < BK / 8; g++)
 #pragma unroll
-        for (int ni = 0; ni < NI; ni++) bq[g][ni] = bsrc[((long long)g * HS + ni * 32) * 2];
+        for (int ni = 0; ni < NI; ni++) bq[g][ni] = bsrc[((long long)(s_first * (BK / 8) + g) * HS + ni * 32) * 2];
 
     HL(0, 0);
     HS_(0, 0);
@@ -365,35 +342,47 @@ __device__ __forceinline__ void halo_tile(float *hsmem, const float *__restrict_
                 HL(1, chunk + 1);
             }
         }
-        const float *img = hsmem + (chunk & 1) * HIMG_FLOATS + (dy * G1 + dx) * LDT;
-        const float *A0 = img + a_base[0], *A1 = img + a_base[MI - 1];
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int g = 0; g < BK / 8; g++) {
-            const f32x4 a0 = *reinterpret_cast<const f32x4 *>(A0 + 8 * g);
-            f32x4 a1 = a0;
-            if (MI == 2) a1 = *reinterpret_cast<const f32x4 *>(A1 + 8 * g);
-            f32x4 b[NI];
-#pragma unroll
-            for (int ni = 0; ni < NI; ni++) b[ni] = bq[g][ni];
-#pragma unroll
-            for (int st = 0; st < 4; st++)
-#pragma unroll
-                for (int ni = 0; ni < NI; ni++) {
-                    acc[0][ni] = mfma32(a0[st], b[ni][st], acc[0][ni]);
-                    if (MI == 2) acc[MI - 1][ni] = mfma32(a1[st], b[ni][st], acc[MI - 1][ni]);
+        // a skipped tap: the staging above and the barrier below stay where they are, only the MFMA block is branched over
+        // (workgroup-uniform).  The B ring holds the next stage that RUNS, so nothing is fetched for a skipped one.
+        if (!SKIPS || !((skip >> tap) & 1)) {
+            int s_next = s + 1;
+            if (SKIPS) {
+                int t = tap + 1 == 9 ? 0 : tap + 1;
+                while ((skip >> t) & 1) {
+                    s_next++;
+                    t = t + 1 == 9 ? 0 : t + 1;
                 }
-            if (s + 1 < NSTAGE && (g == BK / 16 - 1 || g == BK / 8 - 1)) {
-#pragma unroll
-                for (int gg = g + 1 - BK / 16; gg <= g; gg++)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ni++)
-                        bq[gg][ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                            wrs, b_voff, (((s + 1) * (BK / 8) + gg) * HS + ni * 32) * 32, 0));
             }
-            if (g == BK / 16 - 1) __builtin_amdgcn_sched_barrier(0);
+            const float *img = hsmem + (chunk & 1) * HIMG_FLOATS + (dy * tap_stride + dx) * LDT;
+            const float *A0 = img + a_base[0], *A1 = img + a_base[MI - 1];
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int g = 0; g < BK / 8; g++) {
+                const f32x4 a0 = *reinterpret_cast<const f32x4 *>(A0 + 8 * g);
+                f32x4 a1 = a0;
+                if (MI == 2) a1 = *reinterpret_cast<const f32x4 *>(A1 + 8 * g);
+                f32x4 b[NI];
+#pragma unroll
+                for (int ni = 0; ni < NI; ni++) b[ni] = bq[g][ni];
+#pragma unroll
+                for (int st = 0; st < 4; st++)
+#pragma unroll
+                    for (int ni = 0; ni < NI; ni++) {
+                        acc[0][ni] = mfma32(a0[st], b[ni][st], acc[0][ni]);
+                        if (MI == 2) acc[MI - 1][ni] = mfma32(a1[st], b[ni][st], acc[MI - 1][ni]);
+                    }
+                if (s_next < NSTAGE && (g == BK / 16 - 1 || g == BK / 8 - 1)) {
+#pragma unroll
+                    for (int gg = g + 1 - BK / 16; gg <= g; gg++)
+#pragma unroll
+                        for (int ni = 0; ni < NI; ni++)
+                            bq[gg][ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                                wrs, b_voff, ((s_next * (BK / 8) + gg) * HS + ni * 32) * 32, 0));
+                }
+                if (g == BK / 16 - 1) __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_s_setprio(0);
         }
-        __builtin_amdgcn_s_setprio(0);
         tap++; dx++;
         if (dx == 2) { dx = -1; dy++; }
         if (tap == 9) {
@@ -449,14 +438,58 @@ __device__ __forceinline__ void halo_tile(float *hsmem, const float *__restrict_
     }
     __syncthreads();
     for (int t = tid; t < BM; t += 512) {
-        const long long m = (long long)m0 + t;
-        if (m < m_end) {
+        const long long m = sal_index(t);
+        if (m >= 0) {
             float logit = b2[0];
 #pragma unroll
             for (int sb = 0; sb < NSLAB; sb++) logit = logit + red[sb * BM + t];
             sal[m] = sslam_sigmoid(logit);
         }
     }
+}
+
+// One tile of the halo form: cells m0 .. m0 + BM - 1 of the launch, in the zero-padded coordinates above.  SMALL = false: 128 cells,
+// waves 2 (rows) x 4 (columns), 64 x 64 per wave.  SMALL = true: 32 cells, 8 column waves of 32 x 32 - a quarter of the work, used
+// for the rows BEYOND the last whole round of big tiles (below).
+template <bool SMALL>
+__device__ __forceinline__ void halo_tile(float *hsmem, const float *__restrict__ feat, int n_rows, int G, const float *__restrict__ w1p,
+                                          const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
+                                          float *__restrict__ sal, const int m0, const int m_end) {
+    // m_end: one past the last cell this tile computes (n_rows, or the end of the tile's frame in the per-frame tiling)
+    constexpr int WN = SMALL ? 8 : 4, MI = SMALL ? 1 : 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int wm = wave / WN;
+    const int cells = G * G, G1 = G + 1, P = (G + 2) * G1;
+    auto padded = [&](int m) {
+        const int f = m / cells, c = m - f * cells, y = c / G, x = c - y * G;
+        return f * P + (y + 1) * G1 + x;
+    };
+    const int p_lo = padded(m0) - (G + 2);
+
+    // loader: item i of this thread = 8 floats (k-group `kq` of the chunk) of image row (tid >> 2) + 128 i.  Rows outside the
+    // grid get an offset beyond the descriptor (the range check ignores the scalar chunk offset): the loads return zeros.
+    const int kq = tid & 3;
+    int a_voff[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int pr = p_lo + (tid >> 2) + 128 * i;
+        int off = -32;
+        if (pr >= 0) {
+            const int f = pr / P, q = pr - f * P, yy = q / G1, xx = q - yy * G1;
+            const long long m = (long long)f * cells + (yy - 1) * G + xx;
+            if (yy >= 1 && yy <= G && xx < G && m < n_rows) off = (int)((unsigned)m * (SSLAM_C * 4u) + kq * 32u);
+        }
+        a_voff[i] = off;
+    }
+    // A fragment rows of this lane: image row of its cell (floats), + 4 h
+    int a_base[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; mi++) {
+        const int m = min(m0 + wm * 32 * MI + mi * 32 + r, m_end - 1);
+        a_base[mi] = (padded(m) - p_lo) * LDT + 4 * h;
+    }
+    halo_core<SMALL, false>(hsmem, feat, n_rows, w1p, b1, w2, b2, sal, a_voff, a_base, G1, 0,
+                            [=](int t) { return m0 + t < m_end ? (long long)m0 + t : -1LL; });
 }
 
 // Grid = n_big tiles of 128 cells (XCD-aware order) followed by the 32-cell tiles of the remaining rows.  A launch is
@@ -503,6 +536,191 @@ __global__ __launch_bounds__(512, 4) void selector_saliency_halo_frames_kernel(c
         const int u = b - n_big - n_quarter, f = u / ts, j = u - f * ts;
         halo_tile<true>(hsmem, feat, n_rows, G, w1p, b1, w2, b2, sal, f * cells + tb * 128 + j * 32, (f + 1) * cells);
     }
+}
+
+// ---- BORDER-CLASS TILING of the halo form -------------------------------------------------------------------------------------
+// The tilings above place an out-of-grid tap on a zero row and multiply it through: at G = 28 that is 332 of the 7 056 (cell, tap)
+// products of a frame.  Here a frame's cells are sorted by WHICH taps are structurally zero, so that a whole tile can leave those
+// stages out: the fma chain of an output keeps its k order (stage = chunk * 9 + tap) and only loses steps fmaf(0, w, acc), which
+// return acc bit for bit for a finite w (an accumulator of -0 would become +0: the sign of a zero hidden value, which the ReLU
+// maps to +0 either way).  With a NON-FINITE conv weight the skipped 0 x Inf = NaN is not produced: outside the contract.
+//   top      y = 0, every x             skips taps 0 1 2     bottom   y = G - 1, every x          skips taps 6 7 8
+//   left     x = 0, y = 1 .. G - 2      skips taps 0 3 6     right    x = G - 1, y = 1 .. G - 2   skips taps 2 5 8
+//   interior the (G - 2)^2 others       no zero tap          (a corner keeps its other zero taps: 324 of the 332 go)
+// Tiles: BIG = 128 interior cells of ONE frame (interior cell i is (1 + i / (G-2), 1 + i % (G-2))), (G-2)^2 / 128 per frame; the
+// interior cells beyond them (REST) and each border class are POOLED over the frames of the launch, in frame order, 32 per tile,
+// so that only the launch's last tile of a kind has empty slots.  A tile's image is one segment per frame it touches:
+//   interior kinds   the cells c_lo .. c_lo + seg - 1 of the frame in plain y G + x order (every tap of an interior cell is in the
+//                    grid: no zero row at all), dy = G rows
+//   top / bottom     the class row and its in-grid neighbour row, each followed by one zero row (dy = G + 1 rows), after ONE
+//                    leading zero row: 1 + 2 (G + 1) per frame
+//   left / right     the two outer columns, (y, 0) (y, 1) or (y, G-2) (y, G-1) for y = 0 .. G - 1 (dy = 2 rows): 2 G per frame; the
+//                    taps that run never leave it, so it needs no zero row
+enum { BT_BIG, BT_TOP, BT_BOTTOM, BT_LEFT, BT_RIGHT, BT_REST, BT_KINDS };
+
+struct BorderGeom {
+    int f0, nf;          // first frame the tile touches, how many
+    int seg, lead;       // image rows per frame; zero rows in front
+    int dy_rows;         // image rows per dy
+    int c_lo;            // interior kinds: the frame cell of a segment's first row
+    int skip;            // bit t: tap t of every cell of the tile is padding
+    int valid;           // slots that hold a cell
+    int rows;            // lead + nf * seg
+};
+
+// cells of one frame in a pooled kind
+__host__ __device__ inline int border_per_frame(int G, int kind) {
+    const int in = (G - 2) * (G - 2);
+    return kind == BT_TOP || kind == BT_BOTTOM ? G : kind == BT_LEFT || kind == BT_RIGHT ? G - 2 : kind == BT_REST ? in % 128 : 128;
+}
+
+__host__ __device__ inline int border_interior_cell(int G, int i) { return (1 + i / (G - 2)) * G + 1 + i % (G - 2); }
+
+// the cell (frame, y G + x) of slot `slot` of tile `tile`; false: the slot is empty
+__host__ __device__ inline bool border_cell(int G, int F, int kind, int tile, int slot, int &f, int &c) {
+    if (kind == BT_BIG) {
+        const int nb = (G - 2) * (G - 2) / 128;
+        f = tile / nb;
+        c = border_interior_cell(G, (tile - f * nb) * 128 + slot);
+        return true;
+    }
+    const int per = border_per_frame(G, kind);
+    const long long p = (long long)tile * 32 + slot;
+    if (p >= (long long)F * per) return false;
+    f = (int)(p / per);
+    const int j = (int)(p - (long long)f * per);
+    c = kind == BT_TOP ? j : kind == BT_BOTTOM ? (G - 1) * G + j : kind == BT_LEFT ? (1 + j) * G : kind == BT_RIGHT ? (1 + j) * G + G - 1
+                       : border_interior_cell(G, (G - 2) * (G - 2) / 128 * 128 + j);
+    return true;
+}
+
+__host__ __device__ inline BorderGeom border_geom(int G, int F, int kind, int tile) {
+    BorderGeom g;
+    g.lead = 0, g.skip = 0, g.c_lo = 0;
+    if (kind == BT_BIG) {
+        int f, c0, c1;
+        border_cell(G, F, kind, tile, 0, f, c0);
+        border_cell(G, F, kind, tile, 127, f, c1);
+        g.f0 = f, g.nf = 1, g.valid = 128;
+        g.c_lo = c0 - G - 1, g.seg = c1 - c0 + 2 * (G + 1) + 1, g.dy_rows = G;
+    } else {
+        const int per = border_per_frame(G, kind);
+        const long long p0 = (long long)tile * 32, last = (long long)F * per - 1, p1 = p0 + 31 < last ? p0 + 31 : last;
+        g.f0 = (int)(p0 / per), g.nf = (int)(p1 / per) - g.f0 + 1, g.valid = (int)(p1 - p0) + 1;
+        if (kind == BT_REST) {
+            g.c_lo = border_interior_cell(G, (G - 2) * (G - 2) / 128 * 128) - G - 1;
+            g.seg = G * G - g.c_lo, g.dy_rows = G;             // the last interior cell's lower right neighbour is the frame's last cell
+        } else if (kind == BT_TOP || kind == BT_BOTTOM) {
+            g.seg = 2 * (G + 1), g.lead = 1, g.dy_rows = G + 1;
+            g.skip = kind == BT_TOP ? 0x007 : 0x1c0;
+        } else {
+            g.seg = 2 * G, g.dy_rows = 2;
+            g.skip = kind == BT_LEFT ? 0x049 : 0x124;
+        }
+    }
+    g.rows = g.lead + g.nf * g.seg;
+    return g;
+}
+
+// image row of cell c of frame f (a cell of the tile)
+__host__ __device__ inline int border_image_row(const BorderGeom &g, int G, int kind, int f, int c) {
+    const int y = c / G, x = c - y * G;
+    const int local = kind == BT_BIG || kind == BT_REST ? c - g.c_lo
+                      : kind == BT_TOP                   ? x
+                      : kind == BT_BOTTOM                ? G + 1 + x
+                      : kind == BT_LEFT                  ? 2 * y
+                                                         : 2 * y + 1;
+    return g.lead + (f - g.f0) * g.seg + local;
+}
+
+// the launch cell (f G G + y G + x) image row q holds, or -1: a zero row
+__host__ __device__ inline long long border_row_cell(const BorderGeom &g, int G, int kind, int q) {
+    q -= g.lead;
+    if (q < 0 || q >= g.nf * g.seg) return -1;
+    const int j = q / g.seg, rr = q - j * g.seg;
+    int c;
+    if (kind == BT_BIG || kind == BT_REST) {
+        c = g.c_lo + rr;
+    } else if (kind == BT_TOP || kind == BT_BOTTOM) {
+        const int yy = rr / (G + 1), xx = rr - yy * (G + 1);
+        if (xx == G) return -1;
+        c = ((kind == BT_TOP ? 0 : G - 2) + yy) * G + xx;
+    } else {
+        c = (rr >> 1) * G + (kind == BT_LEFT ? 0 : G - 2) + (rr & 1);
+    }
+    return (long long)(g.f0 + j) * G * G + c;
+}
+
+// One tile of the border-class tiling.  SMALL = false: a BIG tile.  SMALL = true: the 32 cells of a tile of a pooled kind.
+template <bool SMALL>
+__device__ __forceinline__ void border_tile(float *hsmem, const float *__restrict__ feat, int n_rows, int G, int F, const float *__restrict__ w1p,
+                                            const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
+                                            float *__restrict__ sal, const int kind, const int tile) {
+    constexpr int WN = SMALL ? 8 : 4, MI = SMALL ? 1 : 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int wm = wave / WN, kq = tid & 3, cells = G * G;
+    const BorderGeom g = border_geom(G, F, kind, tile);
+    int a_voff[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const long long m = border_row_cell(g, G, kind, (tid >> 2) + 128 * i);
+        a_voff[i] = m >= 0 ? (int)((unsigned)m * (SSLAM_C * 4u) + kq * 32u) : -32;
+    }
+    int a_base[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; mi++) {
+        int f, c;
+        border_cell(G, F, kind, tile, min(wm * 32 * MI + mi * 32 + r, g.valid - 1), f, c);      // an empty slot: the last cell again
+        a_base[mi] = border_image_row(g, G, kind, f, c) * LDT + 4 * h;
+    }
+    halo_core<SMALL, SMALL>(hsmem, feat, n_rows, w1p, b1, w2, b2, sal, a_voff, a_base, g.dy_rows, g.skip, [=](int t) {
+        int f, c;
+        return border_cell(G, F, kind, tile, t, f, c) ? (long long)f * cells + c : -1LL;
+    });
+}
+
+// Grid: every BIG tile whole (XCD-aware ranges; at 613 frames 3 065 of them, six rounds of 512 less 7), then the pooled kinds: REST,
+// top, bottom, left, right (`end[k]`: one past the last block of the k-th of them).  Measured against it and dropped: the big tiles
+// cut at the last whole round with the others run as their four quarters, as the tilings above do (A3 5.67 against 5.58 ms).
+struct BorderGrid {
+    int n_big, end[5];
+};
+
+__global__ __launch_bounds__(512, 4) void selector_saliency_border_kernel(const float *__restrict__ feat, int n_rows, int G, int F,
+                                                                          const float *__restrict__ w1p, const float *__restrict__ b1,
+                                                                          const float *__restrict__ w2, const float *__restrict__ b2,
+                                                                          float *__restrict__ sal, BorderGrid gr) {
+    extern __shared__ __attribute__((aligned(16))) float hsmem[];      // 2 x HIMG_FLOATS
+    const int b = blockIdx.x;
+    if (b < gr.n_big) {
+        const int q = gr.n_big / 8, rem = gr.n_big % 8, x = b % 8;
+        const int tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + b / 8;
+        border_tile<false>(hsmem, feat, n_rows, G, F, w1p, b1, w2, b2, sal, BT_BIG, tile);
+    } else {
+        int k = 0, start = gr.n_big;
+        while (k < 4 && b >= gr.end[k]) start = gr.end[k++];
+        border_tile<true>(hsmem, feat, n_rows, G, F, w1p, b1, w2, b2, sal, k == 0 ? BT_REST : k, b - start);      // BT_TOP .. BT_RIGHT are 1 .. 4
+    }
+}
+
+// The plan of a launch: tiles per kind and the most image rows a tile of each kind needs.  false: the form does not apply - fewer
+// than 128 interior cells in a frame, or an image beyond HIMG_ROWS rows (G = 44: two REST segments of 194; G = 60: of 158).
+bool border_plan(int F, int G, long long tiles[BT_KINDS], int max_rows[BT_KINDS]) {
+    for (int k = 0; k < BT_KINDS; k++) tiles[k] = 0, max_rows[k] = 0;
+    if (F <= 0 || G < 3 || (G - 2) * (G - 2) < 128) return false;
+    bool fits = true;
+    for (int k = 0; k < BT_KINDS; k++) {
+        const int per = border_per_frame(G, k);
+        tiles[k] = k == BT_BIG ? (long long)F * ((G - 2) * (G - 2) / 128) : ((long long)F * per + 31) / 32;
+        // a pooled kind repeats after `per` tiles (32 per cells = 32 whole frames), a big tile after a frame's
+        const long long period = k == BT_BIG ? (G - 2) * (G - 2) / 128 : per, scan = tiles[k] < period ? tiles[k] : period;
+        for (long long t = 0; t < scan; t++) {
+            const int rows = border_geom(G, F, k, (int)t).rows;
+            max_rows[k] = rows > max_rows[k] ? rows : max_rows[k];
+        }
+        fits = fits && max_rows[k] <= HIMG_ROWS;
+    }
+    return fits && tiles[BT_BIG] + tiles[BT_REST] + 4 * tiles[BT_TOP] < 0x7fffffffLL;
 }
 
 // ---- latency form 2 (hs = 256, few frames): halo image + the hidden channels split over TWO workgroups ------------------
@@ -719,6 +937,66 @@ static const long long LAT2_DEFAULT_ROWS = 32 * 25 * 6;
 // frame; still ahead at 256 frames: 2.90 vs 3.02 ms).  Measured cross-over: ~400 frames at G = 28 (6.25 vs 6.10 ms at 613)
 static const long long LAT_DEFAULT_ROWS = 128 * 1800;
 
+// HOST ONLY, for the tests and the tools (declared here, not in include/sslam_hip.h): the plan sslam_selector_saliency_ws launches
+// the border-class tiling by.  tiles / max_rows: [6] in the order big, top, bottom, left, right, rest.  SSLAM_E_UNSUPPORTED: the
+// form does not apply to this grid (the arrays are still filled).
+extern "C" int sslami_selector_border_plan(int n_frames, int G, long long *tiles, int *max_rows) {
+    if (!tiles || !max_rows || n_frames <= 0 || G <= 0) return SSLAM_E_INVALID;
+    if ((long long)n_frames * G * G * (SSLAM_C * 4) > 0xffffffffLL) return SSLAM_E_UNSUPPORTED;
+    return border_plan(n_frames, G, tiles, max_rows) ? SSLAM_OK : SSLAM_E_UNSUPPORTED;
+}
+
+// the cells of tiles tile0 .. tile0 + n - 1 of `kind`: fyx[(t * slots + s) * 3 + (0, 1, 2)] = frame, y, x of slot s (slots: 128 for
+// big tiles, else 32), -1 -1 -1 for an empty slot
+extern "C" int sslami_selector_border_owners(int n_frames, int G, int kind, long long tile0, int n, int *fyx) {
+    long long tiles[BT_KINDS];
+    int rows[BT_KINDS];
+    if (!fyx || kind < 0 || kind >= BT_KINDS || tile0 < 0 || n < 0) return SSLAM_E_INVALID;
+    const int rc = sslami_selector_border_plan(n_frames, G, tiles, rows);
+    if (rc != SSLAM_OK) return rc;
+    if (tile0 + n > tiles[kind]) return SSLAM_E_INVALID;
+    const int slots = kind == BT_BIG ? 128 : 32;
+    for (long long t = 0; t < n; t++)
+        for (int s = 0; s < slots; s++) {
+            int f = -1, c = 0, *o = fyx + (t * slots + s) * 3;
+            const bool has = border_cell(G, n_frames, kind, (int)(tile0 + t), s, f, c);
+            o[0] = has ? f : -1, o[1] = has ? c / G : -1, o[2] = has ? c % G : -1;
+        }
+    return SSLAM_OK;
+}
+
+// walks every tile of the plan as the kernel does and counts the (slot, tap) pairs that go wrong: a tap that runs must read, inside
+// the LDS image, the row that holds the neighbour cell - or a zero row where the neighbour is outside the grid - and a tap that is
+// skipped must be padding.  0: the geometry is right.
+extern "C" long long sslami_selector_border_check(int n_frames, int G) {
+    long long tiles[BT_KINDS], bad = 0;
+    int rows[BT_KINDS];
+    const int rc = sslami_selector_border_plan(n_frames, G, tiles, rows);
+    if (rc != SSLAM_OK) return rc;
+    for (int kind = 0; kind < BT_KINDS; kind++)
+        for (long long t = 0; t < tiles[kind]; t++) {
+            const BorderGeom g = border_geom(G, n_frames, kind, (int)t);
+            for (int s = 0, f, c; s < (kind == BT_BIG ? 128 : 32); s++) {
+                if (!border_cell(G, n_frames, kind, (int)t, s, f, c)) {
+                    bad += s < g.valid;
+                    continue;
+                }
+                const int y = c / G, x = c % G, row = border_image_row(g, G, kind, f, c);
+                bad += s >= g.valid;
+                for (int tap = 0; tap < 9; tap++) {
+                    const int dy = tap / 3 - 1, dx = tap % 3 - 1, q = row + dy * g.dy_rows + dx;
+                    const bool in_grid = y + dy >= 0 && y + dy < G && x + dx >= 0 && x + dx < G;
+                    const long long want = in_grid ? ((long long)f * G + y + dy) * G + x + dx : -1;
+                    if ((g.skip >> tap) & 1)
+                        bad += in_grid;
+                    else
+                        bad += q < 0 || q >= HIMG_ROWS || border_row_cell(g, G, kind, q) != want;
+                }
+            }
+        }
+    return bad;
+}
+
 // scratch of latency form 2: the two half-sums of the 1x1 conv per cell and workgroup half (16 bytes per cell)
 extern "C" long long sslam_selector_saliency_workspace_bytes(int n_frames, int G) {
     if (n_frames <= 0 || G <= 0) return SSLAM_E_INVALID;
@@ -739,6 +1017,8 @@ extern "C" int sslam_selector_saliency_ws(const float *feat, int n_frames, int G
     const int variant = (int)sslam_knob(KNOB_CONV_VARIANT, 2);
     const long long lat_rows = sslam_knob(KNOB_CONV_LATENCY_ROWS, LAT_DEFAULT_ROWS);   // 0 forces the throughput form
     const long long lat2_rows = sslam_knob(KNOB_CONV_LAT2_ROWS, LAT2_DEFAULT_ROWS);    // 0 disables latency form 2
+    long long b_tiles[BT_KINDS];
+    int b_rows[BT_KINDS];
     // latency form 2 needs 16 bytes of CALLER-OWNED scratch per cell; without it the 8-wave latency form runs (same bits)
     if (hs == 256 && rows <= lat2_rows && rows <= lat_rows && workspace && workspace_bytes >= rows * 16) {
         const int np = (halo_rows32(G, rows) + 63) / 64;
@@ -764,6 +1044,17 @@ extern "C" int sslam_selector_saliency_ws(const float *feat, int n_frames, int G
     }
     if (hs == 256 && rows <= lat_rows) {
         launch<1, 8, 1, true, 1>(feat, rows, G, w1_packed, b1, w2, b2, sal, st);
+    } else if (hs == 256 && variant == 2 && !sslam_knob(KNOB_CONV_NO_HALO, 0) && halo_rows128(G, rows) <= HIMG_ROWS &&
+               sslam_knob(KNOB_CONV_BORDER, 1) != 0 && border_plan(n_frames, G, b_tiles, b_rows)) {
+        // the border-class tiling, where the frame-crossing halo kernel below ran before (G = 28); the grids of the per-frame
+        // tiling (G = 40 plans, G = 44 / 60 do not) keep it: not measured there
+        BorderGrid gr;
+        gr.n_big = (int)b_tiles[BT_BIG];
+        const int order[5] = {BT_REST, BT_TOP, BT_BOTTOM, BT_LEFT, BT_RIGHT};
+        int end = gr.n_big;
+        for (int k = 0; k < 5; k++) gr.end[k] = end += (int)b_tiles[order[k]];
+        hipLaunchKernelGGL(selector_saliency_border_kernel, dim3((unsigned)end), dim3(512), 2 * HIMG_FLOATS * sizeof(float), st, feat, (int)rows, G,
+                           n_frames, w1_packed, b1, w2, b2, sal, gr);
     } else if (hs == 256 && variant == 2 && !sslam_knob(KNOB_CONV_NO_HALO, 0) && halo_rows128(G, rows) <= HIMG_ROWS) {
         // big tiles up to the last whole round of 2 workgroups x 256 CUs, 32-cell tiles for the rest
         const int n_tiles = (int)((rows + 127) / 128);

@@ -115,6 +115,9 @@ def lib():
                        (L.sslam_sim_argmax_workspace_bytes, [i, i]), (L.sslam_gather_refine_workspace_bytes, [i, i])):
             fn.restype, fn.argtypes = ll, at
         L.sslam_test_set_knob.argtypes = [C.c_char_p, ll, i]
+        L.sslami_selector_border_plan.argtypes = [i, i, p, p]
+        L.sslami_selector_border_owners.argtypes = [i, i, i, ll, i, p]
+        L.sslami_selector_border_check.restype, L.sslami_selector_border_check.argtypes = ll, [i, i]
         L.sslam_select_keypoints.argtypes = [p, i, i, i, i, d, p, p, p, p, p, p]
         L.sslam_gather.argtypes = [p, i, i, p, i, p, p]
         L.sslam_refiner_layout.argtypes = [i, C.POINTER(RefinerLayout)]
@@ -452,6 +455,38 @@ def selector_bf16_halo_groups(n_frames: int, G: int, hs: int = 256) -> int:
     if np_ < 0:
         _check(np_, "selector_bf16_halo_groups")
     return np_
+
+
+BORDER_KINDS = ("big", "top", "bottom", "left", "right", "rest")
+
+
+def selector_border_plan(n_frames: int, G: int):
+    """The border-class tiling of the fp32 conv (csrc/selector.hip) for a launch: (applies, {kind: tiles}, {kind: most image rows a
+    tile needs}).  `applies` False: the planner refuses the grid (the figures say why); host only."""
+    tiles, rows = (C.c_longlong * 6)(), (C.c_int * 6)()
+    rc = lib().sslami_selector_border_plan(n_frames, G, tiles, rows)
+    if rc not in (OK, E_UNSUPPORTED):
+        _check(rc, "selector_border_plan")
+    return rc == OK, dict(zip(BORDER_KINDS, tiles)), dict(zip(BORDER_KINDS, rows))
+
+
+def selector_border_check(n_frames: int, G: int) -> int:
+    """Walks every tile of the plan as the kernel does: the (slot, tap) pairs whose image row is not the neighbour cell's, 0 if the
+    geometry is right."""
+    bad = int(lib().sslami_selector_border_check(n_frames, G))
+    if bad < 0:
+        _check(bad, "selector_border_check")
+    return bad
+
+
+def selector_border_owners(n_frames: int, G: int, kind: str) -> np.ndarray:
+    """(tiles, slots, 3) int32: the (frame, y, x) every slot of every tile of `kind` computes, -1 for an empty slot."""
+    ok, tiles, _ = selector_border_plan(n_frames, G)
+    if not ok:
+        raise SslamHipError(f"selector_border_owners: the border-class tiling does not apply to G = {G}")
+    out = np.empty((tiles[kind], 128 if kind == "big" else 32, 3), np.int32)
+    _check(lib().sslami_selector_border_owners(n_frames, G, BORDER_KINDS.index(kind), 0, tiles[kind], out.ctypes.data), "selector_border_owners")
+    return out
 
 
 def select_keypoints(sal, K, radius=2, pct=0.5, want_idx=True, want_pixel=True, out=None):
