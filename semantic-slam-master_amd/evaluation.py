@@ -9,7 +9,8 @@ Beside them, with the same return conventions, the two functions of the depth gr
 compute_repeatability_depth and compute_ground_truth_matches_depth - and, beside matching.py's matchers, the step that follows
 them: estimate_relative_pose, the rigid motion a match list agrees on (csrc/pose_estimate.hip), and refine_relative_pose, that
 motion - or any other initial pose - refined on the reprojection error (csrc/pose_refine.hip), and optimize_pose_graph, the
-poses of a whole sequence from those motions and their information matrices (csrc_graph/pose_graph.hip).  And, between the selector and all
+poses of a whole sequence from those motions and their information matrices (csrc_graph/pose_graph.hip), with find_loop_candidates and
+optimize_pose_graph_sparse, the loop closures on top of it (csrc_loop/loop.hip).  And, between the selector and all
 of them, refine_keypoints_subcell: the selected cells moved to their sub-cell saliency peaks (csrc_ext/subcell.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
@@ -228,6 +229,51 @@ def optimize_pose_graph(first, second, T, info, n_nodes: int, C_init=None, band=
     C = np.tile(np.eye(4), (n_nodes, 1, 1))
     C[:, :3] = out["C"].cpu().numpy().reshape(n_nodes, 3, 4)
     return C, int(out["status"].cpu()), out["edge_chi2"].cpu().numpy()
+
+
+def find_loop_candidates(descriptors, scores, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2, suppress: int = 5):
+    """The step that proposes loop closures: descriptors (N, K, D) and scores (N, K) float32 of a sequence's frames, D 128 or 256.
+    Every frame gets a place signature - the score-weighted sum of its descriptors, centred on the sequence's mean, normalised -
+    and up to per_frame older frames j <= i - min_gap whose signature's similarity to its own is at least min_sim, best first, none
+    within `suppress` frames of a better one (ssll_frame_signatures, ssll_loop_candidates; include/sslam_loop.h).
+    numpy in, numpy out.  Returns (pairs (P, 2) int32 [older frame, frame], sim (P,) float32): the proposed pairs in frame order."""
+    descriptors, scores = np.ascontiguousarray(descriptors, dtype=np.float32), np.ascontiguousarray(scores, dtype=np.float32)
+    if descriptors.ndim != 3 or scores.shape != descriptors.shape[:2]:
+        raise ValueError(f"descriptors (N, K, D) and scores (N, K) expected, got {descriptors.shape} and {scores.shape}")
+    lib.check_width(int(descriptors.shape[2]))
+    lib.check_loop_arguments(min_gap, min_sim, per_frame, suppress)
+    sig = lib.frame_signatures(_dev(descriptors, torch.float32), _dev(scores, torch.float32))
+    first, second, sim, _ = (t.cpu().numpy() for t in lib.loop_candidates(sig, min_gap, min_sim, per_frame, suppress))
+    filled = first >= 0
+    return np.stack([first[filled], second[filled]], axis=1), sim[filled]
+
+
+def optimize_pose_graph_sparse(first, second, T, info, n_nodes: int, C_init, huber_chi: float = 4.0, damping: float = 0.0, iterations: int = 8,
+                               cg_iterations: int = 512, cg_tol: float = 1e-3):
+    """optimize_pose_graph with pairs anywhere - loop closures among them - solved by preconditioned conjugate gradients
+    (ssll_pose_graph_sparse, include/sslam_loop.h).  first .. info: as optimize_pose_graph takes them; C_init (n_nodes, 4, 4) or
+    (n_nodes, 3, 4) world -> camera is required (optimize_pose_graph's C, or a chain); cg_iterations: the most CG iterations of a
+    step; cg_tol: their relative tolerance.  numpy in, numpy out; one graph.
+    Returns (C (n_nodes, 4, 4), status, chi2 (E,), cg_steps (16,): the CG iterations every step took)."""
+    first, second = [int(v) for v in np.asarray(first).reshape(-1)], [int(v) for v in np.asarray(second).reshape(-1)]
+    T, info = np.asarray(T, dtype=np.float64), np.asarray(info, dtype=np.float64)
+    if T.ndim != 3 or tuple(T.shape[1:]) not in ((4, 4), (3, 4)) or len(T) != len(first) or len(first) != len(second) or not first:
+        raise ValueError(f"T (E, 4, 4) or (E, 3, 4) for E = {len(first)} >= 1 pairs expected, got {T.shape}")
+    if info.shape != (len(first), 6, 6):
+        raise ValueError(f"info ({len(first)}, 6, 6) expected, got {info.shape}")
+    C_init = np.asarray(C_init, dtype=np.float64)
+    if C_init.ndim != 3 or tuple(C_init.shape[1:]) not in ((4, 4), (3, 4)) or len(C_init) != n_nodes:
+        raise ValueError(f"C_init ({n_nodes}, 4, 4) or ({n_nodes}, 3, 4) expected, got {C_init.shape}")
+    lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
+    from sslam_amd.pipeline import SequencePipeline
+    iu = np.triu_indices(6)
+    out = SequencePipeline.optimize_pose_graph_sparse(first, second, _dev(np.ascontiguousarray(T[:, :3]).reshape(-1, 12), torch.float64),
+                                                      _dev(np.ascontiguousarray(info[:, iu[0], iu[1]]), torch.float64), n_nodes,
+                                                      _dev(np.ascontiguousarray(C_init[:, :3]).reshape(n_nodes, 12), torch.float64), huber_chi,
+                                                      damping, iterations, cg_iterations, cg_tol)
+    C = np.tile(np.eye(4), (n_nodes, 1, 1))
+    C[:, :3] = out["C"].cpu().numpy().reshape(n_nodes, 3, 4)
+    return C, int(out["status"].cpu()), out["edge_chi2"].cpu().numpy(), out["cg_steps"].cpu().numpy()
 
 
 def refine_keypoints_subcell(saliency, keypoints):

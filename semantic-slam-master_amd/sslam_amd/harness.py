@@ -429,6 +429,10 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
     refined keypoints (evaluation.geometry_bank); a key "subcell": False puts all three on the cell centres instead - the one
     depth gather, evaluate_result and odometry_result are handed the same choice - and "subcell": True on a pipeline that does
     not localise its keypoints is a ValueError, raised before the sequence is run.
+    A key "graph": True (it needs "refine": True) adds 'odometry'['graph'], the pose graph over every spacing's refined poses
+    (odometry.odometry_result_graph); a key "loops": True or a dictionary of odometry.check_loops' options, cg_iterations, cg_tol
+    and prune_chi (it needs "graph": True) adds 'odometry'['loops'] and 'odometry'['loop_graph'] - loop-closure candidates, verified
+    and used as edges of the sparse graph (odometry.odometry_result_loop_graph).
     Returns StreamingSequence.result() plus 'files' and 'timestamps'."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -460,6 +464,17 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
             raise ValueError('evaluate["graph"] is a flag, True or False')
         if with_graph and not with_refine:
             raise ValueError('evaluate["graph"] optimises over the refined poses\' information matrices: it needs "refine": True')
+        with_loops = evaluate.pop("loops", False)
+        if with_loops is not False:                           # True, or a dictionary of odometry.check_loops' options and the solve's
+            from . import odometry
+            if not with_graph:
+                raise ValueError('evaluate["loops"] closes loops on top of the pose graph: it needs "graph": True')
+            if with_loops is not True and not isinstance(with_loops, dict):
+                raise ValueError('evaluate["loops"] is True or a dictionary of min_gap, min_sim, per_frame, suppress, min_inliers, cg_iterations, '
+                                 'cg_tol, prune_chi')
+            loop_args = {} if with_loops is True else dict(with_loops)
+            solve_args = {key: loop_args.pop(key) for key in ("cg_iterations", "cg_tol", "prune_chi") if key in loop_args}
+            odometry.check_loops(loop_args, **solve_args)
         if not (with_depth or with_odometry) and "camera" in evaluate:
             raise ValueError('evaluate["camera"] describes the depth images: it needs "depth": True')
         if rule is None:
@@ -538,4 +553,10 @@ def run_directory(root: str, sequence: str = "", spacings=(1, 5, 10, 15, 20), pi
                     pipe, res, camera=depth_camera, poses=tum.poses, spacings=tuple(s for s in seq.spacings if s in res),
                     num_pairs=int(evaluate.get("num_pairs", 50)), threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth,
                     subcell=subcell)["graph"]
+            if with_loops is not False:                      # loop-closure edges and the sparse graph over all edges (odometry_result_loop_graph)
+                got = odometry.odometry_result_loop_graph(
+                    pipe, res, camera=depth_camera, poses=tum.poses, spacings=tuple(s for s in seq.spacings if s in res),
+                    num_pairs=int(evaluate.get("num_pairs", 50)), threshold=evaluate.get("threshold", 3.0), kp_depth=kp_depth,
+                    subcell=subcell, loops=loop_args, rule=rule, **solve_args)
+                res["odometry"].update({key: got[key] for key in ("loops", "loop_graph", "loop_graph_unpruned") if key in got})
     return res

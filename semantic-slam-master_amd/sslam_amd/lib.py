@@ -1666,3 +1666,189 @@ def pose_graph(first, second, T, info, C_in, band, huber_chi=4.0, damping=0.0, i
     _run("pose_graph", graph().sslg_pose_graph, (first, second, T, info, C3, ws, *o), _dp(first), _dp(second), _dp(T), _dp(info),
          n_graphs, n_nodes, n_edges, _dp(C3), b, C.c_double(chi), C.c_double(damp), n_iter, _dp(ws), *(_dp(x) for x in o))
     return tuple(o)
+
+
+# ------------------------------------------------------------------------------------------ libsslam_loop.so (include/sslam_loop.h)
+# The fourth library: entries with the prefix ssll_, built from csrc_loop/ with csrc_graph/'s flags, loaded and refused like the others.
+CSRC_LOOP = os.path.join(_PKG, "csrc_loop")
+LOOP_SO_PATH = os.path.join(CSRC_LOOP, "libsslam_loop.so")
+LOOP_EXPORTS = ["ssll_version", "ssll_arch", "ssll_launch_count", "ssll_frame_signatures", "ssll_loop_candidates",
+                "ssll_pose_graph_sparse_workspace_bytes", "ssll_pose_graph_sparse"]
+LOOP_MAX_FRAMES, LOOP_MAX_K, LOOP_MAX_PER_FRAME = 4096, 4096, 8
+SPARSE_MAX_NODES, SPARSE_MAX_EDGES, SPARSE_MAX_GRAPHS, SPARSE_MAX_ITER, SPARSE_MAX_CG = 4096, 65536, 65535, 16, 4096
+LOOP_CANDIDATE_KEYS = ("first", "second", "sim", "count")
+POSE_GRAPH_SPARSE_KEYS = POSE_GRAPH_KEYS + ("cg_steps",)
+
+_loop = None
+
+
+def loop_build(force: bool = False) -> str:
+    """Compile libsslam_loop.so for gfx950 in-tree, as build() compiles the first library."""
+    inc = os.path.join(os.path.dirname(_PKG), "include")
+    srcs = [os.path.join(CSRC_LOOP, f) for f in os.listdir(CSRC_LOOP) if f.endswith((".hip", ".h"))]
+    srcs += [os.path.join(CSRC_GRAPH, "edge_terms.h")] + [os.path.join(inc, h) for h in ("sslam_loop.h", "sslam_graph.h", "sslam_hip.h")]
+    stale = (not os.path.exists(LOOP_SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LOOP_SO_PATH) for s in srcs)
+    if force or stale:
+        subprocess.check_call(["make", "-C", CSRC_LOOP, "-s", "-j4"])
+    return LOOP_SO_PATH
+
+
+def loop():
+    """Load libsslam_loop.so; raises if it has not been built (no silent fallback)."""
+    global _loop
+    if _loop is None:
+        if not os.path.exists(LOOP_SO_PATH):
+            raise SslamHipError(f"{LOOP_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                                f"(or `make -C {CSRC_LOOP}`); this package has no non-HIP execution path")
+        L = C.CDLL(LOOP_SO_PATH)
+        L.ssll_arch.restype = C.c_char_p
+        L.ssll_launch_count.restype = C.c_longlong
+        L.ssll_pose_graph_sparse_workspace_bytes.restype = C.c_size_t
+        p, i, d, f = C.c_void_p, C.c_int, C.c_double, C.c_float
+        L.ssll_pose_graph_sparse_workspace_bytes.argtypes = [i, i, i]
+        L.ssll_frame_signatures.argtypes = [p, p, i, i, i, p, p, p]
+        L.ssll_loop_candidates.argtypes = [p, i, i, i, f, i, i, p, p, p, p, p]
+        L.ssll_pose_graph_sparse.argtypes = [p, p, p, p, i, i, i, p, d, d, i, i, d] + [p] * 12
+        _loop = L
+    return _loop
+
+
+def loop_launch_count() -> int:
+    return int(loop().ssll_launch_count())
+
+
+def check_int(name, v, lo, hi=None) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo or (hi is not None and int(v) > hi):
+        raise ValueError(f"{name} must be an int {'>= ' + str(lo) if hi is None else 'in [' + str(lo) + ', ' + str(hi) + ']'}, got {v!r}")
+    return int(v)
+
+
+def check_cg_iterations(cg_iterations) -> int:
+    """The most conjugate-gradient iterations of a step: an int >= 1, else ValueError; above SPARSE_MAX_CG: SslamHipError - before any
+    device work."""
+    n_cg = check_int("cg_iterations", cg_iterations, 1)
+    if n_cg > SPARSE_MAX_CG:
+        raise SslamHipError(f"pose_graph_sparse: {_ERR[E_UNSUPPORTED]} (cg_iterations <= {SPARSE_MAX_CG}, got {n_cg})")
+    return n_cg
+
+
+def check_cg_tol(cg_tol) -> float:
+    """The relative tolerance of the conjugate gradients: a finite number >= 0, else ValueError - before any device work."""
+    if isinstance(cg_tol, bool) or not isinstance(cg_tol, (int, float, np.integer, np.floating)) or not (float(cg_tol) >= 0.0) or \
+            not np.isfinite(float(cg_tol)):
+        raise ValueError(f"cg_tol must be a finite number >= 0, got {cg_tol!r}")
+    return float(cg_tol)
+
+
+def frame_signatures(descriptors, scores, out=None, workspace=None):
+    """ssll_frame_signatures: descriptors (N, K, D) and scores (N, K) float32 as extract() returns them, D in WIDTHS.  Returns sig
+    (N, D) float32: the score-weighted descriptor sum of every frame, centred on the sequence's mean and normalised
+    (include/sslam_loop.h).  workspace: optional uint8 tensor of at least N * D * 4 bytes.  Two launches, no host read."""
+    _check_bank("descriptors", descriptors, ("K", WIDTHS))
+    n, k, d = (int(x) for x in descriptors.shape)
+    if scores is None:
+        raise ValueError("scores is required")
+    _check_arrays((n, k), ("scores", scores, torch.float32))
+    if n > LOOP_MAX_FRAMES or k > LOOP_MAX_K:
+        raise SslamHipError(f"frame_signatures: {_ERR[E_UNSUPPORTED]} (N <= {LOOP_MAX_FRAMES}, K <= {LOOP_MAX_K}; got {n}, {k})")
+    if out is not None:
+        _check_arrays((n, d), ("out", out, torch.float32))
+    need = 4 * n * d
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
+                                  workspace.numel() < need or not workspace.is_contiguous()):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    dev = common_device(descriptors, scores, out, workspace)
+    sig = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else out
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _run("frame_signatures", loop().ssll_frame_signatures, (descriptors, scores, ws, sig), _dp(descriptors), _dp(scores), n, k, d, _dp(ws),
+         _dp(sig))
+    return sig
+
+
+def loop_candidate_shapes(n_frames: int, per_frame: int) -> dict:
+    """name -> (shape, dtype) of the outputs of loop_candidates."""
+    slots = (n_frames * per_frame,)
+    return {"first": (slots, torch.int32), "second": (slots, torch.int32), "sim": (slots, torch.float32), "count": ((n_frames,), torch.int32)}
+
+
+def check_loop_arguments(min_gap, min_sim, per_frame, suppress) -> tuple:
+    """(min_gap >= 1, finite min_sim, per_frame 1 .. LOOP_MAX_PER_FRAME, suppress >= 0), else ValueError - before any device work."""
+    gap, per, sup = check_int("min_gap", min_gap, 1), check_int("per_frame", per_frame, 1, LOOP_MAX_PER_FRAME), check_int("suppress", suppress, 0)
+    if isinstance(min_sim, bool) or not isinstance(min_sim, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(min_sim)):
+        raise ValueError(f"min_sim must be a finite number, got {min_sim!r}")
+    return gap, float(np.float32(min_sim)), per, sup
+
+
+def loop_candidates(sig, min_gap=30, min_sim=0.3, per_frame=2, suppress=5, out=None):
+    """ssll_loop_candidates: sig (N, D) float32 from frame_signatures.  For every frame i up to per_frame older frames j <= i -
+    min_gap of similarity >= min_sim (rounded to float32), best first, none within `suppress` frames of a better one.  Returns
+    (first, second, sim, count) - LOOP_CANDIDATE_KEYS, loop_candidate_shapes - in match_pairs' pair-list form: first the older
+    frame or -1, second = i or -1.  One launch, no host read."""
+    gap, sim_min, per, sup = check_loop_arguments(min_gap, min_sim, per_frame, suppress)
+    _check_bank("sig", sig, (WIDTHS,))
+    n, d = int(sig.shape[0]), int(sig.shape[1])
+    if n > LOOP_MAX_FRAMES:
+        raise SslamHipError(f"loop_candidates: {_ERR[E_UNSUPPORTED]} (N <= {LOOP_MAX_FRAMES}, got {n})")
+    shapes = loop_candidate_shapes(n, per)
+    o = None if out is None else _outputs(shapes, LOOP_CANDIDATE_KEYS, out)
+    dev = common_device(sig, *(o or ()))
+    o = _outputs(shapes, LOOP_CANDIDATE_KEYS, None, dev) if o is None else o
+    _run("loop_candidates", loop().ssll_loop_candidates, (sig, *o), _dp(sig), n, d, min(gap, 2 ** 31 - 1), C.c_float(sim_min), per,
+         min(sup, 2 ** 31 - 1), *(_dp(x) for x in o))
+    return tuple(o)
+
+
+def pose_graph_sparse_shapes(n_graphs: int, n_nodes: int, n_edges: int) -> dict:
+    """name -> (shape, dtype) of the outputs of pose_graph_sparse: pose_graph_shapes and cg_steps."""
+    return dict(pose_graph_shapes(n_graphs, n_nodes, n_edges), cg_steps=((n_graphs, SPARSE_MAX_ITER), torch.int32))
+
+
+def pose_graph_sparse_workspace_bytes(n_graphs: int, n_nodes: int, n_edges: int) -> int:
+    """ssll_pose_graph_sparse_workspace_bytes, restated: per graph 90 E + 78 (N - 1) + 12 N + (N + 1 + 2 E + 1) // 2 float64 words.
+    Needs no library."""
+    return 8 * n_graphs * (90 * n_edges + 78 * (n_nodes - 1) + 12 * n_nodes + (n_nodes + 1 + 2 * n_edges + 1) // 2)
+
+
+def pose_graph_sparse(first, second, T, info, C_in, huber_chi=4.0, damping=0.0, iterations=8, cg_iterations=512, cg_tol=1e-3, out=None,
+                      workspace=None):
+    """ssll_pose_graph_sparse: pose_graph's operands without a band - an edge may join any two nodes - and the step solved by
+    block-Jacobi preconditioned conjugate gradients: at most cg_iterations (1 .. SPARSE_MAX_CG) per step, stopped at the relative
+    tolerance cg_tol (finite >= 0).  Returns POSE_GRAPH_SPARSE_KEYS' tensors (include/sslam_loop.h), always with the graph axis:
+    pose_graph's and cg_steps (n_graphs, 16), the CG iterations of every step.  out: optional tensors of pose_graph_sparse_shapes
+    (C must not be C_in); workspace: optional uint8 tensor of at least pose_graph_sparse_workspace_bytes.  One launch, no host
+    read; everything is judged before the library is loaded."""
+    chi, damp, n_iter = check_positive("huber_chi", huber_chi), check_damping(damping), check_graph_iterations(iterations)
+    n_cg, tol = check_cg_iterations(cg_iterations), check_cg_tol(cg_tol)
+    if not isinstance(C_in, torch.Tensor) or C_in.dtype != torch.float64 or C_in.dim() not in (2, 3) or int(C_in.shape[-1]) != 12 or \
+            not C_in.is_contiguous():
+        raise ValueError("C_in must be a contiguous float64 tensor of shape (n_graphs, n_nodes, 12) or (n_nodes, 12)")
+    C3 = C_in[None] if C_in.dim() == 2 else C_in
+    n_graphs, n_nodes = int(C3.shape[0]), int(C3.shape[1])
+    if not isinstance(first, torch.Tensor) or first.dim() not in (1, 2):
+        raise ValueError("first must be an int32 tensor of shape (n_graphs, n_edges) or (n_edges,)")
+    n_edges = int(first.shape[-1])
+    if n_graphs < 1 or n_nodes < 1 or n_edges < 1:
+        raise ValueError(f"pose_graph_sparse: at least one graph, node and edge slot expected, got {n_graphs}, {n_nodes}, {n_edges}")
+    if n_graphs > SPARSE_MAX_GRAPHS or n_nodes > SPARSE_MAX_NODES or n_edges > SPARSE_MAX_EDGES:
+        raise SslamHipError(f"pose_graph_sparse: {_ERR[E_UNSUPPORTED]} (n_graphs <= {SPARSE_MAX_GRAPHS}, n_nodes <= {SPARSE_MAX_NODES}, "
+                            f"n_edges <= {SPARSE_MAX_EDGES}; got {n_graphs}, {n_nodes}, {n_edges})")
+    lead = (n_graphs, n_edges)
+    first = _graph_rows("first", first, lead, (), torch.int32)
+    second = _graph_rows("second", second, lead, (), torch.int32)
+    T = _graph_rows("T", T, lead, (12,), torch.float64)
+    info = _graph_rows("info", info, lead, (21,), torch.float64)
+    shapes = pose_graph_sparse_shapes(n_graphs, n_nodes, n_edges)
+    o = None if out is None else _outputs(shapes, POSE_GRAPH_SPARSE_KEYS, out)
+    if o is not None and o[0].data_ptr() == C3.data_ptr():
+        raise ValueError("out `C` must not be C_in")
+    need = pose_graph_sparse_workspace_bytes(n_graphs, n_nodes, n_edges)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
+                                  workspace.numel() < need or not workspace.is_contiguous()):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    dev = common_device(first, second, T, info, C3, workspace, *(o or ()))
+    o = _outputs(shapes, POSE_GRAPH_SPARSE_KEYS, None, dev) if o is None else o
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _run("pose_graph_sparse", loop().ssll_pose_graph_sparse, (first, second, T, info, C3, ws, *o), _dp(first), _dp(second), _dp(T),
+         _dp(info), n_graphs, n_nodes, n_edges, _dp(C3), C.c_double(chi), C.c_double(damp), n_iter, n_cg, C.c_double(tol), _dp(ws),
+         *(_dp(x) for x in o))
+    return tuple(o)

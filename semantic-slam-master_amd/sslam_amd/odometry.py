@@ -197,7 +197,12 @@ def _check_refine(refine, threshold, huber, iterations) -> None:
 def _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations):
     """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it) -> ((P, 18) float64 device tensor -
     (P, 58) with refine -, refine_poses' dictionary or None).  No host read."""
-    first, second = [a for a, _ in pairs], [b for _, b in pairs]
+    return _launch_lists(pipe, keypoints_pixel, kp_depth, [a for a, _ in pairs], [b for _, b in pairs], matches, camera, threshold, hypotheses,
+                         seed, refine, huber, iterations)
+
+
+def _launch_lists(pipe, keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed, refine, huber, iterations):
+    """_launch on pair lists as match_pairs takes them: host sequences, or int32 device tensors that nothing here reads."""
     est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
     cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
            [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
@@ -330,35 +335,53 @@ def _check_graph(spacings, n_frames, num_pairs, band, huber_chi, damping, graph_
     return tuple(lists), lists, n, band
 
 
+def _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations) -> dict:
+    """The chain of the refined spacing-1 poses and the banded graph over the refined pairs `ref` (refine_poses' dictionary, one row
+    per pair of `pairs`) -> optimize_pose_graph's device tensors.  No host read."""
+    start = None
+    if poses is not None:                                    # the chain of odometry() starts at poses[0]: so does this one
+        c0 = np.linalg.inv(np.asarray(poses, dtype=np.float64)[0])[:3].reshape(1, 12)
+        start = torch.from_numpy(np.ascontiguousarray(c0)).to(ref["T"].device)
+    n1 = len(lists[1])
+    C_init = lib.chain_poses(ref["T"][:n1].contiguous(), n, start=start)[0]
+    return pipe.optimize_pose_graph([a for a, _ in pairs], [b for _, b in pairs], ref, ref, n, C_init=C_init, band=band, huber_chi=huber_chi,
+                                    damping=damping, iterations=graph_iterations)
+
+
+def _graph_flat(g) -> list:
+    """A graph's device tensors as float64 pieces of one read-back, in _graph_host's order."""
+    return [g["C"].reshape(-1)] + [g[key].to(torch.float64).reshape(1) for key in _GRAPH_INT] + \
+           [g["cost_in"].reshape(1), g["cost"].reshape(1), g["edge_chi2"]]
+
+
+def _graph_host(rest, n, pairs, poses) -> dict:
+    """The host-side figures of a graph from the 12 n + 7 + len(pairs) numbers _graph_flat laid out."""
+    C = rest[:12 * n].reshape(n, 3, 4)
+    C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
+    graph = {"trajectory": np.stack([np.linalg.inv(c) for c in C44]), "pairs": pairs}
+    graph.update({key: int(rest[12 * n + i]) for i, key in enumerate(_GRAPH_INT)})
+    graph["cost_in"], graph["cost"] = float(rest[12 * n + 5]), float(rest[12 * n + 6])
+    graph["edge_chi2"] = rest[12 * n + 7:12 * n + 7 + len(pairs)].copy()
+    if poses is not None:
+        graph["ate"] = ate_summary(graph["trajectory"], np.asarray(poses, dtype=np.float64)[:n])
+    return graph
+
+
 def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
            graph_iterations) -> dict:
     """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back."""
     pairs = [pr for s in lists for pr in lists[s]]
     packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
-    start = None
-    if poses is not None:                                    # the chain of odometry() starts at poses[0]: so does this one
-        c0 = np.linalg.inv(np.asarray(poses, dtype=np.float64)[0])[:3].reshape(1, 12)
-        start = torch.from_numpy(np.ascontiguousarray(c0)).to(packed.device)
-    n1 = len(lists[1])
-    C_init = lib.chain_poses(ref["T"][:n1].contiguous(), n, start=start)[0]
-    g = pipe.optimize_pose_graph([a for a, _ in pairs], [b for _, b in pairs], ref, ref, n, C_init=C_init, band=band, huber_chi=huber_chi,
-                                 damping=damping, iterations=graph_iterations)
-    flat = torch.cat([packed.reshape(-1), g["C"].reshape(-1)] + [g[key].to(torch.float64).reshape(1) for key in _GRAPH_INT] +
-                     [g["cost_in"].reshape(1), g["cost"].reshape(1), g["edge_chi2"]]).cpu().numpy()          # the ONE read-back
+    g = _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations)
+    flat = torch.cat([packed.reshape(-1)] + _graph_flat(g)).cpu().numpy()          # the ONE read-back
     P, w = len(pairs), int(packed.shape[1])
     host, rest = flat[:P * w].reshape(P, w), flat[P * w:]
     out, at = {}, 0
     for s in lists:
         out[s] = _unpack(host[at:at + len(lists[s])], lists[s], poses, s, True)
         at += len(lists[s])
-    C = rest[:12 * n].reshape(n, 3, 4)
-    C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
-    graph = {"trajectory": np.stack([np.linalg.inv(c) for c in C44]), "pairs": pairs}
-    graph.update({key: int(rest[12 * n + i]) for i, key in enumerate(_GRAPH_INT)})
-    graph["cost_in"], graph["cost"] = float(rest[12 * n + 5]), float(rest[12 * n + 6])
-    graph["edge_chi2"] = rest[12 * n + 7:].copy()
+    graph = _graph_host(rest, n, pairs, poses)
     if poses is not None:
-        graph["ate"] = ate_summary(graph["trajectory"], np.asarray(poses, dtype=np.float64)[:n])
         graph["ate_chain"] = out[1]["ate"]
     out["graph"] = graph
     return out
@@ -417,3 +440,154 @@ def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=Non
         kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
     return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
                   damping, graph_iterations)
+
+
+# ------------------------------------------------------------------------------------------------------------------ loop closures
+LOOP_DEFAULTS = dict(min_gap=30, min_sim=0.3, per_frame=2, suppress=5, min_inliers=12)
+_LOOP_INT = ("status", "inlier_count")
+
+
+def check_loops(loops, cg_iterations=512, cg_tol=1e-3, prune_chi=None) -> dict:
+    """What the loop-closure arguments can be refused for, before any device work -> LOOP_DEFAULTS with `loops` laid over it.
+    loops: None or True (the defaults) or a dictionary of some of min_gap, min_sim, per_frame, suppress (SequencePipeline.
+    find_loop_candidates) and min_inliers, the fewest inliers of its refined pose that make a candidate an edge."""
+    if loops is None or loops is True:
+        loops = {}
+    if not isinstance(loops, dict) or any(key not in LOOP_DEFAULTS for key in loops):
+        raise ValueError(f"loops must be True or a dictionary of {', '.join(LOOP_DEFAULTS)}, got {loops!r}")
+    opt = dict(LOOP_DEFAULTS, **loops)
+    lib.check_loop_arguments(opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])
+    lib.check_int("min_inliers", opt["min_inliers"], 0)
+    lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
+    if prune_chi is not None:
+        lib.check_positive("prune_chi", prune_chi)
+    return opt
+
+
+def _sparse_flat(r) -> list:
+    return _graph_flat(r) + [r["cg_steps"].to(torch.float64)]
+
+
+def _sparse_host(rest, n, pairs, poses) -> dict:
+    graph = _graph_host(rest, n, pairs, poses)
+    at = 12 * n + 7 + len(pairs)
+    graph["cg_steps"] = rest[at:at + lib.SPARSE_MAX_ITER].astype(np.int64)
+    return graph
+
+
+def _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
+                damping, graph_iterations, opt, cg_iterations, cg_tol, prune_chi) -> dict:
+    """One RANSAC and one refinement launch over the spacings' pairs followed by the candidate slots, the chain and the banded graph
+    over the former, the sparse graph over all of them from the banded graph's poses, ONE read-back."""
+    pairs = [pr for s in lists for pr in lists[s]]
+    P, L, dev = len(pairs), int(cand["first"].shape[0]), kp.device
+    of = torch.tensor([a for a, _ in pairs], dtype=torch.int32, device=dev)
+    first = torch.cat([of, cand["first"]])
+    second = torch.cat([torch.tensor([b for _, b in pairs], dtype=torch.int32, device=dev), cand["second"]])
+    packed, ref = _launch_lists(pipe, kp, kp_depth, first, second, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
+    g = _graph_device(pipe, {key: ref[key][:P] for key in ("T", "info", "status")}, pairs, lists, n, poses, band, huber_chi, damping,
+                      graph_iterations)
+    kept = (cand["first"] >= 0) & (ref["status"][P:] != lib.REFINE_NOT_ATTEMPTED) & (ref["inlier_count"][P:] >= int(opt["min_inliers"]))
+    absent = torch.full_like(first, -1)
+    gfirst = torch.cat([of, torch.where(kept, cand["first"], absent[P:])])
+    sparse = lambda f: pipe.optimize_pose_graph_sparse(f, second, ref, ref, n, g["C"], huber_chi, damping, graph_iterations, cg_iterations, cg_tol)
+    runs = [sparse(gfirst)]
+    if prune_chi is not None:
+        runs.append(sparse(torch.where(runs[0]["edge_chi2"] > float(prune_chi) * float(prune_chi), absent, gfirst)))
+    pieces = [packed.reshape(-1)] + _graph_flat(g) + [x for r in runs for x in _sparse_flat(r)] + \
+             [cand[key].to(torch.float64) for key in ("first", "second", "sim", "count")] + [kept.to(torch.float64)]
+    flat = torch.cat(pieces).cpu().numpy()                  # the ONE read-back
+    w = int(packed.shape[1])
+    host, rest = flat[:(P + L) * w].reshape(P + L, w), flat[(P + L) * w:]
+    out, at = {}, 0
+    for s in lists:
+        out[s] = _unpack(host[at:at + len(lists[s])], lists[s], poses, s, True)
+        at += len(lists[s])
+    graph = _graph_host(rest, n, pairs, poses)
+    if poses is not None:
+        graph["ate_chain"] = out[1]["ate"]
+    out["graph"] = graph
+    rest = rest[12 * n + 7 + P:]
+    tail = rest[len(runs) * (12 * n + 7 + P + L + lib.SPARSE_MAX_ITER):]
+    lf, ls = tail[:L].astype(np.int32), tail[L:2 * L].astype(np.int32)
+    rows = host[P:]
+    r = rows[:, 18:]
+    out["loops"] = {"first": lf, "second": ls, "sim": tail[2 * L:3 * L].astype(np.float32), "count": tail[3 * L:3 * L + n].astype(np.int32),
+                    "kept": tail[3 * L + n:] != 0, "match_count": rows[:, 16].astype(np.int64), "T": _as44(r[:, :12]),
+                    "status": r[:, 12].astype(np.int64), "inlier_count": r[:, 15].astype(np.int64), "info": info_matrix(r[:, 19:40])}
+    all_pairs = pairs + [(int(a), int(b)) for a, b in zip(lf, ls)]
+    names = ["loop_graph"] if prune_chi is None else ["loop_graph_unpruned", "loop_graph"]
+    for name in names:
+        out[name] = _sparse_host(rest, n, all_pairs, poses)
+        rest = rest[12 * n + 7 + P + L + lib.SPARSE_MAX_ITER:]
+    return out
+
+
+def odometry_loop_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, spacings=GRAPH_SPACINGS, num_pairs=None, rule=None,
+                        threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, huber=None, iterations: int = 5, *,
+                        subcell=None, band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8, loops=None,
+                        cg_iterations: int = 512, cg_tol: float = 1e-3, prune_chi=None) -> dict:
+    """odometry_graph() with loop closures: the frames are extracted once; SequencePipeline.find_loop_candidates proposes, for
+    every frame, older frames whose place signature resembles its own (loops: check_loops); ONE match_pairs call matches the
+    spacings' pairs followed by the candidate slots (an empty slot is an absent pair), ONE RANSAC and ONE refinement launch run over
+    that list; the chain and the banded graph run over the spacings' pairs exactly as in odometry_graph; a candidate becomes an
+    edge iff its refinement was attempted and its refined pose has at least min_inliers inliers - decided on the device -; the
+    sparse graph (SequencePipeline.optimize_pose_graph_sparse; cg_iterations, cg_tol) runs over ALL edges from the banded graph's
+    poses; ONE read-back.  prune_chi: when given, a second sparse launch from the same poses without the slots whose edge_chi2
+    after the first exceeds prune_chi * prune_chi.
+    Returns odometry_graph()'s dictionary - every spacing and 'graph' byte for byte - and 'loops': 'first', 'second' (-1: an empty
+    slot), 'sim', 'count' as find_loop_candidates lays them out, 'kept' (the slots that became edges), and per slot 'match_count',
+    'T', 'status', 'inlier_count', 'info' of its refined pose; 'loop_graph': 'trajectory', 'pairs' (the spacings' pairs, then the
+    candidate slots), 'status', 'iterations', 'used_edges', 'skipped_edges', 'failed_row', 'cost_in', 'cost', 'edge_chi2' (one per
+    pair of 'pairs'), 'cg_steps' (16,), with poses 'ate'; with prune_chi 'loop_graph' is the second launch's and
+    'loop_graph_unpruned' the first's.  Nobody has measured this on real RGB-D data."""
+    check_subcell(subcell)
+    src = tokens if tokens is not None else images_u8
+    if src is None:
+        raise ValueError("images_u8 or tokens= required")
+    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
+    opt = check_loops(loops, cg_iterations, cg_tol, prune_chi)
+    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
+    _check_refine(True, threshold, huber, iterations)
+    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
+    ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
+    kp = geometry_bank(ex, subcell)
+    kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
+    cand = pipe.find_loop_candidates(ex["descriptors"], ex["scores"], opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])
+    pairs = [pr for s in lists for pr in lists[s]]
+    dev = kp.device
+    first = torch.cat([torch.tensor([a for a, _ in pairs], dtype=torch.int32, device=dev), cand["first"]])
+    second = torch.cat([torch.tensor([b for _, b in pairs], dtype=torch.int32, device=dev), cand["second"]])
+    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=first, second=second, rule=rule)
+    return _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band,
+                       huber_chi, damping, graph_iterations, opt, cg_iterations, cg_tol, prune_chi)
+
+
+def odometry_result_loop_graph(pipe, result: dict, depth=None, camera=None, poses=None, spacings=None, num_pairs=None, threshold: float = 3.0,
+                               hypotheses: int = 256, seed: int = 0, *, kp_depth=None, huber=None, iterations: int = 5, subcell=None,
+                               band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8, loops=None,
+                               cg_iterations: int = 512, cg_tol: float = 1e-3, prune_chi=None, rule=None) -> dict:
+    """odometry_loop_graph() for a StreamingSequence.result() / run_frames / run_directory result: nothing is extracted again and the
+    spacings' pairs keep the match lists the sequence was run with; only the candidate slots are matched, in one match_pairs call
+    under `rule` (MatchRule.mnn_ratio(0.9) if None - give the rule the sequence was run with).  Everything else: as
+    odometry_result_graph() and odometry_loop_graph() take it."""
+    if not isinstance(result, dict) or "frames" not in result or any(key not in result["frames"] for key in ("keypoints_pixel", "descriptors", "scores")):
+        raise ValueError("a StreamingSequence / run_directory result expected")
+    kp = geometry_bank(result["frames"], subcell)
+    if spacings is None:
+        spacings = tuple(sorted(k for k in result if isinstance(k, (int, np.integer)) and not isinstance(k, bool)))
+    if any(s not in result for s in spacings):
+        raise ValueError(f"the result holds no pairs at every spacing of {tuple(spacings)!r}")
+    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
+    opt = check_loops(loops, cg_iterations, cg_tol, prune_chi)
+    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
+    _check_refine(True, threshold, huber, iterations)
+    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
+    desc, scores = result["frames"]["descriptors"][:n], result["frames"]["scores"][:n]
+    cand = pipe.find_loop_candidates(desc, scores, opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])
+    far = pipe.match_pairs(desc, scores, first=cand["first"], second=cand["second"], rule=rule)
+    matches = {key: torch.cat([result[s][key][:len(lists[s])] for s in lists] + [far[key]]) for key in ("matches", "match_count")}
+    if kp_depth is None:
+        kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
+    return _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band,
+                       huber_chi, damping, graph_iterations, opt, cg_iterations, cg_tol, prune_chi)

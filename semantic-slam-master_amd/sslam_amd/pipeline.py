@@ -935,6 +935,61 @@ class SequencePipeline:
         res = lib.pose_graph(first.contiguous(), second, t_rows, info_rows, C_init, band, huber_chi, damping, iterations)
         return {key: t[0] for key, t in zip(lib.POSE_GRAPH_KEYS, res)}
 
+    def find_loop_candidates(self, descriptors, scores, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2,
+                             suppress: int = 5) -> dict:
+        """Loop-closure candidates (csrc_loop/loop.hip): every frame's place signature - the score-weighted sum of its descriptors,
+        centred on the sequence's mean and normalised - and, for every frame i, up to per_frame older frames j <= i - min_gap
+        whose signature's similarity to i's is at least min_sim, best first, none within `suppress` frames of a better one.
+        descriptors (N, K, descriptor_dim), scores (N, K): what extract() returned.  Returns device tensors in match_pairs'
+        pair-list form: first, second (N * per_frame,) int32 - the older frame and i, both -1 in an empty slot: an absent pair -
+        sim (N * per_frame,) float32, count (N,) int32, and signatures (N, descriptor_dim).  Three launches, no host read."""
+        lib.check_loop_arguments(min_gap, min_sim, per_frame, suppress)
+        sig = lib.frame_signatures(descriptors, scores)
+        res = dict(zip(lib.LOOP_CANDIDATE_KEYS, lib.loop_candidates(sig, min_gap, min_sim, per_frame, suppress)))
+        res["signatures"] = sig
+        return res
+
+    @staticmethod
+    def optimize_pose_graph_sparse(first, second, T, info, n_nodes: int, C_init, huber_chi: float = 4.0, damping: float = 0.0,
+                                   iterations: int = 8, cg_iterations: int = 512, cg_tol: float = 1e-3) -> dict:
+        """The pose graph with edges anywhere (csrc_loop/loop.hip): optimize_pose_graph without a band - loop-closure edges are
+        used like any other - the step solved by block-Jacobi preconditioned conjugate gradients, at most cg_iterations per step,
+        stopped at the relative tolerance cg_tol.  first, second, T, info: as optimize_pose_graph takes them (a refinement status
+        of 3 makes the slot absent, on the device).  C_init (n_nodes, 12) float64 world -> camera is required: the banded graph's
+        C, or the chain.  Returns optimize_pose_graph's device tensors and cg_steps (16,) int32, the CG iterations of every step
+        (include/sslam_loop.h).  One launch, no host read."""
+        if isinstance(n_nodes, bool) or not isinstance(n_nodes, (int, np.integer)) or n_nodes < 1:
+            raise ValueError(f"n_nodes must be an integer >= 1, got {n_nodes!r}")
+        n_nodes = int(n_nodes)
+        status = info.get("status") if isinstance(info, dict) else None
+        t_rows = T["T"] if isinstance(T, dict) and "T" in T else T
+        info_rows = info["info"] if isinstance(info, dict) and "info" in info else info
+        if isinstance(first, torch.Tensor) != isinstance(second, torch.Tensor):
+            raise ValueError("first and second must both be device tensors or both host sequences")
+        host = not isinstance(first, torch.Tensor)
+        if host:
+            fa, fb = [int(v) for v in first], [int(v) for v in second]
+            if len(fa) != len(fb) or not fa:
+                raise ValueError("first and second must name the same number of edges, at least one")
+        lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
+        lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
+        for name, t, cols in (("T", t_rows, 12), ("info", info_rows, 21)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or int(t.shape[1]) != cols or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float64 device tensor of shape (E, {cols}) or a dictionary holding one")
+        n_edges = int(t_rows.shape[0])
+        if int(info_rows.shape[0]) != n_edges or (host and len(fa) != n_edges):
+            raise ValueError(f"{n_edges} transforms for {int(info_rows.shape[0])} information matrices and {len(fa) if host else '?'} edges")
+        if not isinstance(C_init, torch.Tensor) or tuple(C_init.shape) != (n_nodes, 12):
+            raise ValueError(f"C_init must be a float64 device tensor of shape ({n_nodes}, 12)")
+        dev = t_rows.device
+        if host:
+            first = torch.tensor(fa, dtype=torch.int32, device=dev)
+            second = torch.tensor(fb, dtype=torch.int32, device=dev)
+        if status is not None:
+            first = torch.where(status == lib.REFINE_NOT_ATTEMPTED, torch.full_like(first, -1), first)
+        res = lib.pose_graph_sparse(first.contiguous(), second, t_rows, info_rows, C_init, huber_chi, damping, iterations, cg_iterations, cg_tol)
+        return {key: t[0] for key, t in zip(lib.POSE_GRAPH_SPARSE_KEYS, res)}
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
