@@ -1,5 +1,6 @@
 // edge_terms.h - the per-edge arithmetic of include/sslam_graph.h (AN EDGE, JACOBIANS, UPDATE), shared by csrc_graph/pose_graph.hip and
-// csrc_loop/loop.hip: one statement of it, so both libraries give the same bits.  Included inside an anonymous namespace.
+// csrc_loop/loop.hip: one statement of it, so both libraries give the same bits.  Included inside an anonymous namespace, through
+// gauss_newton.h (the driver that calls it).
 #pragma once
 
 constexpr int STAGE = 90;           // words staged per edge: BB 21, BA 36, AA 21, GB 6, GA 6

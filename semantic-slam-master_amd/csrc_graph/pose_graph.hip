@@ -1,7 +1,9 @@
 // pose_graph.hip - libsslam_graph.so: the pose graph over relative poses and their information matrices (include/sslam_graph.h
 // states the arithmetic operation by operation; tests/pose_graph_ref.py restates it in numpy float64).
 //   sslg_chain_poses   world -> camera poses from consecutive transforms, one thread per chain: the initial guess.
-//   sslg_pose_graph    one 256-thread workgroup per graph: Gauss-Newton with a Huber weight per edge, node 0 the anchor.
+//   sslg_pose_graph    one 256-thread workgroup per graph: Gauss-Newton with a Huber weight per edge, node 0 the anchor.  The
+//                      driver (the slot counts, the costs, the trial poses, the accept rule, the status words) is gauss_newton.h's,
+//                      shared with csrc_loop/loop.hip; this file is the banded solve it calls, BandedSolver::step.
 // A step of sslg_pose_graph:
 //   assembly       256 edges at a time are STAGED, one thread per edge (the residual, w, and the 90 products w H, -(w H Ad),
 //                  w Ad^T H Ad, w H r, -(w Ad^T H r)), then WALKED in slot order by four groups of 63 threads: a thread owns one entry
@@ -28,7 +30,7 @@ namespace {
 constexpr int NT = 256;
 constexpr int WAVES = NT / 64;
 
-#include "edge_terms.h"           // STAGE, S_*: the words staged per edge; fin, the pose products, Edge, edge_eval, edge_stage, pose_update
+#include "gauss_newton.h"         // the driver: block_sum, block_count, Graph, edge_used, graph_cost, gauss_newton, graph_operands; edge_terms.h
 
 constexpr int WALK = 63;            // entry positions a walking group owns: 21 diagonal, 36 off-diagonal, 6 of g
 constexpr int GROUPS = 4;
@@ -36,148 +38,26 @@ constexpr int TQ = (6 * SSLG_MAX_BAND + 5 + 15) / 16;      // columns of the tra
 
 long long g_launches = 0;   // diagnostic launch counter (sslg_launch_count): relaxed atomic adds, the library's only mutable state
 
-inline bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
-inline bool finite_nonnegative(double v) { return v >= 0.0 && v - v == 0.0; }
-inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 // lane t's x, for a t the compiler knows (two v_readlane_b32)
 __device__ __forceinline__ double lane_value(double x, int t) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(x), t), hi = __builtin_amdgcn_readlane(__double2hiint(x), t);
     return __hiloint2double(hi, lo);
 }
 
-__device__ __forceinline__ double block_sum(double p, double *wsum, int tid) {
-    p = p + __shfl_xor(p, 32);
-    p = p + __shfl_xor(p, 16);
-    p = p + __shfl_xor(p, 8);
-    p = p + __shfl_xor(p, 4);
-    p = p + __shfl_xor(p, 2);
-    p = p + __shfl_xor(p, 1);
-    if ((tid & 63) == 0) wsum[tid >> 6] = p;
-    __syncthreads();
-    p = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    __syncthreads();                                     // wsum may be written again
-    return p;
-}
+// the banded solve: the normal equations of one graph in the workspace (A by rows of W words, then g, y, delta), the window and
+// the ring in LDS
+struct BandedSolver {
+    const Graph &g;
+    const double *C;
+    double chi, damping;
+    double *Ab, *gv, *yv, *dv, *stage, *win, *ring;
+    int *sa, *sb;                                        // the staged edges' nodes; sb < 0: not used
+    int n, bw, W, M;
 
-__device__ __forceinline__ int block_count(int n, int *wcnt, int tid) {
-    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = n;
-    __syncthreads();
-    n = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-    __syncthreads();
-    return n;
-}
+    __device__ __forceinline__ void prepare() {}
 
-struct Graph {
-    const int *first, *second;
-    const double *T, *info;
-    int n_nodes, n_edges, band;
-};
-
-__device__ __forceinline__ bool edge_used(const Graph &g, int e, int &a, int &b) {
-    a = g.first[e];
-    b = g.second[e];
-    if (!(0 <= a && a < b && b < g.n_nodes && b - a <= g.band)) return false;
-    bool ok = true;
-    const double *t = g.T + (long long)e * 12, *h = g.info + (long long)e * 21;
-    for (int k = 0; k < 12; k++) ok = ok && fin(t[k]);
-    for (int k = 0; k < 21; k++) ok = ok && fin(h[k]);
-    return ok;
-}
-
-// the cost at the poses X, in the pass' order; with chi2, s of every used edge (+0.0 elsewhere) is written there
-__device__ __forceinline__ double graph_cost(const Graph &g, const double *X, double chi, double *chi2, double *wsum, int tid) {
-    double part = 0.0;
-    for (int e = tid; e < g.n_edges; e += NT) {
-        int a, b;
-        double rho = 0.0, s = 0.0;
-        if (edge_used(g, e, a, b)) {
-            Edge ed;
-            edge_eval(X + (long long)a * 12, X + (long long)b * 12, g.T + (long long)e * 12, g.info + (long long)e * 21, chi, ed);
-            rho = ed.rho;
-            s = ed.s;
-        }
-        part = part + rho;
-        if (chi2) chi2[e] = s;
-    }
-    return block_sum(part, wsum, tid);
-}
-
-__global__ __launch_bounds__(NT) void pose_graph_kernel(const int *__restrict__ edge_first, const int *__restrict__ edge_second,
-                                                        const double *__restrict__ edge_T, const double *__restrict__ edge_info,
-                                                        int n_nodes, int n_edges, const double *__restrict__ C_in, int band, double chi,
-                                                        double damping, int n_iter, double *workspace, long long ws_words, double *C,
-                                                        int *__restrict__ status, int *__restrict__ iterations,
-                                                        int *__restrict__ used_edges, int *__restrict__ skipped_edges,
-                                                        int *__restrict__ failed_row, double *__restrict__ cost_in,
-                                                        double *__restrict__ cost_out, double *__restrict__ edge_chi2) {
-    extern __shared__ double dyn[];                      // win: M (M + 1) / 2 words, then ring: M words (y, later delta)
-    __shared__ double wsum[WAVES];
-    __shared__ int wcnt[WAVES];
-    __shared__ int sa[NT], sb[NT];                       // the staged edges' nodes; sb < 0: not used
-
-    const int tid = threadIdx.x;
-    const long long gi = blockIdx.x;
-    Graph g;
-    g.first = edge_first + gi * n_edges;
-    g.second = edge_second + gi * n_edges;
-    g.T = edge_T + gi * n_edges * 12;
-    g.info = edge_info + gi * n_edges * 21;
-    g.n_nodes = n_nodes;
-    g.n_edges = n_edges;
-    g.band = band;
-    C_in += gi * n_nodes * 12;
-    C += gi * n_nodes * 12;
-    edge_chi2 += gi * n_edges;
-
-    const int n = 6 * (n_nodes - 1), bw = 6 * band + 5, W = bw + 1, M = W;
-    double *win = dyn, *ring = dyn + (M * (M + 1)) / 2;
-    double *Ab = workspace + gi * ws_words;
-    double *gv = Ab + (long long)n * W, *yv = gv + n, *dv = yv + n;
-    double *trial = dv + n;
-    double *stage = trial + (long long)n_nodes * 12;
-
-    // ---- C <- C_in; the edge counts; whether anything is attempted
-    int bad = 0, used = 0, skipped = 0;
-    for (int k = tid; k < n_nodes * 12; k += NT) {
-        const double v = C_in[k];
-        C[k] = v;
-        bad += !fin(v);
-    }
-    for (int e = tid; e < n_edges; e += NT) {
-        int a, b;
-        const bool u = edge_used(g, e, a, b);
-        used += u;
-        skipped += !u && a != -1;
-    }
-    bad = block_count(bad, wcnt, tid);
-    used = block_count(used, wcnt, tid);
-    skipped = block_count(skipped, wcnt, tid);
-    if (tid == 0) {
-        used_edges[gi] = used;
-        skipped_edges[gi] = skipped;
-    }
-    if (bad != 0 || used == 0) {                         // not attempted (uniform)
-        for (int e = tid; e < n_edges; e += NT) edge_chi2[e] = 0.0;
-        if (tid == 0) {
-            status[gi] = 3;
-            iterations[gi] = 0;
-            failed_row[gi] = -1;
-            cost_in[gi] = 0.0;
-            cost_out[gi] = 0.0;
-        }
-        return;
-    }
-    __syncthreads();                                     // C is read below by other threads than wrote it
-
-    const double c_in = graph_cost(g, C, chi, nullptr, wsum, tid);
-    double cur_cost = c_in;
-    int accepted = 0, failed = -1;
-    bool first_failed = false;
-
-#pragma unroll 1
-    for (int it = 0; it < n_iter; it++) {
+    __device__ __forceinline__ int step(int, const double *&delta) {
+        const int tid = threadIdx.x, n_edges = g.n_edges;
         // ---- assembly at the current poses
         for (long long k = tid; k < (long long)n * W + n; k += NT) Ab[k] = 0.0;      // A and g
         __syncthreads();
@@ -314,11 +194,7 @@ __global__ __launch_bounds__(NT) void pose_graph_kernel(const int *__restrict__ 
             }
             jm = jm + 1 == M ? 0 : jm + 1;
         }
-        if (fail >= 0) {
-            failed = fail;
-            first_failed = it == 0;
-            break;
-        }
+        if (fail >= 0) return fail;
 
         // ---- backward, by rows, in the first wave alone: lane t holds delta_{i+1+t+64q} and L_{i+1+t+64q, i} (q < 4: bw < 256) in
         // registers, the products are formed in parallel, every lane subtracts them in ascending k (a lane's product read by
@@ -362,41 +238,35 @@ __global__ __launch_bounds__(NT) void pose_graph_kernel(const int *__restrict__ 
             }
         }
         __syncthreads();
-
-        // ---- the trial poses and their cost
-        for (int m = tid; m < n_nodes; m += NT) {
-            double cm[12], out[12];
-#pragma unroll
-            for (int k = 0; k < 12; k++) cm[k] = C[(long long)m * 12 + k];
-            if (m == 0) {
-#pragma unroll
-                for (int k = 0; k < 12; k++) out[k] = cm[k];
-            } else {
-                double delta[6];
-#pragma unroll
-                for (int k = 0; k < 6; k++) delta[k] = dv[6 * (m - 1) + k];
-                pose_update(cm, delta, out);
-            }
-#pragma unroll
-            for (int k = 0; k < 12; k++) trial[(long long)m * 12 + k] = out[k];
-        }
-        __syncthreads();
-        const double c_trial = graph_cost(g, trial, chi, nullptr, wsum, tid);
-        if (!(fin(c_trial) && c_trial < cur_cost)) break;      // uniform: every thread holds the same total
-        cur_cost = c_trial;
-        accepted++;
-        for (int k = tid; k < n_nodes * 12; k += NT) C[k] = trial[k];
-        __syncthreads();
+        delta = dv;
+        return -1;
     }
+};
 
-    graph_cost(g, C, chi, edge_chi2, wsum, tid);
-    if (tid == 0) {
-        status[gi] = accepted > 0 ? 0 : (first_failed ? 2 : 1);
-        iterations[gi] = accepted;
-        failed_row[gi] = failed;
-        cost_in[gi] = c_in;
-        cost_out[gi] = cur_cost;
-    }
+__global__ __launch_bounds__(NT) void pose_graph_kernel(const int *__restrict__ edge_first, const int *__restrict__ edge_second,
+                                                        const double *__restrict__ edge_T, const double *__restrict__ edge_info,
+                                                        int n_nodes, int n_edges, const double *__restrict__ C_in, int band, double chi,
+                                                        double damping, int n_iter, double *workspace, long long ws_words, double *C,
+                                                        int *__restrict__ status, int *__restrict__ iterations,
+                                                        int *__restrict__ used_edges, int *__restrict__ skipped_edges,
+                                                        int *__restrict__ failed_row, double *__restrict__ cost_in,
+                                                        double *__restrict__ cost_out, double *__restrict__ edge_chi2) {
+    extern __shared__ double dyn[];                      // win: M (M + 1) / 2 words, then ring: M words (y, later delta)
+    __shared__ double wsum[WAVES];
+    __shared__ int wcnt[WAVES];
+    __shared__ int sa[NT], sb[NT];
+
+    const long long gi = blockIdx.x;
+    const Graph g = graph_of(edge_first, edge_second, edge_T, edge_info, n_nodes, n_edges, band, gi);
+    C += gi * n_nodes * 12;
+
+    const int n = 6 * (n_nodes - 1), bw = 6 * band + 5, W = bw + 1, M = W;
+    double *Ab = workspace + gi * ws_words;
+    double *gv = Ab + (long long)n * W, *yv = gv + n, *dv = yv + n;
+    double *trial = dv + n;
+    BandedSolver solver{g, C, chi, damping, Ab, gv, yv, dv, trial + (long long)n_nodes * 12, dyn, dyn + (M * (M + 1)) / 2, sa, sb, n, bw, W, M};
+    gauss_newton(solver, g, C_in + gi * n_nodes * 12, C, trial, chi, n_iter, wsum, wcnt,
+                 GraphOut{status, iterations, used_edges, skipped_edges, failed_row, cost_in, cost_out, edge_chi2 + gi * n_edges}, gi);
 }
 
 __global__ __launch_bounds__(NT) void chain_kernel(const double *__restrict__ T, const double *__restrict__ C_start, int n_graphs,
@@ -461,18 +331,10 @@ extern "C" int sslg_pose_graph(const int32_t *edge_first, const int32_t *edge_se
                                int n_iter, void *workspace, double *C, int32_t *status, int32_t *iterations, int32_t *used_edges,
                                int32_t *skipped_edges, int32_t *failed_row, double *cost_in, double *cost, double *edge_chi2,
                                void *stream) {
-    if (!edge_first || !edge_second || !edge_T || !edge_info || !C_in || !workspace || !C || !status || !iterations || !used_edges ||
-        !skipped_edges || !failed_row || !cost_in || !cost || !edge_chi2)
+    if (graph_operands(edge_first, edge_second, edge_T, edge_info, C_in, huber_chi, damping, n_iter, SSLG_GRAPH_MAX_ITER, workspace, C,
+                       status, iterations, used_edges, skipped_edges, failed_row, cost_in, cost, edge_chi2) != SSLAM_OK)
         return SSLAM_E_INVALID;
     if (n_edges <= 0 || graph_shape(n_graphs, n_nodes, band) == SSLAM_E_INVALID) return SSLAM_E_INVALID;
-    if (!finite_positive(huber_chi) || !finite_nonnegative(damping) || n_iter < 0 || n_iter > SSLG_GRAPH_MAX_ITER || C == C_in)
-        return SSLAM_E_INVALID;
-    for (const void *p : {(const void *)edge_T, (const void *)edge_info, (const void *)C_in, (const void *)workspace, (const void *)C,
-                          (const void *)cost_in, (const void *)cost, (const void *)edge_chi2})
-        if (misaligned(p, 8)) return SSLAM_E_INVALID;
-    for (const void *p : {(const void *)edge_first, (const void *)edge_second, (const void *)status, (const void *)iterations,
-                          (const void *)used_edges, (const void *)skipped_edges, (const void *)failed_row})
-        if (misaligned(p, 4)) return SSLAM_E_INVALID;
     if (graph_shape(n_graphs, n_nodes, band) != SSLAM_OK || n_edges > SSLG_MAX_EDGES) return SSLAM_E_UNSUPPORTED;
     const int M = 6 * band + 6;
     const size_t lds = ((size_t)M * (M + 1) / 2 + M) * sizeof(double);      // the window and the ring: 159 192 bytes at band 32

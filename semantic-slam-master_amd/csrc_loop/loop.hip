@@ -5,8 +5,9 @@
 //                            workgroup per 32 frames; each forms the mean anew, in frame order, so no workgroup waits for another).
 //   ssll_loop_candidates     one 256-thread workgroup per frame i: S_ij of the older frames into LDS, thread t the frames t, t + 256,
 //                            ..., each one fmaf chain; then per_frame block-wide arg-max picks with suppression around each.
-//   ssll_pose_graph_sparse   one 256-thread workgroup per graph: Gauss-Newton as sslg_pose_graph, the step by block-Jacobi
-//                            preconditioned conjugate gradients.  Per launch the incidence lists (node -> its used slots, ascending);
+//   ssll_pose_graph_sparse   one 256-thread workgroup per graph: sslg_pose_graph's Gauss-Newton driver itself
+//                            (csrc_graph/gauss_newton.h), the step (SparseSolver::step) by block-Jacobi preconditioned
+//                            conjugate gradients.  Per launch (SparseSolver::prepare) the incidence lists (node -> its used slots, ascending);
 //                            per step every used slot's 90 words are STAGED (csrc_graph/edge_terms.h: the same code as the banded
 //                            kernel), a thread per (node, entry) adds a node's terms in list order, a thread per node factorises
 //                            its block; a CG iteration is a thread per row for q = A p and the products, a thread per node for
@@ -23,13 +24,10 @@ constexpr int WAVES = NT / 64;
 constexpr int NODE_WORDS = 27;      // entry positions of a node: 21 of D_m's lower triangle, 6 of g_m
 constexpr int NO_ROW = 0x7fffffff;
 
-#include "../csrc_graph/edge_terms.h"           // STAGE, S_*, fin, tri_lower, the pose products, Edge, edge_eval, edge_stage, pose_update
+#include "../csrc_graph/gauss_newton.h"         // the driver and, through it, edge_terms.h: the same code as the banded kernel
 
 long long g_launches = 0;   // diagnostic launch counter (ssll_launch_count): relaxed atomic adds, the library's only mutable state
 
-inline bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
-inline bool finite_nonnegative(double v) { return v >= 0.0 && v - v == 0.0; }
-inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 inline bool width_ok(int d) { return d == 128 || d == 256; }
 
 // ------------------------------------------------------------------------------------------------------------ signatures
@@ -135,29 +133,6 @@ __global__ __launch_bounds__(NT) void candidates_kernel(const float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ the sparse graph
-__device__ __forceinline__ double block_sum(double p, double *wsum, int tid) {
-    p = p + __shfl_xor(p, 32);
-    p = p + __shfl_xor(p, 16);
-    p = p + __shfl_xor(p, 8);
-    p = p + __shfl_xor(p, 4);
-    p = p + __shfl_xor(p, 2);
-    p = p + __shfl_xor(p, 1);
-    if ((tid & 63) == 0) wsum[tid >> 6] = p;
-    __syncthreads();
-    p = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    __syncthreads();                                     // wsum may be written again
-    return p;
-}
-
-__device__ __forceinline__ int block_count(int n, int *wcnt, int tid) {
-    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = n;
-    __syncthreads();
-    n = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-    __syncthreads();
-    return n;
-}
-
 __device__ __forceinline__ int block_min(int n, int *wcnt, int tid) {
     for (int o = 32; o >= 1; o >>= 1) {
         const int v = __shfl_xor(n, o);
@@ -168,41 +143,6 @@ __device__ __forceinline__ int block_min(int n, int *wcnt, int tid) {
     for (int w = 0; w < WAVES; w++) n = wcnt[w] < n ? wcnt[w] : n;
     __syncthreads();
     return n;
-}
-
-struct Graph {
-    const int *first, *second;
-    const double *T, *info;
-    int n_nodes, n_edges;
-};
-
-__device__ __forceinline__ bool edge_used(const Graph &g, int e, int &a, int &b) {
-    a = g.first[e];
-    b = g.second[e];
-    if (!(0 <= a && a < b && b < g.n_nodes)) return false;
-    bool ok = true;
-    const double *t = g.T + (long long)e * 12, *h = g.info + (long long)e * 21;
-    for (int k = 0; k < 12; k++) ok = ok && fin(t[k]);
-    for (int k = 0; k < 21; k++) ok = ok && fin(h[k]);
-    return ok;
-}
-
-// the cost at the poses X, in the pass' order; with chi2, s of every used edge (+0.0 elsewhere) is written there
-__device__ __forceinline__ double graph_cost(const Graph &g, const double *X, double chi, double *chi2, double *wsum, int tid) {
-    double part = 0.0;
-    for (int e = tid; e < g.n_edges; e += NT) {
-        int a, b;
-        double rho = 0.0, s = 0.0;
-        if (edge_used(g, e, a, b)) {
-            Edge ed;
-            edge_eval(X + (long long)a * 12, X + (long long)b * 12, g.T + (long long)e * 12, g.info + (long long)e * 21, chi, ed);
-            rho = ed.rho;
-            s = ed.s;
-        }
-        part = part + rho;
-        if (chi2) chi2[e] = s;
-    }
-    return block_sum(part, wsum, tid);
 }
 
 // u . v over the n rows, in the cost's order
@@ -234,143 +174,80 @@ inline long long workspace_words(int n_nodes, int n_edges) {      // per graph
     return 90 * E + 78 * nn + 12 * N + (N + 1 + 2 * E + 1) / 2;
 }
 
-__global__ __launch_bounds__(NT) void sparse_kernel(const int *__restrict__ edge_first, const int *__restrict__ edge_second,
-                                                    const double *__restrict__ edge_T, const double *__restrict__ edge_info,
-                                                    int n_nodes, int n_edges, const double *__restrict__ C_in, double chi, double damping,
-                                                    int n_iter, int cg_iterations, double cg_tol, double *workspace, long long ws_words,
-                                                    double *C, int *__restrict__ status, int *__restrict__ iterations,
-                                                    int *__restrict__ used_edges, int *__restrict__ skipped_edges,
-                                                    int *__restrict__ failed_row, double *__restrict__ cost_in,
-                                                    double *__restrict__ cost_out, double *__restrict__ edge_chi2,
-                                                    int *__restrict__ cg_steps) {
-    __shared__ double wsum[WAVES];
-    __shared__ int wcnt[WAVES];
-    __shared__ int sa[NT], sb[NT];                       // a chunk's nodes while the lists are filled; -1: not used
-    __shared__ int cur[SSLL_MAX_NODES + 1];              // per node: its count, then the cursor into its list
-    __shared__ int seg[NT];
-    __shared__ int steps_of[SSLL_GRAPH_MAX_ITER];
+// the sparse solve: one graph's staged terms, blocks, CG vectors and incidence lists in the workspace, the list cursors in LDS
+struct SparseSolver {
+    const Graph &g;
+    const double *C;
+    double chi, damping, tol2;
+    int cg_iterations;
+    double *stage, *Dl, *Lf, *gv, *xv, *rv, *zv, *pv, *qv;
+    int *off, *list;
+    double *wsum;
+    int *wcnt, *sa, *sb, *cur, *seg, *steps_of;          // sa, sb: a chunk's nodes while the lists are filled; -1: not used
 
-    const int tid = threadIdx.x;
-    const long long gi = blockIdx.x;
-    Graph g;
-    g.first = edge_first + gi * n_edges;
-    g.second = edge_second + gi * n_edges;
-    g.T = edge_T + gi * n_edges * 12;
-    g.info = edge_info + gi * n_edges * 21;
-    g.n_nodes = n_nodes;
-    g.n_edges = n_edges;
-    C_in += gi * n_nodes * 12;
-    C += gi * n_nodes * 12;
-    edge_chi2 += gi * n_edges;
-    cg_steps += gi * SSLL_GRAPH_MAX_ITER;
-
-    const int nn = n_nodes - 1, n = 6 * nn;
-    double *stage = workspace + gi * ws_words;
-    double *Dl = stage + (long long)STAGE * n_edges, *Lf = Dl + 21 * nn;
-    double *gv = Lf + 21 * nn, *xv = gv + n, *rv = xv + n, *zv = rv + n, *pv = zv + n, *qv = pv + n;
-    double *trial = qv + n;
-    int *off = reinterpret_cast<int *>(trial + (long long)n_nodes * 12), *list = off + n_nodes + 1;
-
-    // ---- C <- C_in; the edge counts; whether anything is attempted
-    int bad = 0, used = 0, skipped = 0;
-    for (int k = tid; k < n_nodes * 12; k += NT) {
-        const double v = C_in[k];
-        C[k] = v;
-        bad += !fin(v);
-    }
-    for (int e = tid; e < n_edges; e += NT) {
-        int a, b;
-        const bool u = edge_used(g, e, a, b);
-        used += u;
-        skipped += !u && a != -1;
-    }
-    if (tid < SSLL_GRAPH_MAX_ITER) steps_of[tid] = 0;
-    bad = block_count(bad, wcnt, tid);
-    used = block_count(used, wcnt, tid);
-    skipped = block_count(skipped, wcnt, tid);
-    if (tid == 0) {
-        used_edges[gi] = used;
-        skipped_edges[gi] = skipped;
-    }
-    if (bad != 0 || used == 0) {                         // not attempted (uniform)
-        for (int e = tid; e < n_edges; e += NT) edge_chi2[e] = 0.0;
-        if (tid < SSLL_GRAPH_MAX_ITER) cg_steps[tid] = 0;
-        if (tid == 0) {
-            status[gi] = 3;
-            iterations[gi] = 0;
-            failed_row[gi] = -1;
-            cost_in[gi] = 0.0;
-            cost_out[gi] = 0.0;
-        }
-        return;
-    }
-
-    // ---- the incidence lists: counts, an exclusive scan, then the slots a chunk at a time, in slot order
-    for (int m = tid; m <= n_nodes; m += NT) cur[m] = 0;
-    __syncthreads();
-    for (int e = tid; e < n_edges; e += NT) {
-        int a, b;
-        if (edge_used(g, e, a, b)) {
-            atomicAdd(&cur[b], 1);
-            if (a >= 1) atomicAdd(&cur[a], 1);
-        }
-    }
-    __syncthreads();
-    {
-        const int per = (n_nodes + NT - 1) / NT, m0 = tid * per, m1 = m0 + per < n_nodes ? m0 + per : n_nodes;
-        int sum = 0;
-        for (int m = m0; m < m1; m++) sum += cur[m];
-        seg[tid] = sum;
+    __device__ __forceinline__ void prepare() {
+        const int tid = threadIdx.x, n_nodes = g.n_nodes, n_edges = g.n_edges;
+        // ---- the incidence lists: counts, an exclusive scan, then the slots a chunk at a time, in slot order
+        for (int m = tid; m <= n_nodes; m += NT) cur[m] = 0;
         __syncthreads();
-        int run = 0;
-        for (int t = 0; t < tid; t++) run += seg[t];
-        for (int m = m0; m < m1; m++) {
-            const int c = cur[m];
-            off[m] = run;
-            cur[m] = run;
-            run += c;
-        }
-        if (tid == NT - 1) off[n_nodes] = run;           // the last thread's segment ends the nodes (or is empty, after them)
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int base = 0; base < n_edges; base += NT) {
-        const int e = base + tid;
-        int a = -1, b = -1;
-        const bool u = e < n_edges && edge_used(g, e, a, b);
-        sa[tid] = u ? a : -1;
-        sb[tid] = u ? b : -1;
-        __syncthreads();
-        int rank_a = 0, tot_a = 0, rank_b = 0, tot_b = 0;
-        if (u) {
-            const int cnt = n_edges - base < NT ? n_edges - base : NT;
-            for (int c = 0; c < cnt; c++) {
-                const int ca = sa[c], cb = sb[c];
-                const int ha = (ca == a) + (cb == a), hb = (ca == b) + (cb == b);
-                tot_a += ha;
-                tot_b += hb;
-                rank_a += c < tid ? ha : 0;
-                rank_b += c < tid ? hb : 0;
+        for (int e = tid; e < n_edges; e += NT) {
+            int a, b;
+            if (edge_used(g, e, a, b)) {
+                atomicAdd(&cur[b], 1);
+                if (a >= 1) atomicAdd(&cur[a], 1);
             }
-            list[cur[b] + rank_b] = 2 * e;
-            if (a >= 1) list[cur[a] + rank_a] = 2 * e + 1;
         }
         __syncthreads();
-        if (u) {                                             // the last of a node's entries in the chunk moves its cursor
-            if (rank_b + 1 == tot_b) cur[b] += tot_b;
-            if (a >= 1 && rank_a + 1 == tot_a) cur[a] += tot_a;
+        {
+            const int per = (n_nodes + NT - 1) / NT, m0 = tid * per, m1 = m0 + per < n_nodes ? m0 + per : n_nodes;
+            int sum = 0;
+            for (int m = m0; m < m1; m++) sum += cur[m];
+            seg[tid] = sum;
+            __syncthreads();
+            int run = 0;
+            for (int t = 0; t < tid; t++) run += seg[t];
+            for (int m = m0; m < m1; m++) {
+                const int c = cur[m];
+                off[m] = run;
+                cur[m] = run;
+                run += c;
+            }
+            if (tid == NT - 1) off[n_nodes] = run;           // the last thread's segment ends the nodes (or is empty, after them)
         }
         __syncthreads();
+#pragma unroll 1
+        for (int base = 0; base < n_edges; base += NT) {
+            const int e = base + tid;
+            int a = -1, b = -1;
+            const bool u = e < n_edges && edge_used(g, e, a, b);
+            sa[tid] = u ? a : -1;
+            sb[tid] = u ? b : -1;
+            __syncthreads();
+            int rank_a = 0, tot_a = 0, rank_b = 0, tot_b = 0;
+            if (u) {
+                const int cnt = n_edges - base < NT ? n_edges - base : NT;
+                for (int c = 0; c < cnt; c++) {
+                    const int ca = sa[c], cb = sb[c];
+                    const int ha = (ca == a) + (cb == a), hb = (ca == b) + (cb == b);
+                    tot_a += ha;
+                    tot_b += hb;
+                    rank_a += c < tid ? ha : 0;
+                    rank_b += c < tid ? hb : 0;
+                }
+                list[cur[b] + rank_b] = 2 * e;
+                if (a >= 1) list[cur[a] + rank_a] = 2 * e + 1;
+            }
+            __syncthreads();
+            if (u) {                                             // the last of a node's entries in the chunk moves its cursor
+                if (rank_b + 1 == tot_b) cur[b] += tot_b;
+                if (a >= 1 && rank_a + 1 == tot_a) cur[a] += tot_a;
+            }
+            __syncthreads();
+        }
     }
 
-    const double c_in = graph_cost(g, C, chi, nullptr, wsum, tid);
-    double cur_cost = c_in;
-    int accepted = 0, failed = -1;
-    bool first_failed = false;
-    const double tol2 = cg_tol * cg_tol;
-
-#pragma unroll 1
-    for (int it = 0; it < n_iter; it++) {
+    __device__ __forceinline__ int step(int it, const double *&delta) {
+        const int tid = threadIdx.x, n_edges = g.n_edges, nn = g.n_nodes - 1, n = 6 * nn;
         // ---- every used slot's terms at the current poses
 #pragma unroll 1
         for (int e = tid; e < n_edges; e += NT) {
@@ -437,11 +314,7 @@ __global__ __launch_bounds__(NT) void sparse_kernel(const int *__restrict__ edge
             }
         }
         fail = block_min(fail, wcnt, tid);                   // its barriers also publish r, z, p
-        if (fail != NO_ROW) {                                // uniform
-            failed = fail;
-            first_failed = it == 0;
-            break;
-        }
+        if (fail != NO_ROW) return fail;                     // uniform
 
         // ---- conjugate gradients
         double rz = dot(rv, zv, n, wsum, tid);
@@ -496,43 +369,47 @@ __global__ __launch_bounds__(NT) void sparse_kernel(const int *__restrict__ edge
             __syncthreads();
         }
         if (tid == 0) steps_of[it] = steps;
-        __syncthreads();                                     // x is read below by other threads than wrote it
-
-        // ---- the trial poses and their cost
-        for (int m = tid; m < n_nodes; m += NT) {
-            double cm[12], out[12];
-#pragma unroll
-            for (int k = 0; k < 12; k++) cm[k] = C[(long long)m * 12 + k];
-            if (m == 0) {
-#pragma unroll
-                for (int k = 0; k < 12; k++) out[k] = cm[k];
-            } else {
-                double delta[6];
-#pragma unroll
-                for (int k = 0; k < 6; k++) delta[k] = xv[6 * (m - 1) + k];
-                pose_update(cm, delta, out);
-            }
-#pragma unroll
-            for (int k = 0; k < 12; k++) trial[(long long)m * 12 + k] = out[k];
-        }
-        __syncthreads();
-        const double c_trial = graph_cost(g, trial, chi, nullptr, wsum, tid);
-        if (!(fin(c_trial) && c_trial < cur_cost)) break;      // uniform: every thread holds the same total
-        cur_cost = c_trial;
-        accepted++;
-        for (int k = tid; k < n_nodes * 12; k += NT) C[k] = trial[k];
-        __syncthreads();
+        __syncthreads();                                     // x is read next by other threads than wrote it
+        delta = xv;
+        return -1;
     }
+};
 
-    graph_cost(g, C, chi, edge_chi2, wsum, tid);             // its barriers also publish steps_of
-    if (tid < SSLL_GRAPH_MAX_ITER) cg_steps[tid] = steps_of[tid];
-    if (tid == 0) {
-        status[gi] = accepted > 0 ? 0 : (first_failed ? 2 : 1);
-        iterations[gi] = accepted;
-        failed_row[gi] = failed;
-        cost_in[gi] = c_in;
-        cost_out[gi] = cur_cost;
-    }
+__global__ __launch_bounds__(NT) void sparse_kernel(const int *__restrict__ edge_first, const int *__restrict__ edge_second,
+                                                    const double *__restrict__ edge_T, const double *__restrict__ edge_info,
+                                                    int n_nodes, int n_edges, const double *__restrict__ C_in, double chi, double damping,
+                                                    int n_iter, int cg_iterations, double cg_tol, double *workspace, long long ws_words,
+                                                    double *C, int *__restrict__ status, int *__restrict__ iterations,
+                                                    int *__restrict__ used_edges, int *__restrict__ skipped_edges,
+                                                    int *__restrict__ failed_row, double *__restrict__ cost_in,
+                                                    double *__restrict__ cost_out, double *__restrict__ edge_chi2,
+                                                    int *__restrict__ cg_steps) {
+    __shared__ double wsum[WAVES];
+    __shared__ int wcnt[WAVES];
+    __shared__ int sa[NT], sb[NT];
+    __shared__ int cur[SSLL_MAX_NODES + 1];              // per node: its count, then the cursor into its list
+    __shared__ int seg[NT];
+    __shared__ int steps_of[SSLL_GRAPH_MAX_ITER];
+
+    const int tid = threadIdx.x;
+    const long long gi = blockIdx.x;
+    const Graph g = graph_of(edge_first, edge_second, edge_T, edge_info, n_nodes, n_edges, n_nodes, gi);      // no band: b - a < n_nodes
+    C += gi * n_nodes * 12;
+
+    const int nn = n_nodes - 1, n = 6 * nn;
+    double *stage = workspace + gi * ws_words;
+    double *Dl = stage + (long long)STAGE * n_edges, *Lf = Dl + 21 * nn;
+    double *gv = Lf + 21 * nn, *xv = gv + n, *rv = xv + n, *zv = rv + n, *pv = zv + n, *qv = pv + n;
+    double *trial = qv + n;
+    int *off = reinterpret_cast<int *>(trial + (long long)n_nodes * 12), *list = off + n_nodes + 1;
+
+    if (tid < SSLL_GRAPH_MAX_ITER) steps_of[tid] = 0;    // the driver's first barriers publish it
+    SparseSolver solver{g, C, chi, damping, cg_tol * cg_tol, cg_iterations, stage, Dl, Lf, gv, xv, rv, zv, pv, qv, off, list,
+                        wsum, wcnt, sa, sb, cur, seg, steps_of};
+    gauss_newton(solver, g, C_in + gi * n_nodes * 12, C, trial, chi, n_iter, wsum, wcnt,
+                 GraphOut{status, iterations, used_edges, skipped_edges, failed_row, cost_in, cost_out, edge_chi2 + gi * n_edges}, gi);
+    // attempted or not, the driver's last barriers came after the last write of steps_of: zeros where no step was taken
+    if (tid < SSLL_GRAPH_MAX_ITER) cg_steps[gi * SSLL_GRAPH_MAX_ITER + tid] = steps_of[tid];
 }
 
 inline int sparse_shape(int n_graphs, int n_nodes, int n_edges) {
@@ -587,19 +464,11 @@ extern "C" int ssll_pose_graph_sparse(const int32_t *edge_first, const int32_t *
                                       int n_iter, int cg_iterations, double cg_tol, void *workspace, double *C, int32_t *status,
                                       int32_t *iterations, int32_t *used_edges, int32_t *skipped_edges, int32_t *failed_row,
                                       double *cost_in, double *cost, double *edge_chi2, int32_t *cg_steps, void *stream) {
-    if (!edge_first || !edge_second || !edge_T || !edge_info || !C_in || !workspace || !C || !status || !iterations || !used_edges ||
-        !skipped_edges || !failed_row || !cost_in || !cost || !edge_chi2 || !cg_steps)
+    if (graph_operands(edge_first, edge_second, edge_T, edge_info, C_in, huber_chi, damping, n_iter, SSLL_GRAPH_MAX_ITER, workspace, C,
+                       status, iterations, used_edges, skipped_edges, failed_row, cost_in, cost, edge_chi2) != SSLAM_OK)
         return SSLAM_E_INVALID;
-    if (sparse_shape(n_graphs, n_nodes, n_edges) == SSLAM_E_INVALID || cg_iterations <= 0) return SSLAM_E_INVALID;
-    if (!finite_positive(huber_chi) || !finite_nonnegative(damping) || !finite_nonnegative(cg_tol) || n_iter < 0 ||
-        n_iter > SSLL_GRAPH_MAX_ITER || C == C_in)
-        return SSLAM_E_INVALID;
-    for (const void *p : {(const void *)edge_T, (const void *)edge_info, (const void *)C_in, (const void *)workspace, (const void *)C,
-                          (const void *)cost_in, (const void *)cost, (const void *)edge_chi2})
-        if (misaligned(p, 8)) return SSLAM_E_INVALID;
-    for (const void *p : {(const void *)edge_first, (const void *)edge_second, (const void *)status, (const void *)iterations,
-                          (const void *)used_edges, (const void *)skipped_edges, (const void *)failed_row, (const void *)cg_steps})
-        if (misaligned(p, 4)) return SSLAM_E_INVALID;
+    if (!cg_steps || misaligned(cg_steps, 4) || !finite_nonnegative(cg_tol) || cg_iterations <= 0) return SSLAM_E_INVALID;
+    if (sparse_shape(n_graphs, n_nodes, n_edges) == SSLAM_E_INVALID) return SSLAM_E_INVALID;
     if (sparse_shape(n_graphs, n_nodes, n_edges) != SSLAM_OK || cg_iterations > SSLL_MAX_CG) return SSLAM_E_UNSUPPORTED;
     hipLaunchKernelGGL(sparse_kernel, dim3((unsigned)n_graphs), dim3(NT), 0, (hipStream_t)stream, (const int *)edge_first,
                        (const int *)edge_second, edge_T, edge_info, n_nodes, n_edges, C_in, huber_chi, damping, n_iter, cg_iterations,

@@ -53,14 +53,34 @@ class RefinerLayout(C.Structure):
                 ("blk", (C.c_longlong * 8) * 8), ("out_w", C.c_longlong), ("out_b", C.c_longlong)]
 
 
+_INCLUDE = os.path.join(os.path.dirname(_PKG), "include")
+
+
+def _make_if_stale(csrc, so_path, others, force):
+    """make -C csrc if so_path is missing or older than a .hip or .h of csrc or one of `others`, or if forced; -> so_path."""
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))] + others
+    stale = (not os.path.exists(so_path)) or any(os.path.getmtime(s) > os.path.getmtime(so_path) for s in srcs)
+    if force or stale:
+        subprocess.check_call(["make", "-C", csrc, "-s", "-j4"])
+    return so_path
+
+
+def _load(so_path, csrc, prefix, prototypes):
+    """CDLL so_path with <prefix>_arch, <prefix>_launch_count and `prototypes` (a function of the library) set; raises if it has not
+    been built (no silent fallback)."""
+    if not os.path.exists(so_path):
+        raise SslamHipError(f"{so_path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                            f"(or `make -C {csrc}`); this package has no non-HIP execution path")
+    L = C.CDLL(so_path)
+    getattr(L, prefix + "_arch").restype = C.c_char_p
+    getattr(L, prefix + "_launch_count").restype = C.c_longlong
+    prototypes(L)
+    return L
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs.append(os.path.join(os.path.dirname(_PKG), "include", "sslam_hip.h"))
-    stale = (not os.path.exists(SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(SO_PATH) for s in srcs)
-    if force or stale:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
-    return SO_PATH
+    return _make_if_stale(CSRC, SO_PATH, [os.path.join(_INCLUDE, "sslam_hip.h")], force)
 
 
 _lib = None
@@ -96,93 +116,90 @@ def lib():
     """Load libsslam_hip.so; raises if it has not been built (no silent fallback)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise SslamHipError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                f"(or `make -C {CSRC}`); this package has no non-HIP execution path")
-        L = C.CDLL(SO_PATH)
-        L.sslam_arch.restype = C.c_char_p
-        L.sslam_launch_count.restype = C.c_longlong
-        p, i, ll, f, d = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double
-        L.sslam_pack_conv3x3_host.argtypes = [p, i, p]
-        L.sslam_pack_linear_host.argtypes = [p, i, i, p]
-        L.sslam_resample_table_host.argtypes = [i, i, i, p, p, i]
-        L.sslam_preprocess_u8.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, p]
-        L.sslam_preprocess_u8_patches.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, p]
-        L.sslam_bn_tokens.argtypes = [p, i, i, i, i, p, p, p, p, i, f, p, p, p, p]
-        L.sslam_selector_saliency.argtypes = [p, i, i, p, p, p, p, i, p, p]
-        L.sslam_selector_saliency_ws.argtypes = [p, i, i, p, p, p, p, i, p, p, ll, p]
-        for fn, at in ((L.sslam_workspace_bytes, [i, i, i, i]), (L.sslam_selector_saliency_workspace_bytes, [i, i]),
-                       (L.sslam_sim_argmax_workspace_bytes, [i, i]), (L.sslam_gather_refine_workspace_bytes, [i, i])):
-            fn.restype, fn.argtypes = ll, at
-        L.sslam_test_set_knob.argtypes = [C.c_char_p, ll, i]
-        L.sslami_selector_border_plan.argtypes = [i, i, p, p]
-        L.sslami_selector_border_owners.argtypes = [i, i, i, ll, i, p]
-        L.sslami_selector_border_check.restype, L.sslami_selector_border_check.argtypes = ll, [i, i]
-        L.sslam_select_keypoints.argtypes = [p, i, i, i, i, d, p, p, p, p, p, p]
-        L.sslam_gather.argtypes = [p, i, i, p, i, p, p]
-        L.sslam_refiner_layout.argtypes = [i, C.POINTER(RefinerLayout)]
-        L.sslam_refiner_pack_host.argtypes = [p, i, p]
-        L.sslam_refine.argtypes = [p, ll, p, i, p, p]
-        L.sslam_gather_refine.argtypes = [p, i, i, p, i, p, i, p, p]
-        L.sslam_gather_refine_ws.argtypes = [p, i, i, p, i, p, i, p, p, ll, p]
-        L.sslam_keypoint_intensity.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, i, p, p]
-        L.sslam_sim_argmax.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p]
-        L.sslam_sim_argmax_ws.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p, ll, p]
-        L.sslam_match_finalize.argtypes = [p, p, p, i, i, i, p, ll, p, ll, p, p, f, f, f, f, f, p, p, p, p]
-        L.sslam_sim_argmax_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p, p, p, ll, p]
-        L.sslam_match_finalize_pairs.argtypes = [p, p, p, i, i, p, p, i, p, ll, p, f, f, f, f, f, p, p, p, p]
-        L.sslam_match_finalize_rule.argtypes = [p, p, p, p, i, i, i, i, f, p, p, p, p]
-        L.sslam_match_finalize_rule_pairs.argtypes = [p, p, p, p, i, i, p, p, i, i, f, p, p, p, p]
-        L.sslam_match_rank.argtypes = [p, p, p, i, i, i, i, p, p, p, p, p]
-        L.sslam_pose_nn_pairs.argtypes = [p, i, i, i, i, p, p, i, p, d, p, p, p, p, p, p]
-        L.sslam_match_score_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p]
-        L.sslam_keypoint_depth.argtypes = [p, i, i, i, p, i, d, d, p, p]
-        L.sslam_pose_depth_nn_pairs.argtypes = [p, p, i, i, i, i, p, p, i, p] + [d] * 10 + [p, p, p, p, p, p, p]
-        L.sslam_match_score_known_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p, p]
-        L.sslam_pose_ransac_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [i, C.c_uint64] + [p] * 7 + [p]
-        L.sslam_pose_refine_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [p, d, i] + [p] * 12 + [p]
-        L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
-        L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
-        L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
-        L.sslam_row_lse_pairs.argtypes = [p, ll, i, i, p, p, i, p, f, p, p, p, p]
-        L.sslam_edge_pool.argtypes = [p, i, i, p, p, p]
-        L.sslam_val_frame_stats.argtypes = [p, p, p, p, i, i, i, p, p, p, p]
-        L.sslam_val_pair_stats.argtypes = [p, p, i, p, p, p, p, p, i, i, i, f, p, p, p]
-        L.sslam_val_pair_stats_pairs.argtypes = [p, i, i, p, p, p, p, p, p, p, i, i, f, p, p, p]
-        # the width-taking forms: `int d` in front of the stream (of the output pointer in the host-side packers)
-        L.sslam_refiner_layout_d.argtypes = [i, i, C.POINTER(RefinerLayout)]
-        L.sslam_refiner_pack_host_d.argtypes = [p, i, i, p]
-        for name in ("refine", "gather_refine", "gather_refine_ws", "sim_argmax", "sim_argmax_ws", "sim_argmax_pairs", "sim_argmax_rows",
-                     "sim_argmax_rows_pairs", "row_lse", "row_lse_pairs", "val_frame_stats"):
-            at = getattr(L, "sslam_" + name).argtypes
-            getattr(L, f"sslam_{name}_d").argtypes = at[:-1] + [i, at[-1]]
-        L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
-        L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
-        L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
-        L.sslam_selector_bf16_halo_groups.argtypes = [i, i, i]
-        L.sslam_bn_tokens_bf16copy.argtypes = [p, i, i, i, i, p, p, p, p, i, f, p, p, p, p, p]
-        L.sslam_refiner_bf16_bytes.restype = C.c_longlong
-        L.sslam_refiner_bf16_bytes.argtypes = [i]
-        L.sslam_refiner_pack_bf16_host.argtypes = [p, i, p]
-        L.sslam_refine_bf16.argtypes = [p, ll, p, i, p, p]
-        L.sslam_gather_refine_bf16.argtypes = [p, i, i, p, i, p, i, p, p]
-        L.sslam_vit_pack_linear_host.argtypes = [p, i, i, p]
-        L.sslam_vit_pack_mlp_host.argtypes = [p, p, p, p]
-        L.sslam_vit_workspace_bytes.restype = C.c_longlong
-        L.sslam_vit_workspace_bytes.argtypes = [i, i]
-        L.sslam_vit_forward.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, p]
-        L.sslam_vit_forward_patches.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, p]
-        L.sslam_vit_workspace_bytes_form.restype = C.c_longlong
-        L.sslam_vit_workspace_bytes_form.argtypes = [i, i, i]
-        L.sslam_vit_forward_form.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, i, p]
-        L.sslam_vit_forward_patches_form.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, i, p]
-        L.sslam_vit_f32_workspace_bytes.restype = C.c_longlong
-        L.sslam_vit_f32_workspace_bytes.argtypes = [i, i]
-        L.sslam_vit_forward_f32.argtypes = [p, i, i, C.POINTER(VitWeightsF32), p, ll, p, p]
-        L.sslam_vit_forward_f32_form.argtypes = [p, i, i, C.POINTER(VitWeightsF32), p, ll, p, i, p]
-        L.sslam_vit_f32_pack_linear_host.argtypes = [p, i, i, p]
-        _lib = L
+        _lib = _load(SO_PATH, CSRC, "sslam", _prototypes)
     return _lib
+
+
+def _prototypes(L):
+    p, i, ll, f, d = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double
+    L.sslam_pack_conv3x3_host.argtypes = [p, i, p]
+    L.sslam_pack_linear_host.argtypes = [p, i, i, p]
+    L.sslam_resample_table_host.argtypes = [i, i, i, p, p, i]
+    L.sslam_preprocess_u8.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, p]
+    L.sslam_preprocess_u8_patches.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, p]
+    L.sslam_bn_tokens.argtypes = [p, i, i, i, i, p, p, p, p, i, f, p, p, p, p]
+    L.sslam_selector_saliency.argtypes = [p, i, i, p, p, p, p, i, p, p]
+    L.sslam_selector_saliency_ws.argtypes = [p, i, i, p, p, p, p, i, p, p, ll, p]
+    for fn, at in ((L.sslam_workspace_bytes, [i, i, i, i]), (L.sslam_selector_saliency_workspace_bytes, [i, i]),
+                   (L.sslam_sim_argmax_workspace_bytes, [i, i]), (L.sslam_gather_refine_workspace_bytes, [i, i])):
+        fn.restype, fn.argtypes = ll, at
+    L.sslam_test_set_knob.argtypes = [C.c_char_p, ll, i]
+    L.sslami_selector_border_plan.argtypes = [i, i, p, p]
+    L.sslami_selector_border_owners.argtypes = [i, i, i, ll, i, p]
+    L.sslami_selector_border_check.restype, L.sslami_selector_border_check.argtypes = ll, [i, i]
+    L.sslam_select_keypoints.argtypes = [p, i, i, i, i, d, p, p, p, p, p, p]
+    L.sslam_gather.argtypes = [p, i, i, p, i, p, p]
+    L.sslam_refiner_layout.argtypes = [i, C.POINTER(RefinerLayout)]
+    L.sslam_refiner_pack_host.argtypes = [p, i, p]
+    L.sslam_refine.argtypes = [p, ll, p, i, p, p]
+    L.sslam_gather_refine.argtypes = [p, i, i, p, i, p, i, p, p]
+    L.sslam_gather_refine_ws.argtypes = [p, i, i, p, i, p, i, p, p, ll, p]
+    L.sslam_keypoint_intensity.argtypes = [p, i, i, i, i, p, p, i, p, p, i, p, i, p, p]
+    L.sslam_sim_argmax.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p]
+    L.sslam_sim_argmax_ws.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p, p, p, ll, p]
+    L.sslam_match_finalize.argtypes = [p, p, p, i, i, i, p, ll, p, ll, p, p, f, f, f, f, f, p, p, p, p]
+    L.sslam_sim_argmax_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p, p, p, ll, p]
+    L.sslam_match_finalize_pairs.argtypes = [p, p, p, i, i, p, p, i, p, ll, p, f, f, f, f, f, p, p, p, p]
+    L.sslam_match_finalize_rule.argtypes = [p, p, p, p, i, i, i, i, f, p, p, p, p]
+    L.sslam_match_finalize_rule_pairs.argtypes = [p, p, p, p, i, i, p, p, i, i, f, p, p, p, p]
+    L.sslam_match_rank.argtypes = [p, p, p, i, i, i, i, p, p, p, p, p]
+    L.sslam_pose_nn_pairs.argtypes = [p, i, i, i, i, p, p, i, p, d, p, p, p, p, p, p]
+    L.sslam_match_score_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p]
+    L.sslam_keypoint_depth.argtypes = [p, i, i, i, p, i, d, d, p, p]
+    L.sslam_pose_depth_nn_pairs.argtypes = [p, p, i, i, i, i, p, p, i, p] + [d] * 10 + [p, p, p, p, p, p, p]
+    L.sslam_match_score_known_pairs.argtypes = [p, p, p, p, p, i, i, p, p, p, p, p, p]
+    L.sslam_pose_ransac_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [i, C.c_uint64] + [p] * 7 + [p]
+    L.sslam_pose_refine_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [p, d, i] + [p] * 12 + [p]
+    L.sslam_sim_argmax_rows.argtypes = [p, ll, i, p, ll, i, i, p, p, p, p]
+    L.sslam_sim_argmax_rows_pairs.argtypes = [p, ll, i, i, p, p, i, p, p, p, p]
+    L.sslam_row_lse.argtypes = [p, ll, i, p, ll, i, i, p, f, p, p, p, p]
+    L.sslam_row_lse_pairs.argtypes = [p, ll, i, i, p, p, i, p, f, p, p, p, p]
+    L.sslam_edge_pool.argtypes = [p, i, i, p, p, p]
+    L.sslam_val_frame_stats.argtypes = [p, p, p, p, i, i, i, p, p, p, p]
+    L.sslam_val_pair_stats.argtypes = [p, p, i, p, p, p, p, p, i, i, i, f, p, p, p]
+    L.sslam_val_pair_stats_pairs.argtypes = [p, i, i, p, p, p, p, p, p, p, i, i, f, p, p, p]
+    # the width-taking forms: `int d` in front of the stream (of the output pointer in the host-side packers)
+    L.sslam_refiner_layout_d.argtypes = [i, i, C.POINTER(RefinerLayout)]
+    L.sslam_refiner_pack_host_d.argtypes = [p, i, i, p]
+    for name in ("refine", "gather_refine", "gather_refine_ws", "sim_argmax", "sim_argmax_ws", "sim_argmax_pairs", "sim_argmax_rows",
+                 "sim_argmax_rows_pairs", "row_lse", "row_lse_pairs", "val_frame_stats"):
+        at = getattr(L, "sslam_" + name).argtypes
+        getattr(L, f"sslam_{name}_d").argtypes = at[:-1] + [i, at[-1]]
+    L.sslam_f32_to_bf16.argtypes = [p, p, ll, p]
+    L.sslam_pack_conv3x3_bf16_host.argtypes = [p, i, p]
+    L.sslam_selector_saliency_bf16.argtypes = [p, i, i, p, p, p, p, i, p, p]
+    L.sslam_selector_bf16_halo_groups.argtypes = [i, i, i]
+    L.sslam_bn_tokens_bf16copy.argtypes = [p, i, i, i, i, p, p, p, p, i, f, p, p, p, p, p]
+    L.sslam_refiner_bf16_bytes.restype = C.c_longlong
+    L.sslam_refiner_bf16_bytes.argtypes = [i]
+    L.sslam_refiner_pack_bf16_host.argtypes = [p, i, p]
+    L.sslam_refine_bf16.argtypes = [p, ll, p, i, p, p]
+    L.sslam_gather_refine_bf16.argtypes = [p, i, i, p, i, p, i, p, p]
+    L.sslam_vit_pack_linear_host.argtypes = [p, i, i, p]
+    L.sslam_vit_pack_mlp_host.argtypes = [p, p, p, p]
+    L.sslam_vit_workspace_bytes.restype = C.c_longlong
+    L.sslam_vit_workspace_bytes.argtypes = [i, i]
+    L.sslam_vit_forward.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, p]
+    L.sslam_vit_forward_patches.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, p]
+    L.sslam_vit_workspace_bytes_form.restype = C.c_longlong
+    L.sslam_vit_workspace_bytes_form.argtypes = [i, i, i]
+    L.sslam_vit_forward_form.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, i, p]
+    L.sslam_vit_forward_patches_form.argtypes = [p, i, i, C.POINTER(VitWeights), p, ll, p, i, p]
+    L.sslam_vit_f32_workspace_bytes.restype = C.c_longlong
+    L.sslam_vit_f32_workspace_bytes.argtypes = [i, i]
+    L.sslam_vit_forward_f32.argtypes = [p, i, i, C.POINTER(VitWeightsF32), p, ll, p, p]
+    L.sslam_vit_forward_f32_form.argtypes = [p, i, i, C.POINTER(VitWeightsF32), p, ll, p, i, p]
+    L.sslam_vit_f32_pack_linear_host.argtypes = [p, i, i, p]
 
 
 def _check(rc: int, what: str):
@@ -1423,7 +1440,7 @@ def vit_forward_f32(images_chw, weights: VitWeightsF32, workspace, out=None, att
 
 
 # ------------------------------------------------------------------------------------------ libsslam_ext.so (include/sslam_ext.h)
-# The second library: entries with the prefix sslx_, built from csrc_ext/ with csrc/'s flags, loaded and refused like the first.
+# The second library: entries with the prefix sslx_, built from csrc_ext/ with csrc/flags.mk, loaded and refused like the first.
 CSRC_EXT = os.path.join(_PKG, "csrc_ext")
 EXT_SO_PATH = os.path.join(CSRC_EXT, "libsslam_ext.so")
 EXT_EXPORTS = ["sslx_version", "sslx_arch", "sslx_launch_count", "sslx_subcell_keypoints"]
@@ -1435,29 +1452,20 @@ _ext = None
 
 def ext_build(force: bool = False) -> str:
     """Compile libsslam_ext.so for gfx950 in-tree, as build() compiles the first library."""
-    inc = os.path.join(os.path.dirname(_PKG), "include")
-    srcs = [os.path.join(CSRC_EXT, f) for f in os.listdir(CSRC_EXT) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(inc, "sslam_ext.h"), os.path.join(inc, "sslam_hip.h")]
-    stale = (not os.path.exists(EXT_SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(EXT_SO_PATH) for s in srcs)
-    if force or stale:
-        subprocess.check_call(["make", "-C", CSRC_EXT, "-s", "-j4"])
-    return EXT_SO_PATH
+    return _make_if_stale(CSRC_EXT, EXT_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_ext.h", "sslam_hip.h")], force)
 
 
 def ext():
     """Load libsslam_ext.so; raises if it has not been built (no silent fallback)."""
     global _ext
     if _ext is None:
-        if not os.path.exists(EXT_SO_PATH):
-            raise SslamHipError(f"{EXT_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                f"(or `make -C {CSRC_EXT}`); this package has no non-HIP execution path")
-        L = C.CDLL(EXT_SO_PATH)
-        L.sslx_arch.restype = C.c_char_p
-        L.sslx_launch_count.restype = C.c_longlong
-        p, i = C.c_void_p, C.c_int
-        L.sslx_subcell_keypoints.argtypes = [p, i, i, p, i, p, p, p, p]
-        _ext = L
+        _ext = _load(EXT_SO_PATH, CSRC_EXT, "sslx", _ext_prototypes)
     return _ext
+
+
+def _ext_prototypes(L):
+    p, i = C.c_void_p, C.c_int
+    L.sslx_subcell_keypoints.argtypes = [p, i, i, p, i, p, p, p, p]
 
 
 def ext_launch_count() -> int:
@@ -1505,7 +1513,7 @@ def subcell_keypoints(sal, idx, out=None):
 
 
 # ---------------------------------------------------------------------------------------- libsslam_graph.so (include/sslam_graph.h)
-# The third library: entries with the prefix sslg_, built from csrc_graph/ with csrc_ext/'s flags, loaded and refused like the others.
+# The third library: entries with the prefix sslg_, built from csrc_graph/ with csrc/flags.mk, loaded and refused like the others.
 CSRC_GRAPH = os.path.join(_PKG, "csrc_graph")
 GRAPH_SO_PATH = os.path.join(CSRC_GRAPH, "libsslam_graph.so")
 GRAPH_EXPORTS = ["sslg_version", "sslg_arch", "sslg_launch_count", "sslg_chain_poses", "sslg_pose_graph_workspace_bytes", "sslg_pose_graph"]
@@ -1519,32 +1527,23 @@ _graph = None
 
 def graph_build(force: bool = False) -> str:
     """Compile libsslam_graph.so for gfx950 in-tree, as build() compiles the first library."""
-    inc = os.path.join(os.path.dirname(_PKG), "include")
-    srcs = [os.path.join(CSRC_GRAPH, f) for f in os.listdir(CSRC_GRAPH) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(inc, "sslam_graph.h"), os.path.join(inc, "sslam_hip.h")]
-    stale = (not os.path.exists(GRAPH_SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(GRAPH_SO_PATH) for s in srcs)
-    if force or stale:
-        subprocess.check_call(["make", "-C", CSRC_GRAPH, "-s", "-j4"])
-    return GRAPH_SO_PATH
+    return _make_if_stale(CSRC_GRAPH, GRAPH_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_graph.h", "sslam_hip.h")], force)
 
 
 def graph():
     """Load libsslam_graph.so; raises if it has not been built (no silent fallback)."""
     global _graph
     if _graph is None:
-        if not os.path.exists(GRAPH_SO_PATH):
-            raise SslamHipError(f"{GRAPH_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                f"(or `make -C {CSRC_GRAPH}`); this package has no non-HIP execution path")
-        L = C.CDLL(GRAPH_SO_PATH)
-        L.sslg_arch.restype = C.c_char_p
-        L.sslg_launch_count.restype = C.c_longlong
-        L.sslg_pose_graph_workspace_bytes.restype = C.c_size_t
-        p, i, d = C.c_void_p, C.c_int, C.c_double
-        L.sslg_pose_graph_workspace_bytes.argtypes = [i, i, i]
-        L.sslg_chain_poses.argtypes = [p, p, i, i, p, p]
-        L.sslg_pose_graph.argtypes = [p, p, p, p, i, i, i, p, i, d, d, i] + [p] * 11
-        _graph = L
+        _graph = _load(GRAPH_SO_PATH, CSRC_GRAPH, "sslg", _graph_prototypes)
     return _graph
+
+
+def _graph_prototypes(L):
+    L.sslg_pose_graph_workspace_bytes.restype = C.c_size_t
+    p, i, d = C.c_void_p, C.c_int, C.c_double
+    L.sslg_pose_graph_workspace_bytes.argtypes = [i, i, i]
+    L.sslg_chain_poses.argtypes = [p, p, i, i, p, p]
+    L.sslg_pose_graph.argtypes = [p, p, p, p, i, i, i, p, i, d, d, i] + [p] * 11
 
 
 def graph_launch_count() -> int:
@@ -1560,12 +1559,15 @@ def check_band(band) -> int:
     return int(band)
 
 
+def _check_nonnegative(name, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (float(v) >= 0.0) or not np.isfinite(float(v)):
+        raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    return float(v)
+
+
 def check_damping(damping) -> float:
     """What is added to the diagonal of the normal equations: a finite number >= 0, else ValueError - before any device work."""
-    if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) or not (float(damping) >= 0.0) or \
-            not np.isfinite(float(damping)):
-        raise ValueError(f"damping must be a finite number >= 0, got {damping!r}")
-    return float(damping)
+    return _check_nonnegative("damping", damping)
 
 
 def check_graph_iterations(iterations) -> int:
@@ -1601,12 +1603,50 @@ def pose_graph_workspace_bytes(n_graphs: int, n_nodes: int, band: int) -> int:
     return 8 * n_graphs * (n * (6 * band + 6) + 3 * n + 12 * n_nodes + 256 * 90)
 
 
-def _check_graph_sizes(what, n_graphs, n_nodes, n_edges=1):
+def _check_graph_sizes(what, n_graphs, n_nodes, n_edges=1, limits=None):
+    """limits: the most (graphs, nodes, edge slots) of the entry; the third library's if not given."""
+    max_graphs, max_nodes, max_edges = limits or (GRAPH_MAX_GRAPHS, GRAPH_MAX_NODES, GRAPH_MAX_EDGES)
     if n_graphs < 1 or n_nodes < 1 or n_edges < 1:
         raise ValueError(f"{what}: at least one graph, node and edge slot expected, got {n_graphs}, {n_nodes}, {n_edges}")
-    if n_graphs > GRAPH_MAX_GRAPHS or n_nodes > GRAPH_MAX_NODES or n_edges > GRAPH_MAX_EDGES:
-        raise SslamHipError(f"{what}: {_ERR[E_UNSUPPORTED]} (n_graphs <= {GRAPH_MAX_GRAPHS}, n_nodes <= {GRAPH_MAX_NODES}, n_edges <= "
-                            f"{GRAPH_MAX_EDGES}; got {n_graphs}, {n_nodes}, {n_edges})")
+    if n_graphs > max_graphs or n_nodes > max_nodes or n_edges > max_edges:
+        raise SslamHipError(f"{what}: {_ERR[E_UNSUPPORTED]} (n_graphs <= {max_graphs}, n_nodes <= {max_nodes}, n_edges <= "
+                            f"{max_edges}; got {n_graphs}, {n_nodes}, {n_edges})")
+
+
+def _check_workspace(workspace, need):
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
+                                  workspace.numel() < need or not workspace.is_contiguous()):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
+
+
+def _graph_operands(what, first, second, T, info, C_in, limits, shapes_of, keys, out, need_of, workspace):
+    """What pose_graph and pose_graph_sparse judge alike, touching no library: the five operands given the graph axis, the sizes
+    against `limits`, out against shapes_of(n_graphs, n_nodes, n_edges), the workspace against need_of(the same), one device.
+    -> (first, second, T, info, C_in, workspace, *outputs) - outputs and workspace made where not given - and the three sizes."""
+    if not isinstance(C_in, torch.Tensor) or C_in.dtype != torch.float64 or C_in.dim() not in (2, 3) or int(C_in.shape[-1]) != 12 or \
+            not C_in.is_contiguous():
+        raise ValueError("C_in must be a contiguous float64 tensor of shape (n_graphs, n_nodes, 12) or (n_nodes, 12)")
+    C3 = C_in[None] if C_in.dim() == 2 else C_in
+    n_graphs, n_nodes = int(C3.shape[0]), int(C3.shape[1])
+    if not isinstance(first, torch.Tensor) or first.dim() not in (1, 2):
+        raise ValueError("first must be an int32 tensor of shape (n_graphs, n_edges) or (n_edges,)")
+    n_edges = int(first.shape[-1])
+    _check_graph_sizes(what, n_graphs, n_nodes, n_edges, limits)
+    lead = (n_graphs, n_edges)
+    first = _graph_rows("first", first, lead, (), torch.int32)
+    second = _graph_rows("second", second, lead, (), torch.int32)
+    T = _graph_rows("T", T, lead, (12,), torch.float64)
+    info = _graph_rows("info", info, lead, (21,), torch.float64)
+    shapes = shapes_of(n_graphs, n_nodes, n_edges)
+    o = None if out is None else _outputs(shapes, keys, out)
+    if o is not None and o[0].data_ptr() == C3.data_ptr():
+        raise ValueError("out `C` must not be C_in")
+    need = need_of(n_graphs, n_nodes, n_edges)
+    _check_workspace(workspace, need)
+    dev = common_device(first, second, T, info, C3, workspace, *(o or ()))
+    o = _outputs(shapes, keys, None, dev) if o is None else o
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    return (first, second, T, info, C3, ws, *o), (n_graphs, n_nodes, n_edges)
 
 
 def chain_poses(T, n_nodes=None, start=None, out=None):
@@ -1638,38 +1678,16 @@ def pose_graph(first, second, T, info, C_in, band, huber_chi=4.0, damping=0.0, i
     graph axis.  out: optional tensors of pose_graph_shapes (C must not be C_in); workspace: optional uint8 tensor of at least
     pose_graph_workspace_bytes.  One launch, no host read; everything is judged before the library is loaded."""
     b, chi, damp, n_iter = check_band(band), check_positive("huber_chi", huber_chi), check_damping(damping), check_graph_iterations(iterations)
-    if not isinstance(C_in, torch.Tensor) or C_in.dtype != torch.float64 or C_in.dim() not in (2, 3) or int(C_in.shape[-1]) != 12 or \
-            not C_in.is_contiguous():
-        raise ValueError("C_in must be a contiguous float64 tensor of shape (n_graphs, n_nodes, 12) or (n_nodes, 12)")
-    C3 = C_in[None] if C_in.dim() == 2 else C_in
-    n_graphs, n_nodes = int(C3.shape[0]), int(C3.shape[1])
-    if not isinstance(first, torch.Tensor) or first.dim() not in (1, 2):
-        raise ValueError("first must be an int32 tensor of shape (n_graphs, n_edges) or (n_edges,)")
-    n_edges = int(first.shape[-1])
-    _check_graph_sizes("pose_graph", n_graphs, n_nodes, n_edges)
-    lead = (n_graphs, n_edges)
-    first = _graph_rows("first", first, lead, (), torch.int32)
-    second = _graph_rows("second", second, lead, (), torch.int32)
-    T = _graph_rows("T", T, lead, (12,), torch.float64)
-    info = _graph_rows("info", info, lead, (21,), torch.float64)
-    shapes = pose_graph_shapes(n_graphs, n_nodes, n_edges)
-    o = None if out is None else _outputs(shapes, POSE_GRAPH_KEYS, out)
-    if o is not None and o[0].data_ptr() == C3.data_ptr():
-        raise ValueError("out `C` must not be C_in")
-    need = pose_graph_workspace_bytes(n_graphs, n_nodes, b)
-    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
-                                  workspace.numel() < need or not workspace.is_contiguous()):
-        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
-    dev = common_device(first, second, T, info, C3, workspace, *(o or ()))
-    o = _outputs(shapes, POSE_GRAPH_KEYS, None, dev) if o is None else o
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    _run("pose_graph", graph().sslg_pose_graph, (first, second, T, info, C3, ws, *o), _dp(first), _dp(second), _dp(T), _dp(info),
+    t, (n_graphs, n_nodes, n_edges) = _graph_operands("pose_graph", first, second, T, info, C_in, None, pose_graph_shapes, POSE_GRAPH_KEYS, out,
+                                                     lambda g, n, e: pose_graph_workspace_bytes(g, n, b), workspace)
+    first, second, T, info, C3, ws, *o = t
+    _run("pose_graph", graph().sslg_pose_graph, t, _dp(first), _dp(second), _dp(T), _dp(info),
          n_graphs, n_nodes, n_edges, _dp(C3), b, C.c_double(chi), C.c_double(damp), n_iter, _dp(ws), *(_dp(x) for x in o))
     return tuple(o)
 
 
 # ------------------------------------------------------------------------------------------ libsslam_loop.so (include/sslam_loop.h)
-# The fourth library: entries with the prefix ssll_, built from csrc_loop/ with csrc_graph/'s flags, loaded and refused like the others.
+# The fourth library: entries with the prefix ssll_, built from csrc_loop/ with csrc/flags.mk, loaded and refused like the others.
 CSRC_LOOP = os.path.join(_PKG, "csrc_loop")
 LOOP_SO_PATH = os.path.join(CSRC_LOOP, "libsslam_loop.so")
 LOOP_EXPORTS = ["ssll_version", "ssll_arch", "ssll_launch_count", "ssll_frame_signatures", "ssll_loop_candidates",
@@ -1684,33 +1702,25 @@ _loop = None
 
 def loop_build(force: bool = False) -> str:
     """Compile libsslam_loop.so for gfx950 in-tree, as build() compiles the first library."""
-    inc = os.path.join(os.path.dirname(_PKG), "include")
-    srcs = [os.path.join(CSRC_LOOP, f) for f in os.listdir(CSRC_LOOP) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(CSRC_GRAPH, "edge_terms.h")] + [os.path.join(inc, h) for h in ("sslam_loop.h", "sslam_graph.h", "sslam_hip.h")]
-    stale = (not os.path.exists(LOOP_SO_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LOOP_SO_PATH) for s in srcs)
-    if force or stale:
-        subprocess.check_call(["make", "-C", CSRC_LOOP, "-s", "-j4"])
-    return LOOP_SO_PATH
+    shared = [os.path.join(CSRC_GRAPH, h) for h in ("edge_terms.h", "gauss_newton.h")]
+    return _make_if_stale(CSRC_LOOP, LOOP_SO_PATH, shared + [os.path.join(_INCLUDE, h) for h in ("sslam_loop.h", "sslam_graph.h", "sslam_hip.h")], force)
 
 
 def loop():
     """Load libsslam_loop.so; raises if it has not been built (no silent fallback)."""
     global _loop
     if _loop is None:
-        if not os.path.exists(LOOP_SO_PATH):
-            raise SslamHipError(f"{LOOP_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                f"(or `make -C {CSRC_LOOP}`); this package has no non-HIP execution path")
-        L = C.CDLL(LOOP_SO_PATH)
-        L.ssll_arch.restype = C.c_char_p
-        L.ssll_launch_count.restype = C.c_longlong
-        L.ssll_pose_graph_sparse_workspace_bytes.restype = C.c_size_t
-        p, i, d, f = C.c_void_p, C.c_int, C.c_double, C.c_float
-        L.ssll_pose_graph_sparse_workspace_bytes.argtypes = [i, i, i]
-        L.ssll_frame_signatures.argtypes = [p, p, i, i, i, p, p, p]
-        L.ssll_loop_candidates.argtypes = [p, i, i, i, f, i, i, p, p, p, p, p]
-        L.ssll_pose_graph_sparse.argtypes = [p, p, p, p, i, i, i, p, d, d, i, i, d] + [p] * 12
-        _loop = L
+        _loop = _load(LOOP_SO_PATH, CSRC_LOOP, "ssll", _loop_prototypes)
     return _loop
+
+
+def _loop_prototypes(L):
+    L.ssll_pose_graph_sparse_workspace_bytes.restype = C.c_size_t
+    p, i, d, f = C.c_void_p, C.c_int, C.c_double, C.c_float
+    L.ssll_pose_graph_sparse_workspace_bytes.argtypes = [i, i, i]
+    L.ssll_frame_signatures.argtypes = [p, p, i, i, i, p, p, p]
+    L.ssll_loop_candidates.argtypes = [p, i, i, i, f, i, i, p, p, p, p, p]
+    L.ssll_pose_graph_sparse.argtypes = [p, p, p, p, i, i, i, p, d, d, i, i, d] + [p] * 12
 
 
 def loop_launch_count() -> int:
@@ -1734,10 +1744,7 @@ def check_cg_iterations(cg_iterations) -> int:
 
 def check_cg_tol(cg_tol) -> float:
     """The relative tolerance of the conjugate gradients: a finite number >= 0, else ValueError - before any device work."""
-    if isinstance(cg_tol, bool) or not isinstance(cg_tol, (int, float, np.integer, np.floating)) or not (float(cg_tol) >= 0.0) or \
-            not np.isfinite(float(cg_tol)):
-        raise ValueError(f"cg_tol must be a finite number >= 0, got {cg_tol!r}")
-    return float(cg_tol)
+    return _check_nonnegative("cg_tol", cg_tol)
 
 
 def frame_signatures(descriptors, scores, out=None, workspace=None):
@@ -1754,9 +1761,7 @@ def frame_signatures(descriptors, scores, out=None, workspace=None):
     if out is not None:
         _check_arrays((n, d), ("out", out, torch.float32))
     need = 4 * n * d
-    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
-                                  workspace.numel() < need or not workspace.is_contiguous()):
-        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    _check_workspace(workspace, need)
     dev = common_device(descriptors, scores, out, workspace)
     sig = torch.empty((n, d), dtype=torch.float32, device=dev) if out is None else out
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
@@ -1819,36 +1824,11 @@ def pose_graph_sparse(first, second, T, info, C_in, huber_chi=4.0, damping=0.0, 
     read; everything is judged before the library is loaded."""
     chi, damp, n_iter = check_positive("huber_chi", huber_chi), check_damping(damping), check_graph_iterations(iterations)
     n_cg, tol = check_cg_iterations(cg_iterations), check_cg_tol(cg_tol)
-    if not isinstance(C_in, torch.Tensor) or C_in.dtype != torch.float64 or C_in.dim() not in (2, 3) or int(C_in.shape[-1]) != 12 or \
-            not C_in.is_contiguous():
-        raise ValueError("C_in must be a contiguous float64 tensor of shape (n_graphs, n_nodes, 12) or (n_nodes, 12)")
-    C3 = C_in[None] if C_in.dim() == 2 else C_in
-    n_graphs, n_nodes = int(C3.shape[0]), int(C3.shape[1])
-    if not isinstance(first, torch.Tensor) or first.dim() not in (1, 2):
-        raise ValueError("first must be an int32 tensor of shape (n_graphs, n_edges) or (n_edges,)")
-    n_edges = int(first.shape[-1])
-    if n_graphs < 1 or n_nodes < 1 or n_edges < 1:
-        raise ValueError(f"pose_graph_sparse: at least one graph, node and edge slot expected, got {n_graphs}, {n_nodes}, {n_edges}")
-    if n_graphs > SPARSE_MAX_GRAPHS or n_nodes > SPARSE_MAX_NODES or n_edges > SPARSE_MAX_EDGES:
-        raise SslamHipError(f"pose_graph_sparse: {_ERR[E_UNSUPPORTED]} (n_graphs <= {SPARSE_MAX_GRAPHS}, n_nodes <= {SPARSE_MAX_NODES}, "
-                            f"n_edges <= {SPARSE_MAX_EDGES}; got {n_graphs}, {n_nodes}, {n_edges})")
-    lead = (n_graphs, n_edges)
-    first = _graph_rows("first", first, lead, (), torch.int32)
-    second = _graph_rows("second", second, lead, (), torch.int32)
-    T = _graph_rows("T", T, lead, (12,), torch.float64)
-    info = _graph_rows("info", info, lead, (21,), torch.float64)
-    shapes = pose_graph_sparse_shapes(n_graphs, n_nodes, n_edges)
-    o = None if out is None else _outputs(shapes, POSE_GRAPH_SPARSE_KEYS, out)
-    if o is not None and o[0].data_ptr() == C3.data_ptr():
-        raise ValueError("out `C` must not be C_in")
-    need = pose_graph_sparse_workspace_bytes(n_graphs, n_nodes, n_edges)
-    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or
-                                  workspace.numel() < need or not workspace.is_contiguous()):
-        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {need} bytes")
-    dev = common_device(first, second, T, info, C3, workspace, *(o or ()))
-    o = _outputs(shapes, POSE_GRAPH_SPARSE_KEYS, None, dev) if o is None else o
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    _run("pose_graph_sparse", loop().ssll_pose_graph_sparse, (first, second, T, info, C3, ws, *o), _dp(first), _dp(second), _dp(T),
+    t, (n_graphs, n_nodes, n_edges) = _graph_operands("pose_graph_sparse", first, second, T, info, C_in,
+                                                     (SPARSE_MAX_GRAPHS, SPARSE_MAX_NODES, SPARSE_MAX_EDGES), pose_graph_sparse_shapes,
+                                                     POSE_GRAPH_SPARSE_KEYS, out, pose_graph_sparse_workspace_bytes, workspace)
+    first, second, T, info, C3, ws, *o = t
+    _run("pose_graph_sparse", loop().ssll_pose_graph_sparse, t, _dp(first), _dp(second), _dp(T),
          _dp(info), n_graphs, n_nodes, n_edges, _dp(C3), C.c_double(chi), C.c_double(damp), n_iter, n_cg, C.c_double(tol), _dp(ws),
          *(_dp(x) for x in o))
     return tuple(o)

@@ -335,6 +335,42 @@ def _check_graph(spacings, n_frames, num_pairs, band, huber_chi, damping, graph_
     return tuple(lists), lists, n, band
 
 
+def _sequence_preamble(pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber,
+                       iterations, subcell, band, huber_chi, damping, graph_iterations, more=lambda: None) -> tuple:
+    """What odometry_graph and odometry_loop_graph do alike before they match: every argument judged (more(): the caller's own,
+    where they always stood), the frames extracted once, the geometry bank, the keypoints' depth, the spacings' pair list."""
+    check_subcell(subcell)
+    src = tokens if tokens is not None else images_u8
+    if src is None:
+        raise ValueError("images_u8 or tokens= required")
+    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
+    opt = more()
+    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
+    _check_refine(True, threshold, huber, iterations)
+    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
+    ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
+    kp = geometry_bank(ex, subcell)
+    return lists, n, band, opt, camera, rule, ex, kp, gather_keypoint_depth(pipe, depth, kp, n), [pr for s in lists for pr in lists[s]]
+
+
+def _result_preamble(result, keys, depth, kp_depth, camera, poses, spacings, num_pairs, threshold, hypotheses, seed, huber, iterations,
+                     subcell, band, huber_chi, damping, graph_iterations, more=lambda: None) -> tuple:
+    """What odometry_result_graph and odometry_result_loop_graph do alike: the result must hold `keys` per frame; the geometry
+    bank, the result's spacings if none are given, every argument judged (more(): the caller's own)."""
+    if not isinstance(result, dict) or "frames" not in result or any(key not in result["frames"] for key in keys):
+        raise ValueError("a StreamingSequence / run_directory result expected")
+    kp = geometry_bank(result["frames"], subcell)
+    if spacings is None:
+        spacings = tuple(sorted(k for k in result if isinstance(k, (int, np.integer)) and not isinstance(k, bool)))
+    if any(s not in result for s in spacings):
+        raise ValueError(f"the result holds no pairs at every spacing of {tuple(spacings)!r}")
+    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
+    opt = more()
+    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
+    _check_refine(True, threshold, huber, iterations)
+    return kp, lists, n, band, opt, camera
+
+
 def _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations) -> dict:
     """The chain of the refined spacing-1 poses and the banded graph over the refined pairs `ref` (refine_poses' dictionary, one row
     per pair of `pairs`) -> optimize_pose_graph's device tensors.  No host read."""
@@ -367,15 +403,8 @@ def _graph_host(rest, n, pairs, poses) -> dict:
     return graph
 
 
-def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
-           graph_iterations) -> dict:
-    """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back."""
-    pairs = [pr for s in lists for pr in lists[s]]
-    packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
-    g = _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations)
-    flat = torch.cat([packed.reshape(-1)] + _graph_flat(g)).cpu().numpy()          # the ONE read-back
-    P, w = len(pairs), int(packed.shape[1])
-    host, rest = flat[:P * w].reshape(P, w), flat[P * w:]
+def _spacings_and_graph(host, rest, lists, pairs, n, poses) -> dict:
+    """The read-back split: `host`, a row per pair, into every spacing's dictionary; `rest` (_graph_flat's numbers first) into 'graph'."""
     out, at = {}, 0
     for s in lists:
         out[s] = _unpack(host[at:at + len(lists[s])], lists[s], poses, s, True)
@@ -385,6 +414,18 @@ def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypo
         graph["ate_chain"] = out[1]["ate"]
     out["graph"] = graph
     return out
+
+
+def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
+           graph_iterations) -> dict:
+    """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back."""
+    pairs = [pr for s in lists for pr in lists[s]]
+    packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
+    g = _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations)
+    flat = torch.cat([packed.reshape(-1)] + _graph_flat(g)).cpu().numpy()          # the ONE read-back
+    P, w = len(pairs), int(packed.shape[1])
+    host, rest = flat[:P * w].reshape(P, w), flat[P * w:]
+    return _spacings_and_graph(host, rest, lists, pairs, n, poses)
 
 
 def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, spacings=GRAPH_SPACINGS, num_pairs=None, rule=None,
@@ -402,18 +443,9 @@ def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, sp
     'pairs', 'status', 'iterations', 'used_edges', 'skipped_edges', 'failed_row', 'cost_in', 'cost', 'edge_chi2' (one per listed
     pair); with poses also 'ate' (ate_summary of the graph's trajectory) and 'ate_chain' (that of the spacing-1 chain)}}.
     Nobody has measured this on real RGB-D data: no real sequence was at hand when this was written."""
-    check_subcell(subcell)
-    src = tokens if tokens is not None else images_u8
-    if src is None:
-        raise ValueError("images_u8 or tokens= required")
-    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
-    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
-    _check_refine(True, threshold, huber, iterations)
-    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
-    ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
-    kp = geometry_bank(ex, subcell)
-    kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
-    pairs = [pr for s in lists for pr in lists[s]]
+    lists, n, band, _, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
+        pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber, iterations, subcell, band,
+        huber_chi, damping, graph_iterations)
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
     return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
                   damping, graph_iterations)
@@ -425,16 +457,8 @@ def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=Non
     """odometry_graph() for a StreamingSequence.result() / run_frames / run_directory result: nothing is extracted or matched again.
     spacings: those of the result if None.  depth= / kp_depth=, and everything else: as odometry_result() and odometry_graph()
     take them."""
-    if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
-        raise ValueError("a StreamingSequence / run_directory result expected")
-    kp = geometry_bank(result["frames"], subcell)
-    if spacings is None:
-        spacings = tuple(sorted(k for k in result if isinstance(k, (int, np.integer)) and not isinstance(k, bool)))
-    if any(s not in result for s in spacings):
-        raise ValueError(f"the result holds no pairs at every spacing of {tuple(spacings)!r}")
-    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
-    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
-    _check_refine(True, threshold, huber, iterations)
+    kp, lists, n, band, _, camera = _result_preamble(result, ("keypoints_pixel",), depth, kp_depth, camera, poses, spacings, num_pairs, threshold,
+                                                     hypotheses, seed, huber, iterations, subcell, band, huber_chi, damping, graph_iterations)
     matches = {key: torch.cat([result[s][key][:len(lists[s])] for s in lists]) for key in ("matches", "match_count")}
     if kp_depth is None:
         kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
@@ -499,14 +523,7 @@ def _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, thre
     flat = torch.cat(pieces).cpu().numpy()                  # the ONE read-back
     w = int(packed.shape[1])
     host, rest = flat[:(P + L) * w].reshape(P + L, w), flat[(P + L) * w:]
-    out, at = {}, 0
-    for s in lists:
-        out[s] = _unpack(host[at:at + len(lists[s])], lists[s], poses, s, True)
-        at += len(lists[s])
-    graph = _graph_host(rest, n, pairs, poses)
-    if poses is not None:
-        graph["ate_chain"] = out[1]["ate"]
-    out["graph"] = graph
+    out = _spacings_and_graph(host, rest, lists, pairs, n, poses)
     rest = rest[12 * n + 7 + P:]
     tail = rest[len(runs) * (12 * n + 7 + P + L + lib.SPARSE_MAX_ITER):]
     lf, ls = tail[:L].astype(np.int32), tail[L:2 * L].astype(np.int32)
@@ -541,20 +558,10 @@ def odometry_loop_graph(pipe, images_u8=None, depth=None, camera=None, poses=Non
     candidate slots), 'status', 'iterations', 'used_edges', 'skipped_edges', 'failed_row', 'cost_in', 'cost', 'edge_chi2' (one per
     pair of 'pairs'), 'cg_steps' (16,), with poses 'ate'; with prune_chi 'loop_graph' is the second launch's and
     'loop_graph_unpruned' the first's.  Nobody has measured this on real RGB-D data."""
-    check_subcell(subcell)
-    src = tokens if tokens is not None else images_u8
-    if src is None:
-        raise ValueError("images_u8 or tokens= required")
-    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
-    opt = check_loops(loops, cg_iterations, cg_tol, prune_chi)
-    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
-    _check_refine(True, threshold, huber, iterations)
-    rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
-    ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
-    kp = geometry_bank(ex, subcell)
-    kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
+    lists, n, band, opt, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
+        pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber, iterations, subcell, band,
+        huber_chi, damping, graph_iterations, lambda: check_loops(loops, cg_iterations, cg_tol, prune_chi))
     cand = pipe.find_loop_candidates(ex["descriptors"], ex["scores"], opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])
-    pairs = [pr for s in lists for pr in lists[s]]
     dev = kp.device
     first = torch.cat([torch.tensor([a for a, _ in pairs], dtype=torch.int32, device=dev), cand["first"]])
     second = torch.cat([torch.tensor([b for _, b in pairs], dtype=torch.int32, device=dev), cand["second"]])
@@ -571,17 +578,9 @@ def odometry_result_loop_graph(pipe, result: dict, depth=None, camera=None, pose
     spacings' pairs keep the match lists the sequence was run with; only the candidate slots are matched, in one match_pairs call
     under `rule` (MatchRule.mnn_ratio(0.9) if None - give the rule the sequence was run with).  Everything else: as
     odometry_result_graph() and odometry_loop_graph() take it."""
-    if not isinstance(result, dict) or "frames" not in result or any(key not in result["frames"] for key in ("keypoints_pixel", "descriptors", "scores")):
-        raise ValueError("a StreamingSequence / run_directory result expected")
-    kp = geometry_bank(result["frames"], subcell)
-    if spacings is None:
-        spacings = tuple(sorted(k for k in result if isinstance(k, (int, np.integer)) and not isinstance(k, bool)))
-    if any(s not in result for s in spacings):
-        raise ValueError(f"the result holds no pairs at every spacing of {tuple(spacings)!r}")
-    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
-    opt = check_loops(loops, cg_iterations, cg_tol, prune_chi)
-    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
-    _check_refine(True, threshold, huber, iterations)
+    kp, lists, n, band, opt, camera = _result_preamble(
+        result, ("keypoints_pixel", "descriptors", "scores"), depth, kp_depth, camera, poses, spacings, num_pairs, threshold, hypotheses, seed, huber,
+        iterations, subcell, band, huber_chi, damping, graph_iterations, lambda: check_loops(loops, cg_iterations, cg_tol, prune_chi))
     rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
     desc, scores = result["frames"]["descriptors"][:n], result["frames"]["scores"][:n]
     cand = pipe.find_loop_candidates(desc, scores, opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])

@@ -151,6 +151,43 @@ REFINER_ORDER_BLOCK = ["norm1.weight", "norm1.bias", "fc1.weight", "fc1.bias", "
 REFINER_ORDER_TAIL = ["output_proj.weight", "output_proj.bias"]
 
 
+def _graph_edge_rows(first, second, T, info, n_nodes, judge):
+    """What optimize_pose_graph and optimize_pose_graph_sparse judge alike, on the host alone: n_nodes, the edge lists (host
+    sequences become lists of int; device tensors give fa = fb = None), T and info as rows or as the dictionaries that hold them.
+    judge(fa, fb): the caller's own arguments, judged between the lists and the rows.
+    -> n_nodes, fa, fb, the T rows, the info rows, the refinement status or None, the number of edge slots."""
+    if isinstance(n_nodes, bool) or not isinstance(n_nodes, (int, np.integer)) or n_nodes < 1:
+        raise ValueError(f"n_nodes must be an integer >= 1, got {n_nodes!r}")
+    status = info.get("status") if isinstance(info, dict) else None
+    t_rows = T["T"] if isinstance(T, dict) and "T" in T else T
+    info_rows = info["info"] if isinstance(info, dict) and "info" in info else info
+    if isinstance(first, torch.Tensor) != isinstance(second, torch.Tensor):
+        raise ValueError("first and second must both be device tensors or both host sequences")
+    fa = fb = None
+    if not isinstance(first, torch.Tensor):
+        fa, fb = [int(v) for v in first], [int(v) for v in second]
+        if len(fa) != len(fb) or not fa:
+            raise ValueError("first and second must name the same number of edges, at least one")
+    judge(fa, fb)
+    for name, t, cols in (("T", t_rows, 12), ("info", info_rows, 21)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or int(t.shape[1]) != cols or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 device tensor of shape (E, {cols}) or a dictionary holding one")
+    n_edges = int(t_rows.shape[0])
+    if int(info_rows.shape[0]) != n_edges or (fa is not None and len(fa) != n_edges):
+        raise ValueError(f"{n_edges} transforms for {int(info_rows.shape[0])} information matrices and {len(fa) if fa is not None else '?'} edges")
+    return int(n_nodes), fa, fb, t_rows, info_rows, status, n_edges
+
+
+def _graph_edge_lists(fa, fb, first, second, status, dev):
+    """The edge lists on the device (host lists go there now); a refinement status of 3 makes the slot absent, without a read-back."""
+    if fa is not None:
+        first = torch.tensor(fa, dtype=torch.int32, device=dev)
+        second = torch.tensor(fb, dtype=torch.int32, device=dev)
+    if status is not None:
+        first = torch.where(status == lib.REFINE_NOT_ATTEMPTED, torch.full_like(first, -1), first)
+    return first, second
+
+
 def refiner_weight_list(sd: dict):
     n_blocks = len({k.split(".")[1] for k in sd if k.startswith("residual_blocks.")})
     keys = list(REFINER_ORDER_HEAD)
@@ -883,31 +920,16 @@ class SequencePipeline:
         huber_chi, damping, iterations: include/sslam_graph.h.  Returns device tensors: C (n_nodes, 12) float64, status,
         iterations, used_edges, skipped_edges, failed_row () int32, cost_in, cost () float64, edge_chi2 (E,) float64.  Two
         launches at most, no host read.  It reads nothing of the pipeline (a static method: the drop-in calls it without one)."""
-        if isinstance(n_nodes, bool) or not isinstance(n_nodes, (int, np.integer)) or n_nodes < 1:
-            raise ValueError(f"n_nodes must be an integer >= 1, got {n_nodes!r}")
-        n_nodes = int(n_nodes)
-        status = info.get("status") if isinstance(info, dict) else None
-        t_rows = T["T"] if isinstance(T, dict) and "T" in T else T
-        info_rows = info["info"] if isinstance(info, dict) and "info" in info else info
-        host = not isinstance(first, torch.Tensor) and not isinstance(second, torch.Tensor)
-        if isinstance(first, torch.Tensor) != isinstance(second, torch.Tensor):
-            raise ValueError("first and second must both be device tensors or both host sequences")
-        if host:
-            fa, fb = [int(v) for v in first], [int(v) for v in second]
-            if len(fa) != len(fb) or not fa:
-                raise ValueError("first and second must name the same number of edges, at least one")
+        def judge(fa, fb):
+            nonlocal band
+            if band is None and fa is None:
+                raise ValueError("band= is required with device edge lists: the largest b - a is not read back")
             if band is None:
                 band = max([b - a for a, b in zip(fa, fb) if 0 <= a < b] or [1])
-        elif band is None:
-            raise ValueError("band= is required with device edge lists: the largest b - a is not read back")
-        band = lib.check_band(band)
-        lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
-        for name, t, cols in (("T", t_rows, 12), ("info", info_rows, 21)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or int(t.shape[1]) != cols or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float64 device tensor of shape (E, {cols}) or a dictionary holding one")
-        n_edges = int(t_rows.shape[0])
-        if int(info_rows.shape[0]) != n_edges or (host and len(fa) != n_edges):
-            raise ValueError(f"{n_edges} transforms for {int(info_rows.shape[0])} information matrices and {len(fa) if host else '?'} edges")
+            band = lib.check_band(band)
+            lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
+        n_nodes, fa, fb, t_rows, info_rows, status, n_edges = _graph_edge_rows(first, second, T, info, n_nodes, judge)
+        host = fa is not None
         chain_rows = None
         if C_init is None and n_nodes > 1:
             if host:
@@ -919,11 +941,7 @@ class SequencePipeline:
             elif n_edges < n_nodes - 1:
                 raise ValueError(f"C_init=None chains the first {n_nodes - 1} slots: only {n_edges} are listed")
         dev = t_rows.device
-        if host:
-            first = torch.tensor(fa, dtype=torch.int32, device=dev)
-            second = torch.tensor(fb, dtype=torch.int32, device=dev)
-        if status is not None:
-            first = torch.where(status == lib.REFINE_NOT_ATTEMPTED, torch.full_like(first, -1), first)
+        first, second = _graph_edge_lists(fa, fb, first, second, status, dev)
         if C_init is None:
             if n_nodes == 1:
                 rows = t_rows[:0]
@@ -958,35 +976,13 @@ class SequencePipeline:
         of 3 makes the slot absent, on the device).  C_init (n_nodes, 12) float64 world -> camera is required: the banded graph's
         C, or the chain.  Returns optimize_pose_graph's device tensors and cg_steps (16,) int32, the CG iterations of every step
         (include/sslam_loop.h).  One launch, no host read."""
-        if isinstance(n_nodes, bool) or not isinstance(n_nodes, (int, np.integer)) or n_nodes < 1:
-            raise ValueError(f"n_nodes must be an integer >= 1, got {n_nodes!r}")
-        n_nodes = int(n_nodes)
-        status = info.get("status") if isinstance(info, dict) else None
-        t_rows = T["T"] if isinstance(T, dict) and "T" in T else T
-        info_rows = info["info"] if isinstance(info, dict) and "info" in info else info
-        if isinstance(first, torch.Tensor) != isinstance(second, torch.Tensor):
-            raise ValueError("first and second must both be device tensors or both host sequences")
-        host = not isinstance(first, torch.Tensor)
-        if host:
-            fa, fb = [int(v) for v in first], [int(v) for v in second]
-            if len(fa) != len(fb) or not fa:
-                raise ValueError("first and second must name the same number of edges, at least one")
-        lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
-        lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
-        for name, t, cols in (("T", t_rows, 12), ("info", info_rows, 21)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or int(t.shape[1]) != cols or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float64 device tensor of shape (E, {cols}) or a dictionary holding one")
-        n_edges = int(t_rows.shape[0])
-        if int(info_rows.shape[0]) != n_edges or (host and len(fa) != n_edges):
-            raise ValueError(f"{n_edges} transforms for {int(info_rows.shape[0])} information matrices and {len(fa) if host else '?'} edges")
+        def judge(fa, fb):
+            lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
+            lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
+        n_nodes, fa, fb, t_rows, info_rows, status, _ = _graph_edge_rows(first, second, T, info, n_nodes, judge)
         if not isinstance(C_init, torch.Tensor) or tuple(C_init.shape) != (n_nodes, 12):
             raise ValueError(f"C_init must be a float64 device tensor of shape ({n_nodes}, 12)")
-        dev = t_rows.device
-        if host:
-            first = torch.tensor(fa, dtype=torch.int32, device=dev)
-            second = torch.tensor(fb, dtype=torch.int32, device=dev)
-        if status is not None:
-            first = torch.where(status == lib.REFINE_NOT_ATTEMPTED, torch.full_like(first, -1), first)
+        first, second = _graph_edge_lists(fa, fb, first, second, status, t_rows.device)
         res = lib.pose_graph_sparse(first.contiguous(), second, t_rows, info_rows, C_init, huber_chi, damping, iterations, cg_iterations, cg_tol)
         return {key: t[0] for key, t in zip(lib.POSE_GRAPH_SPARSE_KEYS, res)}
 

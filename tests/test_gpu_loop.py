@@ -212,6 +212,63 @@ def test_several_graphs_in_one_launch_are_independent(T):
             assert np.array_equal(_bits(g), _bits(w)), (k, key)
 
 
+# ------------------------------------------------------------------------------------------------- beside the banded solver
+def _driver_cases():
+    """(name, band, cases stacked into one launch): the shapes at which the driver both solvers share can go wrong."""
+    import pose_graph_cases as pc
+    small = pc._with_edges(pc.graph_case("small", 5, (1, 2), 2, 31), "small", first=(1, -1), second=(5, 1))      # absent; a = b = 1
+    assert len(small["first"]) == 7
+    big = pc.graph_case("chunks", 40, (1, 2, 3) * 3, 3, 32)          # three measurements of every edge up to the band
+    big = {k: (v[:300] if k in ("first", "second", "T", "info") else v) for k, v in big.items()}
+    big["T"][100, 5] = np.nan
+    big["info"][280, 20] = np.inf
+    bad = pc.graph_case("nan_in_C_in", 6, (1, 2), 2, 33)
+    bad["C_in"][3, 7] = np.nan
+    return [("small", 2, [small]), ("chunks", 3, [big]), ("nan_in_C_in", 2, [bad]), ("two_graphs", 2, [pc.graph_case("chain", 5, (1,), 2, 34), small])]
+
+
+def run_banded(T, ops, band, c):
+    from sslam_amd import lib
+    n0 = lib.graph_launch_count()
+    out = lib.pose_graph(*(T.from_numpy(ops[k]).cuda() for k in NAMES), band, c["chi"], c["damping"], c["n_iter"])
+    T.cuda.synchronize()
+    assert lib.graph_launch_count() - n0 == 1
+    return {k: t.cpu().numpy() for k, t in zip(KEYS[:-1], out)}
+
+
+def test_both_solvers_share_the_driver_bit_for_bit(T):
+    """The same operands to sslg_pose_graph (a band that admits every listed edge) and to ssll_pose_graph_sparse.  Without a step
+    every output is the driver's alone and the two are equal byte for byte; with three steps the counts and cost_in still are.
+    Each is also held against its own restatement, and a graph of a two-graph launch against its launch alone."""
+    import pose_graph_cases as pc
+    import pose_graph_ref as pg
+    for name, band, cases in _driver_cases():
+        ops = pc.stacked_graphs(cases)
+        used = [pg.used_mask(c["first"], c["second"], c["T"], c["info"], len(c["C_in"]), band) for c in cases]
+        if name == "chunks":
+            assert ops["first"].shape == (1, 300) and used[0][255] and used[0][256] and not used[0][100] and not used[0][280]
+            assert (ops["second"] - ops["first"])[0][used[0]].max() == band
+        for n_iter in (0, 3):
+            c = dict(chi=4.0, damping=0.0, n_iter=n_iter, cg_iterations=512, cg_tol=1e-3)
+            what = f"{name}, {n_iter} iterations"
+            banded, sparse = run_banded(T, ops, band, c), run_sparse(T, ops, c, what)
+            _same(banded, pg.optimize_graphs(ops["first"], ops["second"], ops["T"], ops["info"], ops["C_in"], band, 4.0, 0.0, n_iter), what, KEYS[:-1])
+            _same(sparse, _want(ops, c), what, KEYS)
+            _same(sparse, banded, what + ": the sparse entry beside the banded one",
+                  KEYS[:-1] if n_iter == 0 else ("used_edges", "skipped_edges", "cost_in"))
+            for k, u in enumerate(used):
+                assert banded["used_edges"][k] == u.sum() and banded["skipped_edges"][k] == ((cases[k]["first"] != -1) & ~u).sum(), (what, k)
+            if name == "nan_in_C_in":
+                assert sparse["status"][0] == 3 and not sparse["cg_steps"].any() and not _bits(sparse["edge_chi2"]).any() and not sparse["cost"].any()
+            if len(cases) > 1:
+                for k, case in enumerate(cases):
+                    e = len(case["first"])
+                    for got, alone in ((banded, run_banded(T, _one(case), band, c)), (sparse, run_sparse(T, _one(case), c, what + f" graph {k} alone"))):
+                        for key in alone:
+                            g = got[key][k][:e] if key == "edge_chi2" else got[key][k]
+                            assert np.array_equal(_bits(g), _bits(alone[key][0])), (what, k, key)
+
+
 # ------------------------------------------------------------------------------------------------------- alignment and replay
 @pytest.mark.parametrize("mode", ["lo", "hi"])
 def test_every_pointer_at_its_least_alignment(T, mode):

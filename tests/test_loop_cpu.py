@@ -356,9 +356,10 @@ def test_loop_build_rebuilds_only_a_stale_library(monkeypatch):
     lib.loop_build(force=True)
     assert calls == [["make", "-C", lib.CSRC_LOOP, "-s", "-j4"]]
     real = os.path.getmtime
-    monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith("edge_terms.h") else 0))     # a newer shared header
-    lib.loop_build()
-    assert len(calls) == 2
+    for n, header in enumerate(("edge_terms.h", "gauss_newton.h")):      # a newer shared header, either of them
+        monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith(header) else 0))
+        lib.loop_build()
+        assert len(calls) == 2 + n
 
 
 def test_every_check_comes_before_the_library_is_loaded(monkeypatch):
