@@ -1518,6 +1518,7 @@ CSRC_GRAPH = os.path.join(_PKG, "csrc_graph")
 GRAPH_SO_PATH = os.path.join(CSRC_GRAPH, "libsslam_graph.so")
 GRAPH_EXPORTS = ["sslg_version", "sslg_arch", "sslg_launch_count", "sslg_chain_poses", "sslg_pose_graph_workspace_bytes", "sslg_pose_graph"]
 GRAPH_MAX_BAND, GRAPH_MAX_NODES, GRAPH_MAX_EDGES, GRAPH_MAX_GRAPHS, GRAPH_MAX_ITER = 32, 4096, 1048576, 65535, 16
+GRAPH_MAX_CHAINS = 0x7fffffff // 256      # sslg_chain_poses runs a thread per chain, not a workgroup per graph: its own n_graphs limit
 POSE_GRAPH_KEYS = ("C", "status", "iterations", "used_edges", "skipped_edges", "failed_row", "cost_in", "cost", "edge_chi2")
 # status: a step was accepted / no step accepted / a failed pivot at the first step / not attempted
 GRAPH_OK, GRAPH_NO_STEP, GRAPH_SINGULAR, GRAPH_NOT_ATTEMPTED = 0, 1, 2, 3
@@ -1659,7 +1660,7 @@ def chain_poses(T, n_nodes=None, start=None, out=None):
     n_graphs, nn = int(T3.shape[0]), int(T3.shape[1]) + 1
     if n_nodes is not None and int(n_nodes) != nn:
         raise ValueError(f"T holds {nn - 1} transforms, n_nodes = {n_nodes} needs {int(n_nodes) - 1}")
-    _check_graph_sizes("chain_poses", n_graphs, nn)
+    _check_graph_sizes("chain_poses", n_graphs, nn, limits=(GRAPH_MAX_CHAINS, GRAPH_MAX_NODES, GRAPH_MAX_EDGES))
     if start is not None:
         start = _graph_rows("start", start, (n_graphs,), (12,), torch.float64)
     if out is not None:

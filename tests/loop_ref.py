@@ -65,7 +65,12 @@ def raw_signatures(desc, scores):
 
 def signatures(desc, scores):
     """sig (N, D) float32 of desc (N, K, D), scores (N, K)."""
-    raw = raw_signatures(desc, scores)
+    return finish_signatures(raw_signatures(desc, scores))
+
+
+def finish_signatures(raw):
+    """sig (N, D) float32 of the raw sums (N, D) of ALL the sequence's frames: the mean in frame order, the centring, the norm."""
+    raw = np.asarray(raw, np.float32)
     n = len(raw)
     with np.errstate(**_ERR):
         mean = np.zeros(raw.shape[1], np.float32)
@@ -204,7 +209,13 @@ def matvec(G, D, BA, p):
 
 def pcg(G, D, g, BA, f, cg_iterations, cg_tol):
     """(x (nn, 6), steps) of A x = -g from x = 0."""
+    return pcg_trace(G, D, g, BA, f, cg_iterations, cg_tol)[:2]
+
+
+def pcg_trace(G, D, g, BA, f, cg_iterations, cg_tol):
+    """pcg, and how its loop ended: "count" (cg_iterations taken), "pq" (p . A p not positive and finite) or "tol"."""
     tol2 = np.float64(cg_tol) * np.float64(cg_tol)
+    ended = "count"
     with np.errstate(**_ERR):
         x, r = np.zeros(g.shape), -g
         z = block_solve(f, r)
@@ -215,6 +226,7 @@ def pcg(G, D, g, BA, f, cg_iterations, cg_tol):
             q = matvec(G, D, BA, p)
             pq = dot(p, q)
             if not (pq > 0.0 and np.isfinite(pq)):
+                ended = "pq"
                 break
             alpha = rz / pq
             x = x + alpha * p
@@ -223,11 +235,12 @@ def pcg(G, D, g, BA, f, cg_iterations, cg_tol):
             rz1 = dot(r, z)
             steps += 1
             if rz1 <= tol2 * rz0:
+                ended = "tol"
                 break
             beta = rz1 / rz
             p = z + beta * p
             rz = rz1
-    return x, steps
+    return x, steps, ended
 
 
 def optimize(first, second, T, info, C_in, chi=4.0, damping=0.0, n_iter=8, cg_iterations=512, cg_tol=1e-3, detail=False):

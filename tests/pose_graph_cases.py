@@ -99,6 +99,7 @@ def shape_cases():
         graph_case("band_plus_5", 8, (1, 3), 3, 5),
         graph_case("forty_nodes_five_spacings", 40, SPACINGS, 20, 6, outliers=0.03),
         graph_case("thirty_four_nodes_band_32", 34, (1, 16, 32), 32, 7),
+        graph_case("forty_nodes_band_32_window_slides", 40, (1, 16, 32), 32, 10),      # 234 rows: the 198-row window slides 36 times
         graph_case("huber_branch", 12, (1, 2, 4), 4, 8, chi=1.0, outliers=0.15),
         graph_case("damped", 9, (1, 3), 3, 9, damping=0.5),
     ]
