@@ -6,7 +6,7 @@
 //                      shared with csrc_loop/loop.hip; this file is the banded solve it calls, BandedSolver::step.
 // A step of sslg_pose_graph:
 //   assembly       256 edges at a time are STAGED, one thread per edge (the residual, w, and the 90 products w H, -(w H Ad),
-//                  w Ad^T H Ad, w H r, -(w Ad^T H r)), then WALKED in slot order by four groups of 63 threads: a thread owns one entry
+//                  w Ad^T H Ad, w H r, -(w Ad^T H r)), then WALKED (edge_walk.h) in slot order by four groups of 63 threads: a thread owns one entry
 //                  position (21 of a diagonal block's lower triangle, 36 of an off-diagonal block, 6 of g) of the nodes n with
 //                  n % 4 == its group, so every word of A and g has one writer and takes its terms in ascending slot order.
 //   factorisation  right-looking on a sliding window in LDS: the lower triangle of the trailing (bw + 1) x (bw + 1) block, 64 KB at
@@ -32,17 +32,11 @@ constexpr int WAVES = NT / 64;
 
 #include "gauss_newton.h"         // the driver: block_sum, block_count, Graph, edge_used, graph_cost, gauss_newton, graph_operands; edge_terms.h
 
-constexpr int WALK = 63;            // entry positions a walking group owns: 21 diagonal, 36 off-diagonal, 6 of g
-constexpr int GROUPS = 4;
+#include "edge_walk.h"           // WALK, GROUPS, walk_staged: the assembly's walk, shared with csrc_window/window.hip; lane_value
+
 constexpr int TQ = (6 * SSLG_MAX_BAND + 5 + 15) / 16;      // columns of the trailing block a thread of the 16 x 16 tiling takes: 13
 
 long long g_launches = 0;   // diagnostic launch counter (sslg_launch_count): relaxed atomic adds, the library's only mutable state
-
-// lane t's x, for a t the compiler knows (two v_readlane_b32)
-__device__ __forceinline__ double lane_value(double x, int t) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), t), hi = __builtin_amdgcn_readlane(__double2hiint(x), t);
-    return __hiloint2double(hi, lo);
-}
 
 // the banded solve: the normal equations of one graph in the workspace (A by rows of W words, then g, y, delta), the window and
 // the ring in LDS
@@ -75,40 +69,11 @@ struct BandedSolver {
             sa[tid] = a;
             sb[tid] = b;
             __syncthreads();
-            const int grp = tid / WALK, pos = tid - grp * WALK;
-            if (grp < GROUPS) {
-                const int cnt = n_edges - base < NT ? n_edges - base : NT;
-#pragma unroll 1
-                for (int c = 0; c < cnt; c++) {
-                    const int eb = sb[c], ea = sa[c];
-                    if (eb < 0) continue;
-                    const double *st = stage + c * STAGE;
-                    const int rb = 6 * (eb - 1), ra = 6 * (ea - 1);
-                    const bool own_b = (eb & (GROUPS - 1)) == grp, own_a = ea >= 1 && (ea & (GROUPS - 1)) == grp;
-                    if (pos < 21) {                      // lower triangle of the diagonal blocks
-                        int i = 0;
-                        while (tri_lower(i + 1, 0) <= pos) i++;
-                        const int j = pos - tri_lower(i, 0);
-                        if (own_b) {
-                            double *p = Ab + (long long)(rb + i) * W + (j - i + bw);
-                            *p = *p + st[S_BB + pos];
-                        }
-                        if (own_a) {
-                            double *p = Ab + (long long)(ra + i) * W + (j - i + bw);
-                            *p = *p + st[S_AA + pos];
-                        }
-                    } else if (pos < 57) {               // the off-diagonal block (b, a)
-                        const int q = pos - 21, i = q / 6, j = q - 6 * i;
-                        if (own_b && ea >= 1) {
-                            double *p = Ab + (long long)(rb + i) * W + ((ra + j) - (rb + i) + bw);
-                            *p = *p + st[S_BA + q];
-                        }
-                    } else {                             // g
-                        const int i = pos - 57;
-                        if (own_b) gv[rb + i] = gv[rb + i] + st[S_GB + i];
-                        if (own_a) gv[ra + i] = gv[ra + i] + st[S_GA + i];
-                    }
-                }
+            {
+                double *const band = Ab;
+                const int Wl = W, bwl = bw;
+                walk_staged(sa, sb, stage, n_edges - base < NT ? n_edges - base : NT, tid,
+                            [=](int r, int c) { return band + (long long)r * Wl + (c - r + bwl); }, gv);
             }
             __syncthreads();
         }

@@ -14,7 +14,9 @@ optimize_pose_graph_sparse, the loop closures on top of it (csrc_loop/loop.hip).
 of them, refine_keypoints_subcell: the selected cells moved to their sub-cell saliency peaks (csrc_ext/subcell.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
-result.  There is no CPU implementation here: without the GPU library these functions raise.
+result.  There is no CPU implementation here: without the GPU library these functions raise.  The one exception is PoseWindow, the
+online sliding-window estimator, which is numpy by design (a front end steps it once per frame on the host) and gives the device
+entry's bits.
 
 The two keypoint sets may differ in size: they go to the device as a two-frame bank (2, max(N, M), 2), zero rows behind the
 shorter set, and the entry is told how many rows of each frame count (its n1 / n2 arguments), so the padding is never read.
@@ -229,6 +231,62 @@ def optimize_pose_graph(first, second, T, info, n_nodes: int, C_init=None, band=
     C = np.tile(np.eye(4), (n_nodes, 1, 1))
     C[:, :3] = out["C"].cpu().numpy().reshape(n_nodes, 3, 4)
     return C, int(out["status"].cpu()), out["edge_chi2"].cpu().numpy()
+
+
+class PoseWindow:
+    """The online counterpart of optimize_pose_graph: a sliding window over the last `window` frames (sslw_window_step,
+    include/sslam_window.h) fed one frame at a time with the relative poses refine_relative_pose returned for the pairs
+    (t - s, t), s in `spacings`.  This one class needs NO GPU: it runs the header's statement in numpy float64
+    (sslam_amd/window_numpy.py) and gives the bits the device entry gives - a caller on the device uses
+    SequencePipeline.pose_window_step or online.WindowPoseFrameStepper.
+    window: 2 .. 32 frames, max(spacings) + 1 if None; spacings: up to 8 distinct positive ints; capacity: the frames the
+    trajectory keeps; min_inliers, huber_chi, damping, iterations: as pose_window_step takes them; C_start (4, 4) or (3, 4) world ->
+    camera pose of frame 0, the identity if None."""
+
+    def __init__(self, window=None, spacings=(1, 5, 10, 15, 20), capacity: int = 4096, min_inliers: int = 12, huber_chi: float = 4.0,
+                 damping: float = 0.0, iterations: int = 2, C_start=None):
+        from sslam_amd import window_numpy as wn
+        from sslam_amd.online import _checked_spacings
+        self.spacings = _checked_spacings(spacings, below=2 ** 31)
+        self.window, _, self.capacity, _ = lib.check_window_sizes(max(self.spacings) + 1 if window is None else window, len(self.spacings), capacity)
+        self.min_inliers = lib.check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1)
+        self.huber_chi, self.damping = lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping)
+        self.iterations = lib.check_graph_iterations(iterations)
+        if C_start is not None:
+            C_start = np.asarray(C_start, dtype=np.float64)
+            if tuple(C_start.shape) not in ((4, 4), (3, 4)):
+                raise ValueError(f"C_start (4, 4) or (3, 4) expected, got {C_start.shape}")
+            C_start = np.ascontiguousarray(C_start[:3]).reshape(12)
+        self.C_start, self._wn = C_start, wn
+        self.reset()
+
+    def reset(self) -> None:
+        self.state = self._wn.fresh_state(self.window, len(self.spacings), self.capacity)
+
+    def step(self, T, info, status, inlier_count) -> dict:
+        """T (S, 4, 4) or (S, 3, 4): camera t - s -> camera t for every spacing, in their order; info (S, 6, 6): their information
+        matrices; status, inlier_count (S,): the refinement's (a pair that does not exist yet: status 3).  Returns the entry's
+        outputs by name (lib.WINDOW_OUT_KEYS) as numpy arrays: C_window (window, 12) world -> camera in node order, base, n_nodes,
+        admitted (S,), predicted_from, lost, status, iterations, used_edges, dropped_edges, failed_row, cost_in, cost, edge_chi2."""
+        S = len(self.spacings)
+        T, info = np.asarray(T, dtype=np.float64), np.asarray(info, dtype=np.float64)
+        status, inlier_count = np.asarray(status).reshape(-1), np.asarray(inlier_count).reshape(-1)
+        if T.ndim != 3 or tuple(T.shape) not in ((S, 4, 4), (S, 3, 4)):
+            raise ValueError(f"T ({S}, 4, 4) or ({S}, 3, 4) expected, got {T.shape}")
+        if info.shape != (S, 6, 6):
+            raise ValueError(f"info ({S}, 6, 6) expected, got {info.shape}")
+        if len(status) != S or len(inlier_count) != S:
+            raise ValueError(f"status and inlier_count ({S},) expected")
+        iu = np.triu_indices(6)
+        return self._wn.step(self.state, self.spacings, np.ascontiguousarray(T[:, :3]).reshape(S, 12), np.ascontiguousarray(info[:, iu[0], iu[1]]),
+                             status, inlier_count, self.C_start, self.min_inliers, self.huber_chi, self.damping, self.iterations)
+
+    def trajectory(self) -> np.ndarray:
+        """Camera -> world poses (n, 4, 4) of the frames 0 .. min(frames stepped, capacity) - 1."""
+        n = min(int(self.state["t"]), self.capacity)
+        C = np.tile(np.eye(4), (n, 1, 1))
+        C[:, :3] = self.state["trajectory"][:n].reshape(n, 3, 4)
+        return np.stack([np.linalg.inv(c) for c in C]) if n else np.zeros((0, 4, 4))
 
 
 def find_loop_candidates(descriptors, scores, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2, suppress: int = 5):

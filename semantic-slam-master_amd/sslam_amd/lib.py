@@ -1833,3 +1833,130 @@ def pose_graph_sparse(first, second, T, info, C_in, huber_chi=4.0, damping=0.0, 
          _dp(info), n_graphs, n_nodes, n_edges, _dp(C3), C.c_double(chi), C.c_double(damp), n_iter, n_cg, C.c_double(tol), _dp(ws),
          *(_dp(x) for x in o))
     return tuple(o)
+
+
+# -------------------------------------------------------------------------------------- libsslam_window.so (include/sslam_window.h)
+# The fifth library: entries with the prefix sslw_, built from csrc_window/ with csrc/flags.mk, loaded and refused like the others.
+CSRC_WINDOW = os.path.join(_PKG, "csrc_window")
+WINDOW_SO_PATH = os.path.join(CSRC_WINDOW, "libsslam_window.so")
+WINDOW_EXPORTS = ["sslw_version", "sslw_arch", "sslw_launch_count", "sslw_window_workspace_bytes", "sslw_window_step"]
+WINDOW_MAX_WINDOW, WINDOW_MAX_SPACINGS, WINDOW_MAX_WINDOWS, WINDOW_MAX_FRAME = 32, 8, 65535, 2 ** 31 - 2
+WINDOW_STATE_KEYS = ("t", "ring_first", "ring_second", "ring_T", "ring_info", "ring_C", "trajectory")
+WINDOW_OUT_KEYS = ("C_window", "base", "n_nodes", "admitted", "predicted_from", "lost", "status", "iterations", "used_edges", "dropped_edges",
+                   "failed_row", "cost_in", "cost", "edge_chi2")
+WINDOW_COUNTER_OUT_OF_RANGE = 4      # status, beside GRAPH_OK .. GRAPH_NOT_ATTEMPTED
+
+_window = None
+
+
+def window_build(force: bool = False) -> str:
+    """Compile libsslam_window.so for gfx950 in-tree, as build() compiles the first library."""
+    shared = [os.path.join(CSRC_GRAPH, h) for h in ("edge_terms.h", "gauss_newton.h", "edge_walk.h")]
+    return _make_if_stale(CSRC_WINDOW, WINDOW_SO_PATH, shared + [os.path.join(_INCLUDE, h) for h in ("sslam_window.h", "sslam_graph.h", "sslam_hip.h")],
+                          force)
+
+
+def window():
+    """Load libsslam_window.so; raises if it has not been built (no silent fallback)."""
+    global _window
+    if _window is None:
+        _window = _load(WINDOW_SO_PATH, CSRC_WINDOW, "sslw", _window_prototypes)
+    return _window
+
+
+def _window_prototypes(L):
+    L.sslw_window_workspace_bytes.restype = C.c_size_t
+    p, i, d, ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
+    L.sslw_window_workspace_bytes.argtypes = [i, i, i]
+    L.sslw_window_step.argtypes = [p] * 13 + [i, i, i, i, d, d, i, ll] + [p] * 16
+
+
+def window_launch_count() -> int:
+    return int(window().sslw_launch_count())
+
+
+def check_window_sizes(window, n_spacings, capacity, n_windows=1) -> tuple:
+    """(window 2 .., n_spacings 1 .., capacity 1 .., n_windows 1 ..) as ints, else ValueError; past WINDOW_MAX_*: SslamHipError -
+    before any device work."""
+    w, s, cap, nw = check_int("window", window, 2), check_int("n_spacings", n_spacings, 1), check_int("capacity", capacity, 1), \
+        check_int("n_windows", n_windows, 1)
+    if w > WINDOW_MAX_WINDOW or s > WINDOW_MAX_SPACINGS or nw > WINDOW_MAX_WINDOWS or cap > (2 ** 63 - 1) // 96 // nw:
+        raise SslamHipError(f"window_step: {_ERR[E_UNSUPPORTED]} (window <= {WINDOW_MAX_WINDOW}, n_spacings <= {WINDOW_MAX_SPACINGS}, "
+                            f"n_windows <= {WINDOW_MAX_WINDOWS}, capacity * 96 * n_windows < 2^63; got {w}, {s}, {nw}, {cap})")
+    return w, s, cap, nw
+
+
+def window_state_shapes(n_windows: int, window: int, n_spacings: int, capacity: int) -> dict:
+    """name -> (shape, dtype) of the persistent state of window_step (WINDOW_STATE_KEYS)."""
+    ws = window * n_spacings
+    return {"t": ((n_windows,), torch.int32), "ring_first": ((n_windows, ws), torch.int32), "ring_second": ((n_windows, ws), torch.int32),
+            "ring_T": ((n_windows, ws, 12), torch.float64), "ring_info": ((n_windows, ws, 21), torch.float64),
+            "ring_C": ((n_windows, window, 12), torch.float64), "trajectory": ((n_windows, capacity, 12), torch.float64)}
+
+
+def window_out_shapes(n_windows: int, window: int, n_spacings: int) -> dict:
+    """name -> (shape, dtype) of the outputs of window_step (WINDOW_OUT_KEYS)."""
+    one, real = ((n_windows,), torch.int32), ((n_windows,), torch.float64)
+    return {"C_window": ((n_windows, window, 12), torch.float64), "base": one, "n_nodes": one, "admitted": ((n_windows, n_spacings), torch.int32),
+            "predicted_from": one, "lost": one, "status": one, "iterations": one, "used_edges": one, "dropped_edges": one, "failed_row": one,
+            "cost_in": real, "cost": real, "edge_chi2": ((n_windows, window * n_spacings), torch.float64)}
+
+
+def window_workspace_bytes(n_windows: int, window: int, n_spacings: int) -> int:
+    """sslw_window_workspace_bytes, restated: per window 24 W + 256 * 90 + W S float64 words.  Needs no library."""
+    return 8 * n_windows * (24 * window + 256 * 90 + window * n_spacings)
+
+
+def alloc_window_state(window, n_spacings, capacity, n_windows=1, device="cuda") -> dict:
+    """A fresh state of window_step: t = 0, ring_first = -1, everything else zero."""
+    w, s, cap, nw = check_window_sizes(window, n_spacings, capacity, n_windows)
+    state = {k: torch.zeros(shape, dtype=dt, device=device) for k, (shape, dt) in window_state_shapes(nw, w, s, cap).items()}
+    state["ring_first"].fill_(-1)
+    return state
+
+
+def alloc_window_out(window, n_spacings, n_windows=1, device="cuda") -> dict:
+    """The outputs of window_step as zeroed tensors."""
+    w, s, _, nw = check_window_sizes(window, n_spacings, 1, n_windows)
+    return {k: torch.zeros(shape, dtype=dt, device=device) for k, (shape, dt) in window_out_shapes(nw, w, s).items()}
+
+
+def window_step(state, spacings, new_T, new_info, new_status, new_inliers, C_start=None, min_inliers=12, huber_chi=4.0, damping=0.0,
+                iterations=2, out=None, workspace=None) -> dict:
+    """sslw_window_step: one frame of n_windows sliding windows (include/sslam_window.h).  state: alloc_window_state's dict, read and
+    written; spacings (S,) int32 device tensor; new_T (n_windows, S, 12), new_info (n_windows, S, 21) float64, new_status and
+    new_inliers (n_windows, S) int32 - what pose_refine_pairs wrote for the frame's S pairs (one window may leave the window axis
+    out); C_start (n_windows, 12) float64 or None.  min_inliers: int >= 0; huber_chi: finite > 0; damping: finite >= 0; iterations
+    0 .. GRAPH_MAX_ITER.  Returns WINDOW_OUT_KEYS' tensors as a dict (out: alloc_window_out's, or made here).  workspace: optional
+    uint8 tensor of at least window_workspace_bytes.  One launch, no host read; everything is judged before the library is loaded."""
+    mi, chi, damp, n_iter = check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1), check_positive("huber_chi", huber_chi), check_damping(damping), \
+        check_graph_iterations(iterations)
+    if not isinstance(state, dict) or set(state) != set(WINDOW_STATE_KEYS) or not all(isinstance(v, torch.Tensor) for v in state.values()):
+        raise ValueError(f"state must be a dict of the tensors {', '.join(WINDOW_STATE_KEYS)}")
+    rc, tr = state["ring_C"], state["trajectory"]
+    if rc.dim() != 3 or tr.dim() != 3 or not isinstance(spacings, torch.Tensor) or spacings.dim() != 1:
+        raise ValueError("state `ring_C` (n_windows, window, 12), `trajectory` (n_windows, capacity, 12) and spacings (S,) int32 expected")
+    w, s, cap, nw = check_window_sizes(int(rc.shape[1]), int(spacings.shape[0]), int(tr.shape[1]), int(rc.shape[0]))
+    for key, (shape, dt) in window_state_shapes(nw, w, s, cap).items():
+        _check_arrays(shape, (f"state `{key}`", state[key], dt))
+    _check_arrays((s,), ("spacings", spacings, torch.int32))
+    new_T = _graph_rows("new_T", new_T, (nw, s), (12,), torch.float64)
+    new_info = _graph_rows("new_info", new_info, (nw, s), (21,), torch.float64)
+    new_status = _graph_rows("new_status", new_status, (nw, s), (), torch.int32)
+    new_inliers = _graph_rows("new_inliers", new_inliers, (nw, s), (), torch.int32)
+    if C_start is not None:
+        C_start = _graph_rows("C_start", C_start, (nw,), (12,), torch.float64)
+    shapes = window_out_shapes(nw, w, s)
+    if out is not None and (not isinstance(out, dict) or set(out) != set(WINDOW_OUT_KEYS)):
+        raise ValueError(f"out must be a dict of the tensors {', '.join(WINDOW_OUT_KEYS)}")
+    o = None if out is None else _outputs(shapes, WINDOW_OUT_KEYS, [out[k] for k in WINDOW_OUT_KEYS])
+    need = window_workspace_bytes(nw, w, s)
+    _check_workspace(workspace, need)
+    st = [state[k] for k in WINDOW_STATE_KEYS]
+    dev = common_device(*st, spacings, new_T, new_info, new_status, new_inliers, C_start, workspace, *(o or ()))
+    o = _outputs(shapes, WINDOW_OUT_KEYS, None, dev) if o is None else o
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _run("window_step", window().sslw_window_step, (*st, spacings, new_T, new_info, new_status, new_inliers, C_start, ws, *o),
+         *(_dp(x) for x in st), _dp(spacings), _dp(new_T), _dp(new_info), _dp(new_status), _dp(new_inliers), _dp(C_start), nw, w, s, mi,
+         C.c_double(chi), C.c_double(damp), n_iter, cap, _dp(ws), *(_dp(x) for x in o))
+    return dict(zip(WINDOW_OUT_KEYS, o))

@@ -35,6 +35,9 @@ frame t - s, or -1 while t < s: an absent pair; second = the static slot), runs 
 sslam_match_finalize_pairs over all spacings (include/sslam_hip.h: the pair list is read by the kernels), copies the frame into
 ring slot t mod max(spacings) with a device-indexed copy and increments t.  No host value that changes between steps enters the
 body, so the replayed graph is the same step for every frame.  `spacings=None` is the one-spacing stepper above, untouched.
+
+`WindowPoseFrameStepper` puts the pose stage and the sliding-window estimator (include/sslam_window.h) behind that multi-spacing
+matcher, still in the one captured step: the frame's trajectory while the sequence runs, not after it has ended.
 """
 from __future__ import annotations
 
@@ -52,11 +55,13 @@ def bank_keys(pipe) -> tuple:
     return BANK_KEYS + (lib.SUBCELL_KEYS if pipe.cfg.subcell else ())
 
 
-def _checked_spacings(spacings) -> tuple:
+def _checked_spacings(spacings, below=None) -> tuple:
+    """below: the spacings must also be smaller than it (the pose window keeps them as int32 on the device)."""
     if isinstance(spacings, (str, bytes)) or not hasattr(spacings, "__iter__"):
         raise ValueError(f"spacings must be a sequence of distinct positive ints, got {spacings!r}")
     sp = tuple(spacings)
-    if not sp or any(isinstance(s, bool) or not isinstance(s, int) or s < 1 for s in sp) or len(set(sp)) != len(sp):
+    if not sp or any(isinstance(s, bool) or not isinstance(s, int) or s < 1 or (below is not None and s >= below) for s in sp) or \
+            len(set(sp)) != len(sp):
         raise ValueError(f"spacings must be a non-empty sequence of distinct positive ints, got {spacings!r}")
     return sp
 
@@ -369,3 +374,96 @@ class PoseFrameStepper(RuleFrameStepper):
     def reset(self) -> None:
         super().reset()
         self.kp_depth.fill_(-1)
+
+
+class WindowPoseFrameStepper(RuleFrameStepper):
+    """RuleFrameStepper over several spacings whose step also estimates the camera's trajectory: the online form of
+    odometry_graph.  step() takes the frame's raw depth image beside it; behind the matcher's finalize launch, on the same one
+    stream - as ordinary launches or inside the captured graph - the depth under this frame's keypoints is gathered
+    (sslam_keypoint_depth) into the static slot of a depth ring that lies beside the feature ring, ONE sslam_pose_ransac_pairs and
+    ONE sslam_pose_refine_pairs launch run over the step's S pairs with the matcher's own first_slot / second_slot lists (an absent
+    pair comes out with refinement status 3), and sslw_window_step (include/sslam_window.h) admits the refined pairs into a ring of
+    the last `window` frames' edges, predicts the frame's pose from the nearest admitted pair and optimises the window's poses with
+    its oldest frame held.  The window's frame counter is device memory like the stepper's own, so no host value enters the
+    body.  The static slot is then handed over to the ring with the frame's features.
+    The geometry bank follows pipe.geometry_keypoints (the refined keypoints on a pipeline with subcell=True), as in
+    PoseFrameStepper, whose signature and behaviour this class leaves alone.
+    step() returns what RuleFrameStepper returns with spacings, plus "pose": RANSAC's keys with a leading S axis (T (S, 12), ...)
+    and "refined", the refinement's outputs (T, status, ..., info (S, 21)); and "window": lib.WINDOW_OUT_KEYS' tensors without the
+    window axis (C_window (window, 12), base, n_nodes, admitted (S,), predicted_from, lost, status, ...) - all views of static
+    buffers.  window: max(spacings) + 1 if None; a spacing of `window` or more is matched and refined but never admitted.
+    rule: MatchRule.mnn_ratio(0.9) if None, as odometry() has it; huber: threshold / 3 if None; iterations: the refinement's;
+    min_inliers, huber_chi, damping, graph_iterations: SequencePipeline.pose_window_step's; capacity: the frames trajectory()
+    keeps."""
+
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, depth_height: int, depth_width: int, camera=None,
+                 use_graph: bool = True, tokens_in: bool = False, rule=None, spacings=(1, 5, 10, 15, 20), window=None,
+                 threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, huber=None, iterations: int = 5, min_inliers: int = 12,
+                 huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 2, capacity: int = 4096):
+        from .evaluation import Camera, check_depth_size
+        from .pipeline import MatchRule
+        sp = _checked_spacings(spacings, below=2 ** 31)                  # everything is judged before anything is allocated
+        self.threshold, self.hypotheses, self.seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
+        self.huber, self.iterations = lib.check_huber(self.threshold / 3.0 if huber is None else huber), lib.check_iterations(iterations)
+        self.window, _, self.capacity, _ = lib.check_window_sizes(max(sp) + 1 if window is None else window, len(sp), capacity)
+        self.min_inliers, self.huber_chi = lib.check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1), lib.check_positive("huber_chi", huber_chi)
+        self.damping, self.graph_iterations = lib.check_damping(damping), lib.check_graph_iterations(graph_iterations)
+        self.camera = Camera() if camera is None else camera
+        check_depth_size(depth_width, depth_height, self.camera)
+        super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=sp,
+                         rule=MatchRule.mnn_ratio(0.9) if rule is None else rule)
+        dev, K, S = self.device, self.cfg.num_keypoints, len(sp)
+        self.depth = torch.zeros((1, depth_height, depth_width), dtype=torch.uint16, device=dev)
+        self.kp_depth = torch.full((self.ring + 1, K), -1, dtype=torch.int32, device=dev)      # the depth ring, slot for slot beside the bank
+        self.pose = pipe.alloc_pose(S, K)
+        self.refined = pipe.alloc_pose_refine(S, K)
+        self.win = pipe.alloc_pose_window(self.window, sp, self.capacity)
+
+    def _after_match(self) -> None:
+        p, ring = self.pipe, self.ring
+        kp = p.geometry_keypoints(self.bank)
+        p.keypoint_depth(self.depth, kp[ring:ring + 1], out=self.kp_depth[ring:ring + 1])
+        p.estimate_poses(kp, self.kp_depth, self.first_slot, self.second_slot, self.m, self.camera, self.threshold, self.hypotheses,
+                         self.seed, out=self.pose)
+        p.refine_poses(kp, self.kp_depth, self.first_slot, self.second_slot, self.m, self.camera, self.pose, self.threshold, self.huber,
+                       self.iterations, out=self.refined)
+        p.pose_window_step(self.win, self.refined, None, self.min_inliers, self.huber_chi, self.damping, self.graph_iterations)
+        torch.remainder(self._t, ring, out=self._slot)                   # the ring slot the frame's features take, right after this
+        self.kp_depth[:ring].index_copy_(0, self._slot, self.kp_depth[ring:ring + 1])
+
+    def _reset_window(self) -> None:
+        st = self.win["state"]
+        st["t"].zero_()
+        st["ring_first"].fill_(-1)
+        self.kp_depth.fill_(-1)
+
+    def _capture(self) -> None:
+        super()._capture()
+        self._reset_window()                     # the warm-up passes stepped the window too: the first real frame is frame 0
+
+    @torch.no_grad()
+    def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
+        """image_u8, tokens: as FrameStepper.step takes them; depth_u16: (h, w) or (1, h, w) uint16, the frame's raw depth image."""
+        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dtype != torch.uint16 or depth_u16.numel() != self.depth.numel():
+            raise ValueError(f"depth_u16 must be a uint16 tensor of shape {tuple(self.depth.shape[1:])}")
+        if self.use_graph and self._graph is None:
+            self._capture()                      # before the frame's depth goes into its static buffer, as the image does in the parent
+        self.depth.copy_(depth_u16.reshape(self.depth.shape), non_blocking=True)
+        out = super().step(image_u8, tokens)
+        out["pose"] = dict(self.pose, refined=dict(self.refined))
+        out["window"] = {k: v[0] for k, v in self.win["out"].items()}
+        return out
+
+    def trajectory(self):
+        """Camera -> world poses (n, 4, 4) float64 of the frames 0 .. min(n_frames, capacity) - 1, each as it stood when it left the
+        window (or stands now): odometry_graph's convention.  One read-back."""
+        import numpy as np
+        n = min(self.n_frames, self.capacity)
+        C = self.win["state"]["trajectory"][0, :n].cpu().numpy().reshape(n, 3, 4)
+        C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
+        return np.stack([np.linalg.inv(c) for c in C44]) if n else np.zeros((0, 4, 4))
+
+    def reset(self) -> None:
+        """Forget every earlier frame: the device's counters are zeroed and the ring's slots made absent here, outside the graph."""
+        super().reset()
+        self._reset_window()

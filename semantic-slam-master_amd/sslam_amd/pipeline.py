@@ -986,6 +986,46 @@ class SequencePipeline:
         res = lib.pose_graph_sparse(first.contiguous(), second, t_rows, info_rows, C_init, huber_chi, damping, iterations, cg_iterations, cg_tol)
         return {key: t[0] for key, t in zip(lib.POSE_GRAPH_SPARSE_KEYS, res)}
 
+    def alloc_pose_window(self, window: int, spacings, capacity: int = 4096, n_windows: int = 1) -> dict:
+        """The buffers of pose_window_step() (csrc_window/window.hip) for n_windows sliding windows of `window` frames over the
+        pairs (t - s, t) of `spacings` (distinct positive ints): "state" - lib.alloc_window_state's fresh state, with the trajectory of
+        the first `capacity` frames -, "out" - lib.alloc_window_out's outputs -, "spacings" (S,) int32 and "workspace", all on this
+        pipeline's device.  A spacing of `window` or more is allowed and never admitted."""
+        from .online import _checked_spacings             # online imports this module
+        sp = _checked_spacings(spacings, below=2 ** 31)
+        w, s, cap, nw = lib.check_window_sizes(window, len(sp), capacity, n_windows)
+        dev = self.device
+        return dict(state=lib.alloc_window_state(w, s, cap, nw, dev), out=lib.alloc_window_out(w, s, nw, dev),
+                    spacings=torch.tensor(sp, dtype=torch.int32, device=dev),
+                    workspace=torch.empty(lib.window_workspace_bytes(nw, w, s), dtype=torch.uint8, device=dev))
+
+    @staticmethod
+    def pose_window_step(state: dict, refined: dict, out: dict | None = None, min_inliers: int = 12, huber_chi: float = 4.0,
+                         damping: float = 0.0, iterations: int = 2) -> dict:
+        """One frame of the online estimator (sslw_window_step, include/sslam_window.h): the S refined pairs of this frame - `refined`,
+        the dictionary refine_poses() returned for the pairs (t - spacings[k], t) in the order of the spacings; its T, info, status
+        and inlier_count are read, (S, ...) rows for one window or (n_windows * S, ...) - enter the ring of `state`
+        (alloc_pose_window's dictionary), the frame's pose is predicted from the nearest admitted pair, and the window's poses are
+        optimised with its oldest frame held.  A pair is admitted when its frame is in the window, its status is not 3, it has at
+        least min_inliers inliers and its numbers are finite.  huber_chi, damping, iterations: as optimize_pose_graph takes them;
+        frame 0 stands at [I | 0] (lib.window_step takes a start pose).  Returns lib.WINDOW_OUT_KEYS' device tensors - `out`, or the
+        state's own "out" buffers.  One launch, no host read: the frame counter is device memory, so the call can be captured."""
+        if not isinstance(state, dict) or any(k not in state for k in ("state", "out", "spacings", "workspace")):
+            raise ValueError("state must be alloc_pose_window()'s dictionary")
+        if not isinstance(refined, dict) or any(k not in refined for k in ("T", "info", "status", "inlier_count")):
+            raise ValueError("refined must be refine_poses()' dictionary: T, info, status and inlier_count are read")
+        s = int(state["spacings"].shape[0])
+        nw = int(state["state"]["t"].shape[0])
+        rows = {}
+        for key, tail in (("T", (12,)), ("info", (21,)), ("status", ()), ("inlier_count", ())):
+            t = refined[key]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (nw * s,) + tail or not t.is_contiguous():
+                raise ValueError(f"refined `{key}` must be a contiguous tensor of shape {(nw * s,) + tail}")
+            rows[key] = t.view((nw, s) + tail)
+        return lib.window_step(state["state"], state["spacings"], rows["T"], rows["info"], rows["status"], rows["inlier_count"], None,
+                               min_inliers, huber_chi, damping, iterations, out=state["out"] if out is None else out,
+                               workspace=state["workspace"])
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
