@@ -14,9 +14,9 @@ optimize_pose_graph_sparse, the loop closures on top of it (csrc_loop/loop.hip).
 of them, refine_keypoints_subcell: the selected cells moved to their sub-cell saliency peaks (csrc_ext/subcell.hip).
 
 numpy in -> numpy out like the originals; torch CUDA tensors are accepted too and then nothing leaves the device except the
-result.  There is no CPU implementation here: without the GPU library these functions raise.  The one exception is PoseWindow, the
-online sliding-window estimator, which is numpy by design (a front end steps it once per frame on the host) and gives the device
-entry's bits.
+result.  There is no CPU implementation here: without the GPU library these functions raise.  The exceptions are PoseWindow, the
+online sliding-window estimator, and PlaceBank and EdgeLog, the online loop retrieval and its edge list, which are numpy by design
+(a front end steps them once per frame on the host) and give the device entries' bits.
 
 The two keypoint sets may differ in size: they go to the device as a two-frame bank (2, max(N, M), 2), zero rows behind the
 shorter set, and the entry is told how many rows of each frame count (its n1 / n2 arguments), so the padding is never read.
@@ -287,6 +287,74 @@ class PoseWindow:
         C = np.tile(np.eye(4), (n, 1, 1))
         C[:, :3] = self.state["trajectory"][:n].reshape(n, 3, 4)
         return np.stack([np.linalg.inv(c) for c in C]) if n else np.zeros((0, 4, 4))
+
+
+class PlaceBank:
+    """The online counterpart of find_loop_candidates: a place bank that grows by one frame per step (sslp_place_step,
+    include/sslam_place.h) and answers, at every step, which older frames the new one resembles.  Like PoseWindow it needs NO GPU:
+    it runs the header's statement in numpy float32 (sslam_amd/place_numpy.py) and gives the bits the device entry gives - a caller
+    on the device uses SequencePipeline.place_step or online.LoopWindowPoseFrameStepper.
+    capacity: 1 .. 4096 frames; d: the descriptor width, 128 or 256; min_gap, min_sim, per_frame, suppress: find_loop_candidates'."""
+
+    def __init__(self, capacity: int = 1024, d: int = lib.D_OUT, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2, suppress: int = 5):
+        from sslam_amd import place_numpy as pn
+        self.min_gap, self.min_sim, self.per_frame, self.suppress = lib.check_loop_arguments(min_gap, min_sim, per_frame, suppress)
+        self.capacity, _, self.d = lib.check_place_sizes(capacity, 1, d)
+        self._pn = pn
+        self.reset()
+
+    def reset(self) -> None:
+        self.state = self._pn.fresh_place(self.capacity, self.d)
+
+    def step(self, descriptors, scores) -> dict:
+        """descriptors (K, d), scores (K,) float32 of one frame, K 1 .. 4096.  Returns the entry's outputs by name (lib.PLACE_OUT_KEYS)
+        as numpy arrays: first, second (per_frame,) int32 - the older frame and this one, -1 in an empty slot -, sim, count (1,),
+        status (1,): 0, or 4 once the bank is full, sig (d,): the frame's signature as of this step."""
+        descriptors, scores = np.asarray(descriptors, dtype=np.float32), np.asarray(scores, dtype=np.float32)
+        if descriptors.ndim != 2 or descriptors.shape[1] != self.d or scores.shape != descriptors.shape[:1]:
+            raise ValueError(f"descriptors (K, {self.d}) and scores (K,) expected, got {descriptors.shape} and {scores.shape}")
+        lib.check_place_sizes(self.capacity, int(descriptors.shape[0]), self.d)
+        return self._pn.place_step(self.state, descriptors, scores, self.min_gap, self.min_sim, self.per_frame, self.suppress)
+
+
+class EdgeLog:
+    """The append-only list of verified edges optimize_pose_graph_sparse reads (sslp_edge_log_step, include/sslam_place.h), in numpy:
+    per frame n_slots pairs, the first n_odometry of them odometry pairs held to min_inliers, the others loop candidates held to
+    loop_min_inliers.  No GPU needed; the device entry's bits."""
+
+    def __init__(self, capacity: int = 1024, n_slots: int = 7, n_odometry: int = 5, min_inliers: int = 12, loop_min_inliers: int = 12):
+        from sslam_amd import place_numpy as pn
+        self.capacity, self.n_slots = lib.check_edge_log_sizes(capacity, n_slots)
+        self.n_odometry = lib.check_int("n_odometry", n_odometry, 0, self.n_slots)
+        self.min_inliers = lib.check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1)
+        self.loop_min_inliers = lib.check_int("loop_min_inliers", loop_min_inliers, 0, 2 ** 31 - 1)
+        self._pn = pn
+        self.reset()
+
+    def reset(self) -> None:
+        self.state = self._pn.fresh_log(self.capacity, self.n_slots)
+
+    def step(self, slot_first, T, info, status, inlier_count) -> dict:
+        """slot_first (E,): the global index of every pair's older frame, -1 for none; T (E, 4, 4) or (E, 3, 4), info (E, 6, 6),
+        status, inlier_count (E,): as refine_relative_pose returned them.  Returns logged (E,) int32 and status (1,)."""
+        E = self.n_slots
+        slot_first = np.asarray(slot_first).reshape(-1)
+        T, info = np.asarray(T, dtype=np.float64), np.asarray(info, dtype=np.float64)
+        status, inlier_count = np.asarray(status).reshape(-1), np.asarray(inlier_count).reshape(-1)
+        if T.ndim != 3 or tuple(T.shape) not in ((E, 4, 4), (E, 3, 4)):
+            raise ValueError(f"T ({E}, 4, 4) or ({E}, 3, 4) expected, got {T.shape}")
+        if info.shape != (E, 6, 6):
+            raise ValueError(f"info ({E}, 6, 6) expected, got {info.shape}")
+        if len(slot_first) != E or len(status) != E or len(inlier_count) != E:
+            raise ValueError(f"slot_first, status and inlier_count ({E},) expected")
+        iu = np.triu_indices(6)
+        return self._pn.log_step(self.state, slot_first, np.ascontiguousarray(T[:, :3]).reshape(E, 12), np.ascontiguousarray(info[:, iu[0], iu[1]]),
+                                 status, inlier_count, self.n_odometry, self.min_inliers, self.loop_min_inliers)
+
+    def edges(self) -> tuple:
+        """(first, second, T (n E, 12), info (n E, 21)) of the n frames logged: optimize_pose_graph_sparse's edges in log order."""
+        rows = min(int(self.state["t"]), self.capacity) * self.n_slots
+        return tuple(self.state[k][:rows] for k in ("log_first", "log_second", "log_T", "log_info"))
 
 
 def find_loop_candidates(descriptors, scores, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2, suppress: int = 5):

@@ -1960,3 +1960,184 @@ def window_step(state, spacings, new_T, new_info, new_status, new_inliers, C_sta
          *(_dp(x) for x in st), _dp(spacings), _dp(new_T), _dp(new_info), _dp(new_status), _dp(new_inliers), _dp(C_start), nw, w, s, mi,
          C.c_double(chi), C.c_double(damp), n_iter, cap, _dp(ws), *(_dp(x) for x in o))
     return dict(zip(WINDOW_OUT_KEYS, o))
+
+
+# ---------------------------------------------------------------------------------------- libsslam_place.so (include/sslam_place.h)
+# The sixth library: entries with the prefix sslp_, built from csrc_place/ with csrc/flags.mk, loaded and refused like the others.
+CSRC_PLACE = os.path.join(_PKG, "csrc_place")
+PLACE_SO_PATH = os.path.join(CSRC_PLACE, "libsslam_place.so")
+PLACE_EXPORTS = ["sslp_version", "sslp_arch", "sslp_launch_count", "sslp_place_workspace_bytes", "sslp_place_step", "sslp_edge_log_step"]
+PLACE_MAX_CAPACITY, PLACE_MAX_K, PLACE_MAX_PER_FRAME, PLACE_MAX_SLOTS = 4096, 4096, 8, 16
+PLACE_STATE_KEYS = ("t", "raw", "sum")
+PLACE_OUT_KEYS = ("first", "second", "sim", "count", "status", "sig")
+EDGE_LOG_STATE_KEYS = ("t", "log_first", "log_second", "log_T", "log_info")
+EDGE_LOG_OUT_KEYS = ("logged", "status")
+PLACE_COUNTER_OUT_OF_RANGE = 4       # status of both steps: the counter was outside 0 .. capacity - 1
+
+_place = None
+
+
+def place_build(force: bool = False) -> str:
+    """Compile libsslam_place.so for gfx950 in-tree, as build() compiles the first library."""
+    return _make_if_stale(CSRC_PLACE, PLACE_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_place.h", "sslam_hip.h")], force)
+
+
+def place():
+    """Load libsslam_place.so; raises if it has not been built (no silent fallback)."""
+    global _place
+    if _place is None:
+        _place = _load(PLACE_SO_PATH, CSRC_PLACE, "sslp", _place_prototypes)
+    return _place
+
+
+def _place_prototypes(L):
+    L.sslp_place_workspace_bytes.restype = C.c_size_t
+    p, i, f, ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
+    L.sslp_place_workspace_bytes.argtypes = [i]
+    L.sslp_place_step.argtypes = [p] * 5 + [i, i, i, i, f, i, i] + [p] * 8
+    L.sslp_edge_log_step.argtypes = [p] * 10 + [i, i, i, i, ll] + [p] * 3
+
+
+def place_launch_count() -> int:
+    return int(place().sslp_launch_count())
+
+
+def check_place_sizes(capacity, k=1, d=D_OUT) -> tuple:
+    """(capacity 1 .., k 1 ..) as ints and d in WIDTHS, else ValueError; past PLACE_MAX_*: SslamHipError - before any device work."""
+    cap, kk = check_int("capacity", capacity, 1), check_int("k", k, 1)
+    width = check_width(d)
+    if cap > PLACE_MAX_CAPACITY or kk > PLACE_MAX_K:
+        raise SslamHipError(f"place_step: {_ERR[E_UNSUPPORTED]} (capacity <= {PLACE_MAX_CAPACITY}, k <= {PLACE_MAX_K}; got {cap}, {kk})")
+    return cap, kk, width
+
+
+def place_state_shapes(capacity: int, d: int = D_OUT) -> dict:
+    """name -> (shape, dtype) of the persistent state of place_step (PLACE_STATE_KEYS)."""
+    return {"t": ((1,), torch.int32), "raw": ((capacity, d), torch.float32), "sum": ((d,), torch.float32)}
+
+
+def place_out_shapes(per_frame: int, d: int = D_OUT) -> dict:
+    """name -> (shape, dtype) of the outputs of place_step (PLACE_OUT_KEYS)."""
+    slots, one = ((per_frame,), torch.int32), ((1,), torch.int32)
+    return {"first": slots, "second": slots, "sim": ((per_frame,), torch.float32), "count": one, "status": one, "sig": ((d,), torch.float32)}
+
+
+def place_workspace_bytes(capacity: int) -> int:
+    """sslp_place_workspace_bytes, restated: capacity float32 words.  Needs no library."""
+    return 4 * capacity
+
+
+def alloc_place_state(capacity, d=D_OUT, device="cuda") -> dict:
+    """A fresh state of place_step: t = 0, everything else zero."""
+    cap, _, width = check_place_sizes(capacity, 1, d)
+    return {k: torch.zeros(shape, dtype=dt, device=device) for k, (shape, dt) in place_state_shapes(cap, width).items()}
+
+
+def alloc_place_out(per_frame=2, d=D_OUT, device="cuda") -> dict:
+    """The outputs of place_step: first and second -1 (absent), everything else zero."""
+    per, width = check_int("per_frame", per_frame, 1, PLACE_MAX_PER_FRAME), check_width(d)
+    out = {k: torch.zeros(shape, dtype=dt, device=device) for k, (shape, dt) in place_out_shapes(per, width).items()}
+    out["first"].fill_(-1), out["second"].fill_(-1)
+    return out
+
+
+def _state_dict(name, state, keys):
+    if not isinstance(state, dict) or set(state) != set(keys) or not all(isinstance(v, torch.Tensor) for v in state.values()):
+        raise ValueError(f"{name} must be a dict of the tensors {', '.join(keys)}")
+
+
+def place_step(state, descriptors, scores, min_gap=30, min_sim=0.3, per_frame=2, suppress=5, out=None, workspace=None) -> dict:
+    """sslp_place_step: one frame of a growing place bank (include/sslam_place.h).  state: alloc_place_state's dict, read and
+    written; descriptors (K, D) or (1, K, D) and scores (K,) or (1, K) float32 - one frame as extract() returns it, D the state's
+    width.  min_gap, min_sim, per_frame, suppress: loop_candidates'.  Returns PLACE_OUT_KEYS' tensors as a dict (out:
+    alloc_place_out's, or made here): first / second / sim (per_frame,), count, status (1,), sig (D,) - row t of loop_candidates over
+    frame_signatures of the frames so far, bit for bit; status 4 and an absent row once the bank is full.  workspace: optional uint8
+    tensor of at least place_workspace_bytes.  Three launches, no host read; everything is judged before the library is loaded."""
+    gap, sim_min, per, sup = check_loop_arguments(min_gap, min_sim, per_frame, suppress)
+    _state_dict("state", state, PLACE_STATE_KEYS)
+    raw = state["raw"]
+    if raw.dim() != 2 or not isinstance(descriptors, torch.Tensor) or not isinstance(scores, torch.Tensor):
+        raise ValueError("state `raw` (capacity, D), descriptors (K, D) and scores (K,) float32 tensors expected")
+    if descriptors.dim() == 3 and descriptors.shape[0] == 1:
+        descriptors = descriptors[0]
+    if scores.dim() == 2 and scores.shape[0] == 1:
+        scores = scores[0]
+    if descriptors.dim() != 2:
+        raise ValueError(f"descriptors (K, D) of one frame expected, got {tuple(descriptors.shape)}")
+    cap, k, d = check_place_sizes(int(raw.shape[0]), int(descriptors.shape[0]), int(raw.shape[1]))
+    for key, (shape, dt) in place_state_shapes(cap, d).items():
+        _check_arrays(shape, (f"state `{key}`", state[key], dt))
+    _check_arrays((k, d), ("descriptors", descriptors, torch.float32))
+    _check_arrays((k,), ("scores", scores, torch.float32))
+    shapes = place_out_shapes(per, d)
+    if out is not None and (not isinstance(out, dict) or set(out) != set(PLACE_OUT_KEYS)):
+        raise ValueError(f"out must be a dict of the tensors {', '.join(PLACE_OUT_KEYS)}")
+    o = None if out is None else _outputs(shapes, PLACE_OUT_KEYS, [out[key] for key in PLACE_OUT_KEYS])
+    need = place_workspace_bytes(cap)
+    _check_workspace(workspace, need)
+    st = [state[key] for key in PLACE_STATE_KEYS]
+    dev = common_device(*st, descriptors, scores, workspace, *(o or ()))
+    o = _outputs(shapes, PLACE_OUT_KEYS, None, dev) if o is None else o
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _run("place_step", place().sslp_place_step, (*st, descriptors, scores, ws, *o), *(_dp(x) for x in st), _dp(descriptors), _dp(scores),
+         cap, k, d, min(gap, 2 ** 31 - 1), C.c_float(sim_min), per, min(sup, 2 ** 31 - 1), _dp(ws), *(_dp(x) for x in o))
+    return dict(zip(PLACE_OUT_KEYS, o))
+
+
+def check_edge_log_sizes(capacity, n_slots) -> tuple:
+    """(capacity 1 .., n_slots 1 ..) as ints, else ValueError; past the limits: SslamHipError - before any device work."""
+    cap, e = check_int("capacity", capacity, 1), check_int("n_slots", n_slots, 1)
+    if e > PLACE_MAX_SLOTS or cap > (2 ** 63 - 1) // 168 // e:
+        raise SslamHipError(f"edge_log_step: {_ERR[E_UNSUPPORTED]} (n_slots <= {PLACE_MAX_SLOTS}, capacity * 168 * n_slots < 2^63; got {e}, {cap})")
+    return cap, e
+
+
+def edge_log_shapes(capacity: int, n_slots: int) -> dict:
+    """name -> (shape, dtype) of the persistent state of edge_log_step (EDGE_LOG_STATE_KEYS)."""
+    rows = capacity * n_slots
+    return {"t": ((1,), torch.int32), "log_first": ((rows,), torch.int32), "log_second": ((rows,), torch.int32),
+            "log_T": ((rows, 12), torch.float64), "log_info": ((rows, 21), torch.float64)}
+
+
+def edge_log_out_shapes(n_slots: int) -> dict:
+    return {"logged": ((n_slots,), torch.int32), "status": ((1,), torch.int32)}
+
+
+def alloc_edge_log(capacity, n_slots, device="cuda") -> dict:
+    """A fresh state of edge_log_step: t = 0, log_first = -1 (absent) everywhere, everything else zero."""
+    cap, e = check_edge_log_sizes(capacity, n_slots)
+    state = {k: torch.zeros(shape, dtype=dt, device=device) for k, (shape, dt) in edge_log_shapes(cap, e).items()}
+    state["log_first"].fill_(-1)
+    return state
+
+
+def edge_log_step(state, slot_first, new_T, new_info, new_status, new_inliers, n_odometry, min_inliers=12, loop_min_inliers=12, out=None) -> dict:
+    """sslp_edge_log_step: one frame's E verified pairs appended to the edge log (include/sslam_place.h).  state: alloc_edge_log's
+    dict, read and written; slot_first (E,) int32: the global index of every slot's older frame, -1 for none; new_T (E, 12),
+    new_info (E, 21) float64, new_status, new_inliers (E,) int32 - what pose_refine_pairs wrote for the frame's E pairs.  The slots
+    before n_odometry (0 .. E) are held to min_inliers, the others to loop_min_inliers.  Returns EDGE_LOG_OUT_KEYS' tensors as a dict:
+    logged (E,), status (1,) - 4 and nothing logged once the log is full.  One launch, no host read; everything is judged before the
+    library is loaded."""
+    mi, lmi = check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1), check_int("loop_min_inliers", loop_min_inliers, 0, 2 ** 31 - 1)
+    _state_dict("state", state, EDGE_LOG_STATE_KEYS)
+    if state["log_first"].dim() != 1 or not isinstance(slot_first, torch.Tensor) or slot_first.dim() != 1 or int(slot_first.shape[0]) < 1 or \
+            int(state["log_first"].shape[0]) % int(slot_first.shape[0]):
+        raise ValueError("state `log_first` (capacity * E,) and slot_first (E,) int32 expected")
+    e = int(slot_first.shape[0])
+    cap, e = check_edge_log_sizes(int(state["log_first"].shape[0]) // e, e)
+    n_odo = check_int("n_odometry", n_odometry, 0, e)
+    for key, (shape, dt) in edge_log_shapes(cap, e).items():
+        _check_arrays(shape, (f"state `{key}`", state[key], dt))
+    _check_arrays((e,), ("slot_first", slot_first, torch.int32), ("new_status", new_status, torch.int32), ("new_inliers", new_inliers, torch.int32))
+    _check_arrays((e, 12), ("new_T", new_T, torch.float64))
+    _check_arrays((e, 21), ("new_info", new_info, torch.float64))
+    shapes = edge_log_out_shapes(e)
+    if out is not None and (not isinstance(out, dict) or set(out) != set(EDGE_LOG_OUT_KEYS)):
+        raise ValueError(f"out must be a dict of the tensors {', '.join(EDGE_LOG_OUT_KEYS)}")
+    o = None if out is None else _outputs(shapes, EDGE_LOG_OUT_KEYS, [out[key] for key in EDGE_LOG_OUT_KEYS])
+    st = [state[key] for key in EDGE_LOG_STATE_KEYS]
+    dev = common_device(*st, slot_first, new_T, new_info, new_status, new_inliers, *(o or ()))
+    o = _outputs(shapes, EDGE_LOG_OUT_KEYS, None, dev) if o is None else o
+    _run("edge_log_step", place().sslp_edge_log_step, (*st, slot_first, new_T, new_info, new_status, new_inliers, *o), *(_dp(x) for x in st),
+         _dp(slot_first), _dp(new_T), _dp(new_info), _dp(new_status), _dp(new_inliers), e, n_odo, mi, lmi, cap, *(_dp(x) for x in o))
+    return dict(zip(EDGE_LOG_OUT_KEYS, o))

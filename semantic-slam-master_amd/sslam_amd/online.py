@@ -38,6 +38,9 @@ body, so the replayed graph is the same step for every frame.  `spacings=None` i
 
 `WindowPoseFrameStepper` puts the pose stage and the sliding-window estimator (include/sslam_window.h) behind that multi-spacing
 matcher, still in the one captured step: the frame's trajectory while the sequence runs, not after it has ended.
+`LoopWindowPoseFrameStepper` adds loop closures to it (include/sslam_place.h): a place bank that grows by one frame per step proposes
+older frames, they are verified with the step's other pairs, and every verified pair goes to an edge log the sparse pose graph reads
+on demand (close_loops()).
 """
 from __future__ import annotations
 
@@ -117,9 +120,20 @@ class FrameStepper:
     def _after_match(self) -> None:
         """What a subclass enqueues behind the matcher's finalize launch, on the same stream (RankedFrameStepper: the rank launch)."""
 
+    def _ring_size(self, spacings: tuple) -> int:
+        """The slots of the feature ring: the furthest a spacing reaches back.  LoopWindowPoseFrameStepper keeps more."""
+        return max(spacings)
+
+    def _extra_pairs(self) -> int:
+        """Rows the step's ONE pair list holds behind the spacings' (LoopWindowPoseFrameStepper: its loop candidates)."""
+        return 0
+
+    def _before_match(self) -> None:
+        """What a subclass enqueues between the extraction and the matcher, on the same stream; it may fill the extra pairs."""
+
     def _init_bank(self, spacings: tuple) -> None:
         pipe, dev = self.pipe, self.device
-        ring = self.ring = max(spacings)
+        ring = self.ring = self._ring_size(spacings)
         one = pipe.alloc_extract(1, True)
         for v in one.values():
             v.zero_()
@@ -127,7 +141,8 @@ class FrameStepper:
         self.bank = {k: torch.zeros((ring + 1,) + tuple(one[k].shape[1:]), dtype=one[k].dtype, device=dev) for k in self.bank_keys}
         self._ring = {k: v[:ring] for k, v in self.bank.items()}
         self.cur = {k: (self.bank[k][ring:ring + 1] if k in self.bank_keys else v) for k, v in one.items()}
-        self.m = pipe.alloc_match(len(spacings), self.cfg.num_keypoints, **self._rule_kw())
+        pairs = len(spacings) + self._extra_pairs()
+        self.m = pipe.alloc_match(pairs, self.cfg.num_keypoints, **self._rule_kw())
         i64 = dict(dtype=torch.int64, device=dev)
         self._t = torch.zeros((1,), **i64)                                   # the step counter: frames since reset()
         self._sp = torch.tensor(spacings, **i64)
@@ -135,8 +150,10 @@ class FrameStepper:
         self._seen = torch.zeros((len(spacings),), dtype=torch.bool, device=dev)
         self._absent = torch.full((len(spacings),), -1, **i64)
         self._slot = torch.zeros((1,), **i64)
-        self.first_slot = torch.full((len(spacings),), -1, dtype=torch.int32, device=dev)      # the matcher's pair lists
-        self.second_slot = torch.full((len(spacings),), ring, dtype=torch.int32, device=dev)
+        self.pair_first = torch.full((pairs,), -1, dtype=torch.int32, device=dev)               # the matcher's pair lists
+        self.pair_second = torch.full((pairs,), ring, dtype=torch.int32, device=dev)
+        # the spacings' rows: the whole lists, unless a subclass asked for extra pairs behind them
+        self.first_slot, self.second_slot = self.pair_first[:len(spacings)], self.pair_second[:len(spacings)]
 
     # the captured region: only launches on the current stream, static buffers on both sides
     def _body(self) -> None:
@@ -163,8 +180,9 @@ class FrameStepper:
         torch.remainder(self._back, ring, out=self._back_slot)
         torch.where(self._seen, self._back_slot, self._absent, out=self._first64)
         self.first_slot.copy_(self._first64)
-        self._aux = p.match_pairs(self.bank["descriptors"], self.bank["scores"], self.bank["intensity"], first=self.first_slot,
-                                  second=self.second_slot, out=self.m, **self._rule_kw())
+        self._before_match()
+        self._aux = p.match_pairs(self.bank["descriptors"], self.bank["scores"], self.bank["intensity"], first=self.pair_first,
+                                  second=self.pair_second, out=self.m, **self._rule_kw())
         self._after_match()
         # this frame takes the ring slot of frame t - ring, which no spacing reaches any more
         torch.remainder(self._t, ring, out=self._slot)
@@ -412,11 +430,11 @@ class WindowPoseFrameStepper(RuleFrameStepper):
         check_depth_size(depth_width, depth_height, self.camera)
         super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=sp,
                          rule=MatchRule.mnn_ratio(0.9) if rule is None else rule)
-        dev, K, S = self.device, self.cfg.num_keypoints, len(sp)
+        dev, K, P = self.device, self.cfg.num_keypoints, len(sp) + self._extra_pairs()
         self.depth = torch.zeros((1, depth_height, depth_width), dtype=torch.uint16, device=dev)
         self.kp_depth = torch.full((self.ring + 1, K), -1, dtype=torch.int32, device=dev)      # the depth ring, slot for slot beside the bank
-        self.pose = pipe.alloc_pose(S, K)
-        self.refined = pipe.alloc_pose_refine(S, K)
+        self.pose = pipe.alloc_pose(P, K)
+        self.refined = pipe.alloc_pose_refine(P, K)
         self.win = pipe.alloc_pose_window(self.window, sp, self.capacity)
 
     def _after_match(self) -> None:
@@ -467,3 +485,128 @@ class WindowPoseFrameStepper(RuleFrameStepper):
         """Forget every earlier frame: the device's counters are zeroed and the ring's slots made absent here, outside the graph."""
         super().reset()
         self._reset_window()
+
+
+class LoopWindowPoseFrameStepper(WindowPoseFrameStepper):
+    """WindowPoseFrameStepper that also notices when the camera is back where it was: loop closures while the sequence runs
+    (include/sslam_place.h).  Opt-in: the parent, its signature and its bytes are left alone.
+    The feature, depth and keypoint banks are a ring of `capacity` slots, not of max(spacings): while t < capacity frame j sits in
+    slot j, so every frame the place bank can name is still there to be matched.  The bank's bytes: (capacity + 1) * K * D * 4 for
+    the descriptors - 262 MB at capacity 1024, K = 500, D = 128 - beside (capacity + 1) * K * 24 for scores, intensity, keypoints and
+    depth.  capacity (max(spacings) .. 4096) is also the frames the place bank, the edge log and trajectory() keep.
+    One step, on one stream, as ordinary launches or from the one captured graph: extract; sslp_place_step on the static slot's
+    descriptors and scores; the pair lists become the S spacing rows followed by the L = per_frame candidate rows (a candidate's
+    older frame is its bank slot, its second the static slot, -1 -1 an empty slot); ONE match_pairs; ONE RANSAC and ONE refinement
+    launch over the S + L rows; sslw_window_step on views of the first S rows - the window's outputs are the bytes
+    WindowPoseFrameStepper gives for the same frames -; sslp_edge_log_step over all S + L rows, the spacing rows held to
+    min_inliers, the candidate rows to loops["min_inliers"]; the static slot is handed over to the ring.  Both new counters are
+    device memory: no host value enters the body.
+    loops: None (odometry.LOOP_DEFAULTS) or a dictionary of some of min_gap, min_sim, per_frame, suppress, min_inliers.
+    step() returns the parent's dictionary with S + L rows in matches / match_count / value and "pose" (pair_first keeps naming the S
+    spacing rows: the candidates' frames are device values), "window" as the parent returns it, and "loops": the place step's
+    first, second, sim (L,), count, status (1,), sig (D,), the log's logged (S + L,) and log_status (1,), and "refined": the
+    refinement's outputs of the L candidate rows - all views of static buffers.
+    Past `capacity` frames the spacings, the window and the trajectory carry on (the ring wraps); the place and log entries answer
+    status 4 and the candidate rows read absent.  Nobody has measured this on real RGB-D data."""
+
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, depth_height: int, depth_width: int, camera=None,
+                 use_graph: bool = True, tokens_in: bool = False, rule=None, spacings=(1, 5, 10, 15, 20), window=None,
+                 threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, huber=None, iterations: int = 5, min_inliers: int = 12,
+                 huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 2, loops=None, capacity: int = 1024):
+        from .odometry import check_loops
+        sp = _checked_spacings(spacings, below=2 ** 31)                  # everything is judged before anything is allocated
+        self.loops = check_loops(loops)
+        lib.check_int("min_inliers", self.loops["min_inliers"], 0, 2 ** 31 - 1)
+        cap = lib.check_place_sizes(lib.check_int("capacity", capacity, 1), 1, pipe.descriptor_dim if pipe is not None else lib.D_OUT)[0]
+        if len(sp) <= lib.WINDOW_MAX_SPACINGS:                           # more spacings than that: the parent refuses them by name
+            lib.check_edge_log_sizes(cap, len(sp) + self.loops["per_frame"])
+            if cap < max(sp):
+                raise ValueError(f"capacity must be at least max(spacings) = {max(sp)}: the ring holds every frame a spacing reaches, got {cap}")
+        self._ring_slots = cap
+        super().__init__(pipe, height, width, depth_height, depth_width, camera=camera, use_graph=use_graph, tokens_in=tokens_in, rule=rule,
+                         spacings=sp, window=window, threshold=threshold, hypotheses=hypotheses, seed=seed, huber=huber, iterations=iterations,
+                         min_inliers=min_inliers, huber_chi=huber_chi, damping=damping, graph_iterations=graph_iterations, capacity=cap)
+        o, S, L, dev = self.loops, len(sp), self.loops["per_frame"], self.device
+        self.place = pipe.alloc_place_bank(cap, o["min_gap"], o["min_sim"], L, o["suppress"])
+        self.log = pipe.alloc_edge_log(cap, S + L)
+        self._slot_first = torch.full((S + L,), -1, dtype=torch.int32, device=dev)      # the GLOBAL older frame of every row, for the log
+        self._global64 = torch.zeros((S,), dtype=torch.int64, device=dev)
+        self._filled = torch.zeros((L,), dtype=torch.bool, device=dev)
+        self._static32 = torch.full((L,), self.ring, dtype=torch.int32, device=dev)
+        self._absent32 = torch.full((L,), -1, dtype=torch.int32, device=dev)
+        self._head = {k: self.refined[k][:S] for k in ("T", "info", "status", "inlier_count")}      # the window's rows
+        self._tail = {k: v[S:] for k, v in self.refined.items()}
+
+    def _ring_size(self, spacings: tuple) -> int:
+        return self._ring_slots
+
+    def _extra_pairs(self) -> int:
+        return self.loops["per_frame"]
+
+    def _before_match(self) -> None:
+        S, po = len(self.spacings), self.place["out"]
+        self.pipe.place_step(self.place, self.cur["descriptors"], self.cur["scores"])
+        # while the place step answers, its counter is below capacity and frame j sits in ring slot j: the candidate IS its slot
+        self.pair_first[S:].copy_(po["first"])
+        torch.ge(po["first"], 0, out=self._filled)
+        torch.where(self._filled, self._static32, self._absent32, out=self.pair_second[S:])
+
+    def _after_match(self) -> None:
+        p, ring, S = self.pipe, self.ring, len(self.spacings)
+        kp = p.geometry_keypoints(self.bank)
+        p.keypoint_depth(self.depth, kp[ring:ring + 1], out=self.kp_depth[ring:ring + 1])
+        p.estimate_poses(kp, self.kp_depth, self.pair_first, self.pair_second, self.m, self.camera, self.threshold, self.hypotheses,
+                         self.seed, out=self.pose)
+        p.refine_poses(kp, self.kp_depth, self.pair_first, self.pair_second, self.m, self.camera, self.pose, self.threshold, self.huber,
+                       self.iterations, out=self.refined)
+        p.pose_window_step(self.win, self._head, None, self.min_inliers, self.huber_chi, self.damping, self.graph_iterations)
+        torch.where(self._seen, self._back, self._absent, out=self._global64)      # frame t - s, or -1 before it exists
+        self._slot_first[:S].copy_(self._global64)
+        self._slot_first[S:].copy_(self.place["out"]["first"])
+        p.edge_log_step(self.log, self._slot_first, self.refined, S, self.min_inliers, self.loops["min_inliers"])
+        torch.remainder(self._t, ring, out=self._slot)                   # the ring slot the frame's features take, right after this
+        self.kp_depth[:ring].index_copy_(0, self._slot, self.kp_depth[ring:ring + 1])
+
+    def _reset_window(self) -> None:
+        super()._reset_window()
+        if getattr(self, "place", None) is not None:                     # both new counters; nothing else of either state is read before it is written
+            self.place["state"]["t"].zero_()
+            self.log["state"]["t"].zero_()
+
+    @torch.no_grad()
+    def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
+        out = super().step(image_u8, depth_u16, tokens)
+        out["loops"] = dict(self.place["out"], logged=self.log["out"]["logged"], log_status=self.log["out"]["status"], refined=dict(self._tail))
+        return out
+
+    def close_loops(self, huber_chi: float = 4.0, damping: float = 0.0, iterations: int = 8, cg_iterations: int = 512, cg_tol: float = 1e-3) -> dict:
+        """The corrected trajectory, any time between steps: optimize_pose_graph_sparse over the edge log's first n * (S + L) slots
+        and n nodes, n = min(frames stepped, capacity), from the window's committed trajectory.  Runs outside the captured step,
+        makes ONE read-back and changes no state: stepping on gives the bytes it would have given without the call.
+        Returns trajectory (n, 4, 4) camera -> world (odometry_graph's convention), C (n, 12) world -> camera as the solver wrote
+        it, status, iterations, used_edges, skipped_edges, failed_row, cost_in, cost, cg_steps (16,), edge_chi2 (n * (S + L),) in
+        log order, and loop_edges (P, 2): the logged loop slots [older frame, frame].  A frame with no logged edge - every pair of
+        it refused - leaves its block zero: status 2 at damping 0 and the window's trajectory back, as the batch graph answers."""
+        import numpy as np
+        lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
+        lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
+        n = min(self.n_frames, self.capacity)
+        if n < 1:
+            raise ValueError("close_loops needs at least one stepped frame")
+        S, E = len(self.spacings), len(self.spacings) + self.loops["per_frame"]
+        st, rows = self.log["state"], n * E
+        r = self.pipe.optimize_pose_graph_sparse(st["log_first"][:rows], st["log_second"][:rows], st["log_T"][:rows], st["log_info"][:rows], n,
+                                                 self.win["state"]["trajectory"][0, :n], huber_chi, damping, iterations, cg_iterations, cg_tol)
+        words = ("status", "iterations", "used_edges", "skipped_edges", "failed_row", "cost_in", "cost")
+        flat = torch.cat([r["C"].reshape(-1)] + [r[k].reshape(1).to(torch.float64) for k in words] +
+                         [r["cg_steps"].to(torch.float64), r["edge_chi2"], st["log_first"][:rows].to(torch.float64)]).cpu().numpy()      # the ONE read-back
+        C = flat[:12 * n].reshape(n, 12)
+        out = {k: (float(v) if k.startswith("cost") else int(v)) for k, v in zip(words, flat[12 * n:12 * n + 7])}
+        at = 12 * n + 7
+        first = flat[at + lib.SPARSE_MAX_ITER + rows:].astype(np.int64).reshape(n, E)
+        frame, slot = np.nonzero(first[:, S:] >= 0)
+        C44 = np.concatenate([C.reshape(n, 3, 4), np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
+        out.update(C=C, trajectory=np.stack([np.linalg.inv(c) for c in C44]), cg_steps=flat[at:at + lib.SPARSE_MAX_ITER].astype(np.int64),
+                   edge_chi2=flat[at + lib.SPARSE_MAX_ITER:at + lib.SPARSE_MAX_ITER + rows],
+                   loop_edges=np.stack([first[frame, S + slot], frame], axis=1).astype(np.int64))
+        return out

@@ -1026,6 +1026,53 @@ class SequencePipeline:
                                min_inliers, huber_chi, damping, iterations, out=state["out"] if out is None else out,
                                workspace=state["workspace"])
 
+    def alloc_place_bank(self, capacity: int, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2, suppress: int = 5) -> dict:
+        """The buffers of place_step() (csrc_place/place.hip) for a place bank of up to `capacity` frames (1 .. 4096) at this
+        pipeline's descriptor width: "state" - lib.alloc_place_state's fresh state -, "out" - lib.alloc_place_out's outputs -,
+        "workspace", and the retrieval's arguments min_gap, min_sim, per_frame, suppress as find_loop_candidates takes them."""
+        gap, sim, per, sup = lib.check_loop_arguments(min_gap, min_sim, per_frame, suppress)
+        cap, _, d = lib.check_place_sizes(capacity, 1, self.descriptor_dim)
+        dev = self.device
+        return dict(state=lib.alloc_place_state(cap, d, dev), out=lib.alloc_place_out(per, d, dev), min_gap=gap, min_sim=sim, per_frame=per,
+                    suppress=sup, workspace=torch.empty(lib.place_workspace_bytes(cap), dtype=torch.uint8, device=dev))
+
+    @staticmethod
+    def place_step(state: dict, descriptors, scores, out: dict | None = None) -> dict:
+        """One frame of the online loop retrieval (sslp_place_step, include/sslam_place.h): the frame's descriptors (K, D) or
+        (1, K, D) and scores, as extract() returned them, enter the bank of `state` (alloc_place_bank's dictionary), and the frame's
+        most similar older frames come back in match_pairs' pair-list form: first, second (per_frame,) int32 global frame indices
+        (-1, -1 an empty slot), sim, count, status (1,) and sig (D,) - row t of find_loop_candidates over the frames so far, bit for
+        bit; status 4 and an absent row once the bank is full.  Returns `out`, or the state's own "out" buffers.  Three launches, no
+        host read: the frame counter is device memory, so the call can be captured."""
+        if not isinstance(state, dict) or any(k not in state for k in ("state", "out", "workspace", "min_gap", "min_sim", "per_frame", "suppress")):
+            raise ValueError("state must be alloc_place_bank()'s dictionary")
+        return lib.place_step(state["state"], descriptors, scores, state["min_gap"], state["min_sim"], state["per_frame"], state["suppress"],
+                              out=state["out"] if out is None else out, workspace=state["workspace"])
+
+    def alloc_edge_log(self, capacity: int, n_slots: int) -> dict:
+        """The buffers of edge_log_step() for `capacity` frames of n_slots (1 .. 16) pairs each: "state" - lib.alloc_edge_log's fresh
+        log - and "out" - logged (n_slots,), status (1,)."""
+        cap, e = lib.check_edge_log_sizes(capacity, n_slots)
+        dev = self.device
+        return dict(state=lib.alloc_edge_log(cap, e, dev),
+                    out={k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in lib.edge_log_out_shapes(e).items()})
+
+    @staticmethod
+    def edge_log_step(log: dict, slot_first, refined: dict, n_odometry: int, min_inliers: int = 12, loop_min_inliers: int = 12,
+                      out: dict | None = None) -> dict:
+        """One frame of the edge log (sslp_edge_log_step): the frame's E refined pairs - `refined`, refine_poses()' dictionary, whose T,
+        info, status and inlier_count are read; slot_first (E,) int32, the GLOBAL index of each pair's older frame, -1 for none - are
+        appended to `log` (alloc_edge_log's dictionary) as row t * E + e.  The first n_odometry slots are logged with at least
+        min_inliers inliers, the others with loop_min_inliers; a slot that fails a test is logged absent.  The log's first n * E rows
+        are optimize_pose_graph_sparse's operands over the n frames logged.  Returns logged (E,), status (1,) - `out`, or the log's
+        own.  One launch, no host read."""
+        if not isinstance(log, dict) or any(k not in log for k in ("state", "out")):
+            raise ValueError("log must be alloc_edge_log()'s dictionary")
+        if not isinstance(refined, dict) or any(k not in refined for k in ("T", "info", "status", "inlier_count")):
+            raise ValueError("refined must be refine_poses()' dictionary: T, info, status and inlier_count are read")
+        return lib.edge_log_step(log["state"], slot_first, refined["T"], refined["info"], refined["status"], refined["inlier_count"], n_odometry,
+                                 min_inliers, loop_min_inliers, out=log["out"] if out is None else out)
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts
