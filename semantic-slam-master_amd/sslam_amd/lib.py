@@ -2141,3 +2141,193 @@ def edge_log_step(state, slot_first, new_T, new_info, new_status, new_inliers, n
     _run("edge_log_step", place().sslp_edge_log_step, (*st, slot_first, new_T, new_info, new_status, new_inliers, *o), *(_dp(x) for x in st),
          _dp(slot_first), _dp(new_T), _dp(new_info), _dp(new_status), _dp(new_inliers), e, n_odo, mi, lmi, cap, *(_dp(x) for x in o))
     return dict(zip(EDGE_LOG_OUT_KEYS, o))
+
+
+# ------------------------------------------------------------------------------------------ libsslam_conf.so (include/sslam_conf.h)
+# The seventh library: the keypoint confidence head, entries with the prefix sslc_, built from csrc_conf/ with csrc/flags.mk (and
+# csrc/common.h, csrc/gather_taps.h included from where they are), loaded and refused like the others.
+CSRC_CONF = os.path.join(_PKG, "csrc_conf")
+CONF_SO_PATH = os.path.join(CSRC_CONF, "libsslam_conf.so")
+CONF_EXPORTS = ["sslc_version", "sslc_arch", "sslc_launch_count", "sslc_confidence_layout", "sslc_confidence_pack_host",
+                "sslc_confidence_rows", "sslc_gather_confidence", "sslc_confidence_filter", "sslc_take_rows"]
+CONF_DINO_DIM, CONF_HIDDEN_DIM, CONF_FILTER_MAX_K = 384, 128, 4096
+CONF_STATE_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias", "mlp.4.weight", "mlp.4.bias")
+CONF_FILTER_KEYS = ("slot", "count", "confidence")
+
+_conf = None
+
+
+class ConfidenceLayout(C.Structure):
+    _fields_ = [("d", C.c_int), ("total", C.c_longlong), ("w1", C.c_longlong), ("b1", C.c_longlong), ("w2", C.c_longlong),
+                ("b2", C.c_longlong), ("w3", C.c_longlong), ("b3", C.c_longlong)]
+
+
+def conf_build(force: bool = False) -> str:
+    """Compile libsslam_conf.so for gfx950 in-tree, as build() compiles the first library."""
+    others = [os.path.join(_INCLUDE, h) for h in ("sslam_conf.h", "sslam_hip.h")] + [os.path.join(CSRC, h) for h in ("common.h", "gather_taps.h")]
+    return _make_if_stale(CSRC_CONF, CONF_SO_PATH, others, force)
+
+
+def conf():
+    """Load libsslam_conf.so; raises if it has not been built (no silent fallback)."""
+    global _conf
+    if _conf is None:
+        _conf = _load(CONF_SO_PATH, CSRC_CONF, "sslc", _conf_prototypes)
+    return _conf
+
+
+def _conf_prototypes(L):
+    p, i, ll, f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
+    L.sslc_confidence_layout.argtypes = [i, i, i, C.POINTER(ConfidenceLayout)]
+    L.sslc_confidence_pack_host.argtypes = [p, i, i, i, p]
+    L.sslc_confidence_rows.argtypes = [p, p, ll, i, p, p, p]
+    L.sslc_gather_confidence.argtypes = [p, i, i, p, i, p, i, p, p, p]
+    L.sslc_confidence_filter.argtypes = [p, i, i, f, p, p, p, p]
+    L.sslc_take_rows.argtypes = [p, p, i, i, i, p, p]
+
+
+def conf_launch_count() -> int:
+    return int(conf().sslc_launch_count())
+
+
+def confidence_supported(dino_dim, descriptor_dim, hidden_dim) -> bool:
+    """Whether the kernels are built for a head of these widths (include/sslam_conf.h): 384, 128 or 256, 128."""
+    return (dino_dim, hidden_dim) == (CONF_DINO_DIM, CONF_HIDDEN_DIM) and descriptor_dim in WIDTHS
+
+
+def confidence_layout(descriptor_dim: int, dino_dim: int = CONF_DINO_DIM, hidden_dim: int = CONF_HIDDEN_DIM) -> ConfidenceLayout:
+    """Offsets (floats) of the packed confidence head; SslamHipError (unsupported shape) for widths the kernels are not built for."""
+    lay = ConfidenceLayout()
+    _check(conf().sslc_confidence_layout(int(dino_dim), int(descriptor_dim), int(hidden_dim), C.byref(lay)), "confidence_layout")
+    return lay
+
+
+def confidence_pack(weights: list) -> np.ndarray:
+    """weights: the six fp32 arrays of the head in state_dict order (CONF_STATE_KEYS): mlp.0.weight (h, 384 + d), mlp.0.bias (h),
+    mlp.2.weight (h / 2, h), mlp.2.bias (h / 2), mlp.4.weight (1, h / 2), mlp.4.bias (1).  Returns the packed buffer
+    (sslc_confidence_pack_host); SslamHipError (unsupported shape) unless h = 128 and d is 128 or 256."""
+    ws = [np.ascontiguousarray(w, np.float32) for w in weights]
+    if len(ws) != 6 or ws[0].ndim != 2 or ws[2].ndim != 2:
+        raise ValueError("six arrays in state_dict order expected: mlp.0.weight, mlp.0.bias, mlp.2.weight, mlp.2.bias, mlp.4.weight, mlp.4.bias")
+    h, k1 = int(ws[0].shape[0]), int(ws[0].shape[1])
+    want = [(h, k1), (h,), (h // 2, h), (h // 2,), (1, h // 2), (1,)]
+    if h < 2 or k1 <= CONF_DINO_DIM or [tuple(w.shape) for w in ws] != want:
+        raise ValueError(f"a confidence head of shapes {[tuple(w.shape) for w in ws]}: {want} expected, with more than {CONF_DINO_DIM} inputs")
+    lay = confidence_layout(k1 - CONF_DINO_DIM, CONF_DINO_DIM, h)
+    out = np.empty(lay.total, np.float32)
+    arr = (C.c_void_p * 6)(*[w.ctypes.data for w in ws])
+    _check(conf().sslc_confidence_pack_host(arr, CONF_DINO_DIM, k1 - CONF_DINO_DIM, h, out.ctypes.data), "confidence_pack")
+    return out
+
+
+_CONF_PACKED_WIDTH = {}      # floats -> descriptor width
+
+
+def packed_confidence_width(packed) -> int:
+    """The descriptor width a packed confidence head was laid out for, from its length."""
+    n = int(packed.numel())
+    if not _CONF_PACKED_WIDTH:
+        _CONF_PACKED_WIDTH.update({int(confidence_layout(d).total): d for d in WIDTHS})
+    if n not in _CONF_PACKED_WIDTH:
+        raise ValueError(f"a packed confidence head of {n} floats fits no supported descriptor width {WIDTHS}")
+    return _CONF_PACKED_WIDTH[n]
+
+
+def _f32_rows(name, t, width):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() < 1 or int(t.shape[-1]) != width or not t.is_contiguous() or \
+            t.numel() == 0:
+        raise ValueError(f"{name} must be a contiguous float32 tensor of shape (..., {width})")
+
+
+def confidence_rows(x, desc, packed, out=None):
+    """sslc_confidence_rows: x (..., 384) and desc (..., d) fp32, the features at the keypoints and their descriptors; packed: the
+    head (confidence_pack) on the device -> confidence (...) fp32 in [0, 1].  d is the width `packed` was laid out for."""
+    d = packed_confidence_width(packed)
+    _f32_rows("x", x, C_FEAT)
+    _f32_rows("desc", desc, d)
+    if tuple(x.shape[:-1]) != tuple(desc.shape[:-1]):
+        raise ValueError(f"x of shape {tuple(x.shape)} and desc of shape {tuple(desc.shape)} do not hold the same rows")
+    lead = tuple(x.shape[:-1])
+    _check_arrays(lead, ("out", out, torch.float32))
+    if out is None:
+        out = torch.empty(lead, dtype=torch.float32, device=x.device)
+    _run("confidence_rows", conf().sslc_confidence_rows, (x, desc, packed, out), _dp(x), _dp(desc), x.numel() // C_FEAT, d, _dp(packed), _dp(out))
+    return out
+
+
+def gather_confidence(feat, kp, desc, packed, out=None):
+    """sslc_gather_confidence: the confidence of the keypoints kp (n, K, 2) with descriptors desc (n, K, d), the features taken
+    from feat (n, G, G, 384) by gather()'s arithmetic inside the kernel -> (n, K) fp32: the bits of
+    confidence_rows(gather(feat, kp), desc, packed), nothing of width 384 written."""
+    d = packed_confidence_width(packed)
+    if not isinstance(feat, torch.Tensor) or feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != feat.shape[2] or \
+            int(feat.shape[3]) != C_FEAT or not feat.is_contiguous() or int(feat.shape[1]) < 2:
+        raise ValueError(f"feat must be a contiguous float32 tensor of shape (n, G, G, {C_FEAT}), G >= 2")
+    n, g = int(feat.shape[0]), int(feat.shape[1])
+    if not isinstance(kp, torch.Tensor) or kp.dim() != 3 or int(kp.shape[0]) != n or int(kp.shape[1]) < 1:
+        raise ValueError(f"kp must be a contiguous float32 tensor of shape ({n}, K, 2)")
+    k = int(kp.shape[1])
+    _check_arrays((n, k, 2), ("kp", kp, torch.float32))
+    _check_arrays((n, k, d), ("desc", desc, torch.float32))
+    _check_arrays((n, k), ("out", out, torch.float32))
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=feat.device)
+    _run("gather_confidence", conf().sslc_gather_confidence, (feat, kp, desc, packed, out), _dp(feat), n, g, _dp(kp), k, _dp(desc), d,
+         _dp(packed), _dp(out))
+    return out
+
+
+def confidence_filter_shapes(n: int, k: int) -> dict:
+    """The outputs of confidence_filter for n frames of k keypoints: key -> (shape, dtype), in the entry's order."""
+    return {"slot": ((n, k), torch.int32), "count": ((n,), torch.int32), "confidence": ((n, k), torch.float32)}
+
+
+def check_conf_threshold(threshold) -> float:
+    """threshold as a float32 value: any number (2.0 keeps each frame's best keypoint alone); not a bool, a string or a tensor."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f"threshold must be a number, got {threshold!r}")
+    return float(np.float32(threshold))
+
+
+def confidence_filter(confidence, threshold=0.5, out=None):
+    """sslc_confidence_filter: confidence (n, K) fp32 -> (slot (n, K) int32, count (n,) int32, conf_out (n, K) fp32).  Per frame the
+    slots with confidence >= float32(threshold) in ascending order, the frame's largest confidence alone where none passes; the
+    rest of `slot` repeats the last kept slot and the rest of conf_out is 0 (filter_keypoints_by_confidence's pad).  One launch."""
+    thr = check_conf_threshold(threshold)
+    if not isinstance(confidence, torch.Tensor) or confidence.dim() != 2 or min(confidence.shape) < 1:
+        raise ValueError("confidence must be a contiguous float32 tensor of shape (n, K)")
+    n, k = int(confidence.shape[0]), int(confidence.shape[1])
+    _check_arrays((n, k), ("confidence", confidence, torch.float32))
+    if k > CONF_FILTER_MAX_K:
+        raise SslamHipError(f"confidence_filter: {_ERR[E_UNSUPPORTED]} (K <= {CONF_FILTER_MAX_K}; got K = {k})")
+    shapes = confidence_filter_shapes(n, k)
+    if out is not None:
+        if len(out) != 3:
+            raise ValueError("out must be (slot, count, conf_out)")
+        for key, t in zip(CONF_FILTER_KEYS, out):
+            if t is None:
+                raise ValueError(f"out `{key}` is required")
+            _check_arrays(shapes[key][0], (f"out `{key}`", t, shapes[key][1]))
+    dev = common_device(confidence, *(out or ()))
+    slot, count, co = out if out is not None else (torch.empty(shapes[key][0], dtype=shapes[key][1], device=dev) for key in CONF_FILTER_KEYS)
+    _run("confidence_filter", conf().sslc_confidence_filter, (confidence, slot, count, co), _dp(confidence), n, k, thr, _dp(slot), _dp(count),
+         _dp(co))
+    return slot, count, co
+
+
+def take_rows(src, slot, out=None):
+    """sslc_take_rows: out[f, j, ...] = src[f, slot[f, j], ...] for src (n, K, ...) of a 4-byte dtype (float32, int32) and slot
+    (n, K) int32; out: an optional tensor of src's shape and dtype that is not src.  One launch."""
+    if not isinstance(src, torch.Tensor) or src.dim() < 2 or src.element_size() != 4 or not src.is_contiguous() or src.numel() == 0:
+        raise ValueError("src must be a contiguous tensor of shape (n, K, ...) and a 4-byte dtype")
+    n, k = int(src.shape[0]), int(src.shape[1])
+    _check_arrays((n, k), ("slot", slot, torch.int32))
+    if slot is None:
+        raise ValueError("slot is required")
+    _check_arrays(tuple(src.shape), ("out", out, src.dtype))
+    if out is None:
+        out = torch.empty_like(src)
+    if out.data_ptr() == src.data_ptr():
+        raise ValueError("out must not be src")
+    _run("take_rows", conf().sslc_take_rows, (src, slot, out), _dp(src), _dp(slot), n, k, src.numel() // (n * k), _dp(out))
+    return out

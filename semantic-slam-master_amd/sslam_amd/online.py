@@ -230,7 +230,9 @@ class FrameStepper:
         """image_u8: (H, W, 3) or (1, H, W, 3) uint8, on the device or in host memory (pinned: the copy is asynchronous).
         tokens: (T, 384) / (1, T, 384) fp32 when the stepper was built with tokens_in.  Returns this frame's saliency /
         keypoints_pixel / scores / idx / descriptors / intensity - and, on a pipeline with subcell=True, keypoints_subpatch /
-        keypoints_subpixel / subcell_flags, whose launch is part of the captured graph - (views of static buffers, (K, ...) without
+        keypoints_subpixel / subcell_flags, whose launch is part of the captured graph, and on one with confidence=True the
+        frame's `confidence` (K,), its launch captured likewise (the stepper allocates through alloc_extract; the confidence
+        is returned per frame and not kept in the bank) - (views of static buffers, (K, ...) without
         the batch axis) and,
         from the second frame on, matches (K, 2) int64 / quality (K,) / match_count against the previous frame (None before).
         With spacings: matches (S, K, 2) / quality (S, K) / match_count (S,), one row per spacing in the order given (views of

@@ -44,6 +44,10 @@ class ExtractorConfig:
     precision: str = "fp32"             # "fp32": bit-exact vs the CPU reference (the product default and the parity claim);
                                         # "bf16": BASELINE configs[1] throughput mode - saliency CNN + descriptor MLP on bf16
                                         # MFMA (fp32 accumulate), everything else unchanged; NOT index-exact
+    confidence: bool = False            # behind A7, the keypoint confidence head (include/sslam_conf.h) at the keypoints the
+                                        # descriptors were gathered at: extract() gains `confidence` (n, K); every other output
+                                        # keeps its bytes.  Needs SequencePipeline(confidence_state=...) and precision="fp32".
+                                        # (It stands in front of the two subcell fields, which tests/test_subcell_cpu.py holds last.)
     subcell: bool = False               # after A5, move each keypoint to the vertex of the per-axis parabola through its cell's
                                         # saliency and its neighbours' (include/sslam_ext.h): extract() gains keypoints_subpatch,
                                         # keypoints_subpixel and subcell_flags; every other output keeps its bits
@@ -275,6 +279,26 @@ class PackedRefiner:
         return [t for t in (self.packed, self.packed_bf16) if t is not None]
 
 
+class PackedConfidence:
+    """Device-resident packed UncertaintyEstimator weights (one buffer, sslc_confidence_layout order)."""
+
+    @staticmethod
+    def supported(dino_dim: int, descriptor_dim: int, hidden_dim: int) -> bool:
+        """Shapes the confidence kernel is built for: 384 + (128 | 256) -> 128 -> 64 -> 1."""
+        return lib.confidence_supported(dino_dim, descriptor_dim, hidden_dim)
+
+    def __init__(self, sd: dict, device):
+        ws = [np.ascontiguousarray(_np(sd[k]), np.float32) for k in lib.CONF_STATE_KEYS]
+        hidden = int(ws[0].shape[0]) if ws[0].ndim == 2 else -1
+        self.descriptor_dim = int(ws[0].shape[1]) - lib.C_FEAT if ws[0].ndim == 2 else -1
+        if not self.supported(lib.C_FEAT, self.descriptor_dim, hidden):
+            raise lib.SslamHipError("confidence head shape unsupported by the HIP kernels (384 + 128 | 256 -> 128 -> 64 -> 1)")
+        self.packed = torch.from_numpy(lib.confidence_pack(ws)).to(device)
+
+    def tensors(self) -> list:
+        return [self.packed]
+
+
 class ResampleTables:
     """Pillow coefficient tables on the device, cached per (height, width, size, filter)."""
 
@@ -296,7 +320,7 @@ class ResampleTables:
 class SequencePipeline:
     def __init__(self, cfg: ExtractorConfig, selector_state: dict | None, refiner_state: dict | None, bn_state: dict | None = None,
                  device="cuda", vit=None, empty_shapes: tuple | None = None, vit_precision: str = "bf16",
-                 vit_form: str | None = None):
+                 vit_form: str | None = None, confidence_state: dict | None = None):
         """vit: optional sslam_amd.vit.DinoV3ViT, or any module whose weights convert to it (vit.KEY_MAPS) - enables
         run(images, tokens=None): images -> A0 -> HIP ViT (A1) -> ...; vit_precision "bf16" (throughput form, bf16 MFMA
         operands) or "fp32" (the reference's numerics for A1: fp32 operands on the fp32 matrix pipe, csrc/vit_f32.hip)
@@ -305,7 +329,10 @@ class SequencePipeline:
         selector_state / refiner_state None + empty_shapes=(selector hidden, refiner blocks[, descriptor width = 128]):
         uninitialised packed buffers, to be filled by the rank-0 weight broadcast (shard.pipeline_from_rank0).
         descriptor_dim: the refiner's output width (128 or 256), from its state or from empty_shapes; every descriptor buffer,
-        bank and matcher launch of this pipeline follows it.  precision="bf16" with a 256-wide refiner raises SslamHipError."""
+        bank and matcher launch of this pipeline follows it.  precision="bf16" with a 256-wide refiner raises SslamHipError.
+        confidence_state: the state_dict of an UncertaintyEstimator (mlp.0, mlp.2, mlp.4) whose descriptor_dim is this pipeline's:
+        packed for the confidence kernel; cfg.confidence=True launches it in every extraction, filter_by_confidence uses its
+        output.  cfg.confidence=True without it, or with precision="bf16" (the head has no bf16 form), raises ValueError."""
         self.cfg = cfg
         self.device = torch.device(device)
         lib.lib()   # fail loudly if the HIP library is not built
@@ -319,6 +346,10 @@ class SequencePipeline:
             raise ValueError(f"vit_form must be None or 'few_frame', got {vit_form!r}")
         if vit_form == "few_frame" and vit_precision != "bf16":
             raise ValueError("vit_form='few_frame' names a launch form of the bf16 ViT; the fp32 ViT already follows the batch")
+        if cfg.confidence and confidence_state is None:
+            raise ValueError("confidence=True needs confidence_state, the state_dict of the confidence head")
+        if cfg.confidence and cfg.precision == "bf16":
+            raise ValueError("confidence=True needs precision='fp32': the confidence head has no bf16 form")
         self.bf16 = cfg.precision == "bf16"
         if selector_state is None or refiner_state is None:
             if empty_shapes is None:
@@ -329,6 +360,13 @@ class SequencePipeline:
         else:
             self.selector = PackedSelector(selector_state, self.device, self.bf16)
             self.refiner = PackedRefiner(refiner_state, self.device, self.bf16)
+        self.confidence = None
+        if confidence_state is not None:
+            lib.conf()   # the seventh library, where this pipeline launches from it
+            self.confidence = PackedConfidence(confidence_state, self.device)
+            if self.confidence.descriptor_dim != self.descriptor_dim:
+                raise ValueError(f"the confidence head takes descriptors of width {self.confidence.descriptor_dim}, the refiner writes "
+                                 f"{self.descriptor_dim}")
         self._ws = None             # caller-owned scratch handed to the *_ws entries (the library never allocates)
         self._stage = {}            # pipeline-owned stage temporaries (features, their bf16 copy, the A0 image): see _stage_buffer
         c = lib.C_FEAT
@@ -482,6 +520,8 @@ class SequencePipeline:
         if cfg.subcell:
             for key, (shape, dtype) in lib.subcell_shapes(n, K).items():
                 out[key] = torch.empty(shape, dtype=dtype, device=dev)
+        if cfg.confidence:
+            out["confidence"] = torch.empty((n, K), **f32)
         return out
 
     @staticmethod
@@ -505,6 +545,8 @@ class SequencePipeline:
             out = self.alloc_extract(n, images_u8 is not None)
         elif self.cfg.subcell and any(key not in out for key in lib.SUBCELL_KEYS):      # judged before anything is launched
             raise ValueError(f"out must hold {', '.join(lib.SUBCELL_KEYS)} under subcell=True (alloc_extract)")
+        elif self.cfg.confidence and "confidence" not in out:
+            raise ValueError("out must hold confidence under confidence=True (alloc_extract)")
         for a in range(0, n, step):
             b = min(a + step, n)
             self._extract_group(tokens[a:b], None if images_u8 is None else images_u8[a:b], {k: v[a:b] for k, v in out.items()},
@@ -534,12 +576,38 @@ class SequencePipeline:
             lib.gather_refine_bf16(feat, kp, self.refiner.packed_bf16, self.refiner.n_blocks, out=out["descriptors"])
         else:
             lib.gather_refine(feat, kp, self.refiner.packed, self.refiner.n_blocks, out=out["descriptors"], workspace=ws)
+        if cfg.confidence:
+            # the head reads the features where the descriptors read them: one more gather inside its kernel, nothing 384 wide stored
+            lib.gather_confidence(feat, kp, out["descriptors"], self.confidence.packed, out=out["confidence"])
         if images_ready is not None:
             torch.cuda.current_stream(self.device).wait_event(images_ready)
         if images_u8 is not None and "intensity" in out:
             n, h, w, _ = images_u8.shape
             th, tv = self.tables.get(h, w, cfg.input_size, True)
             lib.keypoint_intensity(images_u8, cfg.input_size, th, tv, out["keypoints_pixel"], out=out["intensity"])
+
+    def filter_by_confidence(self, out: dict, threshold: float = 0.5) -> dict:
+        """The frames of extract() (confidence=True) with their low-confidence keypoints dropped, in extract()'s form and shapes:
+        per frame the keypoints with confidence >= threshold come first, in their order, and the rest of the K slots repeats the
+        last kept one (UncertaintyEstimator.filter_keypoints_by_confidence's pad, and what the selector's own pad does: a
+        repeated keypoint); a frame in which none passes keeps its most confident keypoint.  Every per-keypoint array of `out`
+        (keypoints, scores, idx, descriptors, intensity, the subcell ones) is taken through `slot`; `confidence` is the kept
+        confidences followed by zeros; `count` (n,) and `slot` (n, K) int32 are added; saliency and status pass through.
+        The result goes into match / match_pairs unchanged.  One filter launch and one take per array; no host read."""
+        if "confidence" not in out:
+            raise ValueError("out holds no confidence: extract() under ExtractorConfig(confidence=True) writes it")
+        slot, count, conf = lib.confidence_filter(out["confidence"], threshold)
+        n, k = slot.shape
+        res = {}
+        for key, v in out.items():
+            if key == "confidence":
+                res[key] = conf
+            elif key in ("saliency", "status") or v.dim() < 2 or tuple(v.shape[:2]) != (n, k):
+                res[key] = v
+            else:
+                res[key] = lib.take_rows(v, slot)
+        res["count"], res["slot"] = count, slot
+        return res
 
     def alloc_match(self, n_pairs: int, k: int | None = None, rule: MatchRule | None = None) -> dict:
         """Output buffers of match() for n_pairs pairs (fixed capacity K per pair + device-side count).

@@ -84,6 +84,7 @@ python $ROOT/tools/upload_timeline.py 307 > $OUT/${TAG}_upload_timeline.txt 2>/d
 echo "[9] round-4 additions: the drop-in backbone at the reference's batch sizes, the per-frame stepper, the 4-rank rehearsal"
 python $ROOT/tools/backbone_batch_sweep.py 2>/dev/null | grep -v amdgpu > $OUT/${TAG}_backbone_batch_sweep.txt
 python $ROOT/tools/online_probe.py 2>/dev/null | grep -v amdgpu > $OUT/${TAG}_online_stepper.txt
+python $ROOT/tools/confidence_probe.py --out $OUT/confidence_head.txt > /dev/null 2>&1      # the confidence head beside the descriptor MLP and eager torch
 python $ROOT/bench.py --full --gpus 4 --rehearse-shared-gpu --steps 2 --warmup 1 > $OUT/${TAG}_rehearsal_4ranks.json 2>/dev/null
 # (clock probes need probe builds: tools/build_variant.sh probe csrc/vit_f32.hip vit_f32.hip -DSSLAM_CLOCK_PROBE -> tools/vit_f32_probe.py;
 #  tools/build_variant.sh rtprobe csrc/vit.hip vit.hip -DSSLAM_RT_PROBE -> SSLAM_BENCH_SO=... tools/rt_probe.py 82)
