@@ -170,14 +170,42 @@ def estimate_relative_pose(kp1, kp2, depth1, depth2, matches, camera=None, thres
     return T, out[5][0].cpu().numpy() == 1
 
 
-def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, threshold: float = 3.0, huber=None, iterations: int = 5):
+def match_weights(conf1, conf2, matches, mode: str = "product", sigma0: float = 1.0) -> np.ndarray:
+    """The weight of every match for refine_relative_pose(weights=), from the two frames' keypoint confidences conf1 (N,) and
+    conf2 (M,) float32 (UncertaintyEstimator's output) and matches (P, 2) [idx1, idx2]: (P,) float32.  mode "product": c1 * c2;
+    mode "expected_error": sigma0^2 / (sigma0^2 + e1^2 + e2^2) with e = 1 / (c + 1e-6) - 1 in float64, the error at which the
+    reference's compute_expected_error_loss is least for that confidence (include/sslam_weight.h: sslu_match_weights' bits).  A
+    match with an index outside its frame gets 0.  numpy in, numpy out; needs no GPU."""
+    modes = {"product": lib.WEIGHT_PRODUCT, "expected_error": lib.WEIGHT_EXPECTED_ERROR}
+    if mode not in modes:
+        raise ValueError(f"mode must be one of {tuple(modes)}, got {mode!r}")
+    _, s0 = lib.check_weights(modes[mode], sigma0)
+    c1, c2 = np.asarray(conf1, dtype=np.float32), np.asarray(conf2, dtype=np.float32)
+    mt = np.asarray(matches)
+    if c1.ndim != 1 or c2.ndim != 1:
+        raise ValueError(f"confidences (N,) and (M,) expected, got {c1.shape} and {c2.shape}")
+    if mt.size == 0:
+        return np.zeros(0, np.float32)
+    if mt.ndim != 2 or mt.shape[1] != 2 or mt.dtype.kind not in "iu":
+        raise ValueError(f"matches (P, 2) of integer indices expected, got {mt.shape} {mt.dtype}")
+    from sslam_amd import weight_numpy
+    return weight_numpy.match_weights(c1, c2, mt, modes[mode], s0)
+
+
+def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, threshold: float = 3.0, huber=None, iterations: int = 5,
+                         weights=None):
     """The step behind estimate_relative_pose: the pose T (4, 4) or (3, 4) from camera 1 to camera 2 - that function's, or any other
     initial pose - refined by Gauss-Newton on the Huber cost of the reprojection error over the matches T agrees with at
     `threshold` (sslam_pose_refine_pairs, include/sslam_hip.h).  kp1 .. camera as estimate_relative_pose takes them; huber: the
     Huber delta in pixels, threshold / 3 if None; iterations: the most steps.  numpy in, numpy out; one pair.
     Returns (T (4, 4) float64 - the T given when no step lowers the cost or the result would lose inliers -, inlier mask (P,) bool,
     info (6, 6) float64: the information matrix of the returned pose in the parameters (vx, vy, vz, wx, wy, wz) of a left
-    perturbation in camera 2; zero when the refinement was not attempted)."""
+    perturbation in camera 2; zero when the refinement was not attempted).
+    weights: None, or a (P,) float32 array aligned with matches - match_weights' output, or any other: the weighted refinement
+    runs (sslu_pose_refine_weighted_pairs' statement, include/sslam_weight.h): a match whose weight is not finite and > 0 takes no
+    part, the others' terms are multiplied by their weights, and info is the weighted information matrix.  This form needs NO
+    GPU: it runs the header's statement in numpy float64 (sslam_amd/weight_numpy.py) and gives the bits the device entry gives - a
+    caller on the device uses SequencePipeline.refine_poses(weights=)."""
     from sslam_amd.evaluation import Camera
     camera = Camera() if camera is None else camera
     lib.check_camera(camera)
@@ -186,6 +214,11 @@ def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, thre
     T0 = np.asarray(T, dtype=np.float64)
     if T0.shape not in ((4, 4), (3, 4)):
         raise ValueError(f"T (4, 4) or (3, 4) expected, got {T0.shape}")
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.dtype != np.float32 or weights.shape != (len(np.asarray(matches)),):
+            raise ValueError(f"weights must be None or a float32 array of shape ({len(np.asarray(matches))},), got {weights.dtype} {weights.shape}")
+        return _refine_weighted_numpy(kp1, kp2, depth1, depth2, matches, T0, camera, t, hub, n_iter, weights)
     pair = _pair_on_device("refine_relative_pose", kp1, kp2, depth1, depth2, matches, camera)
     T4 = np.eye(4)
     T4[:3] = T0[:3]
@@ -200,6 +233,37 @@ def refine_relative_pose(kp1, kp2, depth1, depth2, matches, T, camera=None, thre
     info = np.zeros((6, 6))
     info[iu], info[iu[1], iu[0]] = tri, tri
     return T4, out[7][0].cpu().numpy() == 1, info
+
+
+def _refine_weighted_numpy(kp1, kp2, depth1, depth2, matches, T0, camera, t, hub, n_iter, weights):
+    """refine_relative_pose's weighted form: what _pair_on_device judges, judged alike, then sslam_amd/weight_numpy.py.  No GPU."""
+    from sslam_amd import weight_numpy
+    depths = []
+    for name, d in (("depth1", depth1), ("depth2", depth2)):
+        d = d.detach().cpu().numpy() if isinstance(d, torch.Tensor) else d
+        if not isinstance(d, np.ndarray) or d.dtype != np.uint16 or d.ndim != 2:
+            raise ValueError(f"{name} (h, w) uint16 expected: the frame's raw depth image")
+        check_depth_size(d.shape[1], d.shape[0], camera)
+        depths.append(d)
+    k1, k2 = np.asarray(kp1, dtype=np.float32), np.asarray(kp2, dtype=np.float32)
+    if k1.ndim != 2 or k2.ndim != 2 or k1.shape[1] != 2 or k2.shape[1] != 2 or k1.shape[0] < 1 or k2.shape[0] < 1:
+        raise ValueError(f"keypoints (N >= 1, 2) and (M >= 1, 2) expected, got {k1.shape} and {k2.shape}")
+    mt = np.asarray(matches)
+    T4 = np.eye(4)
+    T4[:3] = T0[:3]
+    if mt.size == 0:
+        return T4, np.zeros(0, bool), np.zeros((6, 6))
+    if mt.ndim != 2 or mt.shape[1] != 2 or mt.dtype.kind not in "iu":
+        raise ValueError(f"matches (P, 2) of integer indices expected, got {mt.shape} {mt.dtype}")
+    if max(len(k1), len(k2), len(mt)) > lib.EVAL_MAX_K:
+        raise lib.SslamHipError(f"refine_relative_pose: {max(len(k1), len(k2), len(mt))} keypoints or matches; at most {lib.EVAL_MAX_K} are handled")
+    out = weight_numpy.refine_pair(k1, k2, weight_numpy.keypoint_depth(depths[0], k1), weight_numpy.keypoint_depth(depths[1], k2), mt,
+                                   weights, camera, t, hub, n_iter, np.ascontiguousarray(T0[:3]).reshape(12))
+    T4[:3] = out["T"].reshape(3, 4)
+    iu = np.triu_indices(6)
+    info = np.zeros((6, 6))
+    info[iu], info[iu[1], iu[0]] = out["info"], out["info"]
+    return T4, out["inlier_of_slot"] == 1, info
 
 
 def optimize_pose_graph(first, second, T, info, n_nodes: int, C_init=None, band=None, huber_chi: float = 4.0, damping: float = 0.0,

@@ -2331,3 +2331,109 @@ def take_rows(src, slot, out=None):
         raise ValueError("out must not be src")
     _run("take_rows", conf().sslc_take_rows, (src, slot, out), _dp(src), _dp(slot), n, k, src.numel() // (n * k), _dp(out))
     return out
+
+
+# -------------------------------------------------------------------------------------- libsslam_weight.so (include/sslam_weight.h)
+# The eighth library: per-match weights from keypoint confidences and the pose refinement that takes them, entries with the prefix
+# sslu_, built from csrc_weight/ with csrc/flags.mk (csrc/common.h, csrc/pose_common.h and csrc/pose_refine_common.h included from
+# where they are: the weighted kernel is pose_refine_pairs' own body), loaded and refused like the others.
+CSRC_WEIGHT = os.path.join(_PKG, "csrc_weight")
+WEIGHT_SO_PATH = os.path.join(CSRC_WEIGHT, "libsslam_weight.so")
+WEIGHT_EXPORTS = ["sslu_version", "sslu_arch", "sslu_launch_count", "sslu_match_weights", "sslu_pose_refine_weighted_pairs"]
+WEIGHT_PRODUCT, WEIGHT_EXPECTED_ERROR = 0, 1      # SSLU_WEIGHT_PRODUCT, SSLU_WEIGHT_EXPECTED_ERROR
+POSE_REFINE_WEIGHTED_KEYS = POSE_REFINE_KEYS + ("weight_sum",)
+
+_weight = None
+
+
+def weight_build(force: bool = False) -> str:
+    """Compile libsslam_weight.so for gfx950 in-tree, as build() compiles the first library."""
+    others = [os.path.join(_INCLUDE, h) for h in ("sslam_weight.h", "sslam_hip.h")] + \
+        [os.path.join(CSRC, h) for h in ("common.h", "pose_common.h", "pose_refine_common.h")]
+    return _make_if_stale(CSRC_WEIGHT, WEIGHT_SO_PATH, others, force)
+
+
+def weight():
+    """Load libsslam_weight.so; raises if it has not been built (no silent fallback)."""
+    global _weight
+    if _weight is None:
+        _weight = _load(WEIGHT_SO_PATH, CSRC_WEIGHT, "sslu", _weight_prototypes)
+    return _weight
+
+
+def _weight_prototypes(L):
+    p, i, d = C.c_void_p, C.c_int, C.c_double
+    L.sslu_match_weights.argtypes = [p, i, i, p, p, i, p, p, i, i, d, p, p]
+    L.sslu_pose_refine_weighted_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [p, d, i, p] + [p] * 13 + [p]
+
+
+def weight_launch_count() -> int:
+    return int(weight().sslu_launch_count())
+
+
+def check_weights(mode, sigma0=1.0) -> tuple:
+    """(mode, sigma0) of match_weights: mode WEIGHT_PRODUCT or WEIGHT_EXPECTED_ERROR; sigma0 a finite number > 0 under the second
+    (ignored, and returned as 1.0, under the first) - else ValueError, before any device work."""
+    if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or int(mode) not in (WEIGHT_PRODUCT, WEIGHT_EXPECTED_ERROR):
+        raise ValueError(f"mode must be WEIGHT_PRODUCT ({WEIGHT_PRODUCT}) or WEIGHT_EXPECTED_ERROR ({WEIGHT_EXPECTED_ERROR}), got {mode!r}")
+    return int(mode), (check_positive("sigma0", sigma0) if int(mode) == WEIGHT_EXPECTED_ERROR else 1.0)
+
+
+def pose_refine_weighted_shapes(n_pairs: int, n1: int) -> dict:
+    """name -> (shape, dtype) of the outputs of pose_refine_weighted: pose_refine_shapes and weight_sum (P,) float64."""
+    return {**pose_refine_shapes(n_pairs, n1), "weight_sum": ((n_pairs,), torch.float64)}
+
+
+def match_weights(conf_bank, first, second, matches, count, mode=WEIGHT_PRODUCT, sigma0=1.0, out=None):
+    """sslu_match_weights: conf_bank (n_bank, K) fp32, the keypoint confidences; first / second, matches (P, n1, 2) int64 and count
+    (P,) int32 as pose_refine_pairs takes them; mode and sigma0 as check_weights judges them.
+    Returns weight (P, n1) fp32, every element written: c1 * c2 or sigma0^2 / (sigma0^2 + e1^2 + e2^2) with e = 1 / (c + 1e-6) - 1,
+    +0.0 for a slot that holds no match (include/sslam_weight.h).  out: an optional tensor of that shape.  One launch, no host read."""
+    _check_bank("conf_bank", conf_bank, ("K",))
+    n_bank, k = int(conf_bank.shape[0]), int(conf_bank.shape[1])
+    n_pairs = check_pair_lists(first, second, conf_bank.device)
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_pairs or \
+            int(matches.shape[1]) < 1:
+        raise ValueError(f"matches must be a tensor of shape ({n_pairs}, n1 >= 1, 2)")
+    n1 = int(matches.shape[1])
+    if count is None:
+        raise ValueError("count is required")
+    _check_arrays((n_pairs, n1, 2), ("matches", matches, torch.int64))
+    _check_arrays((n_pairs,), ("count", count, torch.int32))
+    mode, s0 = check_weights(mode, sigma0)
+    _check_arrays((n_pairs, n1), ("out", out, torch.float32))
+    if n_pairs * n1 > 0x7fffffff:
+        raise SslamHipError(f"match_weights: {_ERR[E_UNSUPPORTED]} (n_pairs * n1 <= 2^31 - 1; got {n_pairs * n1})")
+    dev = common_device(conf_bank, first, second, matches, count, out)
+    if out is None:
+        out = torch.empty((n_pairs, n1), dtype=torch.float32, device=dev)
+    _run("match_weights", weight().sslu_match_weights, (conf_bank, first, second, matches, count, out), _dp(conf_bank), n_bank, k,
+         _dp(first), _dp(second), n_pairs, _dp(matches), _dp(count), n1, mode, s0, _dp(out))
+    return out
+
+
+def pose_refine_weighted(kp_bank, kp_depth_bank, first, second, matches, count, camera, T_in, weights, scale_x=1.0, scale_y=1.0,
+                         threshold=3.0, huber=1.0, iterations=5, out=None):
+    """sslu_pose_refine_weighted_pairs: pose_refine_pairs' arguments and weights (P, n1) fp32, the weight of every match slot
+    (match_weights' output, or any other).  A row whose weight is not finite and > 0 is not selected; a selected row's weight
+    multiplies its Huber terms (include/sslam_weight.h).
+    Returns pose_refine_pairs' twelve tensors and weight_sum (P,) float64 - POSE_REFINE_WEIGHTED_KEYS; info is the weighted
+    information matrix.  out: optional tensors of those shapes (T must not be T_in).  One launch, no host read."""
+    n_bank, k, n_pairs, n1, _, doubles = _pose_operands("pose_refine_weighted", kp_bank, first, second, threshold,
+                                                        depth=(kp_depth_bank, camera, scale_x, scale_y), listed=(matches, count))
+    hub, n_iter = check_huber(huber), check_iterations(iterations)
+    _check_pose_rows("T_in", T_in, n_pairs, 12)
+    if weights is None:
+        raise ValueError("weights is required: pose_refine_pairs is the unweighted entry")
+    _check_arrays((n_pairs, n1), ("weights", weights, torch.float32))
+    shapes = pose_refine_weighted_shapes(n_pairs, n1)
+    o = None if out is None else _outputs(shapes, POSE_REFINE_WEIGHTED_KEYS, out)
+    if o is not None and o[0].data_ptr() == T_in.data_ptr():
+        raise ValueError("out `T` must not be T_in")
+    dev = common_device(kp_bank, kp_depth_bank, first, second, matches, count, T_in, weights)
+    o = _outputs(shapes, POSE_REFINE_WEIGHTED_KEYS, None, dev) if o is None else o
+    _run("pose_refine_weighted", weight().sslu_pose_refine_weighted_pairs,
+         (kp_bank, kp_depth_bank, first, second, matches, count, T_in, weights, *o), _dp(kp_bank), _dp(kp_depth_bank), n_bank, k, _dp(first),
+         _dp(second), n_pairs, _dp(matches), _dp(count), n1, *doubles, _dp(T_in), C.c_double(hub), n_iter, _dp(weights),
+         *(_dp(x) for x in o))
+    return tuple(o)

@@ -27,7 +27,7 @@ import torch
 
 from . import lib
 from .evaluation import Camera, check_depth_size, check_subcell, gather_keypoint_depth, geometry_bank, relative_transform
-from .pipeline import MatchRule
+from .pipeline import MatchRule, PoseWeights
 
 _INT_KEYS = ("inlier_count", "usable_count", "best_hypothesis", "refit_kept")
 
@@ -194,23 +194,39 @@ def _check_refine(refine, threshold, huber, iterations) -> None:
         lib.check_iterations(iterations)
 
 
-def _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations):
+def _check_weights(pipe, weights, refine) -> None:
+    """What weights= can be refused for, before any device work: it is a PoseWeights, it needs the refinement it weights and a
+    pipeline that extracts the confidence it is made of."""
+    if weights is None:
+        return
+    if not isinstance(weights, PoseWeights):
+        raise ValueError(f"weights must be None or a PoseWeights, got {type(weights).__name__}")
+    if not refine:
+        raise ValueError("weights= weights the refinement: it needs refine=True")
+    if not getattr(pipe.cfg, "confidence", False):
+        raise ValueError("weights= is made of the keypoint confidence: the pipeline needs ExtractorConfig(confidence=True)")
+
+
+def _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations, weight=None):
     """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it) -> ((P, 18) float64 device tensor -
-    (P, 58) with refine -, refine_poses' dictionary or None).  No host read."""
+    (P, 58) with refine, (P, 59) with a weight tensor (P, n1): weight_sum last -, refine_poses' dictionary or None).  No host read."""
     return _launch_lists(pipe, keypoints_pixel, kp_depth, [a for a, _ in pairs], [b for _, b in pairs], matches, camera, threshold, hypotheses,
-                         seed, refine, huber, iterations)
+                         seed, refine, huber, iterations, weight)
 
 
-def _launch_lists(pipe, keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed, refine, huber, iterations):
+def _launch_lists(pipe, keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed, refine, huber, iterations,
+                  weight=None):
     """_launch on pair lists as match_pairs takes them: host sequences, or int32 device tensors that nothing here reads."""
     est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
     cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
            [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
     ref = None
     if refine:
-        ref = pipe.refine_poses(keypoints_pixel, kp_depth, first, second, matches, camera, est, threshold, huber, iterations)
+        ref = pipe.refine_poses(keypoints_pixel, kp_depth, first, second, matches, camera, est, threshold, huber, iterations, weights=weight)
         cols += [ref["T"]] + [ref[key].to(torch.float64)[:, None] for key in _REFINE_INT] + [ref[key][:, None] for key in _REFINE_REAL] + \
                 [ref["info"]]
+        if weight is not None:
+            cols.append(ref["weight_sum"][:, None])         # the one column a weighted row grows by
     return torch.cat(cols, dim=1), ref                      # integers up to 4096: exact in float64
 
 
@@ -236,20 +252,23 @@ def _unpack(host, pairs, poses, spacing, refine) -> dict:
     out["ransac"] = ransac
     out["refine"] = {"status": got["status"], "iterations": got["iterations"], "selected_count": got["selected_count"],
                      "cost_in": r[:, 16].copy(), "cost": r[:, 17].copy(), "info": info_matrix(r[:, 19:40])}
+    if r.shape[1] > 40:                                      # a weighted row: weight_sum behind info
+        out["refine"]["weight_sum"] = r[:, 40].copy()
     return out
 
 
 def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine=False,
-              huber=None, iterations=5) -> dict:
+              huber=None, iterations=5, weight=None) -> dict:
     """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it), ONE host read-back of (P, 18)
-    float64 ((P, 58) with refine), the host-side figures."""
-    packed, _ = _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations)
+    float64 ((P, 58) with refine, (P, 59) weighted), the host-side figures."""
+    packed, _ = _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations,
+                        weight)
     return _unpack(packed.cpu().numpy(), pairs, poses, spacing, refine)
 
 
 def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None, rule=None,
              threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, refine: bool = False, huber=None,
-             iterations: int = 5, *, subcell=None) -> dict:
+             iterations: int = 5, *, subcell=None, weights=None) -> dict:
     """The relative pose of every pair (i, i + spacing) of a sequence, from its own features: the frames images_u8 (N, H, W, 3)
     uint8 (a pipeline built with vit=) or their ViT tokens (tokens=), their raw depth images depth (N, h, w) uint16 (numpy or
     tensor) and camera (an evaluation.Camera; the default one if None).  The frames are extracted once, the depth under every
@@ -265,8 +284,13 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     'inlier_count', 'rms' and the summaries built from them, and 'refine' holds 'status', 'iterations', 'selected_count', 'cost_in',
     'cost' and 'info' (P, 6, 6), the information matrix of every refined pose.  With refine=False nothing changes.
     subcell: on a pipeline with ExtractorConfig(subcell=True) the depth lookups, RANSAC and the refinement read the refined
-    keypoints (evaluation.geometry_bank); subcell=False forces the cell centres.  The match lists are the same either way."""
+    keypoints (evaluation.geometry_bank); subcell=False forces the cell centres.  The match lists are the same either way.
+    weights: with refine=True on a pipeline with ExtractorConfig(confidence=True), a PoseWeights: one SequencePipeline.match_weights
+    launch makes every match's weight of its two keypoints' confidences and the weighted refinement runs
+    (include/sslam_weight.h); 'refine' then also holds 'weight_sum', and 'info' is the weighted information matrix.  Still ONE
+    read-back.  With weights=None nothing changes."""
     check_subcell(subcell)
+    _check_weights(pipe, weights, refine)
     src = tokens if tokens is not None else images_u8
     if src is None:
         raise ValueError("images_u8 or tokens= required")
@@ -281,8 +305,9 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     kp = geometry_bank(ex, subcell)
     kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
+    weight = None if weights is None else pipe.match_weights(ex["confidence"], [a for a, _ in pairs], [b for _, b in pairs], matches, weights)
     return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine,
-                     huber, iterations)
+                     huber, iterations, weight)
 
 
 def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None,
@@ -417,10 +442,11 @@ def _spacings_and_graph(host, rest, lists, pairs, n, poses) -> dict:
 
 
 def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
-           graph_iterations) -> dict:
-    """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back."""
+           graph_iterations, weight=None) -> dict:
+    """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back.  weight: the
+    (P, n1) weights of the weighted refinement, whose info the graph then reads as it reads the unweighted one."""
     pairs = [pr for s in lists for pr in lists[s]]
-    packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
+    packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations, weight)
     g = _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations)
     flat = torch.cat([packed.reshape(-1)] + _graph_flat(g)).cpu().numpy()          # the ONE read-back
     P, w = len(pairs), int(packed.shape[1])
@@ -430,7 +456,7 @@ def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypo
 
 def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, spacings=GRAPH_SPACINGS, num_pairs=None, rule=None,
                    threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, huber=None, iterations: int = 5, *,
-                   subcell=None, band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8) -> dict:
+                   subcell=None, band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8, weights=None) -> dict:
     """odometry(refine=True) at every spacing of `spacings` at once, and the pose graph over all of their edges
     (SequencePipeline.optimize_pose_graph; csrc_graph/pose_graph.hip): the frames are extracted once, the pairs of all spacings
     matched in one match_pairs call, ONE RANSAC and ONE refinement launch run over the concatenated pair list, the refined
@@ -442,13 +468,16 @@ def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, sp
     Returns {spacing: what odometry(spacing=spacing, refine=True) returns, ..., 'graph': {'trajectory' (N, 4, 4) camera-to-world,
     'pairs', 'status', 'iterations', 'used_edges', 'skipped_edges', 'failed_row', 'cost_in', 'cost', 'edge_chi2' (one per listed
     pair); with poses also 'ate' (ate_summary of the graph's trajectory) and 'ate_chain' (that of the spacing-1 chain)}}.
+    weights: as odometry() takes it - ONE match_weights launch over the concatenated pair list, the weighted refinement, every
+    spacing's 'refine' with 'weight_sum'; the graph reads the weighted information matrices with no change of its own.
     Nobody has measured this on real RGB-D data: no real sequence was at hand when this was written."""
     lists, n, band, _, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
         pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber, iterations, subcell, band,
-        huber_chi, damping, graph_iterations)
+        huber_chi, damping, graph_iterations, lambda: _check_weights(pipe, weights, True))
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
+    weight = None if weights is None else pipe.match_weights(ex["confidence"], [a for a, _ in pairs], [b for _, b in pairs], matches, weights)
     return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
-                  damping, graph_iterations)
+                  damping, graph_iterations, weight)
 
 
 def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=None, spacings=None, num_pairs=None, threshold: float = 3.0,

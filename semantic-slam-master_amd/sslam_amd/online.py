@@ -340,17 +340,25 @@ class PoseFrameStepper(RuleFrameStepper):
     refine=True puts sslam_pose_refine_pairs behind the RANSAC launch, on the same stream and inside the same graph
     (SequencePipeline.refine_poses from RANSAC's pose: huber, threshold / 3 if None, and iterations as odometry() takes them):
     "pose" keeps RANSAC's keys untouched and gains "refined", the refinement's outputs (T, status, iterations, ..., info (21,)) as
-    views of static buffers.  With refine=False no further buffer is allocated and no further launch is made."""
+    views of static buffers.  With refine=False no further buffer is allocated and no further launch is made.
+    weights: with refine=True on a pipeline with ExtractorConfig(confidence=True), a pipeline.PoseWeights: sslu_match_weights
+    makes the step's match weights of the two frames' confidences (self.pair["confidence"], whose slot 1 is handed over to slot 0
+    as the depth is) and sslu_pose_refine_weighted_pairs runs in sslam_pose_refine_pairs' place (include/sslam_weight.h), both
+    inside the captured step: one launch more per step, "refined" gains weight_sum, and its info is the weighted information
+    matrix.  With weights=None there is no new buffer and no new launch."""
 
     def __init__(self, pipe: SequencePipeline, height: int, width: int, depth_height: int, depth_width: int, camera=None,
                  use_graph: bool = True, tokens_in: bool = False, rule=None, threshold: float = 3.0, hypotheses: int = 256,
-                 seed: int = 0, refine: bool = False, huber=None, iterations: int = 5):
+                 seed: int = 0, refine: bool = False, huber=None, iterations: int = 5, weights=None):
         from .evaluation import Camera, check_depth_size
+        from .odometry import _check_weights
         from .pipeline import MatchRule
         self.threshold, self.hypotheses, self.seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
         if not isinstance(refine, bool):
             raise ValueError(f"refine must be a bool, got {refine!r}")
         self.refine = refine
+        _check_weights(pipe, weights, refine)                         # before anything is allocated
+        self.weights = weights
         if refine:
             self.huber, self.iterations = lib.check_huber(self.threshold / 3.0 if huber is None else huber), lib.check_iterations(iterations)
         self.camera = Camera() if camera is None else camera
@@ -363,7 +371,8 @@ class PoseFrameStepper(RuleFrameStepper):
         self._first = torch.zeros((1,), dtype=torch.int32, device=dev)
         self._second = torch.ones((1,), dtype=torch.int32, device=dev)
         self.pose = pipe.alloc_pose(1, K)
-        self.refined = pipe.alloc_pose_refine(1, K) if refine else None
+        self.refined = pipe.alloc_pose_refine(1, K, weighted=weights is not None) if refine else None
+        self.weight = torch.zeros((1, K), dtype=torch.float32, device=dev) if weights is not None else None
 
     def _after_match(self) -> None:
         p = self.pipe
@@ -372,8 +381,12 @@ class PoseFrameStepper(RuleFrameStepper):
         p.estimate_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.threshold,
                          self.hypotheses, self.seed, out=self.pose)
         if self.refine:
+            if self.weights is not None:
+                p.match_weights(self.pair["confidence"], self._first, self._second, self.m, self.weights, out=self.weight)
             p.refine_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.pose, self.threshold,
-                           self.huber, self.iterations, out=self.refined)
+                           self.huber, self.iterations, out=self.refined, weights=self.weight)
+            if self.weights is not None:
+                self.pair["confidence"][0].copy_(self.pair["confidence"][1])
         self.kp_depth[0].copy_(self.kp_depth[1])
 
     @torch.no_grad()

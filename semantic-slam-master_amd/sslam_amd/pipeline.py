@@ -121,6 +121,42 @@ def _checked_rule(rule, k: int):
     return rule
 
 
+@dataclass(frozen=True)
+class PoseWeights:
+    """How a match's weight in the pose refinement is made of its two keypoints' confidences (`weights=` of
+    SequencePipeline.match_weights, odometry.odometry / odometry_graph, online.PoseFrameStepper; include/sslam_weight.h states
+    both forms).  Built by the two constructors."""
+    mode: int
+    sigma0: float = 1.0
+
+    @classmethod
+    def product(cls) -> "PoseWeights":
+        """w = c1 * c2: a match is trusted as far as both of its keypoints are."""
+        return cls(lib.WEIGHT_PRODUCT, 1.0)
+
+    @classmethod
+    def expected_error(cls, sigma0: float = 1.0) -> "PoseWeights":
+        """w = sigma0^2 / (sigma0^2 + e1^2 + e2^2), e = 1 / (c + 1e-6) - 1: the confidence read as the reference's
+        compute_expected_error_loss trains it, 1 / (1 + expected error), and the match weighted by its inverse variance against a
+        floor of sigma0 (in the error's units)."""
+        return cls(lib.WEIGHT_EXPECTED_ERROR, sigma0)
+
+    def __post_init__(self):
+        if self.mode not in (lib.WEIGHT_PRODUCT, lib.WEIGHT_EXPECTED_ERROR) or isinstance(self.mode, bool):
+            raise ValueError(f"unknown weight mode {self.mode!r}")
+        if isinstance(self.sigma0, bool) or not isinstance(self.sigma0, numbers.Real) or not math.isfinite(self.sigma0) or not self.sigma0 > 0:
+            raise ValueError(f"sigma0 must be a finite number > 0, got {self.sigma0!r}")
+        if self.mode == lib.WEIGHT_PRODUCT and self.sigma0 != 1.0:
+            raise ValueError("the product form takes no sigma0: use the constructors")
+
+
+def _checked_weights(weights):
+    """weights=: None or a PoseWeights."""
+    if weights is not None and not isinstance(weights, PoseWeights):
+        raise ValueError(f"weights must be None or a PoseWeights, got {type(weights).__name__}")
+    return weights
+
+
 def _np(v):
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
@@ -939,12 +975,39 @@ class SequencePipeline:
                                   t, n_hyp, seed, out=tuple(res[key][a:b] for key in lib.POSE_RANSAC_KEYS))
         return res
 
-    def alloc_pose_refine(self, n_pairs: int, k: int | None = None) -> dict:
-        """Output buffers of refine_poses() for n_pairs pairs whose match lists hold k slots (num_keypoints by default)."""
+    def alloc_pose_refine(self, n_pairs: int, k: int | None = None, weighted: bool = False) -> dict:
+        """Output buffers of refine_poses() for n_pairs pairs whose match lists hold k slots (num_keypoints by default); weighted:
+        with `weight_sum`, for a call that passes weights."""
+        if weighted:
+            return self._pose_buffers(lib.pose_refine_weighted_shapes, lib.POSE_REFINE_WEIGHTED_KEYS, n_pairs, k)
         return self._pose_buffers(lib.pose_refine_shapes, lib.POSE_REFINE_KEYS, n_pairs, k)
 
+    def match_weights(self, confidence, first, second, matches: dict, weights: PoseWeights, out=None):
+        """Per-match weights for refine_poses(weights=) (csrc_weight/weighted_refine.hip): confidence (N, K) fp32, extract()'s
+        `confidence` for the bank the pairs index (ExtractorConfig(confidence=True)); first / second and matches as estimate_poses
+        takes them; weights: a PoseWeights.  Returns a (P, n1) float32 device tensor aligned with the match slots, +0.0 where a
+        slot holds no match.  out: such a tensor (or a row slice).  One launch per 65 535 pairs, no host read."""
+        if not isinstance(weights, PoseWeights):
+            raise ValueError(f"weights must be a PoseWeights, got {type(weights).__name__}")
+        if not isinstance(confidence, torch.Tensor) or confidence.dim() != 2:
+            raise ValueError("confidence (N, K) float32 expected: extract()'s `confidence`")
+        first, second = (_host_pair_list(name, t) for name, t in (("first", first), ("second", second)))
+        n_pairs = lib.check_pair_lists(first, second)             # a malformed list is refused before anything is uploaded
+        first, second = (t if t.device == confidence.device else t.to(confidence.device) for t in (first, second))
+        mt = _checked_match_lists(matches, n_pairs)
+        n1 = int(mt.shape[1])
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n_pairs, n1) or
+                                not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape ({n_pairs}, {n1})")
+        res = torch.empty((n_pairs, n1), dtype=torch.float32, device=confidence.device) if out is None else out
+        for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
+            b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
+            lib.match_weights(confidence, first[a:b], second[a:b], mt[a:b], matches["match_count"][a:b], weights.mode, weights.sigma0,
+                              out=res[a:b])
+        return res
+
     def refine_poses(self, keypoints_pixel, kp_depth, first, second, matches: dict, camera, pose, threshold: float = 3.0,
-                     huber: float | None = None, iterations: int = 5, out: dict | None = None) -> dict:
+                     huber: float | None = None, iterations: int = 5, out: dict | None = None, weights=None) -> dict:
         """Pose refinement (csrc/pose_refine.hip): for every listed pair, up to `iterations` Gauss-Newton steps on the Huber cost of
         the reprojection error into the second frame, from the initial pose `pose` - the dictionary estimate_poses() returned for
         the same pairs, or any (P, 12) float64 device tensor of [R | t] rows (a motion model's prediction, the previous step's
@@ -956,7 +1019,11 @@ class SequencePipeline:
         inlier_of_slot (P, n1) int32, cost_in, cost, rms (P,) float64 and info (P, 21) float64, the upper triangle of the 6 x 6
         information matrix in the parameters (vx, vy, vz, wx, wy, wz) of a left perturbation in the second camera
         (include/sslam_hip.h).  Under status 1, 2 and 3 T is `pose` bit for bit.  out: alloc_pose_refine buffers (or row slices).
-        One launch per 65 535 pairs, no host read."""
+        One launch per 65 535 pairs, no host read.
+        weights: None, or a (P, n1) float32 device tensor aligned with the match slots - match_weights()' output, or any other:
+        the weighted entry runs instead (include/sslam_weight.h: a row whose weight is not finite and > 0 is not selected, a
+        selected row's weight multiplies its terms, info is the weighted information matrix), the dictionary also holds
+        `weight_sum` (P,) float64, and out is alloc_pose_refine(weighted=True)'s."""
         first, second, n_pairs, _, _ = self._pose_operands("refine_poses", keypoints_pixel, first, second, kp_depth)
         t = lib.check_threshold(threshold)
         n_iter = lib.check_iterations(iterations)
@@ -966,6 +1033,18 @@ class SequencePipeline:
         t_in = pose["T"] if isinstance(pose, dict) and "T" in pose else pose
         if not isinstance(t_in, torch.Tensor) or t_in.dtype != torch.float64 or tuple(t_in.shape) != (n_pairs, 12) or not t_in.is_contiguous():
             raise ValueError(f"pose must be estimate_poses()' dictionary or a contiguous float64 tensor of shape ({n_pairs}, 12)")
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(mt.shape[:2]) or \
+                    not weights.is_contiguous():
+                raise ValueError(f"weights must be None or a contiguous float32 tensor of shape {tuple(mt.shape[:2])}: match_weights()' output")
+            res = self._pose_buffers(lib.pose_refine_weighted_shapes, lib.POSE_REFINE_WEIGHTED_KEYS, n_pairs, int(mt.shape[1]), out,
+                                     "alloc_pose_refine(weighted=True)")
+            for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):
+                b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
+                lib.pose_refine_weighted(keypoints_pixel, kp_depth, first[a:b], second[a:b], mt[a:b], matches["match_count"][a:b], camera,
+                                         t_in[a:b], weights[a:b], sx, sy, t, hub, n_iter,
+                                         out=tuple(res[key][a:b] for key in lib.POSE_REFINE_WEIGHTED_KEYS))
+            return res
         res = self._pose_buffers(lib.pose_refine_shapes, lib.POSE_REFINE_KEYS, n_pairs, int(mt.shape[1]), out, "alloc_pose_refine")
         for a in range(0, n_pairs, MAX_PAIRS_PER_LAUNCH):       # cut as match_pairs cuts
             b = min(a + MAX_PAIRS_PER_LAUNCH, n_pairs)
