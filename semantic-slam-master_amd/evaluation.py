@@ -421,6 +421,64 @@ class EdgeLog:
         return tuple(self.state[k][:rows] for k in ("log_first", "log_second", "log_T", "log_info"))
 
 
+def build_tracks(first, second, matches, count=None, mask=None, n_frames=None, k=None) -> dict:
+    """Feature tracks from the match lists of a sequence's pairs, numpy in -> numpy out with NO GPU (sslam_amd/track_numpy.py: the
+    statement of include/sslam_track.h, the bits sslt_link_pairs + sslt_track_ids give; a caller on the device uses
+    SequencePipeline.link_matches / track_ids).  first, second (P,): the frames a < b of every row; matches (P, n1, 2) [idx1, idx2];
+    count (P,): the listed slots of every row, all of them if None; mask (P, n1): where given only slots with mask == 1 count - the
+    inlier_of_slot of estimate_relative_pose or refine_relative_pose.  Returns prev, next (n_frames, k), prev_frame, next_frame
+    (n_frames,), track_id, age (n_frames, k), n_tracks (1,), root_frame, root_slot, length (n_frames * k,) int32: every keypoint has
+    at most one predecessor and one successor, tracks are numbered by their first keypoint in (frame, slot) order, and a keypoint
+    without a link is a track of length 1."""
+    from sslam_amd import track_numpy as tn
+    return tn.build_tracks(first, second, matches, count, mask, n_frames, k)
+
+
+def track_landmarks(keypoints, kp_depth, C, tracks: dict, camera=None, threshold: float = 3.0, min_obs: int = 2, weights=None) -> dict:
+    """The landmark map of build_tracks' tracks, numpy with NO GPU (the bits of sslt_landmarks): keypoints (N, K, 2) float32 pixels,
+    kp_depth (N, K) int32 raw depths under them, C (N, 12) / (N, 3, 4) / (N, 4, 4) world -> camera poses, camera an
+    sslam_amd.evaluation.Camera (TUM's if None), weights (N, K) float32 or None - UncertaintyEstimator's confidences as they are.
+    Returns xyz (N K, 3), n_obs, n_kept, status, weight_sum, rms per track and residual, kept (N, K) per keypoint."""
+    from sslam_amd import track_numpy as tn
+    from sslam_amd.evaluation import Camera
+    C = np.asarray(C, dtype=np.float64)
+    if C.ndim == 3 and C.shape[1:] == (4, 4):
+        C = C[:, :3]
+    return tn.track_landmarks(keypoints, kp_depth, np.ascontiguousarray(C).reshape(len(C), 12), tracks, Camera() if camera is None else camera,
+                              threshold, min_obs, weights)
+
+
+class TrackBank:
+    """The online counterpart of build_tracks: a track bank that grows by one frame per step (sslt_track_step,
+    include/sslam_track.h).  Like PlaceBank it needs NO GPU: it runs the header's statement in numpy (sslam_amd/track_numpy.py) and
+    gives the bits the device entry gives - a caller on the device uses SequencePipeline.track_step.  After n steps its rows equal
+    build_tracks over the rows stepped so far.  capacity: the frames the bank keeps; k: keypoint slots per frame, 1 .. 4096."""
+
+    def __init__(self, capacity: int = 1024, k: int = 500):
+        from sslam_amd import track_numpy as tn
+        self._bank = tn.TrackBank(capacity, k)
+        self.capacity, self.k = self._bank.capacity, self._bank.k
+
+    @property
+    def state(self) -> dict:
+        return self._bank.state
+
+    def reset(self) -> None:
+        self._bank.reset()
+
+    def step(self, matches, *, first: int = -1, count=None, mask=None) -> dict:
+        """matches (n1, 2) [idx1 in frame `first`, idx2 in this frame]; first: the bank frame the matches come from, -1 for none
+        (the first frame); count: the listed slots, all if None; mask (n1,): only slots with mask == 1 count - all three by keyword: the
+        numpy bank this wraps orders them otherwise.  Returns this frame's track_id, age (k,), n_new (1,) and status (1,): 0, or 4
+        once the bank is full."""
+        matches = np.asarray(matches, dtype=np.int64).reshape(-1, 2)
+        return self._bank.step(matches, len(matches) if count is None else int(count), None if mask is None else np.asarray(mask).reshape(-1),
+                               int(first))
+
+    def tracks(self) -> dict:
+        return self._bank.tracks()
+
+
 def find_loop_candidates(descriptors, scores, min_gap: int = 30, min_sim: float = 0.3, per_frame: int = 2, suppress: int = 5):
     """The step that proposes loop closures: descriptors (N, K, D) and scores (N, K) float32 of a sequence's frames, D 128 or 256.
     Every frame gets a place signature - the score-weighted sum of its descriptors, centred on the sequence's mean, normalised -

@@ -2437,3 +2437,240 @@ def pose_refine_weighted(kp_bank, kp_depth_bank, first, second, matches, count, 
          _dp(second), n_pairs, _dp(matches), _dp(count), n1, *doubles, _dp(T_in), C.c_double(hub), n_iter, _dp(weights),
          *(_dp(x) for x in o))
     return tuple(o)
+
+
+# ---------------------------------------------------------------------------------------- libsslam_track.so (include/sslam_track.h)
+# The ninth library: feature tracks and a landmark map, entries with the prefix sslt_, built from csrc_track/ with csrc/flags.mk,
+# loaded and refused like the others.
+CSRC_TRACK = os.path.join(_PKG, "csrc_track")
+TRACK_SO_PATH = os.path.join(CSRC_TRACK, "libsslam_track.so")
+TRACK_EXPORTS = ["sslt_version", "sslt_arch", "sslt_launch_count", "sslt_link_pairs", "sslt_track_workspace_bytes", "sslt_track_ids",
+                 "sslt_landmarks", "sslt_track_step"]
+TRACK_MAX_K, TRACK_SCAN_TILE, TRACK_MAX_NODES = 4096, 1024, 0x7fffffff      # SSLT_MAX_K, SSLT_SCAN_TILE, n_bank * K
+LINK_KEYS = ("prev", "next", "prev_frame", "next_frame")
+TRACK_ID_KEYS = ("track_id", "age", "n_tracks", "root_frame", "root_slot", "length")
+LANDMARK_KEYS = ("xyz", "n_obs", "n_kept", "status", "weight_sum", "rms", "residual", "kept")
+TRACK_STATE_KEYS = ("t", "next_id", "prev", "next", "prev_frame", "next_frame", "track_id", "age")
+TRACK_OUT_KEYS = ("track_id", "age", "n_new", "status")
+TRACK_COUNTER_OUT_OF_RANGE = 4       # status of track_step: the counter was outside 0 .. capacity - 1
+
+_track = None
+
+
+def track_build(force: bool = False) -> str:
+    """Compile libsslam_track.so for gfx950 in-tree, as build() compiles the first library."""
+    return _make_if_stale(CSRC_TRACK, TRACK_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_track.h", "sslam_hip.h")], force)
+
+
+def track():
+    """Load libsslam_track.so; raises if it has not been built (no silent fallback)."""
+    global _track
+    if _track is None:
+        _track = _load(TRACK_SO_PATH, CSRC_TRACK, "sslt", _track_prototypes)
+    return _track
+
+
+def _track_prototypes(L):
+    L.sslt_track_workspace_bytes.restype = C.c_size_t
+    p, i, d = C.c_void_p, C.c_int, C.c_double
+    L.sslt_track_workspace_bytes.argtypes = [i, i]
+    L.sslt_link_pairs.argtypes = [p, p, i, p, p, p, i, i, i, p, p, p, p, p]
+    L.sslt_track_ids.argtypes = [p, p, i, i] + [p] * 7 + [p]
+    L.sslt_landmarks.argtypes = [p, p, p, i, i] + [d] * 10 + [p] * 6 + [i] + [p] * 8 + [p]
+    L.sslt_track_step.argtypes = [p] * 12 + [i, i, i] + [p] * 4 + [p]
+
+
+def track_launch_count() -> int:
+    return int(track().sslt_launch_count())
+
+
+def check_track_sizes(what: str, n_bank, k, limit_k: bool = False) -> tuple:
+    """(n_bank 1 .., k 1 ..) as ints, else ValueError; n_bank * k past 2^31 - 1, or k past TRACK_MAX_K where the entry keeps a row
+    in LDS: SslamHipError - before any device work."""
+    nb, kk = check_int("n_bank", n_bank, 1), check_int("k", k, 1)
+    if nb * kk > TRACK_MAX_NODES or (limit_k and kk > TRACK_MAX_K):
+        raise SslamHipError(f"{what}: {_ERR[E_UNSUPPORTED]} (n_bank * k <= 2^31 - 1" + (f", k <= {TRACK_MAX_K}" if limit_k else "") +
+                            f"; got {nb}, {kk})")
+    return nb, kk
+
+
+def link_shapes(n_bank: int, k: int) -> dict:
+    """name -> (shape, dtype) of the outputs of link_pairs (LINK_KEYS)."""
+    return {"prev": ((n_bank, k), torch.int32), "next": ((n_bank, k), torch.int32), "prev_frame": ((n_bank,), torch.int32),
+            "next_frame": ((n_bank,), torch.int32)}
+
+
+def track_id_shapes(n_bank: int, k: int) -> dict:
+    """name -> (shape, dtype) of the outputs of track_ids (TRACK_ID_KEYS)."""
+    bank, rows = ((n_bank, k), torch.int32), ((n_bank * k,), torch.int32)
+    return {"track_id": bank, "age": bank, "n_tracks": ((1,), torch.int32), "root_frame": rows, "root_slot": rows, "length": rows}
+
+
+def landmark_shapes(n_bank: int, k: int) -> dict:
+    """name -> (shape, dtype) of the outputs of landmarks (LANDMARK_KEYS): per track (n_bank * k rows), then per keypoint."""
+    n = n_bank * k
+    return {"xyz": ((n, 3), torch.float64), "n_obs": ((n,), torch.int32), "n_kept": ((n,), torch.int32), "status": ((n,), torch.int32),
+            "weight_sum": ((n,), torch.float64), "rms": ((n,), torch.float64), "residual": ((n_bank, k), torch.float64),
+            "kept": ((n_bank, k), torch.int32)}
+
+
+def track_state_shapes(capacity: int, k: int) -> dict:
+    """name -> (shape, dtype) of the persistent state of track_step (TRACK_STATE_KEYS)."""
+    one, bank, frames = ((1,), torch.int32), ((capacity, k), torch.int32), ((capacity,), torch.int32)
+    return {"t": one, "next_id": one, "prev": bank, "next": bank, "prev_frame": frames, "next_frame": frames, "track_id": bank, "age": bank}
+
+
+def track_out_shapes(k: int) -> dict:
+    """name -> (shape, dtype) of the outputs of track_step (TRACK_OUT_KEYS)."""
+    return {"track_id": ((k,), torch.int32), "age": ((k,), torch.int32), "n_new": ((1,), torch.int32), "status": ((1,), torch.int32)}
+
+
+def track_workspace_bytes(n_bank: int, k: int) -> int:
+    """sslt_track_workspace_bytes, restated: 20 bytes per node and one word per scan tile.  Needs no library."""
+    n = n_bank * k
+    return 20 * n + 4 * (-(-n // TRACK_SCAN_TILE))
+
+
+def _dict_out(shapes, keys, out):
+    if out is None:
+        return None
+    if not isinstance(out, dict) or set(out) != set(keys):
+        raise ValueError(f"out must be a dict of the tensors {', '.join(keys)}")
+    return _outputs(shapes, keys, [out[key] for key in keys])
+
+
+def _link_row_operands(n_rows, matches, count, mask, k):
+    """One or many link rows: matches (n_rows, n1, 2) int64, count (n_rows,) int32, mask (n_rows, n1) int32 or None -> n1."""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[2] != 2 or int(matches.shape[0]) != n_rows or \
+            int(matches.shape[1]) < 1:
+        raise ValueError(f"matches must be a tensor of shape ({n_rows}, n1 >= 1, 2)")
+    n1 = int(matches.shape[1])
+    if count is None:
+        raise ValueError("count is required")
+    _check_arrays((n_rows, n1, 2), ("matches", matches, torch.int64))
+    _check_arrays((n_rows,), ("count", count, torch.int32))
+    _check_arrays((n_rows, n1), ("mask", mask, torch.int32))
+    return n1
+
+
+def link_pairs(first, second, matches, count, n_bank, k, mask=None, out=None) -> dict:
+    """sslt_link_pairs: first / second (P,) int32 device lists, matches (P, n1, 2) int64 and count (P,) int32 as match_pairs or
+    match_rank wrote them, mask (P, n1) int32 or None - where given only slots with mask == 1 count (pose_ransac_pairs' or
+    pose_refine_pairs' inlier_of_slot) - over a bank of n_bank frames of k slots.  Returns LINK_KEYS' tensors as a dict: prev, next
+    (n_bank, k), prev_frame, next_frame (n_bank,) int32, -1 meaning none, every element written (include/sslam_track.h: the
+    two-sided lowest-row and lowest-slot rules).  Five launches, no host read."""
+    n_pairs = check_pair_lists(first, second)
+    nb, kk = check_track_sizes("link_pairs", n_bank, k, limit_k=True)
+    n1 = _link_row_operands(n_pairs, matches, count, mask, kk)
+    shapes = link_shapes(nb, kk)
+    o = _dict_out(shapes, LINK_KEYS, out)
+    dev = common_device(first, second, matches, count, mask, *(o or ()))
+    o = _outputs(shapes, LINK_KEYS, None, dev) if o is None else o
+    _run("link_pairs", track().sslt_link_pairs, (first, second, matches, count, mask, *o), _dp(first), _dp(second), n_pairs, _dp(matches),
+         _dp(count), _dp(mask), n1, nb, kk, *(_dp(x) for x in o))
+    return dict(zip(LINK_KEYS, o))
+
+
+def track_ids(prev, prev_frame, out=None, workspace=None) -> dict:
+    """sslt_track_ids: prev (n_bank, k) and prev_frame (n_bank,) int32 of link_pairs (or of a track bank's state).  Returns
+    TRACK_ID_KEYS' tensors as a dict: track_id, age (n_bank, k), n_tracks (1,), root_frame, root_slot, length (n_bank * k,) int32 -
+    roots numbered in ascending (frame, slot) order, rows past n_tracks -1, -1, 0.  workspace: optional uint8 tensor of at least
+    track_workspace_bytes, 8-byte aligned.  5 + ceil(log2 n_bank) launches, no host read."""
+    if not isinstance(prev, torch.Tensor) or prev.dim() != 2:
+        raise ValueError("prev must be an int32 tensor of shape (n_bank, k)")
+    nb, kk = check_track_sizes("track_ids", int(prev.shape[0]), int(prev.shape[1]))
+    _check_arrays((nb, kk), ("prev", prev, torch.int32))
+    if prev_frame is None:
+        raise ValueError("prev_frame is required")
+    _check_arrays((nb,), ("prev_frame", prev_frame, torch.int32))
+    shapes = track_id_shapes(nb, kk)
+    o = _dict_out(shapes, TRACK_ID_KEYS, out)
+    need = track_workspace_bytes(nb, kk)
+    _check_workspace(workspace, need)
+    dev = common_device(prev, prev_frame, workspace, *(o or ()))
+    o = _outputs(shapes, TRACK_ID_KEYS, None, dev) if o is None else o
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    _run("track_ids", track().sslt_track_ids, (prev, prev_frame, ws, *o), _dp(prev), _dp(prev_frame), nb, kk, _dp(ws), *(_dp(x) for x in o))
+    return dict(zip(TRACK_ID_KEYS, o))
+
+
+def check_min_obs(min_obs) -> int:
+    """min_obs of landmarks as an int >= 2, else ValueError."""
+    return check_int("min_obs", min_obs, 2, 2 ** 31 - 1)
+
+
+def landmarks(kp_bank, kp_depth_bank, poses, camera, next_slot, next_frame, root_frame, root_slot, n_tracks, weight=None, scale_x=1.0, scale_y=1.0,
+              threshold=3.0, min_obs=2, out=None) -> dict:
+    """sslt_landmarks: kp_bank (n_bank, k, 2) fp32 and kp_depth_bank (n_bank, k) int32 as pose_refine_pairs takes them; poses (n_bank, 12)
+    or (n_bank, 3, 4) float64, world -> camera [R | t] of every frame (a graph's C); next_slot, next_frame: `next` and `next_frame` of link_pairs; root_frame,
+    root_slot, n_tracks of track_ids; weight (n_bank, k) fp32 or None (1 for every keypoint) - extract()'s `confidence` as it is.
+    Returns LANDMARK_KEYS' tensors as a dict: per track (n_bank * k rows) xyz (3), n_obs, n_kept, status (0 refit over the kept, 1 the
+    first mean, 2 no observation, -1 past n_tracks), weight_sum, rms; per keypoint residual (-1: no observation) and kept
+    (include/sslam_track.h).  Two launches, no host read."""
+    _check_bank("kp_bank", kp_bank, ("K", 2))
+    nb, kk = check_track_sizes("landmarks", int(kp_bank.shape[0]), int(kp_bank.shape[1]))
+    for name, t in (("kp_depth_bank", kp_depth_bank), ("poses", poses), ("next_slot", next_slot), ("next_frame", next_frame), ("root_frame", root_frame),
+                    ("root_slot", root_slot), ("n_tracks", n_tracks)):
+        if t is None:
+            raise ValueError(f"{name} is required")
+    _check_arrays((nb, kk), ("kp_depth_bank", kp_depth_bank, torch.int32), ("next_slot", next_slot, torch.int32), ("weight", weight, torch.float32))
+    _check_arrays((nb,), ("next_frame", next_frame, torch.int32))
+    _check_arrays((nb * kk,), ("root_frame", root_frame, torch.int32), ("root_slot", root_slot, torch.int32))
+    _check_arrays((1,), ("n_tracks", n_tracks, torch.int32))
+    _check_pose_rows("poses", poses, nb, 12)
+    fx, fy, cx, cy, ds, vw, vh = check_camera(camera)
+    doubles = (fx, fy, cx, cy, ds, check_positive("scale_x", scale_x), check_positive("scale_y", scale_y), vw, vh, check_threshold(threshold))
+    mo = check_min_obs(min_obs)
+    shapes = landmark_shapes(nb, kk)
+    o = _dict_out(shapes, LANDMARK_KEYS, out)
+    ins = (kp_bank, kp_depth_bank, poses, next_slot, next_frame, root_frame, root_slot, n_tracks, weight)
+    dev = common_device(*ins, *(o or ()))
+    o = _outputs(shapes, LANDMARK_KEYS, None, dev) if o is None else o
+    _run("landmarks", track().sslt_landmarks, (*ins, *o), _dp(kp_bank), _dp(kp_depth_bank), _dp(poses), nb, kk, *(C.c_double(v) for v in doubles),
+         _dp(next_slot), _dp(next_frame), _dp(root_frame), _dp(root_slot), _dp(n_tracks), _dp(weight), mo, *(_dp(x) for x in o))
+    return dict(zip(LANDMARK_KEYS, o))
+
+
+def alloc_track_state(capacity, k, device="cuda") -> dict:
+    """A fresh state of track_step: t = 0, next_id = 0, everything else zero (nothing of it is read before it is written)."""
+    cap, kk = check_track_sizes("track_step", capacity, k, limit_k=True)
+    return {key: torch.zeros(shape, dtype=dt, device=device) for key, (shape, dt) in track_state_shapes(cap, kk).items()}
+
+
+def alloc_track_out(k, device="cuda") -> dict:
+    """The outputs of track_step: track_id and age -1, n_new and status zero."""
+    kk = check_int("k", k, 1, TRACK_MAX_K)
+    out = {key: torch.zeros(shape, dtype=dt, device=device) for key, (shape, dt) in track_out_shapes(kk).items()}
+    out["track_id"].fill_(-1), out["age"].fill_(-1)
+    return out
+
+
+def track_step(state, matches, count, first, mask=None, out=None) -> dict:
+    """sslt_track_step: one frame of a growing track bank (include/sslam_track.h).  state: alloc_track_state's dict, read and written;
+    matches (n1, 2) or (1, n1, 2) int64, count (1,) int32 and mask (n1,) or (1, n1) int32 or None: this step's link row, one row of
+    link_pairs' operands; first (1,) int32 DEVICE: the bank frame the row's first member names, -1 for none.  Returns TRACK_OUT_KEYS'
+    tensors as a dict (out: alloc_track_out's, or made here): this frame's track_id, age (k,), n_new, status (1,) - 4, ids and ages
+    -1 and the state untouched once the bank is full.  After n steps the state's rows equal link_pairs + track_ids over the rows
+    stepped so far, bit for bit.  One launch, no host value, no host read."""
+    _state_dict("state", state, TRACK_STATE_KEYS)
+    if state["prev"].dim() != 2:
+        raise ValueError("state `prev` (capacity, k) expected")
+    cap, kk = check_track_sizes("track_step", int(state["prev"].shape[0]), int(state["prev"].shape[1]), limit_k=True)
+    for key, (shape, dt) in track_state_shapes(cap, kk).items():
+        _check_arrays(shape, (f"state `{key}`", state[key], dt))
+    if isinstance(matches, torch.Tensor) and matches.dim() == 2:
+        matches = matches[None]
+    if isinstance(mask, torch.Tensor) and mask.dim() == 1:
+        mask = mask[None]
+    n1 = _link_row_operands(1, matches, count, mask, kk)
+    if first is None:
+        raise ValueError("first is required")
+    _check_arrays((1,), ("first", first, torch.int32))
+    shapes = track_out_shapes(kk)
+    o = _dict_out(shapes, TRACK_OUT_KEYS, out)
+    st = [state[key] for key in TRACK_STATE_KEYS]
+    dev = common_device(*st, matches, count, mask, first, *(o or ()))
+    o = _outputs(shapes, TRACK_OUT_KEYS, None, dev) if o is None else o
+    _run("track_step", track().sslt_track_step, (*st, matches, count, mask, first, *o), *(_dp(x) for x in st), _dp(matches), _dp(count),
+         _dp(mask), _dp(first), n1, kk, cap, *(_dp(x) for x in o))
+    return dict(zip(TRACK_OUT_KEYS, o))

@@ -415,14 +415,20 @@ def _graph_flat(g) -> list:
            [g["cost_in"].reshape(1), g["cost"].reshape(1), g["edge_chi2"]]
 
 
+def _graph_words(n: int, n_pairs: int) -> int:
+    """How many numbers _graph_flat lays out for a graph of n nodes over n_pairs listed pairs: C, the five integers, the two costs,
+    edge_chi2.  Whatever follows a graph in a read-back starts there: the one place that says so."""
+    return 12 * n + len(_GRAPH_INT) + 2 + n_pairs
+
+
 def _graph_host(rest, n, pairs, poses) -> dict:
-    """The host-side figures of a graph from the 12 n + 7 + len(pairs) numbers _graph_flat laid out."""
+    """The host-side figures of a graph from the _graph_words(n, len(pairs)) numbers _graph_flat laid out."""
     C = rest[:12 * n].reshape(n, 3, 4)
     C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
     graph = {"trajectory": np.stack([np.linalg.inv(c) for c in C44]), "pairs": pairs}
     graph.update({key: int(rest[12 * n + i]) for i, key in enumerate(_GRAPH_INT)})
     graph["cost_in"], graph["cost"] = float(rest[12 * n + 5]), float(rest[12 * n + 6])
-    graph["edge_chi2"] = rest[12 * n + 7:12 * n + 7 + len(pairs)].copy()
+    graph["edge_chi2"] = rest[12 * n + 7:_graph_words(n, len(pairs))].copy()
     if poses is not None:
         graph["ate"] = ate_summary(graph["trajectory"], np.asarray(poses, dtype=np.float64)[:n])
     return graph
@@ -441,22 +447,73 @@ def _spacings_and_graph(host, rest, lists, pairs, n, poses) -> dict:
     return out
 
 
+def check_tracks(tracks):
+    """tracks= of odometry_graph: None (no tracks: nothing is launched), True (the defaults) or a dictionary of some of threshold
+    (keypoint units, 3.0) and min_obs (>= 2, 2) -> None or the dictionary with both; anything else ValueError, before any device work."""
+    if tracks is None:
+        return None
+    if tracks is True:
+        tracks = {}
+    if not isinstance(tracks, dict) or any(key not in TRACK_DEFAULTS for key in tracks):
+        raise ValueError(f"tracks must be None, True or a dictionary of some of {', '.join(TRACK_DEFAULTS)}, got {tracks!r}")
+    opt = {**TRACK_DEFAULTS, **tracks}
+    return dict(threshold=lib.check_threshold(opt["threshold"]), min_obs=lib.check_min_obs(opt["min_obs"]))
+
+
+TRACK_DEFAULTS = dict(threshold=3.0, min_obs=2)
+_TRACK_ROWS = ("length", "status", "n_kept", "rms")
+
+
+def _tracks_device(pipe, kp, kp_depth, lists, matches, ref, C, n, camera, opt, confidence) -> list:
+    """Links from the spacing-1 rows masked by the refinement's inlier_of_slot, their ids, the landmarks under the graph's C ->
+    float64 pieces for the one read-back, in _tracks_host's order.  No host read."""
+    at = sum(len(lists[s]) for s in list(lists)[:list(lists).index(1)])
+    rows = slice(at, at + len(lists[1]))
+    links = pipe.link_matches([a for a, _ in lists[1]], [b for _, b in lists[1]], {key: matches[key][rows] for key in ("matches", "match_count")},
+                              mask=ref["inlier_of_slot"][rows], n_frames=n, k=int(kp.shape[1]))
+    tr = pipe.track_ids(links)
+    lm = pipe.landmarks(kp[:n], kp_depth[:n], C.reshape(n, 12), tr, camera, opt["threshold"], opt["min_obs"],
+                        weights=None if confidence is None else confidence[:n])
+    f64 = lambda t: t.to(torch.float64).reshape(-1)
+    return [f64(tr["n_tracks"]), f64(tr["track_id"]), f64(tr["length"]), f64(lm["status"]), f64(lm["n_kept"]), lm["rms"], lm["xyz"].reshape(-1)]
+
+
+def _tracks_host(rest, n, k) -> dict:
+    """The host-side figures of the tracks from the 1 + 8 n k numbers _tracks_device laid out."""
+    from .track_numpy import length_statistics
+    N = n * k
+    nt = int(rest[0])
+    track_id = rest[1:1 + N].astype(np.int32).reshape(n, k)
+    cols = {key: rest[1 + (i + 1) * N:1 + (i + 2) * N][:nt] for i, key in enumerate(_TRACK_ROWS)}
+    out = {"n_tracks": nt, "length": length_statistics(cols["length"].astype(np.int64), [nt]), "track_id": track_id,
+           "landmarks": rest[1 + 5 * N:1 + 8 * N].reshape(N, 3)[:nt].copy(), "status": cols["status"].astype(np.int32),
+           "n_kept": cols["n_kept"].astype(np.int32), "rms": cols["rms"].copy()}
+    del out["length"]["n_tracks"]
+    return out
+
+
 def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
-           graph_iterations, weight=None) -> dict:
+           graph_iterations, weight=None, tracks=None, confidence=None) -> dict:
     """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back.  weight: the
-    (P, n1) weights of the weighted refinement, whose info the graph then reads as it reads the unweighted one."""
+    (P, n1) weights of the weighted refinement, whose info the graph then reads as it reads the unweighted one.  tracks:
+    check_tracks' dictionary - the links, ids and landmarks (weighted by `confidence` where given) join the same read-back."""
     pairs = [pr for s in lists for pr in lists[s]]
     packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations, weight)
     g = _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations)
-    flat = torch.cat([packed.reshape(-1)] + _graph_flat(g)).cpu().numpy()          # the ONE read-back
+    more = [] if tracks is None else _tracks_device(pipe, kp, kp_depth, lists, matches, ref, g["C"], n, camera, tracks, confidence)
+    flat = torch.cat([packed.reshape(-1)] + _graph_flat(g) + more).cpu().numpy()          # the ONE read-back
     P, w = len(pairs), int(packed.shape[1])
     host, rest = flat[:P * w].reshape(P, w), flat[P * w:]
-    return _spacings_and_graph(host, rest, lists, pairs, n, poses)
+    out = _spacings_and_graph(host, rest, lists, pairs, n, poses)
+    if tracks is not None:
+        out["tracks"] = _tracks_host(rest[_graph_words(n, P):], n, int(kp.shape[1]))
+    return out
 
 
 def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, spacings=GRAPH_SPACINGS, num_pairs=None, rule=None,
                    threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, tokens=None, huber=None, iterations: int = 5, *,
-                   subcell=None, band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8, weights=None) -> dict:
+                   subcell=None, band=None, huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 8, weights=None,
+                   tracks=None) -> dict:
     """odometry(refine=True) at every spacing of `spacings` at once, and the pose graph over all of their edges
     (SequencePipeline.optimize_pose_graph; csrc_graph/pose_graph.hip): the frames are extracted once, the pairs of all spacings
     matched in one match_pairs call, ONE RANSAC and ONE refinement launch run over the concatenated pair list, the refined
@@ -470,14 +527,23 @@ def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, sp
     pair); with poses also 'ate' (ate_summary of the graph's trajectory) and 'ate_chain' (that of the spacing-1 chain)}}.
     weights: as odometry() takes it - ONE match_weights launch over the concatenated pair list, the weighted refinement, every
     spacing's 'refine' with 'weight_sum'; the graph reads the weighted information matrices with no change of its own.
+    tracks: None, True or a dictionary of some of threshold (keypoint units, 3.0) and min_obs (2) - feature tracks and the landmark
+    map (include/sslam_track.h): the spacing-1 match lists, masked by the refinement's inlier_of_slot, become links
+    (SequencePipeline.link_matches), the links tracks (track_ids), the tracks map points under the graph's poses (landmarks; with
+    weights= given the keypoint confidences weight the observations), all added to the SAME single read-back.  'tracks' then holds
+    'n_tracks', 'length' (mean, median, max, share_ge_2, histogram), 'landmarks' (n_tracks, 3) world points, 'status', 'n_kept',
+    'rms' (n_tracks,) and 'track_id' (N, K).  With tracks=None the call returns and launches exactly what it did before.
     Nobody has measured this on real RGB-D data: no real sequence was at hand when this was written."""
-    lists, n, band, _, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
+    def more():
+        _check_weights(pipe, weights, True)
+        return check_tracks(tracks)
+    lists, n, band, opt, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
         pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber, iterations, subcell, band,
-        huber_chi, damping, graph_iterations, lambda: _check_weights(pipe, weights, True))
+        huber_chi, damping, graph_iterations, more)
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
     weight = None if weights is None else pipe.match_weights(ex["confidence"], [a for a, _ in pairs], [b for _, b in pairs], matches, weights)
     return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
-                  damping, graph_iterations, weight)
+                  damping, graph_iterations, weight, opt, None if weights is None or opt is None else ex["confidence"])
 
 
 def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=None, spacings=None, num_pairs=None, threshold: float = 3.0,
@@ -523,7 +589,7 @@ def _sparse_flat(r) -> list:
 
 def _sparse_host(rest, n, pairs, poses) -> dict:
     graph = _graph_host(rest, n, pairs, poses)
-    at = 12 * n + 7 + len(pairs)
+    at = _graph_words(n, len(pairs))
     graph["cg_steps"] = rest[at:at + lib.SPARSE_MAX_ITER].astype(np.int64)
     return graph
 
@@ -553,8 +619,8 @@ def _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, thre
     w = int(packed.shape[1])
     host, rest = flat[:(P + L) * w].reshape(P + L, w), flat[(P + L) * w:]
     out = _spacings_and_graph(host, rest, lists, pairs, n, poses)
-    rest = rest[12 * n + 7 + P:]
-    tail = rest[len(runs) * (12 * n + 7 + P + L + lib.SPARSE_MAX_ITER):]
+    rest = rest[_graph_words(n, P):]
+    tail = rest[len(runs) * (_graph_words(n, P + L) + lib.SPARSE_MAX_ITER):]
     lf, ls = tail[:L].astype(np.int32), tail[L:2 * L].astype(np.int32)
     rows = host[P:]
     r = rows[:, 18:]
@@ -565,7 +631,7 @@ def _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, thre
     names = ["loop_graph"] if prune_chi is None else ["loop_graph_unpruned", "loop_graph"]
     for name in names:
         out[name] = _sparse_host(rest, n, all_pairs, poses)
-        rest = rest[12 * n + 7 + P + L + lib.SPARSE_MAX_ITER:]
+        rest = rest[_graph_words(n, P + L) + lib.SPARSE_MAX_ITER:]
     return out
 
 

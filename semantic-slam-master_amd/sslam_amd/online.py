@@ -625,3 +625,80 @@ class LoopWindowPoseFrameStepper(WindowPoseFrameStepper):
                    edge_chi2=flat[at + lib.SPARSE_MAX_ITER:at + lib.SPARSE_MAX_ITER + rows],
                    loop_edges=np.stack([first[frame, S + slot], frame], axis=1).astype(np.int64))
         return out
+
+
+class TrackWindowPoseFrameStepper(WindowPoseFrameStepper):
+    """WindowPoseFrameStepper that also follows every keypoint through the sequence: feature tracks while the sequence runs, and a
+    landmark map on demand (include/sslam_track.h).  Opt-in: the parent, its signature and its bytes are left
+    alone.  Behind the parent's launches, on the same stream - as ordinary launches or inside the one captured graph -
+    sslt_track_step runs on the step's spacing-1 row: its match list, masked by that row's refined inlier_of_slot, links this frame's
+    keypoints to the previous frame's; a linked keypoint inherits its track id and its age plus one, the others open new tracks.  The
+    row's first frame is a device value made of the stepper's own counter, so no host value enters the body.  The frame's geometry
+    keypoints and depths are kept in a bank of `capacity` frames beside the track bank's state (a row more takes the frames past it).
+    spacings must hold 1.  step() returns the parent's dictionary plus track_id, track_age (K,), n_new and track_status (1,) - 4
+    once `capacity` frames are in the bank - as views of static buffers.  landmarks() runs outside the captured step."""
+
+    def __init__(self, pipe: SequencePipeline, height: int, width: int, depth_height: int, depth_width: int, camera=None,
+                 use_graph: bool = True, tokens_in: bool = False, rule=None, spacings=(1, 5, 10, 15, 20), window=None,
+                 threshold: float = 3.0, hypotheses: int = 256, seed: int = 0, huber=None, iterations: int = 5, min_inliers: int = 12,
+                 huber_chi: float = 4.0, damping: float = 0.0, graph_iterations: int = 2, capacity: int = 4096):
+        sp = _checked_spacings(spacings, below=2 ** 31)                  # everything is judged before anything is allocated
+        if 1 not in sp:
+            raise ValueError(f"spacings must hold 1: the tracks follow the previous frame's matches, got {spacings!r}")
+        lib.check_track_sizes("track_step", lib.check_int("capacity", capacity, 1), pipe.cfg.num_keypoints, limit_k=True)
+        self._row1 = sp.index(1)
+        super().__init__(pipe, height, width, depth_height, depth_width, camera=camera, use_graph=use_graph, tokens_in=tokens_in, rule=rule,
+                         spacings=sp, window=window, threshold=threshold, hypotheses=hypotheses, seed=seed, huber=huber, iterations=iterations,
+                         min_inliers=min_inliers, huber_chi=huber_chi, damping=damping, graph_iterations=graph_iterations, capacity=capacity)
+        dev, K, cap = self.device, self.cfg.num_keypoints, self.capacity
+        self.tracks = pipe.alloc_track_bank(cap, K)
+        self.track_kp = torch.zeros((cap + 1, K, 2), dtype=torch.float32, device=dev)          # row `cap`: the frames past the bank
+        self.track_depth = torch.full((cap + 1, K), -1, dtype=torch.int32, device=dev)
+        self._track_first64 = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self._track_first = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        self._track_row = torch.zeros((1,), dtype=torch.int64, device=dev)
+
+    def _after_match(self) -> None:
+        super()._after_match()
+        p, ring, r = self.pipe, self.ring, self._row1
+        torch.where(self._seen[r:r + 1], self._back[r:r + 1], self._absent[r:r + 1], out=self._track_first64)      # frame t - 1, or -1
+        self._track_first.copy_(self._track_first64)
+        p.track_step(self.tracks, self.m, self._track_first, mask=self.refined["inlier_of_slot"], row=r)
+        torch.clamp(self._t, max=self.capacity, out=self._track_row)
+        self.track_kp.index_copy_(0, self._track_row, p.geometry_keypoints(self.bank)[ring:ring + 1])
+        self.track_depth.index_copy_(0, self._track_row, self.kp_depth[ring:ring + 1])
+
+    def _reset_window(self) -> None:
+        super()._reset_window()
+        if getattr(self, "tracks", None) is not None:                    # both counters; nothing else of the state is read before it is written
+            self.tracks["state"]["t"].zero_()
+            self.tracks["state"]["next_id"].zero_()
+
+    @torch.no_grad()
+    def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
+        out = super().step(image_u8, depth_u16, tokens)
+        o = self.tracks["out"]
+        out.update(track_id=o["track_id"], track_age=o["age"], n_new=o["n_new"], track_status=o["status"])
+        return out
+
+    def landmarks(self, threshold: float = 3.0, min_obs: int = 2) -> dict:
+        """The tracks and the landmark map so far, any time between steps: sslt_track_ids over the stored links and sslt_landmarks
+        under trajectory()'s poses, n = min(frames stepped, capacity) frames.  Runs outside the captured step, makes ONE read-back and
+        changes no state.  Returns n_tracks, track_id, age (n, K), length, status, n_kept (n_tracks,), rms and landmarks (n_tracks, 3)
+        world points."""
+        import numpy as np
+        thr, mo = lib.check_threshold(threshold), lib.check_min_obs(min_obs)
+        n = min(self.n_frames, self.capacity)
+        if n < 1:
+            raise ValueError("landmarks needs at least one stepped frame")
+        st, K = self.tracks["state"], self.cfg.num_keypoints
+        tr = self.pipe.track_ids({key: st[key][:n] for key in lib.LINK_KEYS})
+        lm = self.pipe.landmarks(self.track_kp[:n], self.track_depth[:n], self.win["state"]["trajectory"][0, :n], tr, self.camera, thr, mo)
+        f64 = lambda t: t.to(torch.float64).reshape(-1)
+        flat = torch.cat([f64(tr["n_tracks"]), f64(tr["track_id"]), f64(tr["age"]), f64(tr["length"]), f64(lm["status"]), f64(lm["n_kept"]),
+                          lm["rms"], lm["xyz"].reshape(-1)]).cpu().numpy()      # the ONE read-back
+        N, nt = n * K, int(flat[0])
+        col = lambda i: flat[1 + i * N:1 + (i + 1) * N]
+        return dict(n_tracks=nt, track_id=col(0).astype(np.int32).reshape(n, K), age=col(1).astype(np.int32).reshape(n, K),
+                    length=col(2)[:nt].astype(np.int32), status=col(3)[:nt].astype(np.int32), n_kept=col(4)[:nt].astype(np.int32),
+                    rms=col(5)[:nt].copy(), landmarks=flat[1 + 6 * N:].reshape(N, 3)[:nt].copy())

@@ -1220,6 +1220,73 @@ class SequencePipeline:
         return lib.edge_log_step(log["state"], slot_first, refined["T"], refined["info"], refined["status"], refined["inlier_count"], n_odometry,
                                  min_inliers, loop_min_inliers, out=log["out"] if out is None else out)
 
+    @staticmethod
+    def _link_mask(mask):
+        """mask of link_matches() / track_step(): None, an int32 tensor, or the dictionary of estimate_poses() / refine_poses(),
+        whose inlier_of_slot is read."""
+        return mask["inlier_of_slot"] if isinstance(mask, dict) and "inlier_of_slot" in mask else mask
+
+    def link_matches(self, first, second, matches: dict, mask=None, n_frames: int | None = None, k: int | None = None,
+                     out: dict | None = None) -> dict:
+        """Match lists to links (sslt_link_pairs, include/sslam_track.h): first / second as match_pairs takes them, matches the
+        dictionary a matcher or rank_matches() returned for them, mask None or the inlier_of_slot (P, n1) int32 of estimate_poses()
+        or refine_poses() (or that dictionary): only slots with mask == 1 count.  n_frames: the frames of the bank, required; k: its
+        slots per frame, num_keypoints by default.  A row links iff first < second and it is the lowest row with that second and
+        with that first; a slot links iff it is the lowest valid slot naming its idx1 and its idx2.  Returns prev, next (n_frames, k),
+        prev_frame, next_frame (n_frames,) int32 device tensors, -1 meaning none.  Five launches, no host read."""
+        if n_frames is None:
+            raise ValueError("link_matches needs n_frames=, the number of frames of the bank")
+        first, second = _host_pair_list("first", first), _host_pair_list("second", second)
+        n_pairs = lib.check_pair_lists(first, second)
+        mt = _checked_match_lists(matches, n_pairs)
+        first, second = (x if x.is_cuda else x.to(mt.device) for x in (first, second))
+        return lib.link_pairs(first, second, mt, matches["match_count"], n_frames, self.cfg.num_keypoints if k is None else k,
+                              mask=self._link_mask(mask), out=out)
+
+    @staticmethod
+    def track_ids(links: dict, out: dict | None = None, workspace=None) -> dict:
+        """Links to tracks (sslt_track_ids): links is link_matches()' dictionary (prev and prev_frame are read) or a track bank's
+        state.  Returns the links and track_id, age (n_frames, k), n_tracks (1,), root_frame, root_slot, length (n_frames * k,) int32
+        in ONE dictionary - landmarks()' `tracks`: roots numbered in ascending (frame, slot) order, a keypoint without a link a
+        track of length 1.  5 + ceil(log2 n_frames) launches, no host read."""
+        if not isinstance(links, dict) or any(key not in links for key in lib.LINK_KEYS):
+            raise ValueError(f"links must be link_matches()' dictionary: {', '.join(lib.LINK_KEYS)}")
+        return {**{key: links[key] for key in lib.LINK_KEYS}, **lib.track_ids(links["prev"], links["prev_frame"], out=out, workspace=workspace)}
+
+    def landmarks(self, keypoints_pixel, kp_depth, C, tracks: dict, camera, threshold: float = 3.0, min_obs: int = 2, weights=None,
+                  out: dict | None = None) -> dict:
+        """Tracks to map points (sslt_landmarks): keypoints_pixel (N, K, 2), kp_depth (N, K) as the pose methods take them, C (N, 12)
+        float64 world -> camera poses - a graph's C -, tracks: track_ids()' dictionary, camera as estimate_poses takes it.  weights:
+        None (1 for every keypoint) or extract()'s `confidence` (N, K) float32 as it is.  Per track: the weighted mean of the
+        observations' world points, the observations within `threshold` (keypoint units) of its reprojection are kept, and with
+        min_obs of them the mean is taken again over those.  Returns lib.LANDMARK_KEYS' device tensors.  Two launches, no host read."""
+        if not isinstance(tracks, dict) or any(key not in tracks for key in ("next", "next_frame", "root_frame", "root_slot", "n_tracks")):
+            raise ValueError("tracks must be track_ids()' dictionary: next, next_frame, root_frame, root_slot and n_tracks are read")
+        sx, sy = self.depth_scales(camera)
+        return lib.landmarks(keypoints_pixel, kp_depth, C, camera, tracks["next"], tracks["next_frame"], tracks["root_frame"],
+                             tracks["root_slot"], tracks["n_tracks"], weights, sx, sy, threshold, min_obs, out=out)
+
+    def alloc_track_bank(self, capacity: int, k: int | None = None) -> dict:
+        """The buffers of track_step() for a track bank of up to `capacity` frames of k slots (num_keypoints by default): "state" -
+        lib.alloc_track_state's fresh state - and "out" - lib.alloc_track_out's outputs."""
+        kk = self.cfg.num_keypoints if k is None else k
+        return dict(state=lib.alloc_track_state(capacity, kk, self.device), out=lib.alloc_track_out(kk, self.device))
+
+    @staticmethod
+    def track_step(state: dict, matches_row: dict, first, mask=None, row: int = 0, out: dict | None = None) -> dict:
+        """One frame of the online tracks (sslt_track_step): row `row` of matches_row - a matcher's dictionary for this step's pairs -
+        is the link row (first, this frame); first: a (1,) int32 DEVICE tensor, the bank frame of the row's first member, -1 for
+        none (the first frame); mask as link_matches takes it.  Returns this frame's track_id, age (k,), n_new, status (1,) - `out`,
+        or the bank's own.  After n steps the bank's rows equal link_matches() + track_ids() over the rows stepped so far, bit for
+        bit.  One launch, no host value, no host read: the call can be captured."""
+        if not isinstance(state, dict) or any(key not in state for key in ("state", "out")):
+            raise ValueError("state must be alloc_track_bank()'s dictionary")
+        if not isinstance(matches_row, dict) or any(key not in matches_row for key in ("matches", "match_count")):
+            raise ValueError("matches_row must be a matcher's dictionary: matches and match_count are read")
+        mk = SequencePipeline._link_mask(mask)
+        return lib.track_step(state["state"], matches_row["matches"][row:row + 1], matches_row["match_count"][row:row + 1], first,
+                              mask=None if mk is None else mk[row:row + 1], out=state["out"] if out is None else out)
+
     def validation_stats(self, out: dict, images: torch.Tensor, spacing: int | None = None, first=None, second=None,
                          temperature: float = 0.1) -> dict:
         """The validation stage (csrc/validate.hip): the per-frame and per-pair statistics from which validation.compose puts

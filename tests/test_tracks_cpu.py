@@ -1,0 +1,502 @@
+"""CPU tests of feature tracks and the landmark map: the interface of the ninth library (include/sslam_track.h, the dynamic symbols
+of libsslam_track.so, sslam_amd.lib.TRACK_EXPORTS and tests/track_table.py hold the same entries), the restatement of
+sslam_amd/track_numpy.py against the method-by-method one of tests/track_ref.py and both against a brute-force definition, the
+online bank against the batch entries on every prefix, the planted fates of the landmark scene, the header's two invariants on the
+restatement, everything the C entries refuse before any device work with one past each size limit, the Python layers' refusals, the
+numpy drop-ins of evaluation.py, and the planted study.  No GPU."""
+import ctypes
+import inspect
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import track_cases as tc
+import track_ref as ref
+import track_table as tt
+from sslam_amd import track_numpy as tn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "sslam_track.h")
+E_INVALID, E_UNSUPPORTED = -1, -2
+LINK, IDS, LAND, STEP = "sslt_link_pairs", "sslt_track_ids", "sslt_landmarks", "sslt_track_step"
+P = [0x10000 * (i + 1) for i in range(24)]       # never dereferenced: every call below is refused before the launch
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def _same(a: dict, b: dict, what):
+    assert set(a) == set(b), what
+    for key in a:
+        x, y = np.asarray(a[key]), np.asarray(b[key])
+        assert x.dtype == y.dtype and x.shape == y.shape, (what, key, x.dtype, y.dtype, x.shape, y.shape)
+        assert np.array_equal(x.view(np.uint8) if x.dtype.kind == "f" else x, y.view(np.uint8) if y.dtype.kind == "f" else y), (what, key)
+
+
+def _tracks(c, mask=True):
+    return tn.build_tracks(c["first"], c["second"], c["matches"], c["count"], c["mask"] if mask and "mask" in c else None, c["n_bank"], c["K"])
+
+
+def _landmarks(s, tr, weight, threshold=3.0, min_obs=2):
+    return tn.landmarks(s["kp"], s["depth"], s["C"], tc.CAMERA, tr["next"], tr["next_frame"], tr["root_frame"], tr["root_slot"], tr["n_tracks"],
+                        weight, threshold, min_obs)
+
+
+# ------------------------------------------------------------------------------------------------------------- the interface
+def test_entries_are_declared_exported_and_listed():
+    from sslam_amd import lib
+    declared = re.findall(r"^(?:int|long long|size_t|const char \*)\s*(sslt_\w+)\s*\(", _header(), flags=re.M)
+    assert len(set(declared)) == len(declared) == 8
+    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    dyn = subprocess.run([nm, "-D", "--defined-only", lib.TRACK_SO_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
+    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslt_ entries leaves the library
+    assert set(lib.TRACK_EXPORTS) == set(declared) and len(set(lib.TRACK_EXPORTS)) == len(lib.TRACK_EXPORTS)
+    assert set(tt.ALIGN) | set(tt.HOST_ONLY) == set(declared) and not set(tt.ALIGN) & set(tt.HOST_ONLY) and set(tt.LIMITS) == set(tt.ALIGN)
+    others = lib.EXPORTS + lib.EXT_EXPORTS + lib.GRAPH_EXPORTS + lib.LOOP_EXPORTS + lib.WINDOW_EXPORTS + lib.PLACE_EXPORTS + lib.CONF_EXPORTS + \
+        lib.WEIGHT_EXPORTS
+    assert not set(lib.TRACK_EXPORTS) & set(others) and all(n.startswith("sslt_") for n in declared)
+    L = lib.track()
+    assert all(hasattr(L, name) for name in lib.TRACK_EXPORTS)
+    assert L.sslt_arch() == b"gfx950" and L.sslt_version() >= 100 and lib.track_launch_count() >= 0
+    consts = {k: int(v) for k, v in re.findall(r"#define (SSLT_\w+) (\d+)\s", open(HEADER).read())}
+    assert consts == dict(SSLT_MAX_K=tt.MAX_K, SSLT_SCAN_TILE=tt.SCAN_TILE)
+    assert (lib.TRACK_MAX_K, lib.TRACK_SCAN_TILE, lib.TRACK_MAX_NODES) == (tt.MAX_K, tt.SCAN_TILE, tt.MAX_NODES) == (tn.MAX_K, tn.SCAN_TILE, 2 ** 31 - 1)
+    assert lib.LINK_KEYS == tn.LINK_KEYS == ref.LINK_KEYS and lib.TRACK_ID_KEYS == tn.TRACK_KEYS and lib.LANDMARK_KEYS == tn.LANDMARK_KEYS
+    assert lib.TRACK_STATE_KEYS == tn.BANK_STATE_KEYS and lib.TRACK_OUT_KEYS == tn.BANK_OUT_KEYS
+    assert lib.TRACK_COUNTER_OUT_OF_RANGE == tn.COUNTER_OUT_OF_RANGE == lib.PLACE_COUNTER_OUT_OF_RANGE == 4
+    # the key lists are the tables' pointer arguments, in the header's order
+    assert list(lib.LINK_KEYS) == list(tt.ALIGN[LINK])[5:] and list(lib.TRACK_ID_KEYS) == list(tt.ALIGN[IDS])[3:]
+    assert list(lib.LANDMARK_KEYS) == list(tt.ALIGN[LAND])[9:] and list(lib.TRACK_STATE_KEYS) == list(tt.ALIGN[STEP])[:8]
+    assert ["out_" + k if k in ("track_id", "age") else k for k in lib.TRACK_OUT_KEYS] == list(tt.ALIGN[STEP])[12:]
+    for entry in tt.ALIGN:
+        pointers = len(tt.ALIGN[entry]) + 1                                      # and the stream
+        assert sum(a is ctypes.c_void_p for a in getattr(L, entry).argtypes) == pointers, entry
+    import __graft_entry__ as entry
+    assert entry.TRACK_LIBRARY == ("csrc_track", "track", "sslt_arch", "TRACK_EXPORTS") and "TRACK_LIBRARY" in inspect.getsource(entry.build)
+    assert inspect.getsource(entry.build).count('"csrc') == 6, "the ninth row is no literal row of build()"
+    assert sorted(f for f in os.listdir(lib.CSRC_TRACK) if not f.startswith(("_", "lib"))) == ["Makefile", "track.hip"]
+    for name in ("sslam_hip.h", "sslam_ext.h", "sslam_graph.h", "sslam_loop.h", "sslam_window.h", "sslam_place.h", "sslam_conf.h", "sslam_weight.h"):
+        assert "sslt_" not in open(os.path.join(ROOT, "include", name)).read(), name
+
+
+def test_the_header_states_both_tables_line_for_line():
+    elem = {"int32_t": 4, "float": 4, "double": 8, "int64_t": 8, "void": 8}     # the workspace holds (root, distance) pairs
+    for entry, row in tt.ALIGN.items():
+        m = re.search(r"\bint\s+" + entry + r"\s*\(([^;{]*?)\)\s*;", _header())
+        assert m, entry
+        args = [re.match(r"(.*?)(\w+)$", " ".join(a.split())).groups() for a in m.group(1).split(",")]
+        pointers = [(t.strip(), n) for t, n in args if "*" in t and n != "stream"]
+        assert [n for _, n in pointers] == list(row), entry
+        for t, n in pointers:
+            assert row[n] == elem[t.replace("const", "").replace("*", "").strip()], (entry, n)
+        assert all(n in row for n in tt.OPTIONAL[entry])
+    raw = open(HEADER).read()
+    for title, lines in (("ALIGNMENT, every entry", tt.header_lines()), ("SIZE LIMITS: the expressions", tt.limit_lines())):
+        start = raw.index(title)
+        stated = re.sub(r"\n \*\s+", " ", raw[start:raw.index("*/", start)]).strip()
+        for line in lines:
+            assert line + " " in stated + " ", f"include/sslam_track.h does not state: {line}"
+        assert len(re.findall(r"\bsslt_\w+: ", stated)) == len(tt.ALIGN)
+    joined = re.sub(r"\n \*\s+", " ", raw)
+    for text in ("0 <= first[p] < second[p] < n_bank", "the lowest valid row with that `second`", "the lowest valid row with that `first`",
+                 "the lowest valid slot of the row naming its idx1", "no sequential greedy pass", "a row (3, 5) bridges a dropped frame",
+                 "EVERY element written", "ascending (frame, slot) order", "ceil(log2 n_bank) rounds", "rows past n_tracks are -1, -1, 0",
+                 "g > 0 && g - g == 0", "Xw_j = (r0j * ex + r1j * ey) + r2j * ez", "L0_j = S0_j / W0", "sqrt(s) < threshold",
+                 "residual of an observation = sqrt(s) for s the SCORE of L - not of L0", "With weight NULL and with a bank of exactly 1.0f",
+                 "Scaling every weight by a power of two", "ONE THREAD PER TRACK", "the STATE IS UNTOUCHED", "no host value enters the step",
+                 "next_frame[a] == -1", "Every refusal comes before anything is launched and writes nothing", "integer atomicMin", "integer atomicAdd"):
+        assert text in joined, text
+    assert tt.workspace_bytes(613, 500) == tn.workspace_bytes(613, 500) == 20 * 306500 + 4 * 300
+    # the LDS arithmetic: two (links) and three (step) arrays of K words, under the 64 KB a workgroup can name statically
+    assert 3 * 4 * tt.MAX_K + 64 <= 64 * 1024
+    assert [tt.launches(IDS, n) for n in (1, 2, 3, 5, 9, 17, 33, 128, 205)] == [5, 6, 7, 8, 9, 10, 11, 12, 13]
+
+
+def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
+    from sslam_amd import lib
+    monkeypatch.setattr(lib, "_track", None)
+    monkeypatch.setattr(lib, "TRACK_SO_PATH", str(tmp_path / "libsslam_track.so"))
+    with pytest.raises(lib.SslamHipError, match="missing: run"):
+        lib.track()
+
+
+def test_track_build_rebuilds_only_a_stale_library(monkeypatch):
+    from sslam_amd import lib
+    calls = []
+    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
+    assert lib.track_build() == lib.TRACK_SO_PATH and calls == [], "an up-to-date library is left alone"
+    lib.track_build(force=True)
+    assert calls == [["make", "-C", lib.CSRC_TRACK, "-s", "-j4"]]
+    real = os.path.getmtime
+    for i, newer in enumerate(("track.hip", "sslam_track.h", "sslam_hip.h")):
+        monkeypatch.setattr(lib.os.path, "getmtime", lambda p, newer=newer: real(p) + (1e6 if p.endswith(os.sep + newer) else 0))
+        lib.track_build()
+        assert len(calls) == 2 + i
+
+
+# ------------------------------------------------------------------------------------------------- links and tracks, three ways
+@pytest.mark.parametrize("masked", [True, False])
+@pytest.mark.parametrize("name", tc.LINK_NAMES + (tc.ONE_TRACK,))
+def test_the_restatement_equals_the_method_and_the_brute_force_definition(name, masked):
+    c = tc.links(name)
+    mask = c["mask"] if masked else None
+    args = (c["first"], c["second"], c["matches"], c["count"], mask, c["n_bank"], c["K"])
+    a, b = tn.link_pairs(*args), ref.link_pairs(*args)
+    _same(a, b, f"{name}: links, vectorised against the five launches")
+    ia, ib = tn.track_ids(a["prev"], a["prev_frame"]), ref.track_ids(a["prev"], a["prev_frame"])
+    _same(ia, ib, f"{name}: ids, one pass against pointer jumping and the tiled scan")
+    if c["n_bank"] * c["K"] > 1100:                                 # the brute force is quadratic
+        return
+    links, track_id, age, lengths = ref.brute_force(*args)
+    assert ref.link_set(a) == links, name
+    n = int(ia["n_tracks"][0])
+    assert n == len(lengths) and np.array_equal(ia["track_id"], track_id) and np.array_equal(ia["age"], age)
+    assert np.array_equal(ia["length"][:n], lengths) and not ia["length"][n:].any()
+    assert (ia["root_frame"][n:] == -1).all() and (ia["root_slot"][n:] == -1).all()
+    # a root is its track's first member, and the roots ascend in (frame, slot)
+    rf, rs = ia["root_frame"][:n].astype(np.int64), ia["root_slot"][:n]
+    assert np.array_equal(ia["track_id"][rf, rs], np.arange(n)) and not ia["age"][rf, rs].any()
+    assert (np.diff(rf * c["K"] + rs) > 0).all()
+    for i in range(n):
+        mem = tn.members(i, a["next"], a["next_frame"], ia["root_frame"], ia["root_slot"])
+        assert len(mem) == ia["length"][i] and all(ia["track_id"][f, s] == i and ia["age"][f, s] == j for j, (f, s) in enumerate(mem))
+
+
+def test_contract_rows_of_the_link_rules():
+    c = tc.links("row_rules")
+    a = tn.link_pairs(c["first"], c["second"], c["matches"], c["count"], c["mask"], c["n_bank"], c["K"])
+    # (0,2) wins frame 2 over (1,2); (3,4) wins first 3 over (3,5); (5,99), (4,4), (6,2), (-1,3), (2,-1) are no rows; (5,6) links
+    # although (5,99) stands before it; (2,3) links: (-1,3) before it is not valid
+    assert a["prev_frame"].tolist() == [-1, -1, 0, 2, 3, -1, 5, 6] and a["next_frame"].tolist() == [2, -1, 3, 4, -1, 6, 7, -1]
+    assert (a["next"][1] == -1).all() and (a["prev"][5] == -1).all() and (a["prev"][0] == -1).all() and (a["next"][7] == -1).all()
+    for f in range(8):
+        assert ((a["next"][f] >= 0).any()) == (a["next_frame"][f] >= 0) or not (a["next"][f] >= 0).any()
+    # the slot rule is two-sided and not greedy: a slot that loses its idx1 to a lower slot does not free its idx2 for a higher one
+    m = np.array([[[0, 0], [0, 1], [2, 1], [3, 3], [4, 3], [4, 5]]], np.int64)
+    one = lambda mask, count=6: tn.link_pairs(np.array([0], np.int32), np.array([1], np.int32), m, np.array([count], np.int32), mask, 2, 6)
+    assert one(None)["next"][0].tolist() == [0, -1, -1, 3, -1, -1], "slots 1, 2, 4 and 5 all lose: 2 to slot 1, which itself lost"
+    assert one(np.array([[0, 1, 1, 1, 1, 1]], np.int32))["next"][0].tolist() == [1, -1, -1, 3, -1, -1], "masked out, slot 0 is no rival"
+    assert one(np.array([[-1, 1, 1, 0, 1, 1]], np.int32))["next"][0].tolist() == [1, -1, -1, -1, 3, -1]
+    assert one(None, 1)["next"][0].tolist() == [0, -1, -1, -1, -1, -1] and one(None, -5)["next"][0].tolist() == [-1] * 6
+    assert one(None, 99)["next"][0].tolist() == one(None)["next"][0].tolist()
+    # a bridged gap: frame 2 has no links, the tracks run 0 - 1 - 3 - 4 - 5
+    b = _tracks(tc.links("bridged_gap"))
+    assert b["prev_frame"].tolist() == [-1, 0, -1, 1, 3, 4] and b["next_frame"].tolist() == [1, 3, -1, 4, 5, -1]
+    assert (b["age"][2] == 0).all() and (b["prev"][2] == -1).all() and (b["next"][2] == -1).all() and b["age"].max() >= 2
+    o = _tracks(tc.links(tc.ONE_TRACK))
+    assert o["length"].max() == 33 and (o["track_id"][:, 3] == o["track_id"][0, 3]).all() and o["age"][:, 3].tolist() == list(range(33))
+    assert int(o["n_tracks"][0]) == 33 * 8 - 32 - 32, "slots (5 -> 6) link too: 32 more links"
+
+
+@pytest.mark.parametrize("name", ["n5_k70", "n17_k8", "bridged_gap", "row_rules", tc.ONE_TRACK])
+def test_the_online_bank_equals_the_batch_entries_on_every_prefix(name):
+    c = tc.links(name)
+    k, n_bank = c["K"], c["n_bank"]
+    steps = tc.steps_of(name)
+    if name == "row_rules":                                         # frames 4 and 5 both name frame 3 first: only the earlier step links
+        steps[5] = (3, 3)
+    bank = tn.TrackBank(n_bank, k)
+    rows = []
+    for t, (a, p) in enumerate(steps):
+        p_ = 0 if p is None else p
+        out = bank.step(c["matches"][p_], c["count"][p_], c["mask"][p_], a)
+        rows.append((a, t, p_))
+        first, second = np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.int32)
+        idx = [r[2] for r in rows]
+        want = tn.build_tracks(first, second, c["matches"][idx], c["count"][idx], c["mask"][idx], t + 1, k)
+        got = bank.tracks()
+        for key in tn.LINK_KEYS + ("track_id", "age"):
+            assert np.array_equal(got[key], want[key]) and got[key].dtype == want[key].dtype, (name, t, key)
+        assert bank.state["t"].tolist() == [t + 1] and bank.state["next_id"].tolist() == want["n_tracks"].tolist()
+        assert np.array_equal(out["track_id"], want["track_id"][t]) and np.array_equal(out["age"], want["age"][t]) and out["status"].tolist() == [0]
+        assert out["n_new"][0] == (want["age"][t] == 0).sum()
+        again = tn.track_ids(bank.state["prev"][:t + 1], bank.state["prev_frame"][:t + 1])       # the stored links reproduce the stored ids
+        assert np.array_equal(again["track_id"], got["track_id"]) and np.array_equal(again["age"], got["age"])
+    before = {key: v.copy() for key, v in bank.state.items()}
+    for _ in range(2):                                              # two steps past capacity
+        out = bank.step(c["matches"][0], c["count"][0], c["mask"][0], 0)
+        assert out["status"].tolist() == [4] and out["n_new"].tolist() == [0] and (out["track_id"] == -1).all() and (out["age"] == -1).all()
+    _same(before, bank.state, f"{name}: the state after two steps past capacity")
+
+
+# ------------------------------------------------------------------------------------------------------------------ landmarks
+def test_planted_fates_of_the_landmark_scene():
+    s = tc.scene()
+    tr = _tracks(s)
+    at = lambda j: int(tr["track_id"][0, s["perm"][0, j]])
+    pl = s["planted"]
+    for min_obs in (2, 3):
+        lm = _landmarks(s, tr, s["weight"], 3.0, min_obs)
+        n = int(tr["n_tracks"][0])
+        row = lambda j: (int(lm["n_obs"][at(j)]), int(lm["n_kept"][at(j)]), int(lm["status"][at(j)]))
+        assert row(pl["clean"]) == (6, 6, 0)                        # 7 members; the last frame's C row is not finite
+        assert row(pl["no_obs"]) == (0, 0, 2) and not lm["xyz"][at(pl["no_obs"])].any()
+        assert row(pl["one_obs"]) == (1, 1, 1)
+        assert row(pl["two_obs"]) == (2, 2, 0 if min_obs == 2 else 1), "min_obs kept and min_obs - 1 kept"
+        assert row(pl["none_kept"]) == (6, 0, 1) and lm["rms"][at(pl["none_kept"])] == 0 and lm["weight_sum"][at(pl["none_kept"])] == 0
+        assert row(pl["weights"])[0] == 2, "zero, NaN, infinite and negative weights observe nothing; the subnormal one does"
+        assert row(pl["one_outlier"]) == (6, 5, 0)
+        assert (lm["status"][n:] == -1).all() and not lm["xyz"][n:].any() and not lm["n_obs"][n:].any()
+        # residual -1 exactly where no observation; kept only on observations; every member of the bad frame unobserved
+        assert ((lm["residual"] == -1) == ~(lm["residual"] >= 0)).all() and not lm["kept"][lm["residual"] < 0].any()
+        assert (lm["residual"][pl["bad_frame"]] == -1).all() and (lm["residual"][s["depth"] <= 0] == -1).all()
+        assert lm["n_obs"].sum() == (lm["residual"] >= 0).sum() and lm["n_kept"].sum() == lm["kept"].sum()
+        f, j = 3, pl["one_outlier"]
+        assert lm["kept"][f, s["perm"][f, j]] == 0 and lm["residual"][f, s["perm"][f, j]] > 10
+        # the refit moved the point: residuals are those of L, and L is nearer the planted point than L0 would be
+        assert np.abs(lm["xyz"][at(j)] - s["Pw"][j]).max() < 1e-3
+        px, nk, st = ref.plain_landmarks(s["kp"], s["depth"], s["C"], tc.CAMERA, tr, s["weight"], 3.0, min_obs)
+        assert np.array_equal(nk, lm["n_kept"][:n]) and np.array_equal(st, lm["status"][:n])
+        assert np.abs(px - lm["xyz"][:n]).max() < 1e-12, "an independent evaluation: matrix products and np.sum"
+    b = tc.behind_scene()
+    lm = _landmarks(b, _tracks(b), b["weight"])
+    assert lm["kept"].tolist() == [[1, 0], [0, 0]] and np.isposinf(lm["residual"][1, 0]) and lm["status"][:2].tolist() == [1, 2]
+    assert lm["weight_sum"][0] == 1000.0 and np.isfinite(lm["rms"][0])
+
+
+def test_the_two_invariants_of_the_header_hold_on_the_restatement():
+    s = tc.scene()
+    tr = _tracks(s)
+    _same(_landmarks(s, tr, None), _landmarks(s, tr, np.ones_like(s["weight"])), "weight NULL against a bank of exactly 1.0f")
+    base = _landmarks(s, tr, s["weight"])
+    for scale in (2.0 ** -20, 2.0 ** 30):
+        w = (s["weight"] * np.float32(scale)).astype(np.float32)
+        w[np.abs(s["weight"]) < 1e-30] = s["weight"][np.abs(s["weight"]) < 1e-30]      # the subnormal one would underflow or change its bits' meaning
+        scaled = _landmarks(s, tr, w)
+        rows = np.ones(len(base["weight_sum"]), bool)
+        rows[int(tr["track_id"][0, s["perm"][0, s["planted"]["weights"]]])] = False     # the track that holds the subnormal weight
+        for key in tn.LANDMARK_KEYS:
+            if key == "weight_sum":
+                assert np.array_equal(scaled[key][rows], base[key][rows] * scale), (scale, key)
+            elif base[key].shape[0] == len(rows) and base[key].ndim <= 2 and key not in ("residual", "kept"):
+                assert np.array_equal(scaled[key][rows].view(np.uint8), base[key][rows].view(np.uint8)), (scale, key)
+        sub = tr["track_id"] != np.flatnonzero(~rows)[0]
+        assert np.array_equal(scaled["residual"][sub], base["residual"][sub]) and np.array_equal(scaled["kept"], base["kept"])
+
+
+# ------------------------------------------------------------------------------------------------------------------- refusals
+def _call(entry, **over):
+    """One C entry with never-dereferenced pointers and valid scalars, `over` replacing arguments by name -> its return code."""
+    from sslam_amd import lib
+    L = lib.track()
+    p = iter(P)
+    ptr = lambda name: ctypes.c_void_p(over[name]) if name in over else ctypes.c_void_p(next(p))
+    d = lambda name, v: ctypes.c_double(over.get(name, v))
+    i = lambda name, v: over.get(name, v)
+    names = list(tt.ALIGN[entry])
+    if entry == LINK:
+        a = [ptr(n) for n in names]
+        args = a[:2] + [i("n_pairs", 3)] + a[2:5] + [i("n1", 8), i("n_bank", 5), i("K", 8)] + a[5:]
+    elif entry == IDS:
+        a = [ptr(n) for n in names]
+        args = a[:2] + [i("n_bank", 5), i("K", 8)] + a[2:]
+    elif entry == LAND:
+        a = [ptr(n) for n in names]
+        cam = [d("fx", 525.0), d("fy", 525.0), d("cx", 319.5), d("cy", 239.5), d("depth_scale", 5000.0), d("scale_x", 1.0), d("scale_y", 1.0),
+               d("view_w", 640.0), d("view_h", 480.0), d("threshold", 3.0)]
+        args = a[:3] + [i("n_bank", 5), i("K", 8)] + cam + a[3:9] + [i("min_obs", 2)] + a[9:]
+    else:
+        a = [ptr(n) for n in names]
+        args = a[:12] + [i("n1", 8), i("K", 8), i("capacity", 5)] + a[12:]
+    before = lib.track_launch_count()
+    rc = getattr(L, entry)(*args, ctypes.c_void_p(0))
+    assert lib.track_launch_count() == before, f"{entry}: a refusal launched something"
+    return rc
+
+
+@pytest.mark.parametrize("entry", list(tt.ALIGN))
+def test_every_entry_refuses_before_any_launch(entry):
+    for name, a in tt.ALIGN[entry].items():
+        if name not in tt.OPTIONAL[entry]:                          # a NULL mask or weight is accepted: that call is not made here
+            assert _call(entry, **{name: 0}) == E_INVALID, (entry, name, "NULL")
+    for name, a in tt.ALIGN[entry].items():
+        assert _call(entry, **{name: 0x10000 * 30 + a // 2}) == E_INVALID, (entry, name, "misaligned")
+    sizes = {LINK: ("n_pairs", "n1", "n_bank", "K"), IDS: ("n_bank", "K"), LAND: ("n_bank", "K"), STEP: ("n1", "K", "capacity")}[entry]
+    for name in sizes:
+        for v in (0, -1):
+            assert _call(entry, **{name: v}) == E_INVALID, (entry, name, v)
+    if entry == LAND:
+        for name in ("fx", "fy", "depth_scale", "scale_x", "scale_y", "view_w", "view_h"):
+            for v in (0.0, -1.0, float("nan"), float("inf")):
+                assert _call(entry, **{name: v}) == E_INVALID, (name, v)
+        for name in ("cx", "cy"):
+            for v in (float("nan"), float("inf")):
+                assert _call(entry, **{name: v}) == E_INVALID, (name, v)
+        for v in (-1.0, float("nan"), float("inf")):
+            assert _call(entry, threshold=v) == E_INVALID
+        for v in (1, 0, -3):
+            assert _call(entry, min_obs=v) == E_INVALID
+
+
+def test_one_past_each_size_limit_is_unsupported():
+    """The size-limit expressions at their boundaries by refusal alone: one past each is SSLAM_E_UNSUPPORTED; AT the limit the call
+    gets past the dispatch tests only on a device (tests/test_gpu_tracks.py), so here the workspace size speaks for it."""
+    from sslam_amd import lib
+    L = lib.track()
+    bank = "capacity"
+    for entry, other in ((LINK, "n_bank"), (IDS, "n_bank"), (LAND, "n_bank"), (STEP, bank)):
+        assert _call(entry, **{other: 2 ** 31 - 1, "K": 2}) == E_UNSUPPORTED, entry
+        assert _call(entry, **{other: 2 ** 28, "K": 8}) == E_UNSUPPORTED, entry           # 2^31 exactly: one past
+        assert _call(entry, **{other: 65536, "K": 32768}) == E_UNSUPPORTED, entry
+    for entry in (LINK, STEP):
+        assert _call(entry, K=tt.MAX_K + 1) == E_UNSUPPORTED, entry
+    assert _call(LINK, K=tt.MAX_K + 1, n_bank=-1) == E_INVALID, "an invalid size is invalid first"
+    assert L.sslt_track_workspace_bytes(2 ** 31 - 1, 1) == tt.workspace_bytes(2 ** 31 - 1, 1) == 20 * (2 ** 31 - 1) + 4 * 2 ** 21
+    assert L.sslt_track_workspace_bytes(2 ** 28, 8) == 0 and L.sslt_track_workspace_bytes(0, 8) == 0 and L.sslt_track_workspace_bytes(8, -1) == 0
+    assert L.sslt_track_workspace_bytes(1, 1) == 24 and L.sslt_track_workspace_bytes(128, 8) == 20 * 1024 + 4
+    assert L.sslt_track_workspace_bytes(205, 5) == 20 * 1025 + 8
+    for n_bank, k in ((613, 500), (1, 1), (33, 70)):
+        assert lib.track_workspace_bytes(n_bank, k) == L.sslt_track_workspace_bytes(n_bank, k) == tt.workspace_bytes(n_bank, k)
+
+
+def test_the_python_layers_refuse_before_any_device_work():
+    import torch
+    from sslam_amd import lib
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32)
+    m, cnt = torch.zeros((3, 8, 2), dtype=torch.int64), i32(3)
+    before = lib.track_launch_count()
+    with pytest.raises(ValueError, match="CUDA tensors only"):
+        lib.link_pairs(i32(3), i32(3), m, cnt, 5, 8)
+    with pytest.raises(ValueError, match="matches must be"):
+        lib.link_pairs(i32(3), i32(3), m[:2], cnt, 5, 8)
+    with pytest.raises(ValueError, match="mask must be"):
+        lib.link_pairs(i32(3), i32(3), m, cnt, 5, 8, mask=i32(3, 7))
+    with pytest.raises(ValueError, match="count is required"):
+        lib.link_pairs(i32(3), i32(3), m, None, 5, 8)
+    with pytest.raises(lib.SslamHipError, match="unsupported shape"):
+        lib.link_pairs(i32(3), i32(3), m, cnt, 5, tt.MAX_K + 1)
+    with pytest.raises(lib.SslamHipError, match="unsupported shape"):
+        lib.check_track_sizes("track_ids", 2 ** 28, 8)
+    assert lib.check_track_sizes("track_ids", 2 ** 31 - 1, 1) == (2 ** 31 - 1, 1) and lib.check_track_sizes("x", 4, 8192) == (4, 8192)
+    with pytest.raises(ValueError, match="n_bank"):
+        lib.check_track_sizes("track_ids", 0, 8)
+    with pytest.raises(ValueError, match="prev_frame"):
+        lib.track_ids(i32(5, 8), i32(4))
+    with pytest.raises(ValueError, match="CUDA tensors only"):
+        lib.track_ids(i32(5, 8), i32(5))
+    kp, C = torch.zeros((5, 8, 2)), torch.zeros((5, 12), dtype=torch.float64)
+    land = lambda **kw: lib.landmarks(kp, i32(5, 8), kw.pop("C", C), kw.pop("camera", tc.CAMERA), i32(5, 8), i32(5), i32(40), i32(40), i32(1), **kw)
+    with pytest.raises(ValueError, match="min_obs"):
+        land(min_obs=1)
+    with pytest.raises(ValueError, match="threshold"):
+        land(threshold=float("nan"))
+    with pytest.raises(ValueError, match="weight must be"):
+        land(weight=torch.zeros((5, 8), dtype=torch.float64))
+    with pytest.raises(ValueError, match="poses must be"):
+        land(C=torch.zeros((4, 12), dtype=torch.float64))
+    with pytest.raises(ValueError, match="camera"):
+        land(camera=object())
+    with pytest.raises(ValueError, match="CUDA tensors only"):
+        land()
+    st = lib.alloc_track_state(4, 8, device="cpu")
+    assert set(st) == set(lib.TRACK_STATE_KEYS) and all(not v.any() for v in st.values())
+    out = lib.alloc_track_out(8, device="cpu")
+    assert (out["track_id"] == -1).all() and (out["age"] == -1).all() and out["n_new"].tolist() == [0]
+    with pytest.raises(ValueError, match="state must be a dict"):
+        lib.track_step({k: v for k, v in st.items() if k != "age"}, m[0], cnt[:1], i32(1))
+    with pytest.raises(ValueError, match="first"):
+        lib.track_step(st, m[0], cnt[:1], i32(2))
+    with pytest.raises(ValueError, match="CUDA tensors only"):
+        lib.track_step(st, m[0], cnt[:1], i32(1), mask=i32(8))
+    with pytest.raises(lib.SslamHipError, match="unsupported shape"):
+        lib.alloc_track_state(4, tt.MAX_K + 1, device="cpu")
+    assert lib.track_launch_count() == before
+    from sslam_amd.pipeline import SequencePipeline
+    for name in ("link_matches", "track_ids", "landmarks", "alloc_track_bank", "track_step"):
+        assert callable(getattr(SequencePipeline, name)), name
+    with pytest.raises(ValueError, match="links must be"):
+        SequencePipeline.track_ids({"prev": i32(5, 8)})
+    with pytest.raises(ValueError, match="alloc_track_bank"):
+        SequencePipeline.track_step({}, {}, i32(1))
+
+
+# ------------------------------------------------------------------------------------------------------------- the drop-ins
+def test_the_numpy_drop_ins_of_evaluation():
+    import evaluation as ev
+    c = tc.links("n5_k70")
+    tr = ev.build_tracks(c["first"], c["second"], c["matches"], c["count"], c["mask"], c["n_bank"], c["K"])
+    _same(tr, _tracks(c), "evaluation.build_tracks")
+    clean = tc.links("n5_k70", True)
+    assert ev.build_tracks(clean["first"], clean["second"], clean["matches"])["prev"].shape == (5, 70), "sizes from the lists themselves"
+    with pytest.raises(ValueError):
+        ev.build_tracks(c["first"], c["second"][:2], c["matches"])
+    with pytest.raises(ValueError):
+        ev.build_tracks(c["first"], c["second"], c["matches"], k=5000)
+    s = tc.scene()
+    tr = _tracks(s)
+    C44 = np.tile(np.eye(4), (s["n_bank"], 1, 1))
+    C44[:, :3] = s["C"].reshape(-1, 3, 4)
+    for C in (s["C"], s["C"].reshape(-1, 3, 4), C44):
+        _same(ev.track_landmarks(s["kp"], s["depth"], C, tr, weights=s["weight"]), _landmarks(s, tr, s["weight"]), "evaluation.track_landmarks")
+    with pytest.raises(ValueError):
+        ev.track_landmarks(s["kp"], s["depth"], s["C"], tr, min_obs=1)
+    bank = ev.TrackBank(capacity=5, k=70)
+    for t, (a, p) in enumerate(tc.steps_of("n5_k70")):
+        p = 0 if p is None else p
+        out = bank.step(c["matches"][p], first=a, count=c["count"][p], mask=c["mask"][p])
+        assert out["status"].tolist() == [0]
+    want = _tracks(c)
+    got = bank.tracks()
+    assert all(np.array_equal(got[key], want[key]) for key in got)
+    assert bank.step(c["matches"][0], first=0)["status"].tolist() == [4]
+    with pytest.raises(TypeError):
+        bank.step(c["matches"][0], 0)                               # keyword-only: track_numpy.TrackBank orders them otherwise
+    bank.reset()
+    assert bank.state["t"].tolist() == [0]
+    st = tn.length_statistics(want["length"], want["n_tracks"])
+    n = int(want["n_tracks"][0])
+    assert st["n_tracks"] == n and st["histogram"].sum() == n and (st["histogram"] * np.arange(len(st["histogram"]))).sum() == 5 * 70
+    assert st["max"] == want["length"].max() and 0 < st["share_ge_2"] < 1 and st["mean"] == pytest.approx(350 / n)
+    assert tn.length_statistics(np.zeros(4, np.int32), [0])["n_tracks"] == 0
+
+
+# ----------------------------------------------------------------------------------------------------------- the planted study
+def study(seed: int):
+    """One seed of the planted study on the RESTATEMENT: 12 frames x 150 points, per-keypoint noise of sigma 0.3 px (3 in 4) or 3 px,
+    confidence = 1 / (1 + sigma), exact poses.  -> mean landmark error in mm over the tracks with status 0 in both runs, weighted and
+    uniform, and the mean track length."""
+    s = tc.scene(seed, 12, 150, (0.3, 3.0), dirty=False)
+    tr = _tracks(s)
+    w, u = _landmarks(s, tr, s["weight"], 6.0), _landmarks(s, tr, None, 6.0)
+    n = int(tr["n_tracks"][0])
+    point = np.empty(n, np.int64)
+    for j in range(s["K"]):                                         # the planted point of every track: the one its root shows
+        for f in range(s["n_bank"]):
+            point[tr["track_id"][f, s["perm"][f, j]]] = j
+    both = (w["status"][:n] == 0) & (u["status"][:n] == 0)
+    err = lambda lm: float(np.linalg.norm(lm["xyz"][:n][both] - s["Pw"][point[both]], axis=1).mean() * 1e3)
+    return err(w), err(u), float(tr["length"][:n].mean()), int(both.sum())
+
+
+STUDY_SEEDS = 20
+STUDY_SHARE = 18        # the restatement is better in 20 of 20 seeds; the margin of two seeds
+
+
+def test_planted_study_exact_case_and_the_direction_of_the_weights():
+    """PLANTED data, not real data: the scene, the trajectory, the noise and the confidences are made up; what it shows is that the
+    arithmetic is right and which way a calibrated confidence moves the map.
+    Exact case: exact poses, keypoints exact in float32, depths exact multiples of the quantum -> the landmarks are the planted points
+    to float64 round-off: the bound is twice the error of a direct float64 evaluation (tests/track_ref.py::plain_landmarks).
+    Noisy case: the weighted mean error against the uniform one over 20 seeds; asserted is only the direction, in STUDY_SHARE seeds."""
+    e = tc.exact_scene()
+    tr = _tracks(e)
+    lm = _landmarks(e, tr, None)
+    ids = tr["track_id"][0, e["perm"][0]]
+    assert int(tr["n_tracks"][0]) == e["K"] and (tr["length"][:e["K"]] == e["n_bank"]).all() and (lm["n_kept"][ids] == e["n_bank"]).all()
+    direct = np.abs(ref.plain_landmarks(e["kp"], e["depth"], e["C"], tc.CAMERA, tr)[0][ids] - e["Pw"]).max()
+    err = np.abs(lm["xyz"][ids] - e["Pw"]).max()
+    print(f"exact case: restatement {err:.3e} m, direct float64 evaluation {direct:.3e} m, rms {lm['rms'][ids].max():.3e} px")
+    assert 0 < direct < 1e-15 and err <= 2 * direct
+    assert lm["rms"][ids].max() < 1e-10 and lm["residual"].max() < 1e-10
+    rows = [study(seed) for seed in range(STUDY_SEEDS)]
+    better = sum(w <= u for w, u, _, _ in rows)
+    w, u = np.mean([r[0] for r in rows]), np.mean([r[1] for r in rows])
+    print(f"planted study over {STUDY_SEEDS} seeds: weighted {w:.3f} mm, uniform {u:.3f} mm, weighted no worse in {better}; "
+          f"mean track length {np.mean([r[2] for r in rows]):.2f}, {np.mean([r[3] for r in rows]):.0f} tracks per seed")
+    assert better >= STUDY_SHARE
