@@ -1,4 +1,4 @@
-# The compiler, the target and the compile flags of the four libraries, stated once: the bit-for-bit contracts between them
+# The compiler, the target and the compile flags of every library, stated once: the bit-for-bit contracts between them
 # (-ffp-contract=off, the correctly rounded divide and sqrt) rest on every object being compiled alike.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950

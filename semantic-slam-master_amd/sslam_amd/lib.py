@@ -1,11 +1,17 @@
-"""ctypes binding of libsslam_hip.so (include/sslam_hip.h) and, at the end, of libsslam_ext.so (include/sslam_ext.h) for torch tensors.
+"""ctypes binding of the native libraries (include/*.h) for torch tensors.
+
+Each library has a section below: its export list, its constants, its prototypes function and its wrappers.  How the libraries are
+built and loaded is stated once, in the class Library and the table LIBRARIES at the end of this file: one row per library with
+its symbol prefix, source directory, header, export list, the prerequisites outside its directory and its prototypes function.
+lib(), ext(), ... , build(), ext_build(), ... and launch_count(), ext_launch_count(), ... are one-line definitions over that table.
 
 PyTorch is used for device memory and streams only: every wrapper passes raw device pointers and the current
-HIP stream to the C ABI.  There is NO fallback: if the library is missing or a call fails, an exception is raised.
+HIP stream to the C ABI.  There is NO fallback: if a library is missing or a call fails, an exception is raised.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 import subprocess
 
@@ -14,7 +20,6 @@ import torch
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(_PKG, "csrc")
-SO_PATH = os.path.join(CSRC, "libsslam_hip.so")
 
 OK, E_INVALID, E_UNSUPPORTED, E_LAUNCH = 0, -1, -2, -3
 _ERR = {E_INVALID: "invalid argument", E_UNSUPPORTED: "unsupported shape", E_LAUNCH: "kernel launch failed"}
@@ -54,11 +59,13 @@ class RefinerLayout(C.Structure):
 
 
 _INCLUDE = os.path.join(os.path.dirname(_PKG), "include")
+_MK = [os.path.join(CSRC, "flags.mk"), os.path.join(CSRC, "rules.mk")]      # every Makefile's rule depends on both
 
 
 def _make_if_stale(csrc, so_path, others, force):
-    """make -C csrc if so_path is missing or older than a .hip or .h of csrc or one of `others`, or if forced; -> so_path."""
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))] + others
+    """make -C csrc if so_path is missing or older than a .hip or .h of csrc, one of `others`, flags.mk or rules.mk, or if forced;
+    -> so_path."""
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))] + others + _MK
     stale = (not os.path.exists(so_path)) or any(os.path.getmtime(s) > os.path.getmtime(so_path) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", csrc, "-s", "-j4"])
@@ -78,12 +85,38 @@ def _load(so_path, csrc, prefix, prototypes):
     return L
 
 
-def build(force: bool = False) -> str:
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    return _make_if_stale(CSRC, SO_PATH, [os.path.join(_INCLUDE, "sslam_hip.h")], force)
+@dataclasses.dataclass
+class Library:
+    """A row of LIBRARIES (at the end of this file): one native library, its source directory and how it is built and loaded."""
+    name: str               # "lib", "ext", ...: the loader is the module function of that name
+    prefix: str             # of every exported symbol, without the underscore
+    directory: str          # the source directory, beside this package; its Makefile names the library OUT
+    so: str                 # the file name of the shared object, built into the source directory
+    header: str             # the public header, a file name under include/
+    exports: list
+    deps: tuple             # the prerequisites outside the directory, relative to it: the DEPS of its Makefile, the header among them
+    prototypes: object      # a function of the loaded library that sets restype and argtypes
+    handle: object = None   # the loaded library, once load() has run
 
+    def __post_init__(self):
+        self.csrc = os.path.join(_PKG, self.directory)
+        self.so_path = os.path.join(self.csrc, self.so)
+        self.header_path = os.path.join(_INCLUDE, self.header)
+        self.prerequisites = [os.path.normpath(os.path.join(self.csrc, d)) for d in self.deps]
 
-_lib = None
+    def build(self, force: bool = False) -> str:
+        """Compile the library for gfx950 in-tree if it is stale or forced (hipcc cross-compiles without a GPU); -> so_path."""
+        return _make_if_stale(self.csrc, self.so_path, self.prerequisites, force)
+
+    def load(self):
+        """The loaded library, with its prototypes set; raises if it has not been built (no silent fallback)."""
+        if self.handle is None:
+            self.handle = _load(self.so_path, self.csrc, self.prefix, self.prototypes)
+        return self.handle
+
+    def launch_count(self) -> int:
+        return int(getattr(self.load(), self.prefix + "_launch_count")())
+
 
 EXPORTS = [
     "sslam_version", "sslam_arch", "sslam_launch_count", "sslam_pack_conv3x3_host", "sslam_pack_linear_host",
@@ -110,14 +143,6 @@ EXPORTS = [
     "sslam_keypoint_depth", "sslam_pose_depth_nn_pairs", "sslam_match_score_known_pairs",
     "sslam_pose_ransac_pairs", "sslam_pose_refine_pairs",
 ]
-
-
-def lib():
-    """Load libsslam_hip.so; raises if it has not been built (no silent fallback)."""
-    global _lib
-    if _lib is None:
-        _lib = _load(SO_PATH, CSRC, "sslam", _prototypes)
-    return _lib
 
 
 def _prototypes(L):
@@ -275,10 +300,6 @@ def packed_refiner_width(packed, n_blocks: int) -> int:
     if _PACKED_WIDTH[key] is not None:
         return _PACKED_WIDTH[key]
     raise ValueError(f"a packed refiner buffer of {n} floats fits no supported output width {WIDTHS} at {n_blocks} blocks")
-
-
-def launch_count() -> int:
-    return int(lib().sslam_launch_count())
 
 
 def workspace_bytes(n_frames: int, G: int, K: int, n_pairs: int) -> int:
@@ -1440,36 +1461,15 @@ def vit_forward_f32(images_chw, weights: VitWeightsF32, workspace, out=None, att
 
 
 # ------------------------------------------------------------------------------------------ libsslam_ext.so (include/sslam_ext.h)
-# The second library: entries with the prefix sslx_, built from csrc_ext/ with csrc/flags.mk, loaded and refused like the first.
-CSRC_EXT = os.path.join(_PKG, "csrc_ext")
-EXT_SO_PATH = os.path.join(CSRC_EXT, "libsslam_ext.so")
+# Sub-cell keypoint localisation: entries with the prefix sslx_ (row "ext" of LIBRARIES).
 EXT_EXPORTS = ["sslx_version", "sslx_arch", "sslx_launch_count", "sslx_subcell_keypoints"]
 SUBCELL_MAX_CELLS, SUBCELL_MAX_K = 4096, 4096
 FLAG_X, FLAG_Y, FLAG_RANGE = 1, 2, 4           # bits of subcell_keypoints' flags
-
-_ext = None
-
-
-def ext_build(force: bool = False) -> str:
-    """Compile libsslam_ext.so for gfx950 in-tree, as build() compiles the first library."""
-    return _make_if_stale(CSRC_EXT, EXT_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_ext.h", "sslam_hip.h")], force)
-
-
-def ext():
-    """Load libsslam_ext.so; raises if it has not been built (no silent fallback)."""
-    global _ext
-    if _ext is None:
-        _ext = _load(EXT_SO_PATH, CSRC_EXT, "sslx", _ext_prototypes)
-    return _ext
 
 
 def _ext_prototypes(L):
     p, i = C.c_void_p, C.c_int
     L.sslx_subcell_keypoints.argtypes = [p, i, i, p, i, p, p, p, p]
-
-
-def ext_launch_count() -> int:
-    return int(ext().sslx_launch_count())
 
 
 def subcell_shapes(n: int, k: int) -> dict:
@@ -1513,30 +1513,13 @@ def subcell_keypoints(sal, idx, out=None):
 
 
 # ---------------------------------------------------------------------------------------- libsslam_graph.so (include/sslam_graph.h)
-# The third library: entries with the prefix sslg_, built from csrc_graph/ with csrc/flags.mk, loaded and refused like the others.
-CSRC_GRAPH = os.path.join(_PKG, "csrc_graph")
-GRAPH_SO_PATH = os.path.join(CSRC_GRAPH, "libsslam_graph.so")
+# The banded pose graph: entries with the prefix sslg_ (row "graph" of LIBRARIES).
 GRAPH_EXPORTS = ["sslg_version", "sslg_arch", "sslg_launch_count", "sslg_chain_poses", "sslg_pose_graph_workspace_bytes", "sslg_pose_graph"]
 GRAPH_MAX_BAND, GRAPH_MAX_NODES, GRAPH_MAX_EDGES, GRAPH_MAX_GRAPHS, GRAPH_MAX_ITER = 32, 4096, 1048576, 65535, 16
 GRAPH_MAX_CHAINS = 0x7fffffff // 256      # sslg_chain_poses runs a thread per chain, not a workgroup per graph: its own n_graphs limit
 POSE_GRAPH_KEYS = ("C", "status", "iterations", "used_edges", "skipped_edges", "failed_row", "cost_in", "cost", "edge_chi2")
 # status: a step was accepted / no step accepted / a failed pivot at the first step / not attempted
 GRAPH_OK, GRAPH_NO_STEP, GRAPH_SINGULAR, GRAPH_NOT_ATTEMPTED = 0, 1, 2, 3
-
-_graph = None
-
-
-def graph_build(force: bool = False) -> str:
-    """Compile libsslam_graph.so for gfx950 in-tree, as build() compiles the first library."""
-    return _make_if_stale(CSRC_GRAPH, GRAPH_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_graph.h", "sslam_hip.h")], force)
-
-
-def graph():
-    """Load libsslam_graph.so; raises if it has not been built (no silent fallback)."""
-    global _graph
-    if _graph is None:
-        _graph = _load(GRAPH_SO_PATH, CSRC_GRAPH, "sslg", _graph_prototypes)
-    return _graph
 
 
 def _graph_prototypes(L):
@@ -1545,10 +1528,6 @@ def _graph_prototypes(L):
     L.sslg_pose_graph_workspace_bytes.argtypes = [i, i, i]
     L.sslg_chain_poses.argtypes = [p, p, i, i, p, p]
     L.sslg_pose_graph.argtypes = [p, p, p, p, i, i, i, p, i, d, d, i] + [p] * 11
-
-
-def graph_launch_count() -> int:
-    return int(graph().sslg_launch_count())
 
 
 def check_band(band) -> int:
@@ -1688,31 +1667,13 @@ def pose_graph(first, second, T, info, C_in, band, huber_chi=4.0, damping=0.0, i
 
 
 # ------------------------------------------------------------------------------------------ libsslam_loop.so (include/sslam_loop.h)
-# The fourth library: entries with the prefix ssll_, built from csrc_loop/ with csrc/flags.mk, loaded and refused like the others.
-CSRC_LOOP = os.path.join(_PKG, "csrc_loop")
-LOOP_SO_PATH = os.path.join(CSRC_LOOP, "libsslam_loop.so")
+# Loop closures and the sparse pose graph: entries with the prefix ssll_ (row "loop" of LIBRARIES).
 LOOP_EXPORTS = ["ssll_version", "ssll_arch", "ssll_launch_count", "ssll_frame_signatures", "ssll_loop_candidates",
                 "ssll_pose_graph_sparse_workspace_bytes", "ssll_pose_graph_sparse"]
 LOOP_MAX_FRAMES, LOOP_MAX_K, LOOP_MAX_PER_FRAME = 4096, 4096, 8
 SPARSE_MAX_NODES, SPARSE_MAX_EDGES, SPARSE_MAX_GRAPHS, SPARSE_MAX_ITER, SPARSE_MAX_CG = 4096, 65536, 65535, 16, 4096
 LOOP_CANDIDATE_KEYS = ("first", "second", "sim", "count")
 POSE_GRAPH_SPARSE_KEYS = POSE_GRAPH_KEYS + ("cg_steps",)
-
-_loop = None
-
-
-def loop_build(force: bool = False) -> str:
-    """Compile libsslam_loop.so for gfx950 in-tree, as build() compiles the first library."""
-    shared = [os.path.join(CSRC_GRAPH, h) for h in ("edge_terms.h", "gauss_newton.h")]
-    return _make_if_stale(CSRC_LOOP, LOOP_SO_PATH, shared + [os.path.join(_INCLUDE, h) for h in ("sslam_loop.h", "sslam_graph.h", "sslam_hip.h")], force)
-
-
-def loop():
-    """Load libsslam_loop.so; raises if it has not been built (no silent fallback)."""
-    global _loop
-    if _loop is None:
-        _loop = _load(LOOP_SO_PATH, CSRC_LOOP, "ssll", _loop_prototypes)
-    return _loop
 
 
 def _loop_prototypes(L):
@@ -1722,10 +1683,6 @@ def _loop_prototypes(L):
     L.ssll_frame_signatures.argtypes = [p, p, i, i, i, p, p, p]
     L.ssll_loop_candidates.argtypes = [p, i, i, i, f, i, i, p, p, p, p, p]
     L.ssll_pose_graph_sparse.argtypes = [p, p, p, p, i, i, i, p, d, d, i, i, d] + [p] * 12
-
-
-def loop_launch_count() -> int:
-    return int(loop().ssll_launch_count())
 
 
 def check_int(name, v, lo, hi=None) -> int:
@@ -1836,9 +1793,7 @@ def pose_graph_sparse(first, second, T, info, C_in, huber_chi=4.0, damping=0.0, 
 
 
 # -------------------------------------------------------------------------------------- libsslam_window.so (include/sslam_window.h)
-# The fifth library: entries with the prefix sslw_, built from csrc_window/ with csrc/flags.mk, loaded and refused like the others.
-CSRC_WINDOW = os.path.join(_PKG, "csrc_window")
-WINDOW_SO_PATH = os.path.join(CSRC_WINDOW, "libsslam_window.so")
+# The sliding-window graph of the online stepper: entries with the prefix sslw_ (row "window" of LIBRARIES).
 WINDOW_EXPORTS = ["sslw_version", "sslw_arch", "sslw_launch_count", "sslw_window_workspace_bytes", "sslw_window_step"]
 WINDOW_MAX_WINDOW, WINDOW_MAX_SPACINGS, WINDOW_MAX_WINDOWS, WINDOW_MAX_FRAME = 32, 8, 65535, 2 ** 31 - 2
 WINDOW_STATE_KEYS = ("t", "ring_first", "ring_second", "ring_T", "ring_info", "ring_C", "trajectory")
@@ -1846,33 +1801,12 @@ WINDOW_OUT_KEYS = ("C_window", "base", "n_nodes", "admitted", "predicted_from", 
                    "failed_row", "cost_in", "cost", "edge_chi2")
 WINDOW_COUNTER_OUT_OF_RANGE = 4      # status, beside GRAPH_OK .. GRAPH_NOT_ATTEMPTED
 
-_window = None
-
-
-def window_build(force: bool = False) -> str:
-    """Compile libsslam_window.so for gfx950 in-tree, as build() compiles the first library."""
-    shared = [os.path.join(CSRC_GRAPH, h) for h in ("edge_terms.h", "gauss_newton.h", "edge_walk.h")]
-    return _make_if_stale(CSRC_WINDOW, WINDOW_SO_PATH, shared + [os.path.join(_INCLUDE, h) for h in ("sslam_window.h", "sslam_graph.h", "sslam_hip.h")],
-                          force)
-
-
-def window():
-    """Load libsslam_window.so; raises if it has not been built (no silent fallback)."""
-    global _window
-    if _window is None:
-        _window = _load(WINDOW_SO_PATH, CSRC_WINDOW, "sslw", _window_prototypes)
-    return _window
-
 
 def _window_prototypes(L):
     L.sslw_window_workspace_bytes.restype = C.c_size_t
     p, i, d, ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
     L.sslw_window_workspace_bytes.argtypes = [i, i, i]
     L.sslw_window_step.argtypes = [p] * 13 + [i, i, i, i, d, d, i, ll] + [p] * 16
-
-
-def window_launch_count() -> int:
-    return int(window().sslw_launch_count())
 
 
 def check_window_sizes(window, n_spacings, capacity, n_windows=1) -> tuple:
@@ -1963,9 +1897,7 @@ def window_step(state, spacings, new_T, new_info, new_status, new_inliers, C_sta
 
 
 # ---------------------------------------------------------------------------------------- libsslam_place.so (include/sslam_place.h)
-# The sixth library: entries with the prefix sslp_, built from csrc_place/ with csrc/flags.mk, loaded and refused like the others.
-CSRC_PLACE = os.path.join(_PKG, "csrc_place")
-PLACE_SO_PATH = os.path.join(CSRC_PLACE, "libsslam_place.so")
+# The growing place bank and the edge log of online loop closures: entries with the prefix sslp_ (row "place" of LIBRARIES).
 PLACE_EXPORTS = ["sslp_version", "sslp_arch", "sslp_launch_count", "sslp_place_workspace_bytes", "sslp_place_step", "sslp_edge_log_step"]
 PLACE_MAX_CAPACITY, PLACE_MAX_K, PLACE_MAX_PER_FRAME, PLACE_MAX_SLOTS = 4096, 4096, 8, 16
 PLACE_STATE_KEYS = ("t", "raw", "sum")
@@ -1974,21 +1906,6 @@ EDGE_LOG_STATE_KEYS = ("t", "log_first", "log_second", "log_T", "log_info")
 EDGE_LOG_OUT_KEYS = ("logged", "status")
 PLACE_COUNTER_OUT_OF_RANGE = 4       # status of both steps: the counter was outside 0 .. capacity - 1
 
-_place = None
-
-
-def place_build(force: bool = False) -> str:
-    """Compile libsslam_place.so for gfx950 in-tree, as build() compiles the first library."""
-    return _make_if_stale(CSRC_PLACE, PLACE_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_place.h", "sslam_hip.h")], force)
-
-
-def place():
-    """Load libsslam_place.so; raises if it has not been built (no silent fallback)."""
-    global _place
-    if _place is None:
-        _place = _load(PLACE_SO_PATH, CSRC_PLACE, "sslp", _place_prototypes)
-    return _place
-
 
 def _place_prototypes(L):
     L.sslp_place_workspace_bytes.restype = C.c_size_t
@@ -1996,10 +1913,6 @@ def _place_prototypes(L):
     L.sslp_place_workspace_bytes.argtypes = [i]
     L.sslp_place_step.argtypes = [p] * 5 + [i, i, i, i, f, i, i] + [p] * 8
     L.sslp_edge_log_step.argtypes = [p] * 10 + [i, i, i, i, ll] + [p] * 3
-
-
-def place_launch_count() -> int:
-    return int(place().sslp_launch_count())
 
 
 def check_place_sizes(capacity, k=1, d=D_OUT) -> tuple:
@@ -2144,36 +2057,18 @@ def edge_log_step(state, slot_first, new_T, new_info, new_status, new_inliers, n
 
 
 # ------------------------------------------------------------------------------------------ libsslam_conf.so (include/sslam_conf.h)
-# The seventh library: the keypoint confidence head, entries with the prefix sslc_, built from csrc_conf/ with csrc/flags.mk (and
-# csrc/common.h, csrc/gather_taps.h included from where they are), loaded and refused like the others.
-CSRC_CONF = os.path.join(_PKG, "csrc_conf")
-CONF_SO_PATH = os.path.join(CSRC_CONF, "libsslam_conf.so")
+# The keypoint confidence head: entries with the prefix sslc_ (row "conf" of LIBRARIES; csrc/common.h and csrc/gather_taps.h are
+# included from where they are).
 CONF_EXPORTS = ["sslc_version", "sslc_arch", "sslc_launch_count", "sslc_confidence_layout", "sslc_confidence_pack_host",
                 "sslc_confidence_rows", "sslc_gather_confidence", "sslc_confidence_filter", "sslc_take_rows"]
 CONF_DINO_DIM, CONF_HIDDEN_DIM, CONF_FILTER_MAX_K = 384, 128, 4096
 CONF_STATE_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias", "mlp.4.weight", "mlp.4.bias")
 CONF_FILTER_KEYS = ("slot", "count", "confidence")
 
-_conf = None
-
 
 class ConfidenceLayout(C.Structure):
     _fields_ = [("d", C.c_int), ("total", C.c_longlong), ("w1", C.c_longlong), ("b1", C.c_longlong), ("w2", C.c_longlong),
                 ("b2", C.c_longlong), ("w3", C.c_longlong), ("b3", C.c_longlong)]
-
-
-def conf_build(force: bool = False) -> str:
-    """Compile libsslam_conf.so for gfx950 in-tree, as build() compiles the first library."""
-    others = [os.path.join(_INCLUDE, h) for h in ("sslam_conf.h", "sslam_hip.h")] + [os.path.join(CSRC, h) for h in ("common.h", "gather_taps.h")]
-    return _make_if_stale(CSRC_CONF, CONF_SO_PATH, others, force)
-
-
-def conf():
-    """Load libsslam_conf.so; raises if it has not been built (no silent fallback)."""
-    global _conf
-    if _conf is None:
-        _conf = _load(CONF_SO_PATH, CSRC_CONF, "sslc", _conf_prototypes)
-    return _conf
 
 
 def _conf_prototypes(L):
@@ -2184,10 +2079,6 @@ def _conf_prototypes(L):
     L.sslc_gather_confidence.argtypes = [p, i, i, p, i, p, i, p, p, p]
     L.sslc_confidence_filter.argtypes = [p, i, i, f, p, p, p, p]
     L.sslc_take_rows.argtypes = [p, p, i, i, i, p, p]
-
-
-def conf_launch_count() -> int:
-    return int(conf().sslc_launch_count())
 
 
 def confidence_supported(dino_dim, descriptor_dim, hidden_dim) -> bool:
@@ -2334,41 +2225,17 @@ def take_rows(src, slot, out=None):
 
 
 # -------------------------------------------------------------------------------------- libsslam_weight.so (include/sslam_weight.h)
-# The eighth library: per-match weights from keypoint confidences and the pose refinement that takes them, entries with the prefix
-# sslu_, built from csrc_weight/ with csrc/flags.mk (csrc/common.h, csrc/pose_common.h and csrc/pose_refine_common.h included from
-# where they are: the weighted kernel is pose_refine_pairs' own body), loaded and refused like the others.
-CSRC_WEIGHT = os.path.join(_PKG, "csrc_weight")
-WEIGHT_SO_PATH = os.path.join(CSRC_WEIGHT, "libsslam_weight.so")
+# Per-match weights from keypoint confidences and the pose refinement that takes them: entries with the prefix sslu_ (row "weight"
+# of LIBRARIES; csrc/pose_refine_common.h is included from where it is: the weighted kernel is pose_refine_pairs' own body).
 WEIGHT_EXPORTS = ["sslu_version", "sslu_arch", "sslu_launch_count", "sslu_match_weights", "sslu_pose_refine_weighted_pairs"]
 WEIGHT_PRODUCT, WEIGHT_EXPECTED_ERROR = 0, 1      # SSLU_WEIGHT_PRODUCT, SSLU_WEIGHT_EXPECTED_ERROR
 POSE_REFINE_WEIGHTED_KEYS = POSE_REFINE_KEYS + ("weight_sum",)
-
-_weight = None
-
-
-def weight_build(force: bool = False) -> str:
-    """Compile libsslam_weight.so for gfx950 in-tree, as build() compiles the first library."""
-    others = [os.path.join(_INCLUDE, h) for h in ("sslam_weight.h", "sslam_hip.h")] + \
-        [os.path.join(CSRC, h) for h in ("common.h", "pose_common.h", "pose_refine_common.h")]
-    return _make_if_stale(CSRC_WEIGHT, WEIGHT_SO_PATH, others, force)
-
-
-def weight():
-    """Load libsslam_weight.so; raises if it has not been built (no silent fallback)."""
-    global _weight
-    if _weight is None:
-        _weight = _load(WEIGHT_SO_PATH, CSRC_WEIGHT, "sslu", _weight_prototypes)
-    return _weight
 
 
 def _weight_prototypes(L):
     p, i, d = C.c_void_p, C.c_int, C.c_double
     L.sslu_match_weights.argtypes = [p, i, i, p, p, i, p, p, i, i, d, p, p]
     L.sslu_pose_refine_weighted_pairs.argtypes = [p, p, i, i, p, p, i, p, p, i] + [d] * 10 + [p, d, i, p] + [p] * 13 + [p]
-
-
-def weight_launch_count() -> int:
-    return int(weight().sslu_launch_count())
 
 
 def check_weights(mode, sigma0=1.0) -> tuple:
@@ -2440,10 +2307,7 @@ def pose_refine_weighted(kp_bank, kp_depth_bank, first, second, matches, count, 
 
 
 # ---------------------------------------------------------------------------------------- libsslam_track.so (include/sslam_track.h)
-# The ninth library: feature tracks and a landmark map, entries with the prefix sslt_, built from csrc_track/ with csrc/flags.mk,
-# loaded and refused like the others.
-CSRC_TRACK = os.path.join(_PKG, "csrc_track")
-TRACK_SO_PATH = os.path.join(CSRC_TRACK, "libsslam_track.so")
+# Feature tracks and a landmark map: entries with the prefix sslt_ (row "track" of LIBRARIES).
 TRACK_EXPORTS = ["sslt_version", "sslt_arch", "sslt_launch_count", "sslt_link_pairs", "sslt_track_workspace_bytes", "sslt_track_ids",
                  "sslt_landmarks", "sslt_track_step"]
 TRACK_MAX_K, TRACK_SCAN_TILE, TRACK_MAX_NODES = 4096, 1024, 0x7fffffff      # SSLT_MAX_K, SSLT_SCAN_TILE, n_bank * K
@@ -2454,21 +2318,6 @@ TRACK_STATE_KEYS = ("t", "next_id", "prev", "next", "prev_frame", "next_frame", 
 TRACK_OUT_KEYS = ("track_id", "age", "n_new", "status")
 TRACK_COUNTER_OUT_OF_RANGE = 4       # status of track_step: the counter was outside 0 .. capacity - 1
 
-_track = None
-
-
-def track_build(force: bool = False) -> str:
-    """Compile libsslam_track.so for gfx950 in-tree, as build() compiles the first library."""
-    return _make_if_stale(CSRC_TRACK, TRACK_SO_PATH, [os.path.join(_INCLUDE, h) for h in ("sslam_track.h", "sslam_hip.h")], force)
-
-
-def track():
-    """Load libsslam_track.so; raises if it has not been built (no silent fallback)."""
-    global _track
-    if _track is None:
-        _track = _load(TRACK_SO_PATH, CSRC_TRACK, "sslt", _track_prototypes)
-    return _track
-
 
 def _track_prototypes(L):
     L.sslt_track_workspace_bytes.restype = C.c_size_t
@@ -2478,10 +2327,6 @@ def _track_prototypes(L):
     L.sslt_track_ids.argtypes = [p, p, i, i] + [p] * 7 + [p]
     L.sslt_landmarks.argtypes = [p, p, p, i, i] + [d] * 10 + [p] * 6 + [i] + [p] * 8 + [p]
     L.sslt_track_step.argtypes = [p] * 12 + [i, i, i] + [p] * 4 + [p]
-
-
-def track_launch_count() -> int:
-    return int(track().sslt_launch_count())
 
 
 def check_track_sizes(what: str, n_bank, k, limit_k: bool = False) -> tuple:
@@ -2674,3 +2519,58 @@ def track_step(state, matches, count, first, mask=None, out=None) -> dict:
     _run("track_step", track().sslt_track_step, (*st, matches, count, mask, first, *o), *(_dp(x) for x in st), _dp(matches), _dp(count),
          _dp(mask), _dp(first), n1, kk, cap, *(_dp(x) for x in o))
     return dict(zip(TRACK_OUT_KEYS, o))
+
+
+# ------------------------------------------------------------------------------------------------------ the native libraries
+# One row per library, in build order: name, prefix, directory, shared object, header, export list, DEPS of its Makefile, prototypes.
+_HIP_H, _GRAPH_H = "../../include/sslam_hip.h", "../../include/sslam_graph.h"
+LIBRARIES = {row.name: row for row in (
+    Library("lib", "sslam", "csrc", "libsslam_hip.so", "sslam_hip.h", EXPORTS, (_HIP_H,), _prototypes),
+    Library("ext", "sslx", "csrc_ext", "libsslam_ext.so", "sslam_ext.h", EXT_EXPORTS, ("../../include/sslam_ext.h", _HIP_H), _ext_prototypes),
+    Library("graph", "sslg", "csrc_graph", "libsslam_graph.so", "sslam_graph.h", GRAPH_EXPORTS, (_GRAPH_H, _HIP_H), _graph_prototypes),
+    Library("loop", "ssll", "csrc_loop", "libsslam_loop.so", "sslam_loop.h", LOOP_EXPORTS,
+            ("../csrc_graph/edge_terms.h", "../csrc_graph/gauss_newton.h", "../../include/sslam_loop.h", _GRAPH_H, _HIP_H), _loop_prototypes),
+    Library("window", "sslw", "csrc_window", "libsslam_window.so", "sslam_window.h", WINDOW_EXPORTS,
+            ("../csrc_graph/edge_terms.h", "../csrc_graph/gauss_newton.h", "../csrc_graph/edge_walk.h", "../../include/sslam_window.h", _GRAPH_H,
+             _HIP_H), _window_prototypes),
+    Library("place", "sslp", "csrc_place", "libsslam_place.so", "sslam_place.h", PLACE_EXPORTS, ("../../include/sslam_place.h", _HIP_H),
+            _place_prototypes),
+    Library("conf", "sslc", "csrc_conf", "libsslam_conf.so", "sslam_conf.h", CONF_EXPORTS,
+            ("../csrc/common.h", "../csrc/gather_taps.h", "../../include/sslam_conf.h", _HIP_H), _conf_prototypes),
+    Library("weight", "sslu", "csrc_weight", "libsslam_weight.so", "sslam_weight.h", WEIGHT_EXPORTS,
+            ("../csrc/common.h", "../csrc/pose_common.h", "../csrc/pose_refine_common.h", "../../include/sslam_weight.h", _HIP_H),
+            _weight_prototypes),
+    Library("track", "sslt", "csrc_track", "libsslam_track.so", "sslam_track.h", TRACK_EXPORTS, ("../../include/sslam_track.h", _HIP_H),
+            _track_prototypes),
+)}
+SO_PATH = LIBRARIES["lib"].so_path      # where the first library is built; to load another file, set LIBRARIES["lib"].so_path
+
+
+# The names the wrappers above and the rest of the tree call: the loader, the builder and the launch counter of each row.
+def lib(): return LIBRARIES["lib"].load()                                                               # noqa: E704
+def ext(): return LIBRARIES["ext"].load()                                                               # noqa: E704
+def graph(): return LIBRARIES["graph"].load()                                                           # noqa: E704
+def loop(): return LIBRARIES["loop"].load()                                                             # noqa: E704
+def window(): return LIBRARIES["window"].load()                                                         # noqa: E704
+def place(): return LIBRARIES["place"].load()                                                           # noqa: E704
+def conf(): return LIBRARIES["conf"].load()                                                             # noqa: E704
+def weight(): return LIBRARIES["weight"].load()                                                         # noqa: E704
+def track(): return LIBRARIES["track"].load()                                                           # noqa: E704
+def build(force: bool = False) -> str: return LIBRARIES["lib"].build(force)                             # noqa: E704
+def ext_build(force: bool = False) -> str: return LIBRARIES["ext"].build(force)                         # noqa: E704
+def graph_build(force: bool = False) -> str: return LIBRARIES["graph"].build(force)                     # noqa: E704
+def loop_build(force: bool = False) -> str: return LIBRARIES["loop"].build(force)                       # noqa: E704
+def window_build(force: bool = False) -> str: return LIBRARIES["window"].build(force)                   # noqa: E704
+def place_build(force: bool = False) -> str: return LIBRARIES["place"].build(force)                     # noqa: E704
+def conf_build(force: bool = False) -> str: return LIBRARIES["conf"].build(force)                       # noqa: E704
+def weight_build(force: bool = False) -> str: return LIBRARIES["weight"].build(force)                   # noqa: E704
+def track_build(force: bool = False) -> str: return LIBRARIES["track"].build(force)                     # noqa: E704
+def launch_count() -> int: return LIBRARIES["lib"].launch_count()                                       # noqa: E704
+def ext_launch_count() -> int: return LIBRARIES["ext"].launch_count()                                   # noqa: E704
+def graph_launch_count() -> int: return LIBRARIES["graph"].launch_count()                               # noqa: E704
+def loop_launch_count() -> int: return LIBRARIES["loop"].launch_count()                                 # noqa: E704
+def window_launch_count() -> int: return LIBRARIES["window"].launch_count()                             # noqa: E704
+def place_launch_count() -> int: return LIBRARIES["place"].launch_count()                               # noqa: E704
+def conf_launch_count() -> int: return LIBRARIES["conf"].launch_count()                                 # noqa: E704
+def weight_launch_count() -> int: return LIBRARIES["weight"].launch_count()                             # noqa: E704
+def track_launch_count() -> int: return LIBRARIES["track"].launch_count()                               # noqa: E704

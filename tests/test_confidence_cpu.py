@@ -1,13 +1,11 @@
 """CPU tests of the keypoint confidence head: the numpy restatement (tests/confidence_ref.py) against what the reference's own
 UncertaintyEstimator computed (tests/golden/confidence.npz, written by tests/golden/make_golden_confidence.py), the drop-in
-models.uncertainty_estimator - its surface and its eager path - against the same fixture, and the interface of the seventh
-library: include/sslam_conf.h, the dynamic symbols of libsslam_conf.so, sslam_amd.lib.CONF_EXPORTS and tests/conf_table.py hold
-the same entries.  No GPU."""
+models.uncertainty_estimator - its surface and its eager path - against the same fixture, and the interface of
+libsslam_conf.so: include/sslam_conf.h, sslam_amd.lib.CONF_EXPORTS and tests/conf_table.py hold the same entries (the built
+library's symbols are tests/test_libraries_cpu.py).  No GPU."""
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -192,20 +190,11 @@ def _header():
 
 
 def test_header_symbols_exports_and_table_agree():
+    """The table and the constants against the export list; that list against the header and the built library is
+    tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|const char \*)\s*(sslc_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared) == 9
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.CONF_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslc_ entries leaves the library
-    assert set(lib.CONF_EXPORTS) == set(declared) and len(set(lib.CONF_EXPORTS)) == len(lib.CONF_EXPORTS)
+    declared = lib.CONF_EXPORTS
     assert set(ct.ALIGN) | set(ct.HOST_ONLY) == set(declared) and not set(ct.ALIGN) & set(ct.HOST_ONLY) and set(ct.LIMITS) == set(ct.ALIGN)
-    others = lib.EXPORTS + lib.EXT_EXPORTS + lib.GRAPH_EXPORTS + lib.LOOP_EXPORTS + lib.WINDOW_EXPORTS + lib.PLACE_EXPORTS
-    assert not set(lib.CONF_EXPORTS) & set(others) and all(n.startswith("sslc_") for n in declared)
-    L = lib.conf()
-    assert all(hasattr(L, name) for name in lib.CONF_EXPORTS)
-    assert L.sslc_arch() == b"gfx950" and L.sslc_version() >= 100 and lib.conf_launch_count() >= 0
     consts = {k: int(v) for k, v in re.findall(r"#define (SSLC_\w+) (\d+)\s", open(HEADER).read())}
     assert re.findall(r"#define SSLC_CONF_MIN (\S+)f ", open(HEADER).read()) == ["1.17549435e-38"] and \
         ref.CONF_MIN == np.float32(1.17549435e-38) == np.finfo(np.float32).tiny
@@ -213,8 +202,6 @@ def test_header_symbols_exports_and_table_agree():
     assert (lib.CONF_DINO_DIM, lib.CONF_HIDDEN_DIM, lib.CONF_FILTER_MAX_K) == (ct.DINO_DIM, ct.HIDDEN_DIM, ct.FILTER_MAX_K) == \
         (ref.DINO_DIM, ref.HIDDEN_DIM, ref.FILTER_MAX_K)
     assert lib.CONF_STATE_KEYS == ref.STATE_KEYS == cases.STATE_KEYS
-    import __graft_entry__ as entry
-    assert entry.CONF_LIBRARY == ("csrc_conf", "conf", "sslc_arch", "CONF_EXPORTS") and "CONF_LIBRARY" in inspect.getsource(entry.build)
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -242,37 +229,6 @@ def test_the_header_states_both_tables_line_for_line():
     assert 4 * ct.TILE_ROWS * (ct.DINO_DIM + 256 + 4) <= 160 * 1024 and 2 * 4 * ct.TILE_ROWS * (ct.DINO_DIM + 128 + 4) <= 160 * 1024, \
         "one 256-wide tile, two 128-wide tiles fit a CU's 160 KB of LDS"
     assert 4 * ct.FILTER_MAX_K + 4 * 3 * 256 + 4 <= 64 * 1024, "the filter's static LDS fits 64 KB"
-
-
-def test_the_other_six_libraries_are_as_they_were():
-    from sslam_amd import lib
-    for name in ("sslam_hip.h", "sslam_ext.h", "sslam_graph.h", "sslam_loop.h", "sslam_window.h", "sslam_place.h"):
-        assert "sslc_" not in open(os.path.join(ROOT, "include", name)).read(), name
-    dirs = (lib.CSRC, lib.CSRC_EXT, lib.CSRC_GRAPH, lib.CSRC_LOOP, lib.CSRC_WINDOW, lib.CSRC_PLACE)
-    assert not [f for d in dirs for f in os.listdir(d) if "conf" in f]
-    assert sorted(f for f in os.listdir(lib.CSRC_CONF) if not f.startswith(("_", "lib"))) == ["Makefile", "confidence.hip"]
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_conf", None)
-    monkeypatch.setattr(lib, "CONF_SO_PATH", str(tmp_path / "libsslam_conf.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.conf()
-
-
-def test_conf_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.conf_build() == lib.CONF_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.conf_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_CONF, "-s", "-j4"]]
-    real = os.path.getmtime
-    for i, newer in enumerate(("confidence.hip", "sslam_conf.h", "gather_taps.h")):
-        monkeypatch.setattr(lib.os.path, "getmtime", lambda p, newer=newer: real(p) + (1e6 if p.endswith(newer) else 0))
-        lib.conf_build()
-        assert len(calls) == 2 + i
 
 
 # ------------------------------------------------------------------------------------------------------------- host-side layers

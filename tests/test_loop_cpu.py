@@ -1,13 +1,11 @@
 """Loop closures without a GPU: the restatement (tests/loop_ref.py) against independent statements - the oracle's similarity
 chain, a brute-force candidate search, the banded restatement (tests/pose_graph_ref.py) and a dense solve of independently formed
-normal equations - the planted loop study DESIGN.md section 4l records, and the interface of the fourth library:
-include/sslam_loop.h, the dynamic symbols of libsslam_loop.so, sslam_amd.lib.LOOP_EXPORTS and tests/loop_table.py hold the same
-entries, every host-side check raises before the library is loaded, and one past each size limit is refused."""
+normal equations - the planted loop study DESIGN.md section 4l records, and the interface of libsslam_loop.so:
+include/sslam_loop.h, sslam_amd.lib.LOOP_EXPORTS and tests/loop_table.py hold the same entries (the built library's symbols are
+tests/test_libraries_cpu.py), every host-side check raises before the library is loaded, and one past each size limit is refused."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -287,18 +285,11 @@ def _header():
 
 
 def test_header_symbols_exports_and_table_agree():
+    """The table, the constants and the key lists against the export list; that list against the header and the built library is
+    tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|size_t|const char \*)\s*(ssll_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared)
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.LOOP_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but ssll_ entries leaves the library
-    assert set(lib.LOOP_EXPORTS) == set(declared) and len(set(lib.LOOP_EXPORTS)) == len(lib.LOOP_EXPORTS)
+    declared = lib.LOOP_EXPORTS
     assert set(lt.ALIGN) | set(lt.HOST_ONLY) == set(declared) and not set(lt.ALIGN) & set(lt.HOST_ONLY) and set(lt.LIMITS) == set(lt.ALIGN)
-    L = lib.loop()
-    assert all(hasattr(L, name) for name in lib.LOOP_EXPORTS)
-    assert L.ssll_arch() == b"gfx950" and L.ssll_version() >= 100 and lib.loop_launch_count() >= 0
     consts = {k: int(v) for k, v in re.findall(r"#define (SSLL_\w+) (\d+)", open(HEADER).read())}
     assert consts == dict(SSLL_MAX_FRAMES=lt.MAX_FRAMES, SSLL_MAX_K=lt.MAX_K, SSLL_MAX_PER_FRAME=lt.MAX_PER_FRAME, SSLL_MAX_NODES=lt.MAX_NODES,
                           SSLL_MAX_EDGES=lt.MAX_EDGES, SSLL_MAX_GRAPHS=lt.MAX_GRAPHS, SSLL_GRAPH_MAX_ITER=lt.MAX_ITER, SSLL_MAX_CG=lt.MAX_CG,
@@ -308,13 +299,6 @@ def test_header_symbols_exports_and_table_agree():
         (lt.MAX_FRAMES, lt.MAX_K, lt.MAX_PER_FRAME, lt.MAX_NODES, lt.MAX_EDGES, lt.MAX_GRAPHS, lt.MAX_ITER, lt.MAX_CG) == \
         (ref.MAX_FRAMES, ref.MAX_K, ref.MAX_PER_FRAME, ref.MAX_NODES, ref.MAX_EDGES, ref.MAX_GRAPHS, ref.MAX_ITER, ref.MAX_CG)
     assert lib.POSE_GRAPH_SPARSE_KEYS == ref.KEYS and lib.LOOP_CANDIDATE_KEYS == ref.CANDIDATE_KEYS
-
-
-def test_the_other_three_libraries_are_as_they_were():
-    from sslam_amd import lib
-    assert not [n for n in lib.EXPORTS + lib.EXT_EXPORTS + lib.GRAPH_EXPORTS if n.startswith("ssll_") or "loop" in n or "sparse" in n]
-    for name in ("sslam_hip.h", "sslam_ext.h", "sslam_graph.h"):
-        assert "ssll_" not in open(os.path.join(ROOT, "include", name)).read()
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -338,28 +322,6 @@ def test_the_header_states_both_tables_line_for_line():
     for text_ in ("acc = fmaf(scores[i][kk], desc[i][kk][c], acc)", "fmaxf(sqrtf(ss_i), 1e-12f)", "acc = fmaf(sig[i][c], sig[j][c], acc)",
                   "rz1 <= (cg_tol * cg_tol) * rz0", "there is no band test", "WHY CENTRED"):
         assert text_ in raw, text_
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_loop", None)
-    monkeypatch.setattr(lib, "LOOP_SO_PATH", str(tmp_path / "libsslam_loop.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.loop()
-
-
-def test_loop_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.loop_build() == lib.LOOP_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.loop_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_LOOP, "-s", "-j4"]]
-    real = os.path.getmtime
-    for n, header in enumerate(("edge_terms.h", "gauss_newton.h")):      # a newer shared header, either of them
-        monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith(header) else 0))
-        lib.loop_build()
-        assert len(calls) == 2 + n
 
 
 def test_every_check_comes_before_the_library_is_loaded(monkeypatch):

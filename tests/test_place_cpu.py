@@ -1,13 +1,11 @@
-"""Online loop closures without a GPU: the interface of the sixth library - include/sslam_place.h, the dynamic symbols of
-libsslam_place.so, sslam_amd.lib.PLACE_EXPORTS and tests/place_table.py hold the same entries -, one past each size limit and every
+"""Online loop closures without a GPU: the interface of libsslam_place.so - include/sslam_place.h,
+sslam_amd.lib.PLACE_EXPORTS and tests/place_table.py hold the same entries; the built library's symbols are tests/test_libraries_cpu.py -, one past each size limit and every
 invalid operand refused before a launch, the host-side checks of every layer, the restatement (tests/place_ref.py) held to the
 batch entries' restatement (tests/loop_ref.py) row by row, the numpy drop-ins held to the restatement, the edge log's contract
 rows, and the planted study DESIGN.md §4n records."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -32,23 +30,12 @@ def _header(name="sslam_place.h"):
     return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
 
 
-def _declared(prefix, name):
-    return re.findall(r"^(?:int|long long|size_t|const char \*)\s*(" + prefix + r"_\w+)\s*\(", _header(name), flags=re.M)
-
-
 def test_header_symbols_exports_and_table_agree():
+    """The table, the constants and the key lists against the export list; that list against the header and the built library is
+    tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = _declared("sslp", "sslam_place.h")
-    assert len(set(declared)) == len(declared) == 6
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.PLACE_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslp_ entries leaves the library
-    assert set(lib.PLACE_EXPORTS) == set(declared) and len(set(lib.PLACE_EXPORTS)) == len(lib.PLACE_EXPORTS)
+    declared = lib.PLACE_EXPORTS
     assert set(pt.ALIGN) | set(pt.HOST_ONLY) == set(declared) and not set(pt.ALIGN) & set(pt.HOST_ONLY) and set(pt.LIMITS) == set(pt.ALIGN)
-    L = lib.place()
-    assert all(hasattr(L, name) for name in lib.PLACE_EXPORTS)
-    assert L.sslp_arch() == b"gfx950" and L.sslp_version() >= 100 and lib.place_launch_count() >= 0
     consts = {k: int(v) for k, v in re.findall(r"#define (SSLP_\w+) (\d+)", open(HEADER).read())}
     assert consts == dict(SSLP_MAX_CAPACITY=pt.MAX_CAPACITY, SSLP_MAX_K=pt.MAX_K, SSLP_MAX_PER_FRAME=pt.MAX_PER_FRAME, SSLP_MAX_SLOTS=pt.MAX_SLOTS,
                           SSLP_FRAMES_PER_GROUP=pt.FRAMES_PER_GROUP)
@@ -60,25 +47,6 @@ def test_header_symbols_exports_and_table_agree():
     assert lib.EDGE_LOG_STATE_KEYS == ref.LOG_STATE_KEYS and lib.EDGE_LOG_OUT_KEYS == ref.LOG_OUT_KEYS
     assert list(lib.PLACE_STATE_KEYS) == list(pt.ALIGN[PLACE])[:3] and list(lib.PLACE_OUT_KEYS) == list(pt.ALIGN[PLACE])[6:]
     assert list(lib.EDGE_LOG_STATE_KEYS) == list(pt.ALIGN[LOG])[:5] and list(lib.EDGE_LOG_OUT_KEYS) == list(pt.ALIGN[LOG])[10:]
-
-
-def test_the_other_five_libraries_are_as_they_were():
-    from sslam_amd import lib
-    others = dict(sslam=(lib.EXPORTS, "sslam_hip.h", 81), sslx=(lib.EXT_EXPORTS, "sslam_ext.h", 4), sslg=(lib.GRAPH_EXPORTS, "sslam_graph.h", 6),
-                  ssll=(lib.LOOP_EXPORTS, "sslam_loop.h", 7), sslw=(lib.WINDOW_EXPORTS, "sslam_window.h", 5))
-    for prefix, (exports, header, count) in others.items():
-        assert len(exports) == len(set(exports)) == count, prefix
-        assert all(n.startswith(prefix + "_") for n in exports), prefix
-        assert "sslp_" not in open(os.path.join(ROOT, "include", header)).read(), header
-    for prefix in ("sslx", "sslg", "ssll", "sslw"):
-        assert set(others[prefix][0]) == set(_declared(prefix, others[prefix][1])), prefix
-    assert not [n for n in lib.PLACE_EXPORTS if any(word in n for word in ("graph", "sparse", "window", "subcell", "candidates", "signatures"))]
-    assert not [f for d in (lib.CSRC, lib.CSRC_EXT, lib.CSRC_GRAPH, lib.CSRC_LOOP, lib.CSRC_WINDOW) for f in os.listdir(d) if "place" in f]
-    assert sorted(f for f in os.listdir(lib.CSRC_PLACE) if not f.startswith(("_", "lib"))) == ["Makefile", "place.hip"]
-    import __graft_entry__ as entry
-    import inspect
-    src = inspect.getsource(entry.build)
-    assert src.count('"csrc') == 6 and '("csrc_place", "place", "sslp_arch", "PLACE_EXPORTS")' in src
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -103,27 +71,6 @@ def test_the_header_states_both_tables_line_for_line():
         assert text in raw, text
     assert 4 * (pt.FRAMES_PER_GROUP * 257 + 256 + 4) <= 64 * 1024 and 4 * pt.MAX_CAPACITY + 64 <= 64 * 1024, "both kernels' static LDS fits 64 KB"
     assert (pt.MAX_CAPACITY - 1) * 256 + 255 < 2 ** 31 and (pt.MAX_K - 1) * 256 + 255 < 2 ** 31, "frame * d and keypoint * d fit 31 bits"
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_place", None)
-    monkeypatch.setattr(lib, "PLACE_SO_PATH", str(tmp_path / "libsslam_place.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.place()
-
-
-def test_place_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.place_build() == lib.PLACE_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.place_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_PLACE, "-s", "-j4"]]
-    real = os.path.getmtime
-    monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith("sslam_place.h") else 0))     # a newer header
-    lib.place_build()
-    assert len(calls) == 2
 
 
 # ------------------------------------------------------------------------------------------------------------ the size limits

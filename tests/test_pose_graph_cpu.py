@@ -1,12 +1,10 @@
 """The pose graph without a GPU: the restatement (tests/pose_graph_ref.py) against an independent dense solve and independent
-normal equations, the planted study DESIGN.md §4k records, the contract's rows, and the interface of the third library -
-include/sslam_graph.h, the dynamic symbols of libsslam_graph.so, sslam_amd.lib.GRAPH_EXPORTS and tests/graph_table.py hold the
-same entries - with every host-side check raising before the library is loaded and one past each size limit refused."""
+normal equations, the planted study DESIGN.md §4k records, the contract's rows, and the interface of libsslam_graph.so -
+include/sslam_graph.h, sslam_amd.lib.GRAPH_EXPORTS and tests/graph_table.py hold the same entries; the built library's symbols are
+tests/test_libraries_cpu.py - with every host-side check raising before the library is loaded and one past each size limit refused."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -155,34 +153,19 @@ def _header():
 
 
 def test_header_symbols_exports_and_table_agree():
+    """The tables (this library's and, as when it arrived, the two before it), the constants and the key list against the export
+    lists; those lists against the headers and the built libraries are tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|size_t|const char \*)\s*(sslg_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared)
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.GRAPH_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslg_ entries leaves the library
-    assert set(lib.GRAPH_EXPORTS) == set(declared) and len(set(lib.GRAPH_EXPORTS)) == len(lib.GRAPH_EXPORTS)
+    declared = lib.GRAPH_EXPORTS
     assert set(gt.ALIGN) | set(gt.HOST_ONLY) == set(declared) and not set(gt.ALIGN) & set(gt.HOST_ONLY) and set(gt.LIMITS) == set(gt.ALIGN)
-    G = lib.graph()
-    assert all(hasattr(G, name) for name in lib.GRAPH_EXPORTS)
-    assert G.sslg_arch() == b"gfx950" and G.sslg_version() >= 100 and lib.graph_launch_count() >= 0
+    assert set(lib.EXT_EXPORTS) == set(et.ALIGN) | set(et.HOST_ONLY)
+    assert set(lib.EXPORTS) == set(lt.ALIGN) | set(lt.HOST_ONLY)
     consts = dict(re.findall(r"#define (SSLG_\w+) (\d+)", open(HEADER).read()))
     assert {k: int(v) for k, v in consts.items()} == dict(SSLG_MAX_BAND=gt.MAX_BAND, SSLG_MAX_NODES=gt.MAX_NODES, SSLG_MAX_EDGES=gt.MAX_EDGES,
                                                            SSLG_MAX_GRAPHS=gt.MAX_GRAPHS, SSLG_GRAPH_MAX_ITER=gt.MAX_ITER)
     assert (lib.GRAPH_MAX_BAND, lib.GRAPH_MAX_NODES, lib.GRAPH_MAX_EDGES, lib.GRAPH_MAX_GRAPHS, lib.GRAPH_MAX_ITER) == \
         (gt.MAX_BAND, gt.MAX_NODES, gt.MAX_EDGES, gt.MAX_GRAPHS, gt.MAX_ITER) == (ref.MAX_BAND, ref.MAX_NODES, ref.MAX_EDGES, ref.MAX_GRAPHS, ref.MAX_ITER)
     assert lib.POSE_GRAPH_KEYS == ref.KEYS
-
-
-def test_the_other_two_libraries_are_as_they_were():
-    from sslam_amd import lib
-    assert set(lib.EXT_EXPORTS) == set(et.ALIGN) | set(et.HOST_ONLY)
-    assert set(lib.EXPORTS) == set(lt.ALIGN) | set(lt.HOST_ONLY)
-    assert not [n for n in lib.EXPORTS + lib.EXT_EXPORTS if n.startswith("sslg_") or "graph" in n]
-    for name in ("sslam_hip.h", "sslam_ext.h"):
-        assert "sslg_" not in open(os.path.join(ROOT, "include", name)).read()
-    assert not [f for f in os.listdir(lib.CSRC) + os.listdir(lib.CSRC_EXT) if "graph" in f]
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -205,27 +188,6 @@ def test_the_header_states_both_tables_line_for_line():
         assert len(re.findall(r"\bsslg_\w+: ", stated)) == count
     for text_ in ("k ascending from max(0, i - bw)", "bw = 6 * band + 5", "0.5 * (D_21 - D_12)", "s <= huber_chi * huber_chi", "A_ii = A_ii + damping"):
         assert text_ in raw, text_
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_graph", None)
-    monkeypatch.setattr(lib, "GRAPH_SO_PATH", str(tmp_path / "libsslam_graph.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.graph()
-
-
-def test_graph_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.graph_build() == lib.GRAPH_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.graph_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_GRAPH, "-s", "-j4"]]
-    real = os.path.getmtime
-    monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith("sslam_graph.h") else 0))     # a newer header
-    lib.graph_build()
-    assert len(calls) == 2
 
 
 def test_every_check_comes_before_the_library_is_loaded(monkeypatch):

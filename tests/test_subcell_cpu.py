@@ -1,11 +1,9 @@
 """Sub-cell keypoint localisation without a GPU: the restatement (tests/subcell_ref.py) against the float64 parabola, its bounds,
-the planted-bump and pose studies DESIGN.md §4j records, and the interface of the second library - include/sslam_ext.h, the
-dynamic symbols of libsslam_ext.so, sslam_amd.lib.EXT_EXPORTS and tests/ext_table.py hold the same entries - with every host-side
+the planted-bump and pose studies DESIGN.md §4j records, and the interface of libsslam_ext.so - include/sslam_ext.h,
+sslam_amd.lib.EXT_EXPORTS and tests/ext_table.py hold the same entries; the built library's symbols are tests/test_libraries_cpu.py - with every host-side
 check raising before the library is loaded."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -159,22 +157,6 @@ def test_planted_bumps_under_noise_are_recorded():
         assert np.isfinite([r["rms"], r["max"], r["grid_rms"]]).all()
 
 
-def test_ext_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.ext_build() == lib.EXT_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.ext_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_EXT, "-s", "-j4"]]
-    real = os.path.getmtime
-    monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith("subcell.hip") else 0))     # a newer source
-    lib.ext_build()
-    assert len(calls) == 2
-    monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith("sslam_ext.h") else 0))     # a newer header
-    lib.ext_build()
-    assert len(calls) == 3
-
-
 def test_pose_study_refined_keypoints_give_the_better_translation():
     """40 seeded pairs, 36 planted points on a jittered lattice of the 28 x 28 grid rendered as sigma = 1 bumps, depths 1.5 - 4 m,
     0.5 - 2 degrees and up to 5 cm per axis between the cameras; oracle selection, matches by planted identity, RANSAC
@@ -195,19 +177,10 @@ def _header():
 
 
 def test_header_symbols_exports_and_table_agree():
+    """The table against the export list; that list against the header and the built library is tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|const char \*)\s*(sslx_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared)
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.EXT_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslx_ entries leaves the library
-    assert set(lib.EXT_EXPORTS) == set(declared) and len(set(lib.EXT_EXPORTS)) == len(lib.EXT_EXPORTS)
+    declared = lib.EXT_EXPORTS
     assert set(et.ALIGN) | set(et.HOST_ONLY) == set(declared) and not set(et.ALIGN) & set(et.HOST_ONLY)
-    assert not set(lib.EXT_EXPORTS) & set(lib.EXPORTS) and not any(name.startswith("sslam_") for name in declared)
-    X = lib.ext()
-    assert all(hasattr(X, name) for name in lib.EXT_EXPORTS)
-    assert X.sslx_arch() == b"gfx950" and X.sslx_version() >= 100 and lib.ext_launch_count() >= 0
 
 
 def test_a_row_names_the_device_pointers_of_its_prototype_and_the_header_states_it():
@@ -229,22 +202,6 @@ def test_a_row_names_the_device_pointers_of_its_prototype_and_the_header_states_
     assert len(re.findall(r"\bsslx_\w+: ", stated)) == len(et.ALIGN)
     for text_ in ("off = (a - b) / (den + den)", "a >= 0 && b >= 0", "den > 0", "off >= -0.5f && off <= 0.5f", "kp_xy_sub * 16.0f + 8.0f"):
         assert text_ in raw, text_
-
-
-def test_the_first_library_is_as_it_was():
-    """Nothing of this feature went into libsslam_hip.so: its sources, header and export list name no sub-cell entry."""
-    from sslam_amd import lib
-    assert not [name for name in lib.EXPORTS if "subcell" in name]
-    assert "subcell" not in open(os.path.join(ROOT, "include", "sslam_hip.h")).read()
-    assert not [f for f in os.listdir(lib.CSRC) if "subcell" in f]
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_ext", None)
-    monkeypatch.setattr(lib, "EXT_SO_PATH", str(tmp_path / "libsslam_ext.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.ext()
 
 
 def test_every_check_comes_before_the_library_is_loaded(monkeypatch):

@@ -1,15 +1,12 @@
-"""CPU tests of feature tracks and the landmark map: the interface of the ninth library (include/sslam_track.h, the dynamic symbols
-of libsslam_track.so, sslam_amd.lib.TRACK_EXPORTS and tests/track_table.py hold the same entries), the restatement of
+"""CPU tests of feature tracks and the landmark map: the interface of libsslam_track.so (include/sslam_track.h, sslam_amd.lib.TRACK_EXPORTS and
+tests/track_table.py hold the same entries; the built library's symbols are tests/test_libraries_cpu.py), the restatement of
 sslam_amd/track_numpy.py against the method-by-method one of tests/track_ref.py and both against a brute-force definition, the
 online bank against the batch entries on every prefix, the planted fates of the landmark scene, the header's two invariants on the
 restatement, everything the C entries refuse before any device work with one past each size limit, the Python layers' refusals, the
 numpy drop-ins of evaluation.py, and the planted study.  No GPU."""
 import ctypes
-import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -49,21 +46,12 @@ def _landmarks(s, tr, weight, threshold=3.0, min_obs=2):
 
 # ------------------------------------------------------------------------------------------------------------- the interface
 def test_entries_are_declared_exported_and_listed():
+    """The table, the constants and the key lists against the export list; that list against the header and the built library is
+    tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|size_t|const char \*)\s*(sslt_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared) == 8
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.TRACK_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslt_ entries leaves the library
-    assert set(lib.TRACK_EXPORTS) == set(declared) and len(set(lib.TRACK_EXPORTS)) == len(lib.TRACK_EXPORTS)
+    declared = lib.TRACK_EXPORTS
     assert set(tt.ALIGN) | set(tt.HOST_ONLY) == set(declared) and not set(tt.ALIGN) & set(tt.HOST_ONLY) and set(tt.LIMITS) == set(tt.ALIGN)
-    others = lib.EXPORTS + lib.EXT_EXPORTS + lib.GRAPH_EXPORTS + lib.LOOP_EXPORTS + lib.WINDOW_EXPORTS + lib.PLACE_EXPORTS + lib.CONF_EXPORTS + \
-        lib.WEIGHT_EXPORTS
-    assert not set(lib.TRACK_EXPORTS) & set(others) and all(n.startswith("sslt_") for n in declared)
     L = lib.track()
-    assert all(hasattr(L, name) for name in lib.TRACK_EXPORTS)
-    assert L.sslt_arch() == b"gfx950" and L.sslt_version() >= 100 and lib.track_launch_count() >= 0
     consts = {k: int(v) for k, v in re.findall(r"#define (SSLT_\w+) (\d+)\s", open(HEADER).read())}
     assert consts == dict(SSLT_MAX_K=tt.MAX_K, SSLT_SCAN_TILE=tt.SCAN_TILE)
     assert (lib.TRACK_MAX_K, lib.TRACK_SCAN_TILE, lib.TRACK_MAX_NODES) == (tt.MAX_K, tt.SCAN_TILE, tt.MAX_NODES) == (tn.MAX_K, tn.SCAN_TILE, 2 ** 31 - 1)
@@ -77,12 +65,6 @@ def test_entries_are_declared_exported_and_listed():
     for entry in tt.ALIGN:
         pointers = len(tt.ALIGN[entry]) + 1                                      # and the stream
         assert sum(a is ctypes.c_void_p for a in getattr(L, entry).argtypes) == pointers, entry
-    import __graft_entry__ as entry
-    assert entry.TRACK_LIBRARY == ("csrc_track", "track", "sslt_arch", "TRACK_EXPORTS") and "TRACK_LIBRARY" in inspect.getsource(entry.build)
-    assert inspect.getsource(entry.build).count('"csrc') == 6, "the ninth row is no literal row of build()"
-    assert sorted(f for f in os.listdir(lib.CSRC_TRACK) if not f.startswith(("_", "lib"))) == ["Makefile", "track.hip"]
-    for name in ("sslam_hip.h", "sslam_ext.h", "sslam_graph.h", "sslam_loop.h", "sslam_window.h", "sslam_place.h", "sslam_conf.h", "sslam_weight.h"):
-        assert "sslt_" not in open(os.path.join(ROOT, "include", name)).read(), name
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -116,28 +98,6 @@ def test_the_header_states_both_tables_line_for_line():
     # the LDS arithmetic: two (links) and three (step) arrays of K words, under the 64 KB a workgroup can name statically
     assert 3 * 4 * tt.MAX_K + 64 <= 64 * 1024
     assert [tt.launches(IDS, n) for n in (1, 2, 3, 5, 9, 17, 33, 128, 205)] == [5, 6, 7, 8, 9, 10, 11, 12, 13]
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_track", None)
-    monkeypatch.setattr(lib, "TRACK_SO_PATH", str(tmp_path / "libsslam_track.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.track()
-
-
-def test_track_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.track_build() == lib.TRACK_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.track_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_TRACK, "-s", "-j4"]]
-    real = os.path.getmtime
-    for i, newer in enumerate(("track.hip", "sslam_track.h", "sslam_hip.h")):
-        monkeypatch.setattr(lib.os.path, "getmtime", lambda p, newer=newer: real(p) + (1e6 if p.endswith(os.sep + newer) else 0))
-        lib.track_build()
-        assert len(calls) == 2 + i
 
 
 # ------------------------------------------------------------------------------------------------- links and tracks, three ways

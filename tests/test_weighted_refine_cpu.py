@@ -1,6 +1,6 @@
-"""CPU tests of confidence-weighted pose refinement: the interface of the eighth library (include/sslam_weight.h, the dynamic
-symbols of libsslam_weight.so, sslam_amd.lib.WEIGHT_EXPORTS and tests/weight_table.py hold the same entries; the other seven
-libraries are as they were), the seeded cases of tests/weighted_refine_cases.py against their margins, the restatement of
+"""CPU tests of confidence-weighted pose refinement: the interface of libsslam_weight.so (include/sslam_weight.h,
+sslam_amd.lib.WEIGHT_EXPORTS and tests/weight_table.py hold the same entries; the built library's symbols are
+tests/test_libraries_cpu.py), the seeded cases of tests/weighted_refine_cases.py against their margins, the restatement of
 tests/weighted_refine_ref.py against an independent implementation and a finite-difference gradient, the two invariants of the
 header on the restatement, the value type and the refusals of the Python layers, the numpy drop-ins, everything the C entries
 refuse before any device work, and the planted study that says what a calibrated weight buys.  No GPU."""
@@ -8,8 +8,6 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -38,20 +36,12 @@ def _rel(a, b):
 
 # ------------------------------------------------------------------------------------------------------------- the interface
 def test_entries_are_declared_exported_and_listed():
+    """The table, the constants and the key lists against the export list; that list against the header and the built library is
+    tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|const char \*)\s*(sslu_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared) == 5
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.WEIGHT_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslu_ entries leaves the library
-    assert set(lib.WEIGHT_EXPORTS) == set(declared) and len(set(lib.WEIGHT_EXPORTS)) == len(lib.WEIGHT_EXPORTS)
+    declared = lib.WEIGHT_EXPORTS
     assert set(wt.ALIGN) | set(wt.HOST_ONLY) == set(declared) and not set(wt.ALIGN) & set(wt.HOST_ONLY) and set(wt.LIMITS) == set(wt.ALIGN)
-    others = lib.EXPORTS + lib.EXT_EXPORTS + lib.GRAPH_EXPORTS + lib.LOOP_EXPORTS + lib.WINDOW_EXPORTS + lib.PLACE_EXPORTS + lib.CONF_EXPORTS
-    assert not set(lib.WEIGHT_EXPORTS) & set(others) and all(n.startswith("sslu_") for n in declared)
     L = lib.weight()
-    assert all(hasattr(L, name) for name in lib.WEIGHT_EXPORTS)
-    assert L.sslu_arch() == b"gfx950" and L.sslu_version() >= 100 and lib.weight_launch_count() >= 0
     consts = {k: int(v) for k, v in re.findall(r"#define (SSLU_\w+) (\d+)\s", open(HEADER).read())}
     assert consts == dict(SSLU_WEIGHT_PRODUCT=wt.WEIGHT_PRODUCT, SSLU_WEIGHT_EXPECTED_ERROR=wt.WEIGHT_EXPECTED_ERROR)
     assert (lib.WEIGHT_PRODUCT, lib.WEIGHT_EXPECTED_ERROR) == (wt.WEIGHT_PRODUCT, wt.WEIGHT_EXPECTED_ERROR) == (wr.PRODUCT, wr.EXPECTED_ERROR)
@@ -61,8 +51,6 @@ def test_entries_are_declared_exported_and_listed():
     import torch
     sh = lib.pose_refine_weighted_shapes(3, 7)
     assert sh["weight_sum"] == ((3,), torch.float64) and {k: v for k, v in sh.items() if k != "weight_sum"} == lib.pose_refine_shapes(3, 7)
-    import __graft_entry__ as entry
-    assert entry.WEIGHT_LIBRARY == ("csrc_weight", "weight", "sslu_arch", "WEIGHT_EXPORTS") and "WEIGHT_LIBRARY" in inspect.getsource(entry.build)
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -97,51 +85,14 @@ def test_the_header_states_both_tables_line_for_line():
     body = open(shared).read()
     for name in ("refine_h", "refine_terms", "refine_solve", "refine_update", "pose_refine_body"):
         assert re.search(r"\b" + name + r"\s*\(", body), name
-    for src in (os.path.join(lib.CSRC, "pose_refine.hip"), os.path.join(lib.CSRC_WEIGHT, "weighted_refine.hip")):
+    for src in (os.path.join(lib.CSRC, "pose_refine.hip"), os.path.join(lib.LIBRARIES["weight"].csrc, "weighted_refine.hip")):
         text = open(src).read()
         assert "pose_refine_common.h" in text and "refine_solve" not in text and "refine_update" not in text and "LDL" not in text.split("#include")[1], src
-    for mk in (os.path.join(lib.CSRC, "Makefile"), os.path.join(lib.CSRC_WEIGHT, "Makefile")):
-        assert "pose_refine_common.h" in open(mk).read(), mk
+    assert shared in lib.LIBRARIES["weight"].prerequisites      # and the first library's objects depend on every header of its directory
     # the LDS arithmetic: 4 KB of weights beside the chunk, under the 64 KB a workgroup can name statically
     assert wt.static_lds_bytes(False) == 41872 and wt.static_lds_bytes(True) == 45968 == wt.static_lds_bytes(False) + 4 * wt.CHUNK
     assert wt.static_lds_bytes(True) <= 64 * 1024
     assert wt.MAX_K == lib.EVAL_MAX_K and wt.MAX_K // wt.THREADS <= 32, "a thread's selected rows fit one 32-bit register"
-
-
-def test_the_other_seven_libraries_are_as_they_were():
-    from sslam_amd import lib
-    for name in ("sslam_hip.h", "sslam_ext.h", "sslam_graph.h", "sslam_loop.h", "sslam_window.h", "sslam_place.h", "sslam_conf.h"):
-        assert "sslu_" not in open(os.path.join(ROOT, "include", name)).read(), name
-    dirs = (lib.CSRC, lib.CSRC_EXT, lib.CSRC_GRAPH, lib.CSRC_LOOP, lib.CSRC_WINDOW, lib.CSRC_PLACE, lib.CSRC_CONF)
-    assert not [f for d in dirs for f in os.listdir(d) if "weight" in f]
-    mine = sorted(f for f in os.listdir(lib.CSRC_WEIGHT) if not f.startswith(("_", "lib")))
-    assert mine == ["Makefile", "weighted_refine.hip"]
-    assert not [f for f in mine if any(word in f for word in ("conf", "place", "loop", "window", "graph", "subcell"))]
-    assert sorted(f for f in os.listdir(lib.CSRC_CONF) if not f.startswith(("_", "lib"))) == ["Makefile", "confidence.hip"]
-    assert sorted(f for f in os.listdir(lib.CSRC_PLACE) if not f.startswith(("_", "lib"))) == ["Makefile", "place.hip"]
-    assert sorted(f for f in os.listdir(lib.CSRC_WINDOW) if not f.startswith(("_", "lib"))) == ["Makefile", "window.hip"]
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_weight", None)
-    monkeypatch.setattr(lib, "WEIGHT_SO_PATH", str(tmp_path / "libsslam_weight.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.weight()
-
-
-def test_weight_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.weight_build() == lib.WEIGHT_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.weight_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_WEIGHT, "-s", "-j4"]]
-    real = os.path.getmtime
-    for i, newer in enumerate(("weighted_refine.hip", "sslam_weight.h", "pose_refine_common.h", "pose_common.h")):
-        monkeypatch.setattr(lib.os.path, "getmtime", lambda p, newer=newer: real(p) + (1e6 if p.endswith(os.sep + newer) else 0))
-        lib.weight_build()
-        assert len(calls) == 2 + i
 
 
 # ------------------------------------------------------------------------------------------------------------- the case lists

@@ -1,12 +1,10 @@
-"""The sliding-window estimator without a GPU: the interface of the fifth library - include/sslam_window.h, the dynamic symbols of
-libsslam_window.so, sslam_amd.lib.WINDOW_EXPORTS and tests/window_table.py hold the same entries -, one past each size limit and
+"""The sliding-window estimator without a GPU: the interface of libsslam_window.so - include/sslam_window.h,
+sslam_amd.lib.WINDOW_EXPORTS and tests/window_table.py hold the same entries; the built library's symbols are tests/test_libraries_cpu.py -, one past each size limit and
 every invalid operand refused before a launch, the host-side checks of every layer, the restatement's (tests/window_ref.py)
 contract rows, and the planted study DESIGN.md §4m records."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,35 +26,17 @@ def _header():
 
 
 def test_header_symbols_exports_and_table_agree():
+    """The table, the constants and the key lists against the export list; that list against the header and the built library is
+    tests/test_libraries_cpu.py."""
     from sslam_amd import lib
-    declared = re.findall(r"^(?:int|long long|size_t|const char \*)\s*(sslw_\w+)\s*\(", _header(), flags=re.M)
-    assert len(set(declared)) == len(declared) == 5
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    dyn = subprocess.run([nm, "-D", "--defined-only", lib.WINDOW_SO_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT\s+(\w+)$", dyn, flags=re.M))
-    assert exported == set(declared), sorted(exported ^ set(declared))          # nothing but sslw_ entries leaves the library
-    assert set(lib.WINDOW_EXPORTS) == set(declared) and len(set(lib.WINDOW_EXPORTS)) == len(lib.WINDOW_EXPORTS)
+    declared = lib.WINDOW_EXPORTS
     assert set(wt.ALIGN) | set(wt.HOST_ONLY) == set(declared) and not set(wt.ALIGN) & set(wt.HOST_ONLY) and set(wt.LIMITS) == set(wt.ALIGN)
-    L = lib.window()
-    assert all(hasattr(L, name) for name in lib.WINDOW_EXPORTS)
-    assert L.sslw_arch() == b"gfx950" and L.sslw_version() >= 100 and lib.window_launch_count() >= 0
     consts = {k: int(v) for k, v in re.findall(r"#define (SSLW_\w+) (\d+)", open(HEADER).read())}
     assert consts == dict(SSLW_MAX_WINDOW=wt.MAX_WINDOW, SSLW_MAX_SPACINGS=wt.MAX_SPACINGS, SSLW_MAX_WINDOWS=wt.MAX_WINDOWS, SSLW_MAX_FRAME=wt.MAX_FRAME)
     assert (lib.WINDOW_MAX_WINDOW, lib.WINDOW_MAX_SPACINGS, lib.WINDOW_MAX_WINDOWS, lib.WINDOW_MAX_FRAME) == \
         (wt.MAX_WINDOW, wt.MAX_SPACINGS, wt.MAX_WINDOWS, wt.MAX_FRAME) == (ref.MAX_WINDOW, ref.MAX_SPACINGS, ref.MAX_WINDOWS, ref.MAX_FRAME)
     assert lib.WINDOW_OUT_KEYS == ref.OUT_KEYS and lib.WINDOW_STATE_KEYS == ref.STATE_KEYS and wt.MAX_ITER == lib.GRAPH_MAX_ITER == pg.MAX_ITER
     assert list(lib.WINDOW_STATE_KEYS) == list(wt.ALIGN[ENTRY])[:7] and list(lib.WINDOW_OUT_KEYS) == list(wt.ALIGN[ENTRY])[14:]
-
-
-def test_no_other_library_carries_the_new_entries():
-    from sslam_amd import lib
-    others = lib.EXPORTS + lib.EXT_EXPORTS + lib.GRAPH_EXPORTS + lib.LOOP_EXPORTS
-    assert not [n for n in others if n.startswith("sslw_")]
-    assert not [n for n in lib.WINDOW_EXPORTS if any(word in n for word in ("graph", "loop", "sparse", "subcell"))]
-    for name in ("sslam_hip.h", "sslam_ext.h", "sslam_graph.h", "sslam_loop.h"):
-        assert "sslw_" not in open(os.path.join(ROOT, "include", name)).read()
-    assert not [f for d in (lib.CSRC, lib.CSRC_EXT, lib.CSRC_GRAPH, lib.CSRC_LOOP) for f in os.listdir(d) if "window" in f]
-    assert sorted(f for f in os.listdir(lib.CSRC_WINDOW) if not f.startswith(("_", "lib"))) == ["Makefile", "window.hip"]
 
 
 def test_the_header_states_both_tables_line_for_line():
@@ -78,27 +58,6 @@ def test_the_header_states_both_tables_line_for_line():
                  f"{wt.lds_bytes(32) // 1000} {wt.lds_bytes(32) % 1000} bytes at W = 32", f"{wt.lds_bytes(21) // 1000} {wt.lds_bytes(21) % 1000}"):
         assert text in raw, text
     assert wt.lds_bytes(wt.MAX_WINDOW) + 4096 <= 160 * 1024, "the triangle, g, y, delta and the static words fit a CU's LDS"
-
-
-def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
-    from sslam_amd import lib
-    monkeypatch.setattr(lib, "_window", None)
-    monkeypatch.setattr(lib, "WINDOW_SO_PATH", str(tmp_path / "libsslam_window.so"))
-    with pytest.raises(lib.SslamHipError, match="missing: run"):
-        lib.window()
-
-
-def test_window_build_rebuilds_only_a_stale_library(monkeypatch):
-    from sslam_amd import lib
-    calls = []
-    monkeypatch.setattr(lib.subprocess, "check_call", lambda cmd, **kw: calls.append(cmd))
-    assert lib.window_build() == lib.WINDOW_SO_PATH and calls == [], "an up-to-date library is left alone"
-    lib.window_build(force=True)
-    assert calls == [["make", "-C", lib.CSRC_WINDOW, "-s", "-j4"]]
-    real = os.path.getmtime
-    monkeypatch.setattr(lib.os.path, "getmtime", lambda p: real(p) + (1e6 if p.endswith("gauss_newton.h") else 0))     # a newer shared driver
-    lib.window_build()
-    assert len(calls) == 2
 
 
 # ------------------------------------------------------------------------------------------------------------ the size limits

@@ -14,7 +14,7 @@ for p in (ROOT, os.path.join(ROOT, "semantic-slam-master_amd"), os.path.join(ROO
 import torch
 from sslam_amd import lib
 if os.environ.get("SSLAM_BENCH_SO"):            # a variant build of the library (experiments)
-    lib.SO_PATH = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
+    lib.LIBRARIES["lib"].so_path = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
 from models.dino_backbone import DinoBackbone
 from sslam_amd.vit import DinoV3ViT
 args, forms, repeats = sys.argv[1:], ["fp32", "bf16", "bf16_few", "eager"], 5

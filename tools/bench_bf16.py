@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import synth
 from sslam_amd import lib
 if os.environ.get("SSLAM_BENCH_SO"):            # a variant build of the library (experiments)
-    lib.SO_PATH = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
+    lib.LIBRARIES["lib"].so_path = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
 
 def timeit(fn, n=10):
     for _ in range(3): fn()

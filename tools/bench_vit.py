@@ -7,7 +7,7 @@ for p in (ROOT, os.path.join(ROOT, "semantic-slam-master_amd"), os.path.join(ROO
 import torch
 from sslam_amd import lib
 if os.environ.get("SSLAM_BENCH_SO"):            # a variant build of the library (experiments)
-    lib.SO_PATH = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
+    lib.LIBRARIES["lib"].so_path = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
 from sslam_amd.vit import DinoV3ViT
 from sslam_amd.vit_hip import HipViT, HipViTF32
 

@@ -9,7 +9,7 @@ for p in (ROOT, os.path.join(ROOT, "semantic-slam-master_amd"), os.path.join(ROO
 import synth
 from sslam_amd import lib
 if len(sys.argv) > 1:
-    lib.SO_PATH = os.path.abspath(sys.argv[1])
+    lib.LIBRARIES["lib"].so_path = os.path.abspath(sys.argv[1])
 from sslam_amd.pipeline import PackedRefiner
 
 F, K, G = 613, 500, 28
@@ -36,5 +36,5 @@ d1 = lib.gather_refine(feat, kp, ref.packed, ref.n_blocks)
 t1 = timed(lambda: lib.gather_refine(feat, kp, ref.packed, ref.n_blocks))
 t2 = timed(lambda: lib.refine(x, ref.packed, ref.n_blocks))
 fl = F * K * 1572864
-print(f"{os.path.basename(lib.SO_PATH)}: gather+MLP {t1:6.3f} ms ({fl / t1 / 1e9:6.1f} TF)   MLP (x_in) {t2:6.3f} ms ({fl / t2 / 1e9:6.1f} TF)"
+print(f"{os.path.basename(lib.LIBRARIES['lib'].so_path)}: gather+MLP {t1:6.3f} ms ({fl / t1 / 1e9:6.1f} TF)   MLP (x_in) {t2:6.3f} ms ({fl / t2 / 1e9:6.1f} TF)"
       f"   checksum {float(d1.double().sum()):.9f}", flush=True)

@@ -9,7 +9,7 @@ for p in (ROOT, os.path.join(ROOT, "semantic-slam-master_amd"), os.path.join(ROO
 import synth
 from sslam_amd import lib
 if len(sys.argv) > 1:                      # a variant build of the library (experiments)
-    lib.SO_PATH = os.path.abspath(sys.argv[1])
+    lib.LIBRARIES["lib"].so_path = os.path.abspath(sys.argv[1])
 from sslam_amd.pipeline import PackedRefiner
 
 F, K, G = 613, 500, 28
@@ -39,5 +39,5 @@ def timed(fn, reps=20):
 fl = F * K * 1572864
 t1 = timed(lambda: lib.gather_refine_bf16(feat, kp, ref.packed_bf16, ref.n_blocks))
 t2 = timed(lambda: lib.refine_bf16(x, ref.packed_bf16, ref.n_blocks))
-print(f"{os.path.basename(lib.SO_PATH)}: gather+MLP {t1:6.3f} ms ({fl / t1 / 1e9:7.1f} TF = {fl / t1 / 1e9 / 2500:.3f} of the bf16 peak)   "
+print(f"{os.path.basename(lib.LIBRARIES['lib'].so_path)}: gather+MLP {t1:6.3f} ms ({fl / t1 / 1e9:7.1f} TF = {fl / t1 / 1e9 / 2500:.3f} of the bf16 peak)   "
       f"MLP (x_in) {t2:6.3f} ms ({fl / t2 / 1e9:7.1f} TF)", flush=True)

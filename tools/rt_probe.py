@@ -9,7 +9,7 @@ for p in (ROOT, os.path.join(ROOT, "semantic-slam-master_amd"), os.path.join(ROO
     sys.path.insert(0, p)
 from sslam_amd import lib
 if os.environ.get("SSLAM_BENCH_SO"):            # a probe build kept beside the product library (tools/build_variant.sh)
-    lib.SO_PATH = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
+    lib.LIBRARIES["lib"].so_path = os.path.abspath(os.environ["SSLAM_BENCH_SO"])
 L = lib.lib()
 if not hasattr(L, "sslam_probe_vit"):
     sys.exit("libsslam_hip.so was not built with -DSSLAM_RT_PROBE")

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "semantic-slam-master_amd"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 from sslam_amd import lib
-lib.SO_PATH = os.path.abspath(sys.argv[1])
+lib.LIBRARIES["lib"].so_path = os.path.abspath(sys.argv[1])
 from sslam_amd.vit import DinoV3ViT
 from sslam_amd.vit_hip import HipViTF32
 L = lib.lib()
