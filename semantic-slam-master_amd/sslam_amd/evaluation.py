@@ -32,12 +32,14 @@ import numpy as np
 import torch
 
 from . import lib
-from .pipeline import MatchRule
+from .pipeline import MatchRule, _np
+from .readback import Readback
 
 TUM_K = np.array([[525.0, 0, 319.5], [0, 525.0, 239.5], [0, 0, 1]])      # test_repeatability.py:179-183
 
 _REP_KEYS = ("gt_count", "dist_sum", "dist_median")
 _DQ_KEYS = ("gt_count", "tp", "fp", "fn", "value_sum", "match_count")
+_SUMS = ("value_sum", "dist_sum", "dist_median")       # the float64 figures among the per-pair numbers; the others are counts
 
 
 def relative_pose(pose1, pose2) -> np.ndarray:
@@ -113,15 +115,11 @@ def pair_transforms(poses, pairs) -> np.ndarray:
     return np.stack([relative_transform(poses[a], poses[b])[:3] for a, b in pairs]) if pairs else np.zeros((0, 3, 4))
 
 
-def _host(v):
-    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-
-
 def _pair_arrays(stats: dict, keys) -> dict:
     missing = [key for key in keys + ("num_keypoints",) if key not in stats]
     if missing:
         raise ValueError(f"stats lack {missing}")
-    out = {key: _host(stats[key]) for key in keys}
+    out = {key: _np(stats[key]) for key in keys}
     n = {len(v) for v in out.values()}
     if len(n) != 1 or 0 in n:
         raise ValueError("stats must hold one entry per pair, for at least one pair")
@@ -310,7 +308,7 @@ def gather_keypoint_depth(pipe, depth, keypoints_pixel, n_frames: int):
 def _score_depth(pipe, keypoints_pixel, pairs, poses, depth, camera, threshold: float, matches: dict, sequence: str,
                  kp_depth=None) -> dict:
     """_score against the depth ground truth: the gather (unless kp_depth holds its result already), the two scoring launches, ONE
-    host read-back of (10, P) float64."""
+    host read-back of the ten per-pair figures."""
     lib.check_threshold(threshold)
     first, second = [a for a, _ in pairs], [b for _, b in pairs]
     T = pair_transforms(poses, pairs)
@@ -318,16 +316,15 @@ def _score_depth(pipe, keypoints_pixel, pairs, poses, depth, camera, threshold: 
     if kp_depth is None:
         kp_depth = gather_keypoint_depth(pipe, depth, keypoints_pixel, pairs[-1][1] + 1)
     sc = pipe.pose_depth_scores(keypoints_pixel, kp_depth, first, second, T, camera, threshold, matches=matches)
-    keys = _DEPTH_DQ_KEYS + ("valid_count", "dist_sum", "dist_median")
-    rows = [sc[key] if key != "match_count" else matches["match_count"] for key in keys]
-    host = torch.stack([r.to(torch.float64) for r in rows]).cpu().numpy()       # integers up to 4096: exact in float64
-    st = {key: (host[i] if key in ("value_sum", "dist_sum", "dist_median") else host[i].astype(np.int64)) for i, key in enumerate(keys)}
-    st["num_keypoints"] = k
+    rb = Readback()
+    for key in _DEPTH_DQ_KEYS + ("valid_count", "dist_sum", "dist_median"):
+        rb.add(key, sc[key] if key != "match_count" else matches["match_count"], np.float64 if key in _SUMS else np.int64)
+    st = dict(rb.fetch(), num_keypoints=k)                  # the ONE read-back
     return {"repeatability": depth_repeatability_summary(st, sequence), "descriptor_quality": depth_descriptor_quality_summary(st, sequence)}
 
 
 def _score(pipe, keypoints_pixel, pairs, poses, use_pose: bool, threshold: float, matches: dict, sequence: str) -> dict:
-    """Score the listed pairs of a keypoint bank and, with poses, their M4 lists; ONE host read-back of (rows, P) float64."""
+    """Score the listed pairs of a keypoint bank and, with poses, their M4 lists; ONE host read-back of the per-pair figures."""
     if poses is None and use_pose:
         raise ValueError("use_pose=True needs poses (N, 4, 4); pass use_pose=False for the raw repeatability")
     if not pairs:
@@ -336,21 +333,18 @@ def _score(pipe, keypoints_pixel, pairs, poses, use_pose: bool, threshold: float
     first, second = [a for a, _ in pairs], [b for _, b in pairs]
     H = None if poses is None else pair_homographies(poses, pairs)
     k = int(keypoints_pixel.shape[1])
-    rows = []
+    rb = Readback()
     if H is not None:                                    # descriptor quality: always against the posed ground truth
         dq = pipe.pose_scores(keypoints_pixel, first, second, H, threshold, matches=matches)
-        rows += [dq[key] if key != "match_count" else matches["match_count"] for key in _DQ_KEYS]
+        for key in _DQ_KEYS:
+            rb.add("dq." + key, dq[key] if key != "match_count" else matches["match_count"], np.float64 if key in _SUMS else np.int64)
     rep = dq if (H is not None and use_pose) else pipe.pose_scores(keypoints_pixel, first, second, None, threshold)
-    rows += [rep[key] for key in _REP_KEYS]
-    host = torch.stack([r.to(torch.float64) for r in rows]).cpu().numpy()       # integers up to 4096: exact in float64
-    out = {"descriptor_quality": None}
-    if H is not None:
-        st = {key: (host[i] if key == "value_sum" else host[i].astype(np.int64)) for i, key in enumerate(_DQ_KEYS)}
-        out["descriptor_quality"] = descriptor_quality_summary(dict(st, num_keypoints=k), sequence)
-        host = host[len(_DQ_KEYS):]
-    st = {key: (host[i].astype(np.int64) if key == "gt_count" else host[i]) for i, key in enumerate(_REP_KEYS)}
-    out["repeatability"] = repeatability_summary(dict(st, num_keypoints=k), sequence)
-    return out
+    for key in _REP_KEYS:
+        rb.add("rep." + key, rep[key], np.float64 if key in _SUMS else np.int64)
+    host = rb.fetch()                                    # the ONE read-back
+    of = lambda prefix, keys: dict({key: host[prefix + key] for key in keys}, num_keypoints=k)
+    return {"descriptor_quality": None if H is None else descriptor_quality_summary(of("dq.", _DQ_KEYS), sequence),
+            "repeatability": repeatability_summary(of("rep.", _REP_KEYS), sequence)}
 
 
 def evaluate(pipe, images_u8=None, poses=None, spacing: int = 1, num_pairs: int = 50, use_pose: bool = True,

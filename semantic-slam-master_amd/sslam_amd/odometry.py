@@ -22,19 +22,22 @@ no real RGB-D sequence was at hand when this was written.  3.0 keypoint units is
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
 from . import lib
 from .evaluation import Camera, check_depth_size, check_subcell, gather_keypoint_depth, geometry_bank, relative_transform
-from .pipeline import MatchRule, PoseWeights
+from .pipeline import GraphSettings, MatchRule, PoseSettings, _np
+from .readback import Readback
 
 _INT_KEYS = ("inlier_count", "usable_count", "best_hypothesis", "refit_kept")
 
 
 def _as44(T) -> np.ndarray:
     """(P, 4, 4) float64 from (P, 12), (P, 3, 4) or (P, 4, 4)."""
-    T = np.asarray(T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T, dtype=np.float64)
+    T = np.asarray(_np(T), dtype=np.float64)
     if T.ndim == 2 and T.shape[1] == 12:
         T = T.reshape(-1, 3, 4)
     if T.ndim != 3 or tuple(T.shape[1:]) not in ((3, 4), (4, 4)):
@@ -123,6 +126,13 @@ def chain(T, start=None) -> np.ndarray:
     return np.stack(out)
 
 
+def camera_to_world(C) -> np.ndarray:
+    """(n, 4, 4) float64 camera-to-world poses - a trajectory as TUM's groundtruth.txt and ate_summary have it - from the
+    world-to-camera rows (n, 12) or (n, 3, 4) a pose graph or the window writes: every matrix inverted on its own."""
+    C = _as44(C)
+    return np.stack([np.linalg.inv(c) for c in C]) if len(C) else np.zeros((0, 4, 4))
+
+
 def consecutive_pairs(n_frames: int, spacing: int = 1, num_pairs=None) -> list:
     """The pairs (i, i + spacing), i = 0 .. n_frames - spacing - 1, the first num_pairs of them if given."""
     for name, v, lo in (("n_frames", n_frames, 0), ("spacing", spacing, 1)):
@@ -134,11 +144,9 @@ def consecutive_pairs(n_frames: int, spacing: int = 1, num_pairs=None) -> list:
     return [(i, i + int(spacing)) for i in range(p if num_pairs is None else min(p, int(num_pairs)))]
 
 
-def _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n_frames, keypoints_shape=None):
-    """Everything odometry / odometry_result can refuse before any device work -> the Camera to use."""
-    lib.check_threshold(threshold)
-    lib.check_hypotheses(hypotheses)
-    lib.check_seed(seed)
+def _check_arguments(depth, kp_depth, camera, poses, n_frames, keypoints_shape=None):
+    """What odometry / odometry_result can refuse of the sequence's own data before any device work (their settings are judged where
+    the PoseSettings is built) -> the Camera to use."""
     camera = Camera() if camera is None else camera
     lib.check_camera(camera)
     if poses is not None and len(_check_poses(poses)) < n_frames:
@@ -161,7 +169,7 @@ def _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed
 
 def info_matrix(info) -> np.ndarray:
     """(P, 6, 6) symmetric information matrices from refine_poses' info (P, 21), the upper triangles row-major."""
-    info = np.asarray(info.detach().cpu().numpy() if isinstance(info, torch.Tensor) else info, dtype=np.float64)
+    info = np.asarray(_np(info), dtype=np.float64)
     if info.ndim != 2 or info.shape[1] != 21:
         raise ValueError(f"info (P, 21) expected, got {info.shape}")
     iu = np.triu_indices(6)
@@ -185,85 +193,60 @@ _REFINE_INT = ("status", "iterations", "selected_count", "inlier_count")
 _REFINE_REAL = ("cost_in", "cost", "rms")
 
 
-def _check_refine(refine, threshold, huber, iterations) -> None:
-    """What the refinement's arguments can be refused for, before any device work."""
-    if not isinstance(refine, bool):
-        raise ValueError(f"refine must be a bool, got {refine!r}")
-    if refine:
-        lib.check_huber(float(threshold) / 3.0 if huber is None else huber)
-        lib.check_iterations(iterations)
+def _launch(pipe, rb, keypoints_pixel, kp_depth, pairs, matches, camera, pose, weight=None):
+    """_launch_lists on a host list of pairs."""
+    return _launch_lists(pipe, rb, keypoints_pixel, kp_depth, [a for a, _ in pairs], [b for _, b in pairs], matches, camera, pose, weight)
 
 
-def _check_weights(pipe, weights, refine) -> None:
-    """What weights= can be refused for, before any device work: it is a PoseWeights, it needs the refinement it weights and a
-    pipeline that extracts the confidence it is made of."""
-    if weights is None:
-        return
-    if not isinstance(weights, PoseWeights):
-        raise ValueError(f"weights must be None or a PoseWeights, got {type(weights).__name__}")
-    if not refine:
-        raise ValueError("weights= weights the refinement: it needs refine=True")
-    if not getattr(pipe.cfg, "confidence", False):
-        raise ValueError("weights= is made of the keypoint confidence: the pipeline needs ExtractorConfig(confidence=True)")
+def _launch_lists(pipe, rb, keypoints_pixel, kp_depth, first, second, matches, camera, pose, weight=None):
+    """The RANSAC launch on the listed pairs and, with pose.refine, the refinement launch behind it (weighted by `weight` (P, n1) where
+    given).  first / second as match_pairs takes them: host sequences, or int32 device tensors that nothing here reads.  What the host
+    wants of both joins the read-back rb, a row per pair: 'ransac.<key>', 'match_count' and 'refine.<key>'.  No host read ->
+    refine_poses' dictionary, or None."""
+    est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, pose.threshold, pose.hypotheses, pose.seed)
+    rb.add("match_count", matches["match_count"], np.int64)
+    for key in ("T", "rms"):
+        rb.add("ransac." + key, est[key], np.float64)
+    for key in _INT_KEYS:
+        rb.add("ransac." + key, est[key], np.int64)
+    if not pose.refine:
+        return None
+    ref = pipe.refine_poses(keypoints_pixel, kp_depth, first, second, matches, camera, est, pose.threshold, pose.huber, pose.iterations,
+                            weights=weight)
+    for key in _REFINE_INT:
+        rb.add("refine." + key, ref[key], np.int64)
+    for key in ("T", "info") + _REFINE_REAL + (() if weight is None else ("weight_sum",)):
+        rb.add("refine." + key, ref[key], np.float64)
+    return ref
 
 
-def _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations, weight=None):
-    """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it) -> ((P, 18) float64 device tensor -
-    (P, 58) with refine, (P, 59) with a weight tensor (P, n1): weight_sum last -, refine_poses' dictionary or None).  No host read."""
-    return _launch_lists(pipe, keypoints_pixel, kp_depth, [a for a, _ in pairs], [b for _, b in pairs], matches, camera, threshold, hypotheses,
-                         seed, refine, huber, iterations, weight)
-
-
-def _launch_lists(pipe, keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed, refine, huber, iterations,
-                  weight=None):
-    """_launch on pair lists as match_pairs takes them: host sequences, or int32 device tensors that nothing here reads."""
-    est = pipe.estimate_poses(keypoints_pixel, kp_depth, first, second, matches, camera, threshold, hypotheses, seed)
-    cols = [est["T"]] + [est[key].to(torch.float64)[:, None] for key in _INT_KEYS] + \
-           [matches["match_count"].to(torch.float64)[:, None], est["rms"][:, None]]
-    ref = None
-    if refine:
-        ref = pipe.refine_poses(keypoints_pixel, kp_depth, first, second, matches, camera, est, threshold, huber, iterations, weights=weight)
-        cols += [ref["T"]] + [ref[key].to(torch.float64)[:, None] for key in _REFINE_INT] + [ref[key][:, None] for key in _REFINE_REAL] + \
-                [ref["info"]]
-        if weight is not None:
-            cols.append(ref["weight_sum"][:, None])         # the one column a weighted row grows by
-    return torch.cat(cols, dim=1), ref                      # integers up to 4096: exact in float64
-
-
-def _unpack(host, pairs, poses, spacing, refine) -> dict:
-    """The host-side figures from the rows _launch packed, read back."""
-    T = _as44(host[:, :12])
-    out = {"pairs": list(pairs), "T": T}
-    out.update({key: host[:, 12 + i].astype(np.int64) for i, key in enumerate(_INT_KEYS)})
-    out["match_count"] = host[:, 16].astype(np.int64)
-    out["rms"] = host[:, 17].copy()
-    if not refine:
-        _summaries(out, T, poses, pairs, spacing)
+def _pairs_host(host, rows, pairs, poses, spacing) -> dict:
+    """The host-side figures of `pairs`, the rows `rows` (a slice) of the launch whose read-back `host` is."""
+    of = lambda name: host[name][rows]
+    out = {"pairs": list(pairs), "T": _as44(of("ransac.T"))}
+    out.update({key: of("ransac." + key) for key in _INT_KEYS})
+    out.update(match_count=of("match_count"), rms=of("ransac.rms"))
+    if "refine.T" not in host:
+        _summaries(out, out["T"], poses, pairs, spacing)
         return out
     ransac = {key: out[key] for key in ("T", "inlier_count", "rms", "match_count")}
-    _summaries(ransac, T, poses, pairs, spacing)
+    _summaries(ransac, ransac["T"], poses, pairs, spacing)
     del ransac["match_count"]
-    r = host[:, 18:]
-    out["T"] = _as44(r[:, :12])
-    got = {key: r[:, 12 + i].astype(np.int64) for i, key in enumerate(_REFINE_INT)}
-    out["inlier_count"] = got["inlier_count"]
-    out["rms"] = r[:, 18].copy()
+    out.update(T=_as44(of("refine.T")), inlier_count=of("refine.inlier_count"), rms=of("refine.rms"))
     _summaries(out, out["T"], poses, pairs, spacing)
     out["ransac"] = ransac
-    out["refine"] = {"status": got["status"], "iterations": got["iterations"], "selected_count": got["selected_count"],
-                     "cost_in": r[:, 16].copy(), "cost": r[:, 17].copy(), "info": info_matrix(r[:, 19:40])}
-    if r.shape[1] > 40:                                      # a weighted row: weight_sum behind info
-        out["refine"]["weight_sum"] = r[:, 40].copy()
+    out["refine"] = {key: of("refine." + key) for key in ("status", "iterations", "selected_count", "cost_in", "cost")}
+    out["refine"]["info"] = info_matrix(of("refine.info"))
+    if "refine.weight_sum" in host:
+        out["refine"]["weight_sum"] = of("refine.weight_sum")
     return out
 
 
-def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine=False,
-              huber=None, iterations=5, weight=None) -> dict:
-    """The RANSAC launch on the listed pairs (and, with refine, the refinement launch behind it), ONE host read-back of (P, 18)
-    float64 ((P, 58) with refine, (P, 59) weighted), the host-side figures."""
-    packed, _ = _launch(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, refine, huber, iterations,
-                        weight)
-    return _unpack(packed.cpu().numpy(), pairs, poses, spacing, refine)
+def _estimate(pipe, keypoints_pixel, kp_depth, pairs, matches, camera, poses, spacing, pose, weight=None) -> dict:
+    """The launches of `pose` (a PoseSettings) on the listed pairs, ONE host read-back, the host-side figures."""
+    rb = Readback()
+    _launch(pipe, rb, keypoints_pixel, kp_depth, pairs, matches, camera, pose, weight)
+    return _pairs_host(rb.fetch(), slice(None), pairs, poses, spacing)
 
 
 def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None, rule=None,
@@ -290,7 +273,8 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     (include/sslam_weight.h); 'refine' then also holds 'weight_sum', and 'info' is the weighted information matrix.  Still ONE
     read-back.  With weights=None nothing changes."""
     check_subcell(subcell)
-    _check_weights(pipe, weights, refine)
+    pose = PoseSettings(threshold, hypotheses, seed, refine, huber, iterations, weights)
+    pose.check_pipeline(pipe)
     src = tokens if tokens is not None else images_u8
     if src is None:
         raise ValueError("images_u8 or tokens= required")
@@ -298,16 +282,14 @@ def odometry(pipe, images_u8=None, depth=None, camera=None, poses=None, spacing:
     if not pairs:
         raise ValueError(f"{int(src.shape[0])} frames hold no pair at spacing {spacing}")
     n = pairs[-1][1] + 1
-    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
-    _check_refine(refine, threshold, huber, iterations)
+    camera = _check_arguments(depth, None, camera, poses, n)
     rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
     ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
     kp = geometry_bank(ex, subcell)
     kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
     matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
     weight = None if weights is None else pipe.match_weights(ex["confidence"], [a for a, _ in pairs], [b for _, b in pairs], matches, weights)
-    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine,
-                     huber, iterations, weight)
+    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, pose, weight)
 
 
 def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spacing: int = 1, num_pairs=None,
@@ -319,6 +301,7 @@ def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spa
     gather_keypoint_depth returned for result["frames"]["keypoints_pixel"], as evaluation.evaluate_result takes it.
     refine, huber, iterations, subcell: as odometry() takes them; a kp_depth= bank must have been gathered under the same bank
     (evaluation.geometry_bank(result["frames"], subcell))."""
+    pose = PoseSettings(threshold, hypotheses, seed, refine, huber, iterations)
     if not isinstance(result, dict) or "frames" not in result or "keypoints_pixel" not in result["frames"]:
         raise ValueError("a StreamingSequence / run_directory result expected")
     kp = geometry_bank(result["frames"], subcell)
@@ -326,13 +309,12 @@ def odometry_result(pipe, result: dict, depth=None, camera=None, poses=None, spa
     if not pairs or spacing not in result:
         raise ValueError(f"the result holds no pair at spacing {spacing}")
     n = pairs[-1][1] + 1
-    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
-    _check_refine(refine, threshold, huber, iterations)
+    camera = _check_arguments(depth, kp_depth, camera, poses, n, kp.shape)
     mm = result[spacing]
     matches = {key: mm[key][:len(pairs)] for key in ("matches", "match_count")}
     if kp_depth is None:
         kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
-    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, threshold, hypotheses, seed, refine, huber, iterations)
+    return _estimate(pipe, kp, kp_depth, pairs, matches, camera, poses, spacing, pose)
 
 
 # ------------------------------------------------------------------------------------------------ the pose graph over all spacings
@@ -340,9 +322,9 @@ GRAPH_SPACINGS = (1, 5, 10, 15, 20)          # the reference's own set
 _GRAPH_INT = ("status", "iterations", "used_edges", "skipped_edges", "failed_row")
 
 
-def _check_graph(spacings, n_frames, num_pairs, band, huber_chi, damping, graph_iterations) -> tuple:
-    """What the graph's arguments can be refused for, before any device work -> (the spacings that hold a pair, their pair lists,
-    the number of frames they name, the band)."""
+def _check_graph(spacings, n_frames, num_pairs, band) -> tuple:
+    """What the graph's spacings and band can be refused for, before any device work -> (the spacings that hold a pair, their pair
+    lists, the number of frames they name, the band).  The solver's settings are a GraphSettings, judged where it is built."""
     spacings = tuple(spacings)
     if not spacings or len(set(spacings)) != len(spacings) or 1 not in spacings:
         raise ValueError(f"spacings must be distinct and hold 1 (the chain is the initial guess), got {spacings!r}")
@@ -354,34 +336,49 @@ def _check_graph(spacings, n_frames, num_pairs, band, huber_chi, damping, graph_
     lists = {s: [(a, b) for a, b in p if b < n] for s, p in lists.items()}
     lists = {s: p for s, p in lists.items() if p}
     band = lib.check_band(max(lists) if band is None else band)
-    lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(graph_iterations)
     if n > lib.GRAPH_MAX_NODES:
         raise lib.SslamHipError(f"odometry_graph: {n} frames, the pose graph takes {lib.GRAPH_MAX_NODES}")
     return tuple(lists), lists, n, band
 
 
-def _sequence_preamble(pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber,
-                       iterations, subcell, band, huber_chi, damping, graph_iterations, more=lambda: None) -> tuple:
-    """What odometry_graph and odometry_loop_graph do alike before they match: every argument judged (more(): the caller's own,
-    where they always stood), the frames extracted once, the geometry bank, the keypoints' depth, the spacings' pair list."""
+@dataclass
+class _Sequence:
+    """What a graph call works on once its arguments are judged: the geometry bank kp and the depth under it, the pair list of every
+    spacing that holds one, the n frames they name (the graph's nodes), the band, the camera and the true poses or None; from the
+    frames themselves also what was extracted, ex, and the rule to match it under."""
+    kp: torch.Tensor
+    lists: dict
+    n: int
+    band: int
+    camera: object
+    poses: object
+    kp_depth: torch.Tensor | None = None
+    ex: dict | None = None
+    rule: MatchRule | None = None
+
+    @property
+    def pairs(self) -> list:
+        return [pr for s in self.lists for pr in self.lists[s]]
+
+
+def _sequence_preamble(pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, subcell, band) -> _Sequence:
+    """What odometry_graph and odometry_loop_graph do alike before they match: the sequence's arguments judged, the frames extracted
+    once, the geometry bank, the keypoints' depth."""
     check_subcell(subcell)
     src = tokens if tokens is not None else images_u8
     if src is None:
         raise ValueError("images_u8 or tokens= required")
-    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
-    opt = more()
-    camera = _check_arguments(depth, None, camera, poses, threshold, hypotheses, seed, n)
-    _check_refine(True, threshold, huber, iterations)
+    _, lists, n, band = _check_graph(spacings, int(src.shape[0]), num_pairs, band)
+    camera = _check_arguments(depth, None, camera, poses, n)
     rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
     ex = pipe.extract(pipe.tokens_from_images(images_u8[:n]) if tokens is None else tokens[:n], None)
     kp = geometry_bank(ex, subcell)
-    return lists, n, band, opt, camera, rule, ex, kp, gather_keypoint_depth(pipe, depth, kp, n), [pr for s in lists for pr in lists[s]]
+    return _Sequence(kp, lists, n, band, camera, poses, gather_keypoint_depth(pipe, depth, kp, n), ex, rule)
 
 
-def _result_preamble(result, keys, depth, kp_depth, camera, poses, spacings, num_pairs, threshold, hypotheses, seed, huber, iterations,
-                     subcell, band, huber_chi, damping, graph_iterations, more=lambda: None) -> tuple:
-    """What odometry_result_graph and odometry_result_loop_graph do alike: the result must hold `keys` per frame; the geometry
-    bank, the result's spacings if none are given, every argument judged (more(): the caller's own)."""
+def _result_preamble(pipe, result, keys, depth, kp_depth, camera, poses, spacings, num_pairs, subcell, band) -> _Sequence:
+    """What odometry_result_graph and odometry_result_loop_graph do alike: the result must hold `keys` per frame; the geometry bank,
+    the result's spacings if none are given, the sequence's arguments judged, the keypoints' depth gathered unless it is given."""
     if not isinstance(result, dict) or "frames" not in result or any(key not in result["frames"] for key in keys):
         raise ValueError("a StreamingSequence / run_directory result expected")
     kp = geometry_bank(result["frames"], subcell)
@@ -389,11 +386,9 @@ def _result_preamble(result, keys, depth, kp_depth, camera, poses, spacings, num
         spacings = tuple(sorted(k for k in result if isinstance(k, (int, np.integer)) and not isinstance(k, bool)))
     if any(s not in result for s in spacings):
         raise ValueError(f"the result holds no pairs at every spacing of {tuple(spacings)!r}")
-    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band, huber_chi, damping, graph_iterations)
-    opt = more()
-    camera = _check_arguments(depth, kp_depth, camera, poses, threshold, hypotheses, seed, n, kp.shape)
-    _check_refine(True, threshold, huber, iterations)
-    return kp, lists, n, band, opt, camera
+    _, lists, n, band = _check_graph(spacings, int(kp.shape[0]), num_pairs, band)
+    camera = _check_arguments(depth, kp_depth, camera, poses, n, kp.shape)
+    return _Sequence(kp, lists, n, band, camera, poses, gather_keypoint_depth(pipe, depth, kp, n) if kp_depth is None else kp_depth)
 
 
 def _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations) -> dict:
@@ -409,41 +404,35 @@ def _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, g
                                     damping=damping, iterations=graph_iterations)
 
 
-def _graph_flat(g) -> list:
-    """A graph's device tensors as float64 pieces of one read-back, in _graph_host's order."""
-    return [g["C"].reshape(-1)] + [g[key].to(torch.float64).reshape(1) for key in _GRAPH_INT] + \
-           [g["cost_in"].reshape(1), g["cost"].reshape(1), g["edge_chi2"]]
+def _read_graph(rb, name, g) -> None:
+    """A graph's device tensors join the read-back rb under '<name>.<key>'; a sparse graph's cg_steps with them."""
+    for key in _GRAPH_INT + (("cg_steps",) if "cg_steps" in g else ()):
+        rb.add(f"{name}.{key}", g[key], np.int64)
+    for key in ("C", "cost_in", "cost", "edge_chi2"):
+        rb.add(f"{name}.{key}", g[key], np.float64)
 
 
-def _graph_words(n: int, n_pairs: int) -> int:
-    """How many numbers _graph_flat lays out for a graph of n nodes over n_pairs listed pairs: C, the five integers, the two costs,
-    edge_chi2.  Whatever follows a graph in a read-back starts there: the one place that says so."""
-    return 12 * n + len(_GRAPH_INT) + 2 + n_pairs
-
-
-def _graph_host(rest, n, pairs, poses) -> dict:
-    """The host-side figures of a graph from the _graph_words(n, len(pairs)) numbers _graph_flat laid out."""
-    C = rest[:12 * n].reshape(n, 3, 4)
-    C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
-    graph = {"trajectory": np.stack([np.linalg.inv(c) for c in C44]), "pairs": pairs}
-    graph.update({key: int(rest[12 * n + i]) for i, key in enumerate(_GRAPH_INT)})
-    graph["cost_in"], graph["cost"] = float(rest[12 * n + 5]), float(rest[12 * n + 6])
-    graph["edge_chi2"] = rest[12 * n + 7:_graph_words(n, len(pairs))].copy()
+def _graph_host(host, name, pairs, poses) -> dict:
+    """The host-side figures of the graph _read_graph recorded as `name`."""
+    graph = {"trajectory": camera_to_world(host[name + ".C"]), "pairs": pairs}
+    graph.update({key: int(host[f"{name}.{key}"]) for key in _GRAPH_INT})
+    graph.update(cost_in=float(host[name + ".cost_in"]), cost=float(host[name + ".cost"]), edge_chi2=host[name + ".edge_chi2"])
     if poses is not None:
-        graph["ate"] = ate_summary(graph["trajectory"], np.asarray(poses, dtype=np.float64)[:n])
+        graph["ate"] = ate_summary(graph["trajectory"], np.asarray(poses, dtype=np.float64)[:len(graph["trajectory"])])
+    if name + ".cg_steps" in host:
+        graph["cg_steps"] = host[name + ".cg_steps"]
     return graph
 
 
-def _spacings_and_graph(host, rest, lists, pairs, n, poses) -> dict:
-    """The read-back split: `host`, a row per pair, into every spacing's dictionary; `rest` (_graph_flat's numbers first) into 'graph'."""
+def _spacings_and_graph(host, lists, pairs, poses) -> dict:
+    """Every spacing's dictionary from its rows of the launch, and 'graph'."""
     out, at = {}, 0
     for s in lists:
-        out[s] = _unpack(host[at:at + len(lists[s])], lists[s], poses, s, True)
+        out[s] = _pairs_host(host, slice(at, at + len(lists[s])), lists[s], poses, s)
         at += len(lists[s])
-    graph = _graph_host(rest, n, pairs, poses)
+    out["graph"] = _graph_host(host, "graph", pairs, poses)
     if poses is not None:
-        graph["ate_chain"] = out[1]["ate"]
-    out["graph"] = graph
+        out["graph"]["ate_chain"] = out[1]["ate"]
     return out
 
 
@@ -461,52 +450,48 @@ def check_tracks(tracks):
 
 
 TRACK_DEFAULTS = dict(threshold=3.0, min_obs=2)
-_TRACK_ROWS = ("length", "status", "n_kept", "rms")
-
-
-def _tracks_device(pipe, kp, kp_depth, lists, matches, ref, C, n, camera, opt, confidence) -> list:
-    """Links from the spacing-1 rows masked by the refinement's inlier_of_slot, their ids, the landmarks under the graph's C ->
-    float64 pieces for the one read-back, in _tracks_host's order.  No host read."""
+def _tracks_device(pipe, rb, seq, matches, ref, C, opt, confidence) -> None:
+    """Links from the spacing-1 rows masked by the refinement's inlier_of_slot, their ids, the landmarks under the graph's C; what
+    the host wants of them joins the read-back rb under 'tracks.<key>'.  No host read."""
+    lists, n = seq.lists, seq.n
     at = sum(len(lists[s]) for s in list(lists)[:list(lists).index(1)])
     rows = slice(at, at + len(lists[1]))
     links = pipe.link_matches([a for a, _ in lists[1]], [b for _, b in lists[1]], {key: matches[key][rows] for key in ("matches", "match_count")},
-                              mask=ref["inlier_of_slot"][rows], n_frames=n, k=int(kp.shape[1]))
+                              mask=ref["inlier_of_slot"][rows], n_frames=n, k=int(seq.kp.shape[1]))
     tr = pipe.track_ids(links)
-    lm = pipe.landmarks(kp[:n], kp_depth[:n], C.reshape(n, 12), tr, camera, opt["threshold"], opt["min_obs"],
+    lm = pipe.landmarks(seq.kp[:n], seq.kp_depth[:n], C.reshape(n, 12), tr, seq.camera, opt["threshold"], opt["min_obs"],
                         weights=None if confidence is None else confidence[:n])
-    f64 = lambda t: t.to(torch.float64).reshape(-1)
-    return [f64(tr["n_tracks"]), f64(tr["track_id"]), f64(tr["length"]), f64(lm["status"]), f64(lm["n_kept"]), lm["rms"], lm["xyz"].reshape(-1)]
+    rb.add("tracks.n_tracks", tr["n_tracks"], np.int64)
+    rb.add("tracks.track_id", tr["track_id"], np.int32)
+    for key, t, dtype in (("length", tr["length"], np.int64), ("status", lm["status"], np.int32), ("n_kept", lm["n_kept"], np.int32),
+                          ("rms", lm["rms"], np.float64), ("xyz", lm["xyz"], np.float64)):
+        rb.add("tracks." + key, t, dtype, rows="tracks.n_tracks")         # a row per keypoint on the device, n_tracks of them filled
 
 
-def _tracks_host(rest, n, k) -> dict:
-    """The host-side figures of the tracks from the 1 + 8 n k numbers _tracks_device laid out."""
+def _tracks_host(host) -> dict:
+    """The host-side figures of the tracks _tracks_device recorded."""
     from .track_numpy import length_statistics
-    N = n * k
-    nt = int(rest[0])
-    track_id = rest[1:1 + N].astype(np.int32).reshape(n, k)
-    cols = {key: rest[1 + (i + 1) * N:1 + (i + 2) * N][:nt] for i, key in enumerate(_TRACK_ROWS)}
-    out = {"n_tracks": nt, "length": length_statistics(cols["length"].astype(np.int64), [nt]), "track_id": track_id,
-           "landmarks": rest[1 + 5 * N:1 + 8 * N].reshape(N, 3)[:nt].copy(), "status": cols["status"].astype(np.int32),
-           "n_kept": cols["n_kept"].astype(np.int32), "rms": cols["rms"].copy()}
+    nt = int(host["tracks.n_tracks"][0])
+    out = {"n_tracks": nt, "length": length_statistics(host["tracks.length"], [nt]), "track_id": host["tracks.track_id"],
+           "landmarks": host["tracks.xyz"], "status": host["tracks.status"], "n_kept": host["tracks.n_kept"], "rms": host["tracks.rms"]}
     del out["length"]["n_tracks"]
     return out
 
 
-def _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi, damping,
-           graph_iterations, weight=None, tracks=None, confidence=None) -> dict:
-    """One RANSAC and one refinement launch over the concatenated pair lists, the chain, the graph, ONE read-back.  weight: the
+def _graph(pipe, seq, matches, pose, graph, weight=None, tracks=None, confidence=None) -> dict:
+    """One RANSAC and one refinement launch over the concatenated pair lists of seq, the chain, the graph, ONE read-back.  weight: the
     (P, n1) weights of the weighted refinement, whose info the graph then reads as it reads the unweighted one.  tracks:
     check_tracks' dictionary - the links, ids and landmarks (weighted by `confidence` where given) join the same read-back."""
-    pairs = [pr for s in lists for pr in lists[s]]
-    packed, ref = _launch(pipe, kp, kp_depth, pairs, matches, camera, threshold, hypotheses, seed, True, huber, iterations, weight)
-    g = _graph_device(pipe, ref, pairs, lists, n, poses, band, huber_chi, damping, graph_iterations)
-    more = [] if tracks is None else _tracks_device(pipe, kp, kp_depth, lists, matches, ref, g["C"], n, camera, tracks, confidence)
-    flat = torch.cat([packed.reshape(-1)] + _graph_flat(g) + more).cpu().numpy()          # the ONE read-back
-    P, w = len(pairs), int(packed.shape[1])
-    host, rest = flat[:P * w].reshape(P, w), flat[P * w:]
-    out = _spacings_and_graph(host, rest, lists, pairs, n, poses)
+    rb, pairs = Readback(), seq.pairs
+    ref = _launch(pipe, rb, seq.kp, seq.kp_depth, pairs, matches, seq.camera, pose, weight)
+    g = _graph_device(pipe, ref, pairs, seq.lists, seq.n, seq.poses, seq.band, graph.huber_chi, graph.damping, graph.iterations)
+    _read_graph(rb, "graph", g)
     if tracks is not None:
-        out["tracks"] = _tracks_host(rest[_graph_words(n, P):], n, int(kp.shape[1]))
+        _tracks_device(pipe, rb, seq, matches, ref, g["C"], tracks, confidence)
+    host = rb.fetch()                                        # the ONE read-back
+    out = _spacings_and_graph(host, seq.lists, pairs, seq.poses)
+    if tracks is not None:
+        out["tracks"] = _tracks_host(host)
     return out
 
 
@@ -534,16 +519,14 @@ def odometry_graph(pipe, images_u8=None, depth=None, camera=None, poses=None, sp
     'n_tracks', 'length' (mean, median, max, share_ge_2, histogram), 'landmarks' (n_tracks, 3) world points, 'status', 'n_kept',
     'rms' (n_tracks,) and 'track_id' (N, K).  With tracks=None the call returns and launches exactly what it did before.
     Nobody has measured this on real RGB-D data: no real sequence was at hand when this was written."""
-    def more():
-        _check_weights(pipe, weights, True)
-        return check_tracks(tracks)
-    lists, n, band, opt, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
-        pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber, iterations, subcell, band,
-        huber_chi, damping, graph_iterations, more)
-    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=[a for a, _ in pairs], second=[b for _, b in pairs], rule=rule)
-    weight = None if weights is None else pipe.match_weights(ex["confidence"], [a for a, _ in pairs], [b for _, b in pairs], matches, weights)
-    return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
-                  damping, graph_iterations, weight, opt, None if weights is None or opt is None else ex["confidence"])
+    pose = PoseSettings(threshold, hypotheses, seed, True, huber, iterations, weights)
+    pose.check_pipeline(pipe)
+    graph, opt = GraphSettings(huber_chi, damping, graph_iterations), check_tracks(tracks)
+    seq = _sequence_preamble(pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, subcell, band)
+    ex, first, second = seq.ex, [a for a, _ in seq.pairs], [b for _, b in seq.pairs]
+    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=first, second=second, rule=seq.rule)
+    weight = None if weights is None else pipe.match_weights(ex["confidence"], first, second, matches, weights)
+    return _graph(pipe, seq, matches, pose, graph, weight, opt, None if weights is None or opt is None else ex["confidence"])
 
 
 def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=None, spacings=None, num_pairs=None, threshold: float = 3.0,
@@ -552,18 +535,14 @@ def odometry_result_graph(pipe, result: dict, depth=None, camera=None, poses=Non
     """odometry_graph() for a StreamingSequence.result() / run_frames / run_directory result: nothing is extracted or matched again.
     spacings: those of the result if None.  depth= / kp_depth=, and everything else: as odometry_result() and odometry_graph()
     take them."""
-    kp, lists, n, band, _, camera = _result_preamble(result, ("keypoints_pixel",), depth, kp_depth, camera, poses, spacings, num_pairs, threshold,
-                                                     hypotheses, seed, huber, iterations, subcell, band, huber_chi, damping, graph_iterations)
-    matches = {key: torch.cat([result[s][key][:len(lists[s])] for s in lists]) for key in ("matches", "match_count")}
-    if kp_depth is None:
-        kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
-    return _graph(pipe, kp, kp_depth, lists, matches, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
-                  damping, graph_iterations)
+    pose, graph = PoseSettings(threshold, hypotheses, seed, True, huber, iterations), GraphSettings(huber_chi, damping, graph_iterations)
+    seq = _result_preamble(pipe, result, ("keypoints_pixel",), depth, kp_depth, camera, poses, spacings, num_pairs, subcell, band)
+    matches = {key: torch.cat([result[s][key][:len(seq.lists[s])] for s in seq.lists]) for key in ("matches", "match_count")}
+    return _graph(pipe, seq, matches, pose, graph)
 
 
 # ------------------------------------------------------------------------------------------------------------------ loop closures
 LOOP_DEFAULTS = dict(min_gap=30, min_sim=0.3, per_frame=2, suppress=5, min_inliers=12)
-_LOOP_INT = ("status", "inlier_count")
 
 
 def check_loops(loops, cg_iterations=512, cg_tol=1e-3, prune_chi=None) -> dict:
@@ -583,55 +562,40 @@ def check_loops(loops, cg_iterations=512, cg_tol=1e-3, prune_chi=None) -> dict:
     return opt
 
 
-def _sparse_flat(r) -> list:
-    return _graph_flat(r) + [r["cg_steps"].to(torch.float64)]
-
-
-def _sparse_host(rest, n, pairs, poses) -> dict:
-    graph = _graph_host(rest, n, pairs, poses)
-    at = _graph_words(n, len(pairs))
-    graph["cg_steps"] = rest[at:at + lib.SPARSE_MAX_ITER].astype(np.int64)
-    return graph
-
-
-def _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band, huber_chi,
-                damping, graph_iterations, opt, cg_iterations, cg_tol, prune_chi) -> dict:
+def _loop_graph(pipe, seq, matches, cand, pose, graph, opt, cg_iterations, cg_tol, prune_chi) -> dict:
     """One RANSAC and one refinement launch over the spacings' pairs followed by the candidate slots, the chain and the banded graph
     over the former, the sparse graph over all of them from the banded graph's poses, ONE read-back."""
-    pairs = [pr for s in lists for pr in lists[s]]
-    P, L, dev = len(pairs), int(cand["first"].shape[0]), kp.device
+    rb, pairs = Readback(), seq.pairs
+    P, dev = len(pairs), seq.kp.device
     of = torch.tensor([a for a, _ in pairs], dtype=torch.int32, device=dev)
     first = torch.cat([of, cand["first"]])
     second = torch.cat([torch.tensor([b for _, b in pairs], dtype=torch.int32, device=dev), cand["second"]])
-    packed, ref = _launch_lists(pipe, kp, kp_depth, first, second, matches, camera, threshold, hypotheses, seed, True, huber, iterations)
-    g = _graph_device(pipe, {key: ref[key][:P] for key in ("T", "info", "status")}, pairs, lists, n, poses, band, huber_chi, damping,
-                      graph_iterations)
+    ref = _launch_lists(pipe, rb, seq.kp, seq.kp_depth, first, second, matches, seq.camera, pose)
+    g = _graph_device(pipe, {key: ref[key][:P] for key in ("T", "info", "status")}, pairs, seq.lists, seq.n, seq.poses, seq.band,
+                      graph.huber_chi, graph.damping, graph.iterations)
     kept = (cand["first"] >= 0) & (ref["status"][P:] != lib.REFINE_NOT_ATTEMPTED) & (ref["inlier_count"][P:] >= int(opt["min_inliers"]))
     absent = torch.full_like(first, -1)
     gfirst = torch.cat([of, torch.where(kept, cand["first"], absent[P:])])
-    sparse = lambda f: pipe.optimize_pose_graph_sparse(f, second, ref, ref, n, g["C"], huber_chi, damping, graph_iterations, cg_iterations, cg_tol)
-    runs = [sparse(gfirst)]
+    sparse = lambda f: pipe.optimize_pose_graph_sparse(f, second, ref, ref, seq.n, g["C"], graph.huber_chi, graph.damping, graph.iterations,
+                                                       cg_iterations, cg_tol)
+    runs = {"loop_graph": sparse(gfirst)}
     if prune_chi is not None:
-        runs.append(sparse(torch.where(runs[0]["edge_chi2"] > float(prune_chi) * float(prune_chi), absent, gfirst)))
-    pieces = [packed.reshape(-1)] + _graph_flat(g) + [x for r in runs for x in _sparse_flat(r)] + \
-             [cand[key].to(torch.float64) for key in ("first", "second", "sim", "count")] + [kept.to(torch.float64)]
-    flat = torch.cat(pieces).cpu().numpy()                  # the ONE read-back
-    w = int(packed.shape[1])
-    host, rest = flat[:(P + L) * w].reshape(P + L, w), flat[(P + L) * w:]
-    out = _spacings_and_graph(host, rest, lists, pairs, n, poses)
-    rest = rest[_graph_words(n, P):]
-    tail = rest[len(runs) * (_graph_words(n, P + L) + lib.SPARSE_MAX_ITER):]
-    lf, ls = tail[:L].astype(np.int32), tail[L:2 * L].astype(np.int32)
-    rows = host[P:]
-    r = rows[:, 18:]
-    out["loops"] = {"first": lf, "second": ls, "sim": tail[2 * L:3 * L].astype(np.float32), "count": tail[3 * L:3 * L + n].astype(np.int32),
-                    "kept": tail[3 * L + n:] != 0, "match_count": rows[:, 16].astype(np.int64), "T": _as44(r[:, :12]),
-                    "status": r[:, 12].astype(np.int64), "inlier_count": r[:, 15].astype(np.int64), "info": info_matrix(r[:, 19:40])}
-    all_pairs = pairs + [(int(a), int(b)) for a, b in zip(lf, ls)]
-    names = ["loop_graph"] if prune_chi is None else ["loop_graph_unpruned", "loop_graph"]
-    for name in names:
-        out[name] = _sparse_host(rest, n, all_pairs, poses)
-        rest = rest[_graph_words(n, P + L) + lib.SPARSE_MAX_ITER:]
+        gone = runs["loop_graph"]["edge_chi2"] > float(prune_chi) * float(prune_chi)
+        runs = {"loop_graph_unpruned": runs["loop_graph"], "loop_graph": sparse(torch.where(gone, absent, gfirst))}
+    _read_graph(rb, "graph", g)
+    for name, r in runs.items():
+        _read_graph(rb, name, r)
+    for key, dtype in (("first", np.int32), ("second", np.int32), ("sim", np.float32), ("count", np.int32)):
+        rb.add("loops." + key, cand[key], dtype)
+    rb.add("loops.kept", kept, np.bool_)
+    host = rb.fetch()                                        # the ONE read-back
+    out = _spacings_and_graph(host, seq.lists, pairs, seq.poses)
+    out["loops"] = {key: host["loops." + key] for key in ("first", "second", "sim", "count", "kept")}
+    out["loops"].update(match_count=host["match_count"][P:], T=_as44(host["refine.T"][P:]), status=host["refine.status"][P:],
+                        inlier_count=host["refine.inlier_count"][P:], info=info_matrix(host["refine.info"][P:]))
+    all_pairs = pairs + [(int(a), int(b)) for a, b in zip(host["loops.first"], host["loops.second"])]
+    for name in runs:
+        out[name] = _graph_host(host, name, all_pairs, seq.poses)
     return out
 
 
@@ -653,16 +617,15 @@ def odometry_loop_graph(pipe, images_u8=None, depth=None, camera=None, poses=Non
     candidate slots), 'status', 'iterations', 'used_edges', 'skipped_edges', 'failed_row', 'cost_in', 'cost', 'edge_chi2' (one per
     pair of 'pairs'), 'cg_steps' (16,), with poses 'ate'; with prune_chi 'loop_graph' is the second launch's and
     'loop_graph_unpruned' the first's.  Nobody has measured this on real RGB-D data."""
-    lists, n, band, opt, camera, rule, ex, kp, kp_depth, pairs = _sequence_preamble(
-        pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, threshold, hypotheses, seed, huber, iterations, subcell, band,
-        huber_chi, damping, graph_iterations, lambda: check_loops(loops, cg_iterations, cg_tol, prune_chi))
+    pose, graph = PoseSettings(threshold, hypotheses, seed, True, huber, iterations), GraphSettings(huber_chi, damping, graph_iterations)
+    opt = check_loops(loops, cg_iterations, cg_tol, prune_chi)
+    seq = _sequence_preamble(pipe, images_u8, tokens, depth, camera, poses, spacings, num_pairs, rule, subcell, band)
+    ex, pairs, dev = seq.ex, seq.pairs, seq.kp.device
     cand = pipe.find_loop_candidates(ex["descriptors"], ex["scores"], opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])
-    dev = kp.device
     first = torch.cat([torch.tensor([a for a, _ in pairs], dtype=torch.int32, device=dev), cand["first"]])
     second = torch.cat([torch.tensor([b for _, b in pairs], dtype=torch.int32, device=dev), cand["second"]])
-    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=first, second=second, rule=rule)
-    return _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band,
-                       huber_chi, damping, graph_iterations, opt, cg_iterations, cg_tol, prune_chi)
+    matches = pipe.match_pairs(ex["descriptors"], ex["scores"], first=first, second=second, rule=seq.rule)
+    return _loop_graph(pipe, seq, matches, cand, pose, graph, opt, cg_iterations, cg_tol, prune_chi)
 
 
 def odometry_result_loop_graph(pipe, result: dict, depth=None, camera=None, poses=None, spacings=None, num_pairs=None, threshold: float = 3.0,
@@ -673,15 +636,13 @@ def odometry_result_loop_graph(pipe, result: dict, depth=None, camera=None, pose
     spacings' pairs keep the match lists the sequence was run with; only the candidate slots are matched, in one match_pairs call
     under `rule` (MatchRule.mnn_ratio(0.9) if None - give the rule the sequence was run with).  Everything else: as
     odometry_result_graph() and odometry_loop_graph() take it."""
-    kp, lists, n, band, opt, camera = _result_preamble(
-        result, ("keypoints_pixel", "descriptors", "scores"), depth, kp_depth, camera, poses, spacings, num_pairs, threshold, hypotheses, seed, huber,
-        iterations, subcell, band, huber_chi, damping, graph_iterations, lambda: check_loops(loops, cg_iterations, cg_tol, prune_chi))
+    pose, graph = PoseSettings(threshold, hypotheses, seed, True, huber, iterations), GraphSettings(huber_chi, damping, graph_iterations)
+    opt = check_loops(loops, cg_iterations, cg_tol, prune_chi)
+    seq = _result_preamble(pipe, result, ("keypoints_pixel", "descriptors", "scores"), depth, kp_depth, camera, poses, spacings, num_pairs, subcell,
+                           band)
     rule = MatchRule.mnn_ratio(0.9) if rule is None else rule
-    desc, scores = result["frames"]["descriptors"][:n], result["frames"]["scores"][:n]
+    desc, scores = result["frames"]["descriptors"][:seq.n], result["frames"]["scores"][:seq.n]
     cand = pipe.find_loop_candidates(desc, scores, opt["min_gap"], opt["min_sim"], opt["per_frame"], opt["suppress"])
     far = pipe.match_pairs(desc, scores, first=cand["first"], second=cand["second"], rule=rule)
-    matches = {key: torch.cat([result[s][key][:len(lists[s])] for s in lists] + [far[key]]) for key in ("matches", "match_count")}
-    if kp_depth is None:
-        kp_depth = gather_keypoint_depth(pipe, depth, kp, n)
-    return _loop_graph(pipe, kp, kp_depth, lists, matches, cand, n, camera, poses, threshold, hypotheses, seed, huber, iterations, band,
-                       huber_chi, damping, graph_iterations, opt, cg_iterations, cg_tol, prune_chi)
+    matches = {key: torch.cat([result[s][key][:len(seq.lists[s])] for s in seq.lists] + [far[key]]) for key in ("matches", "match_count")}
+    return _loop_graph(pipe, seq, matches, cand, pose, graph, opt, cg_iterations, cg_tol, prune_chi)

@@ -47,7 +47,8 @@ from __future__ import annotations
 import torch
 
 from . import lib
-from .pipeline import N_PREFIX, SequencePipeline, _checked_rule
+from .pipeline import N_PREFIX, GraphSettings, PoseSettings, SequencePipeline, _checked_rule
+from .readback import Readback
 
 
 BANK_KEYS = ("descriptors", "scores", "intensity", "keypoints_pixel")      # what an earlier frame is kept for
@@ -295,6 +296,16 @@ class RuleFrameStepper(FrameStepper):
         self.rule = _checked_rule(rule, pipe.cfg.num_keypoints)      # before anything is allocated
         super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=spacings)
 
+    def _take_depth(self, depth_u16) -> None:
+        """The depth input of the steppers that take one (they own self.depth, the static buffer): the frame's raw depth image is
+        judged, the step captured first if it has not been - before the frame's depth goes into its static buffer, as the image
+        does in FrameStepper.step - and the image copied."""
+        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dtype != torch.uint16 or depth_u16.numel() != self.depth.numel():
+            raise ValueError(f"depth_u16 must be a uint16 tensor of shape {tuple(self.depth.shape[1:])}")
+        if self.use_graph and self._graph is None:
+            self._capture()
+        self.depth.copy_(depth_u16.reshape(self.depth.shape), non_blocking=True)
+
 
 class RankedFrameStepper(RuleFrameStepper):
     """RuleFrameStepper whose step also ranks: behind the finalize launch, on the same one stream, sslam_match_rank keeps the
@@ -351,16 +362,10 @@ class PoseFrameStepper(RuleFrameStepper):
                  use_graph: bool = True, tokens_in: bool = False, rule=None, threshold: float = 3.0, hypotheses: int = 256,
                  seed: int = 0, refine: bool = False, huber=None, iterations: int = 5, weights=None):
         from .evaluation import Camera, check_depth_size
-        from .odometry import _check_weights
         from .pipeline import MatchRule
-        self.threshold, self.hypotheses, self.seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
-        if not isinstance(refine, bool):
-            raise ValueError(f"refine must be a bool, got {refine!r}")
-        self.refine = refine
-        _check_weights(pipe, weights, refine)                         # before anything is allocated
-        self.weights = weights
-        if refine:
-            self.huber, self.iterations = lib.check_huber(self.threshold / 3.0 if huber is None else huber), lib.check_iterations(iterations)
+        st = self.settings = PoseSettings(threshold, hypotheses, seed, refine, huber, iterations, weights)      # before anything is allocated
+        st.check_pipeline(pipe)
+        self.threshold, self.huber, self.refine, self.weights = st.threshold, st.huber, st.refine, st.weights
         self.camera = Camera() if camera is None else camera
         check_depth_size(depth_width, depth_height, self.camera)      # before anything is allocated
         super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=None,
@@ -375,28 +380,23 @@ class PoseFrameStepper(RuleFrameStepper):
         self.weight = torch.zeros((1, K), dtype=torch.float32, device=dev) if weights is not None else None
 
     def _after_match(self) -> None:
-        p = self.pipe
+        p, st = self.pipe, self.settings
         kp = p.geometry_keypoints(self.pair)          # the refined bank on a pipeline with subcell=True, else the cell centres
         p.keypoint_depth(self.depth, kp[1:2], out=self.kp_depth[1:2])
-        p.estimate_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.threshold,
-                         self.hypotheses, self.seed, out=self.pose)
-        if self.refine:
-            if self.weights is not None:
-                p.match_weights(self.pair["confidence"], self._first, self._second, self.m, self.weights, out=self.weight)
-            p.refine_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.pose, self.threshold,
-                           self.huber, self.iterations, out=self.refined, weights=self.weight)
-            if self.weights is not None:
+        p.estimate_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, st.threshold, st.hypotheses, st.seed, out=self.pose)
+        if st.refine:
+            if st.weights is not None:
+                p.match_weights(self.pair["confidence"], self._first, self._second, self.m, st.weights, out=self.weight)
+            p.refine_poses(kp, self.kp_depth, self._first, self._second, self.m, self.camera, self.pose, st.threshold, st.huber, st.iterations,
+                           out=self.refined, weights=self.weight)
+            if st.weights is not None:
                 self.pair["confidence"][0].copy_(self.pair["confidence"][1])
         self.kp_depth[0].copy_(self.kp_depth[1])
 
     @torch.no_grad()
     def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
         """image_u8, tokens: as FrameStepper.step takes them; depth_u16: (h, w) or (1, h, w) uint16, the frame's raw depth image."""
-        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dtype != torch.uint16 or depth_u16.numel() != self.depth.numel():
-            raise ValueError(f"depth_u16 must be a uint16 tensor of shape {tuple(self.depth.shape[1:])}")
-        if self.use_graph and self._graph is None:
-            self._capture()                      # before the frame's depth goes into its static buffer, as the image does in the parent
-        self.depth.copy_(depth_u16.reshape(self.depth.shape), non_blocking=True)
+        self._take_depth(depth_u16)
         first = self.n_frames == 0
         out = super().step(image_u8, tokens)
         out["pose"] = None if first else {k: v[0] for k, v in self.pose.items()}
@@ -414,8 +414,9 @@ class WindowPoseFrameStepper(RuleFrameStepper):
     odometry_graph.  step() takes the frame's raw depth image beside it; behind the matcher's finalize launch, on the same one
     stream - as ordinary launches or inside the captured graph - the depth under this frame's keypoints is gathered
     (sslam_keypoint_depth) into the static slot of a depth ring that lies beside the feature ring, ONE sslam_pose_ransac_pairs and
-    ONE sslam_pose_refine_pairs launch run over the step's S pairs with the matcher's own first_slot / second_slot lists (an absent
-    pair comes out with refinement status 3), and sslw_window_step (include/sslam_window.h) admits the refined pairs into a ring of
+    ONE sslam_pose_refine_pairs launch run over the step's pairs with the matcher's own pair_first / pair_second lists (an absent
+    pair comes out with refinement status 3; a subclass may have asked for extra pairs behind the S spacing rows), and
+    sslw_window_step (include/sslam_window.h), on the S spacing rows, admits the refined pairs into a ring of
     the last `window` frames' edges, predicts the frame's pose from the nearest admitted pair and optimises the window's poses with
     its oldest frame held.  The window's frame counter is device memory like the stepper's own, so no host value enters the
     body.  The static slot is then handed over to the ring with the frame's features.
@@ -436,11 +437,11 @@ class WindowPoseFrameStepper(RuleFrameStepper):
         from .evaluation import Camera, check_depth_size
         from .pipeline import MatchRule
         sp = _checked_spacings(spacings, below=2 ** 31)                  # everything is judged before anything is allocated
-        self.threshold, self.hypotheses, self.seed = lib.check_threshold(threshold), lib.check_hypotheses(hypotheses), lib.check_seed(seed)
-        self.huber, self.iterations = lib.check_huber(self.threshold / 3.0 if huber is None else huber), lib.check_iterations(iterations)
+        st = self.settings = PoseSettings(threshold, hypotheses, seed, True, huber, iterations)
+        self.threshold, self.huber = st.threshold, st.huber
         self.window, _, self.capacity, _ = lib.check_window_sizes(max(sp) + 1 if window is None else window, len(sp), capacity)
-        self.min_inliers, self.huber_chi = lib.check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1), lib.check_positive("huber_chi", huber_chi)
-        self.damping, self.graph_iterations = lib.check_damping(damping), lib.check_graph_iterations(graph_iterations)
+        self.min_inliers = lib.check_int("min_inliers", min_inliers, 0, 2 ** 31 - 1)
+        self.graph_settings = GraphSettings(huber_chi, damping, graph_iterations)
         self.camera = Camera() if camera is None else camera
         check_depth_size(depth_width, depth_height, self.camera)
         super().__init__(pipe, height, width, use_graph=use_graph, tokens_in=tokens_in, spacings=sp,
@@ -450,19 +451,26 @@ class WindowPoseFrameStepper(RuleFrameStepper):
         self.kp_depth = torch.full((self.ring + 1, K), -1, dtype=torch.int32, device=dev)      # the depth ring, slot for slot beside the bank
         self.pose = pipe.alloc_pose(P, K)
         self.refined = pipe.alloc_pose_refine(P, K)
+        # the spacings' rows, which the window reads: all of the rows, unless a subclass asked for extra pairs behind them
+        self._window_rows = {k: self.refined[k][:len(sp)] for k in ("T", "info", "status", "inlier_count")}
         self.win = pipe.alloc_pose_window(self.window, sp, self.capacity)
 
     def _after_match(self) -> None:
-        p, ring = self.pipe, self.ring
+        p, ring, st, g = self.pipe, self.ring, self.settings, self.graph_settings
         kp = p.geometry_keypoints(self.bank)
         p.keypoint_depth(self.depth, kp[ring:ring + 1], out=self.kp_depth[ring:ring + 1])
-        p.estimate_poses(kp, self.kp_depth, self.first_slot, self.second_slot, self.m, self.camera, self.threshold, self.hypotheses,
-                         self.seed, out=self.pose)
-        p.refine_poses(kp, self.kp_depth, self.first_slot, self.second_slot, self.m, self.camera, self.pose, self.threshold, self.huber,
-                       self.iterations, out=self.refined)
-        p.pose_window_step(self.win, self.refined, None, self.min_inliers, self.huber_chi, self.damping, self.graph_iterations)
+        p.estimate_poses(kp, self.kp_depth, self.pair_first, self.pair_second, self.m, self.camera, st.threshold, st.hypotheses, st.seed,
+                         out=self.pose)
+        p.refine_poses(kp, self.kp_depth, self.pair_first, self.pair_second, self.m, self.camera, self.pose, st.threshold, st.huber,
+                       st.iterations, out=self.refined)
+        p.pose_window_step(self.win, self._window_rows, None, self.min_inliers, g.huber_chi, g.damping, g.iterations)
+        self._after_window()
         torch.remainder(self._t, ring, out=self._slot)                   # the ring slot the frame's features take, right after this
         self.kp_depth[:ring].index_copy_(0, self._slot, self.kp_depth[ring:ring + 1])
+
+    def _after_window(self) -> None:
+        """What a subclass enqueues behind the window step, before the static depth slot is handed over to the ring
+        (LoopWindowPoseFrameStepper: its edge log)."""
 
     def _reset_window(self) -> None:
         st = self.win["state"]
@@ -477,11 +485,7 @@ class WindowPoseFrameStepper(RuleFrameStepper):
     @torch.no_grad()
     def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
         """image_u8, tokens: as FrameStepper.step takes them; depth_u16: (h, w) or (1, h, w) uint16, the frame's raw depth image."""
-        if not isinstance(depth_u16, torch.Tensor) or depth_u16.dtype != torch.uint16 or depth_u16.numel() != self.depth.numel():
-            raise ValueError(f"depth_u16 must be a uint16 tensor of shape {tuple(self.depth.shape[1:])}")
-        if self.use_graph and self._graph is None:
-            self._capture()                      # before the frame's depth goes into its static buffer, as the image does in the parent
-        self.depth.copy_(depth_u16.reshape(self.depth.shape), non_blocking=True)
+        self._take_depth(depth_u16)
         out = super().step(image_u8, tokens)
         out["pose"] = dict(self.pose, refined=dict(self.refined))
         out["window"] = {k: v[0] for k, v in self.win["out"].items()}
@@ -490,11 +494,8 @@ class WindowPoseFrameStepper(RuleFrameStepper):
     def trajectory(self):
         """Camera -> world poses (n, 4, 4) float64 of the frames 0 .. min(n_frames, capacity) - 1, each as it stood when it left the
         window (or stands now): odometry_graph's convention.  One read-back."""
-        import numpy as np
-        n = min(self.n_frames, self.capacity)
-        C = self.win["state"]["trajectory"][0, :n].cpu().numpy().reshape(n, 3, 4)
-        C44 = np.concatenate([C, np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
-        return np.stack([np.linalg.inv(c) for c in C44]) if n else np.zeros((0, 4, 4))
+        from .odometry import camera_to_world
+        return camera_to_world(self.win["state"]["trajectory"][0, :min(self.n_frames, self.capacity)])
 
     def reset(self) -> None:
         """Forget every earlier frame: the device's counters are zeroed and the ring's slots made absent here, outside the graph."""
@@ -549,7 +550,6 @@ class LoopWindowPoseFrameStepper(WindowPoseFrameStepper):
         self._filled = torch.zeros((L,), dtype=torch.bool, device=dev)
         self._static32 = torch.full((L,), self.ring, dtype=torch.int32, device=dev)
         self._absent32 = torch.full((L,), -1, dtype=torch.int32, device=dev)
-        self._head = {k: self.refined[k][:S] for k in ("T", "info", "status", "inlier_count")}      # the window's rows
         self._tail = {k: v[S:] for k, v in self.refined.items()}
 
     def _ring_size(self, spacings: tuple) -> int:
@@ -566,27 +566,17 @@ class LoopWindowPoseFrameStepper(WindowPoseFrameStepper):
         torch.ge(po["first"], 0, out=self._filled)
         torch.where(self._filled, self._static32, self._absent32, out=self.pair_second[S:])
 
-    def _after_match(self) -> None:
-        p, ring, S = self.pipe, self.ring, len(self.spacings)
-        kp = p.geometry_keypoints(self.bank)
-        p.keypoint_depth(self.depth, kp[ring:ring + 1], out=self.kp_depth[ring:ring + 1])
-        p.estimate_poses(kp, self.kp_depth, self.pair_first, self.pair_second, self.m, self.camera, self.threshold, self.hypotheses,
-                         self.seed, out=self.pose)
-        p.refine_poses(kp, self.kp_depth, self.pair_first, self.pair_second, self.m, self.camera, self.pose, self.threshold, self.huber,
-                       self.iterations, out=self.refined)
-        p.pose_window_step(self.win, self._head, None, self.min_inliers, self.huber_chi, self.damping, self.graph_iterations)
+    def _after_window(self) -> None:
+        S = len(self.spacings)
         torch.where(self._seen, self._back, self._absent, out=self._global64)      # frame t - s, or -1 before it exists
         self._slot_first[:S].copy_(self._global64)
         self._slot_first[S:].copy_(self.place["out"]["first"])
-        p.edge_log_step(self.log, self._slot_first, self.refined, S, self.min_inliers, self.loops["min_inliers"])
-        torch.remainder(self._t, ring, out=self._slot)                   # the ring slot the frame's features take, right after this
-        self.kp_depth[:ring].index_copy_(0, self._slot, self.kp_depth[ring:ring + 1])
+        self.pipe.edge_log_step(self.log, self._slot_first, self.refined, S, self.min_inliers, self.loops["min_inliers"])
 
     def _reset_window(self) -> None:
         super()._reset_window()
-        if getattr(self, "place", None) is not None:                     # both new counters; nothing else of either state is read before it is written
-            self.place["state"]["t"].zero_()
-            self.log["state"]["t"].zero_()
+        self.place["state"]["t"].zero_()                                 # both new counters; nothing else of either state is read before it is written
+        self.log["state"]["t"].zero_()
 
     @torch.no_grad()
     def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
@@ -603,7 +593,8 @@ class LoopWindowPoseFrameStepper(WindowPoseFrameStepper):
         log order, and loop_edges (P, 2): the logged loop slots [older frame, frame].  A frame with no logged edge - every pair of
         it refused - leaves its block zero: status 2 at damping 0 and the window's trajectory back, as the batch graph answers."""
         import numpy as np
-        lib.check_positive("huber_chi", huber_chi), lib.check_damping(damping), lib.check_graph_iterations(iterations)
+        from .odometry import _GRAPH_INT, camera_to_world
+        g = GraphSettings(huber_chi, damping, iterations)
         lib.check_cg_iterations(cg_iterations), lib.check_cg_tol(cg_tol)
         n = min(self.n_frames, self.capacity)
         if n < 1:
@@ -611,18 +602,18 @@ class LoopWindowPoseFrameStepper(WindowPoseFrameStepper):
         S, E = len(self.spacings), len(self.spacings) + self.loops["per_frame"]
         st, rows = self.log["state"], n * E
         r = self.pipe.optimize_pose_graph_sparse(st["log_first"][:rows], st["log_second"][:rows], st["log_T"][:rows], st["log_info"][:rows], n,
-                                                 self.win["state"]["trajectory"][0, :n], huber_chi, damping, iterations, cg_iterations, cg_tol)
-        words = ("status", "iterations", "used_edges", "skipped_edges", "failed_row", "cost_in", "cost")
-        flat = torch.cat([r["C"].reshape(-1)] + [r[k].reshape(1).to(torch.float64) for k in words] +
-                         [r["cg_steps"].to(torch.float64), r["edge_chi2"], st["log_first"][:rows].to(torch.float64)]).cpu().numpy()      # the ONE read-back
-        C = flat[:12 * n].reshape(n, 12)
-        out = {k: (float(v) if k.startswith("cost") else int(v)) for k, v in zip(words, flat[12 * n:12 * n + 7])}
-        at = 12 * n + 7
-        first = flat[at + lib.SPARSE_MAX_ITER + rows:].astype(np.int64).reshape(n, E)
+                                                 self.win["state"]["trajectory"][0, :n], g.huber_chi, g.damping, g.iterations, cg_iterations, cg_tol)
+        rb = Readback()
+        for key in _GRAPH_INT + ("cg_steps",):
+            rb.add(key, r[key], np.int64)
+        for key in ("cost_in", "cost", "C", "edge_chi2"):
+            rb.add(key, r[key], np.float64)
+        rb.add("log_first", st["log_first"][:rows].reshape(n, E), np.int64)
+        host = rb.fetch()                                                # the ONE read-back
+        out = {key: host[key].item() for key in _GRAPH_INT + ("cost_in", "cost")}
+        first = host["log_first"]
         frame, slot = np.nonzero(first[:, S:] >= 0)
-        C44 = np.concatenate([C.reshape(n, 3, 4), np.broadcast_to(np.array([0.0, 0.0, 0.0, 1.0]), (n, 1, 4))], axis=1)
-        out.update(C=C, trajectory=np.stack([np.linalg.inv(c) for c in C44]), cg_steps=flat[at:at + lib.SPARSE_MAX_ITER].astype(np.int64),
-                   edge_chi2=flat[at + lib.SPARSE_MAX_ITER:at + lib.SPARSE_MAX_ITER + rows],
+        out.update(C=host["C"], trajectory=camera_to_world(host["C"]), cg_steps=host["cg_steps"], edge_chi2=host["edge_chi2"],
                    loop_edges=np.stack([first[frame, S + slot], frame], axis=1).astype(np.int64))
         return out
 
@@ -670,9 +661,8 @@ class TrackWindowPoseFrameStepper(WindowPoseFrameStepper):
 
     def _reset_window(self) -> None:
         super()._reset_window()
-        if getattr(self, "tracks", None) is not None:                    # both counters; nothing else of the state is read before it is written
-            self.tracks["state"]["t"].zero_()
-            self.tracks["state"]["next_id"].zero_()
+        self.tracks["state"]["t"].zero_()                                # both counters; nothing else of the state is read before it is written
+        self.tracks["state"]["next_id"].zero_()
 
     @torch.no_grad()
     def step(self, image_u8: torch.Tensor, depth_u16: torch.Tensor, tokens: torch.Tensor | None = None) -> dict:
@@ -694,11 +684,11 @@ class TrackWindowPoseFrameStepper(WindowPoseFrameStepper):
         st, K = self.tracks["state"], self.cfg.num_keypoints
         tr = self.pipe.track_ids({key: st[key][:n] for key in lib.LINK_KEYS})
         lm = self.pipe.landmarks(self.track_kp[:n], self.track_depth[:n], self.win["state"]["trajectory"][0, :n], tr, self.camera, thr, mo)
-        f64 = lambda t: t.to(torch.float64).reshape(-1)
-        flat = torch.cat([f64(tr["n_tracks"]), f64(tr["track_id"]), f64(tr["age"]), f64(tr["length"]), f64(lm["status"]), f64(lm["n_kept"]),
-                          lm["rms"], lm["xyz"].reshape(-1)]).cpu().numpy()      # the ONE read-back
-        N, nt = n * K, int(flat[0])
-        col = lambda i: flat[1 + i * N:1 + (i + 1) * N]
-        return dict(n_tracks=nt, track_id=col(0).astype(np.int32).reshape(n, K), age=col(1).astype(np.int32).reshape(n, K),
-                    length=col(2)[:nt].astype(np.int32), status=col(3)[:nt].astype(np.int32), n_kept=col(4)[:nt].astype(np.int32),
-                    rms=col(5)[:nt].copy(), landmarks=flat[1 + 6 * N:].reshape(N, 3)[:nt].copy())
+        rb = Readback()
+        for key in ("n_tracks", "track_id", "age"):
+            rb.add(key, tr[key], np.int32)
+        for key, t, dtype in (("length", tr["length"], np.int32), ("status", lm["status"], np.int32), ("n_kept", lm["n_kept"], np.int32),
+                              ("rms", lm["rms"], np.float64), ("landmarks", lm["xyz"], np.float64)):
+            rb.add(key, t, dtype, rows="n_tracks")                       # a row per keypoint on the device, n_tracks of them filled
+        host = rb.fetch()                                                # the ONE read-back
+        return dict(host, n_tracks=int(host["n_tracks"][0]))

@@ -157,7 +157,56 @@ def _checked_weights(weights):
     return weights
 
 
+@dataclass(frozen=True)
+class PoseSettings:
+    """How the pose of a pair is estimated, judged ONCE where a public call of odometry or a stepper of online takes the values and
+    handed on whole: RANSAC's threshold (keypoint units), hypotheses and seed; refine, and with it the refinement's huber (None:
+    threshold / 3) and iterations; weights, None or the PoseWeights of the weighted refinement.  The fields hold the checked values;
+    without refine, huber and iterations are kept as given and read by nobody."""
+    threshold: float = 3.0
+    hypotheses: int = 256
+    seed: int = 0
+    refine: bool = False
+    huber: float | None = None
+    iterations: int = 5
+    weights: PoseWeights | None = None
+
+    def __post_init__(self):
+        checked = dict(threshold=lib.check_threshold(self.threshold), hypotheses=lib.check_hypotheses(self.hypotheses), seed=lib.check_seed(self.seed))
+        if not isinstance(self.refine, bool):
+            raise ValueError(f"refine must be a bool, got {self.refine!r}")
+        if self.refine:
+            checked.update(huber=lib.check_huber(checked["threshold"] / 3.0 if self.huber is None else self.huber),
+                           iterations=lib.check_iterations(self.iterations))
+        if _checked_weights(self.weights) is not None and not self.refine:
+            raise ValueError("weights= weights the refinement: it needs refine=True")
+        for key, v in checked.items():
+            object.__setattr__(self, key, v)
+
+    def check_pipeline(self, pipe) -> None:
+        """The one check that needs the pipeline: weights are made of the confidence it must extract.  Without weights `pipe` is not
+        touched (it may be None)."""
+        if self.weights is not None and not getattr(pipe.cfg, "confidence", False):
+            raise ValueError("weights= is made of the keypoint confidence: the pipeline needs ExtractorConfig(confidence=True)")
+
+
+@dataclass(frozen=True)
+class GraphSettings:
+    """The solver settings of a pose graph - optimize_pose_graph, optimize_pose_graph_sparse, pose_window_step: huber_chi, damping and
+    the most Gauss-Newton iterations (include/sslam_graph.h), judged once like PoseSettings.  The band is no setting: it follows from
+    the pair lists (odometry._check_graph)."""
+    huber_chi: float = 4.0
+    damping: float = 0.0
+    iterations: int = 8
+
+    def __post_init__(self):
+        for key, v in dict(huber_chi=lib.check_positive("huber_chi", self.huber_chi), damping=lib.check_damping(self.damping),
+                           iterations=lib.check_graph_iterations(self.iterations)).items():
+            object.__setattr__(self, key, v)
+
+
 def _np(v):
+    """A tensor, wherever it lives, or anything array-like as a numpy array."""
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
 

@@ -29,9 +29,9 @@ Defaults are the reference's configuration values (configs/train_config.yaml:52-
 from __future__ import annotations
 
 import numpy as np
-import torch
 
 from . import lib
+from .pipeline import _np
 
 TERMS = ("desc", "variance", "repeat", "peakiness", "activation", "edge", "sparsity")
 METRICS = ("num_matches", "mean_saliency", "max_saliency", "saliency_variance", "descriptor_variance")
@@ -47,10 +47,6 @@ BATCH = 4               # training.batch_size :84
 _FRAME_KEYS = ("sal_mean", "sal_var", "sal_max", "sal_dx", "sal_dy", "sal_high", "sal_ss", "edge_a", "edge_e", "edge_max",
                "desc_mean", "desc_m2")
 _PAIR_KEYS = ("first", "repeat", "n_matches", "ce_sum", "pad_ce")
-
-
-def _host(v):
-    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
 
 def _check_batch(batch) -> int:
@@ -85,14 +81,14 @@ def compose(stats: dict, batch: int = BATCH, weights: dict | None = None, target
     if missing:
         raise ValueError(f"stats lack {missing}: pass the dictionary of validation_stats")
     g, k = int(stats["grid"]), int(stats["num_keypoints"])
-    fr = {key: _host(stats[key]).astype(np.float64) for key in _FRAME_KEYS}
-    first = _host(stats["first"]).astype(np.int64)
-    pr = {key: _host(stats[key]).astype(np.float64) for key in ("repeat", "n_matches", "ce_sum", "pad_ce")}
+    fr = {key: _np(stats[key]).astype(np.float64) for key in _FRAME_KEYS}
+    first = _np(stats["first"]).astype(np.int64)
+    pr = {key: _np(stats[key]).astype(np.float64) for key in ("repeat", "n_matches", "ce_sum", "pad_ce")}
     n_pairs, n_frames = first.shape[0], fr["sal_mean"].shape[0]
     if n_pairs == 0 or n_pairs % batch:
         raise ValueError(f"{n_pairs} pairs do not make whole batches of {batch}: ragged last batch")
     if "second" in stats:
-        second = _host(stats["second"]).astype(np.int64)
+        second = _np(stats["second"]).astype(np.int64)
         if ((second < 0) | (second >= n_frames)).any():
             raise ValueError("an absent pair (index outside the bank) has no loss: list present pairs only")
     if ((first < 0) | (first >= n_frames)).any():

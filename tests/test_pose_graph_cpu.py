@@ -245,15 +245,15 @@ def test_the_layers_judge_their_arguments_first(tmp_path):
         run_directory(str(tmp_path / "nowhere"), "none", (1, 5), evaluate={"odometry": True, "refine": True, "graph": 1})
     for spacings in ((), (5, 10), (1, 1)):
         with pytest.raises(ValueError, match="spacings"):
-            od._check_graph(spacings, 12, None, None, 4.0, 0.0, 8)
-    sp, lists, n, band = od._check_graph(od.GRAPH_SPACINGS, 12, None, None, 4.0, 0.0, 8)
+            od._check_graph(spacings, 12, None, None)
+    sp, lists, n, band = od._check_graph(od.GRAPH_SPACINGS, 12, None, None)
     assert sp == (1, 5, 10) and n == 12 and band == 10 and [len(lists[s]) for s in sp] == [11, 7, 2]
-    sp, lists, n, band = od._check_graph((1, 3), 9, 4, None, 4.0, 0.0, 8)
+    sp, lists, n, band = od._check_graph((1, 3), 9, 4, None)
     assert n == 5 and lists[3] == [(0, 3), (1, 4)] and band == 3
     with pytest.raises(ValueError):
-        od._check_graph((1, 5), 1, None, None, 4.0, 0.0, 8)
+        od._check_graph((1, 5), 1, None, None)
     with pytest.raises(ValueError):
-        od._check_graph((1, 5), 12, None, None, 4.0, -1.0, 8)
+        od.GraphSettings(4.0, -1.0, 8)                               # the record every graph call builds of its solver settings
     import evaluation as dropin
     for args in (([0], [1], np.zeros((1, 12)), np.zeros((1, 6, 6)), 2), ([0], [1], np.zeros((1, 4, 4)), np.zeros((1, 21)), 2),
                  ([0], [1, 2], np.zeros((1, 4, 4)), np.zeros((1, 6, 6)), 2)):
